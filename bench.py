@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Faster-OreFSDet on MI355X -- headline benchmark (BASELINE.json: images/s at 640x640, 25-shot).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 `value` follows the reference's own FPS protocol (d2z:evaluation/evaluator.py:138-161, SURVEY 8d metric (i)): one step =
@@ -11,8 +11,12 @@ meta-architecture's forward: support-cache check, the whole detector (fused prep
 CenterNet head -> top-k/decode/NMS -> ROIAlign + cascade ROI head -> NMS -> top-100) as one replayed hipGraph, the count read-back,
 `Instances`, `detector_postprocess`.  The image tensor is resident in HBM when the timed region starts (the tier rule for `value`);
 the same protocol fed a host uint8 image (H2D copy inside the step, what a dataloader hands over) is reported as
-"protocol_host_image".  The K steps are repeated until the timed region is >= --min-time seconds (default 1 s) so a small --steps
-still gives a stable figure; `value` = images of all repeats / their time.
+"protocol_host_image".  After >= W warm-up steps (and >= 0.5 s of them) the timed region is exactly K = --steps steps; --min-time
+S repeats the K steps until the region is >= S seconds instead.  `value` = images of the timed steps / their time, `ms_per_step` =
+their time / their number.
+--dump-outputs DIR: after the timed region, the detections of its last step (what the caller of model() receives: pred_boxes,
+scores, pred_classes of the Instances) are written as DIR/instances_<field>.npy in float32; inputs and weights are seeded, so two
+builds run with the same arguments can be compared output for output.
 Beside it, never as `value`: "engine_sequential" (the C-ABI engine call alone, no per-image sync), "in_flight" (4 bs=1 forwards in
 flight on 4 streams), "folded_serving", "train_step" / "train_step_bs16", and "gpu_idle_us_per_image" (a protocol step minus the same
 graph replayed back to back = what the per-image sync leaves idle on the GPU).
@@ -340,6 +344,15 @@ def train_leg(device, steps=8, warmup=4, size=640, shots=24, batch=1, graph=True
     return out
 
 
+def dump_outputs(dirname, inst):
+    """The arrays of one detection result (Instances of model()'s output) as <dirname>/instances_<field>.npy, float32."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    fields = {"pred_boxes": inst.pred_boxes.tensor, "scores": inst.scores, "pred_classes": inst.pred_classes}
+    for name, t in fields.items():
+        np.save(os.path.join(dirname, f"instances_{name}.npy"), t.detach().cpu().numpy().astype(np.float32))
+
+
 def self_launch(n):
     """One fresh process per GPU: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment, the same argv.  Children are started as
     subprocesses of the same interpreter (no fork of a GPU-initialised process, no exec from one)."""
@@ -420,8 +433,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=500)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--min-time", type=float, default=1.0, help="repeat the K timed steps until the timed region is at least this long (s)")
+    ap.add_argument("--warmup", type=int, default=20, help="warm-up steps before the timed region (at least 5, and at least 0.5 s of them)")
+    ap.add_argument("--min-time", type=float, default=None,
+                    help="repeat the K timed steps until the timed region is at least this long (s); default: exactly K timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-train-leg", action="store_true", help="skip the train-step measurements printed as \"train_step\"")
@@ -503,6 +519,8 @@ def main():
     imgs = [t.to(device) for t in host_imgs]
     use_graph = not args.no_graph
     K, W = max(args.steps, 1), max(args.warmup, 5)
+    head_min = args.min_time or 0.0                          # 0: the headline region is exactly K steps
+    extra_min = 0.5 if args.min_time is None else min(args.min_time, 0.5)
 
     def sync_all():
         torch.cuda.synchronize()
@@ -532,11 +550,16 @@ def main():
         out_last[0] = model(requests[i % len(requests)])
         torch.cuda.synchronize()
 
-    for i in range(W):
+    # at least W warm-up steps and at least 0.5 s of them, so that a short timed region starts with the clocks already up
+    t0, i = time.perf_counter(), 0
+    while i < W or time.perf_counter() - t0 < 0.5:
         proto_step(i)
-    n_steps, elapsed = timed_region(proto_step, K, args.min_time)
+        i += 1
+    n_steps, elapsed = timed_region(proto_step, K, head_min)
     total_images = world * n_steps
     n_det_proto = len(out_last[0][0]["instances"])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out_last[0][0]["instances"])
     eng = model.engine()
 
     extras = {}
@@ -549,7 +572,7 @@ def main():
             torch.cuda.synchronize()
         for i in range(5):
             host_step(i)
-        n_h, el_h = timed_region(host_step, K, min(args.min_time, 0.5))
+        n_h, el_h = timed_region(host_step, K, extra_min)
         extras["protocol_host_image"] = {"images_per_s": round(world * n_h / el_h, 2), "ms_per_image": round(el_h / n_h * 1e3, 4),
                                          "note": "same protocol, image handed over as a host uint8 tensor (PCIe copy inside the step)"}
         # the C-ABI engine call alone: one image at a time on one stream, no per-image host sync, no Instances / postprocess
@@ -557,7 +580,7 @@ def main():
             eng.eval_forward(imgs[i % len(imgs)], use_graph=use_graph)
         for i in range(5):
             eng_step(i)
-        n_e, el_e = timed_region(eng_step, K, min(args.min_time, 0.5))
+        n_e, el_e = timed_region(eng_step, K, extra_min)
         extras["engine_sequential"] = {"images_per_s": round(world * n_e / el_e, 2), "ms_per_image": round(el_e / n_e * 1e3, 4),
                                        "note": "ore_engine_eval_fwd (one hipGraph replay per image) back to back on one stream, no per-image sync"}
         # per-image latency of the engine call with a host sync after every image
@@ -584,7 +607,7 @@ def main():
                     engines[i % len(engines)].eval_forward(imgs[i % len(imgs)], use_graph=use_graph)
             for i in range(2 * len(engines)):
                 fl_step(i)
-            n_f, el_f = timed_region(fl_step, K, min(args.min_time, 0.5))
+            n_f, el_f = timed_region(fl_step, K, extra_min)
             ref = None                                       # every concurrent engine must reproduce engine 0 bit for bit
             for e, st in zip(engines, streams):
                 with torch.cuda.stream(st):
@@ -613,7 +636,7 @@ def main():
                     efs[j % S].eval_forward_batch(packs[j % len(packs)], use_graph=use_graph)
             for j in range(2 * S):
                 fstep(j)
-            nb, f_el = timed_region(fstep, max(K // args.fold, S), min(args.min_time, 0.5))
+            nb, f_el = timed_region(fstep, max(K // args.fold, S), extra_min)
             extras["folded_serving"] = {"images_per_s": round(world * nb * args.fold / f_el, 2), "requests_per_pass": args.fold,
                                         "passes_in_flight": S, "ms_per_pass": round(f_el / nb * 1e3, 4),
                                         "note": "the same bs=1 requests, %d folded into one engine pass (ore_engine_eval_batch_fwd), %d passes "

@@ -781,8 +781,41 @@ def gen_eval_end_to_end(sd0, shots=5):
     save("eval_end_to_end", shots=np.int64(shots), df_seed=np.int64(23), **out)
 
 
+def gen_fsod_config_keys(names=("finetune_R_50_C4_1x", "finetune_R_50_F", "finetune_dla", "finetune_dla2")):
+    """tests/golden/fsod_config_keys.json: for each reference config that the package does not ship, every key it sets (its _BASE_
+    resolved the way merge_from_file resolves it: base first, the file's own keys over it) as {"MODEL.X.Y": value}.  Data only:
+    which keys and values a config hands to get_cfg, not the file."""
+    import json
+    import yaml
+
+    def load(path):
+        with open(path) as f:
+            d = yaml.safe_load(f)
+        base = d.pop("_BASE_", None)
+        flat = load(os.path.join(os.path.dirname(path), base)) if base else {}
+        flat.update(flatten(d))
+        return flat
+
+    def flatten(d, pre=""):
+        out = {}
+        for k, v in d.items():
+            if isinstance(v, dict):
+                out.update(flatten(v, pre + k + "."))
+            else:
+                out[pre + k] = v
+        return out
+
+    out = {n + ".yaml": load(os.path.join(shims.REF, "configs", "fsod", n + ".yaml")) for n in names}
+    with open(os.path.join(OUT, "fsod_config_keys.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("fsod_config_keys.json:", {k: len(v) for k, v in out.items()})
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "split":
+    if len(sys.argv) > 1 and sys.argv[1] == "configs":
+        gen_fsod_config_keys()
+    elif len(sys.argv) > 1 and sys.argv[1] == "split":
         gen_dataset_split()
     elif len(sys.argv) > 1 and sys.argv[1] == "eval":
         torch.manual_seed(0)

@@ -3,6 +3,8 @@ of bench.py's output format is caught on the CPU.  (The numbers themselves are p
 import json
 import os
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -119,3 +121,48 @@ def test_bench_self_launch_returns_promptly_when_a_rank_dies():
     assert r.returncode == 7, (r.returncode, r.stderr[-1000:])
     assert time.time() - t0 < 60
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_dump_outputs_writes_the_returned_arrays(tmp_path):
+    """`bench.py --dump-outputs DIR`: the arrays of the Instances model() returned, one float32 .npy per field, values unchanged."""
+    import sys
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from detectron2.structures import Boxes, Instances
+    inst = Instances((640, 640))
+    inst.pred_boxes = Boxes(torch.tensor([[1.5, 2.0, 30.25, 40.0], [0.0, 0.0, 639.0, 639.0]]))
+    inst.scores = torch.tensor([0.9, 0.125])
+    inst.pred_classes = torch.zeros(2, dtype=torch.int64)
+    bench.dump_outputs(str(tmp_path / "out"), inst)
+    got = {f: np.load(tmp_path / "out" / f"instances_{f}.npy") for f in ("pred_boxes", "scores", "pred_classes")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["pred_boxes"], inst.pred_boxes.tensor.numpy()) and np.array_equal(got["scores"], inst.scores.numpy())
+    assert np.array_equal(got["pred_classes"], np.zeros(2, np.float32))
+
+
+@pytest.mark.gpu
+def test_bench_times_exactly_the_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py --steps 3 --dump-outputs DIR` on the MI355X: the headline region is exactly 3 timed steps, and DIR holds the
+    detections model() returned in the last of them (rank 0, after the timed region), float32, as many as the line reports."""
+    import subprocess
+    import sys
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "5", "--no-train-leg",
+                        "--no-extras", "--no-cpu-baseline", "--profile-passes", "1", "--dump-outputs", str(tmp_path / "out")],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["config"]["timed_steps"] == 3
+    # ms_per_step is the time of ONE of the 3 timed steps (timed_region_s is printed rounded to 1 ms)
+    assert abs(d["ms_per_step"] * 3 - d["config"]["timed_region_s"] * 1e3) <= 0.5 + 1e-3 * d["ms_per_step"]
+    assert abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 0.01                                 # images/s of bs=1 steps
+    got = {f: np.load(tmp_path / "out" / f"instances_{f}.npy") for f in ("pred_boxes", "scores", "pred_classes")}
+    n = d["config"]["detections_returned"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["pred_boxes"].shape == (n, 4) and got["scores"].shape == (n,) and got["pred_classes"].shape == (n,)
+    assert n > 0 and np.isfinite(got["pred_boxes"]).all() and (np.diff(got["scores"]) <= 0).all()

@@ -1,34 +1,82 @@
-"""The reference's entry script, EXECUTED (ref:fsod_train_net.py:36-118), with faster-orefsdet_amd/ first on sys.path: the drop-in claim
-of SURVEY 8b checked by running the script's own `setup()` and `Trainer` overrides instead of its import lines.
+"""The drop-in claim of SURVEY 8b for the reference's entry script (ref:fsod_train_net.py:36-118), checked by running an entry
+script's `setup()`, `main()` and `Trainer` overrides with faster-orefsdet_amd/ first on sys.path, instead of its import lines alone.
 
-CPU only and only where /root/reference exists (this container): the reference never travels to the GPU box, so the test is
-skipped there.  The ore dataset is not shipped with the reference; a synthetic COCO-format dataset + support dataframe is written
-into a scratch working directory under the paths the reference hard-codes (./datasets/coco/..., ref:fewx/data/datasets/builtin.py:8-30,
-ref:fewx/data/dataset_mapper.py:80-82)."""
+The reference's file itself is NOT executed: it is outside the repository.  `_load_script` below is a RE-STATEMENT of that script's
+calls -- the public detectron2 train_net pattern -- made against this package's surface (fewx.config.get_cfg,
+DatasetMapperWithSupport, fewx.data.build loaders, fewx.solver.build_optimizer, fewx.evaluation.COCOEvaluator, default_setup +
+setup_logger, DetectionCheckpointer).  The tests prove that these calls work on the package; if the reference script changes, this
+re-statement has to follow it by hand.  The test names ("reference_script_*") name the script whose calls are re-stated.
+Configs: the package's own configs/fsod/*.yaml, and for the reference configs it does not ship their stored key/value sets
+(tests/golden/fsod_config_keys.json).  CPU only.  The ore dataset is not shipped; a synthetic COCO-format dataset + support
+dataframe is written into a scratch working directory under the paths the reference hard-codes (./datasets/coco/...,
+ref:fewx/data/datasets/builtin.py:8-30, ref:fewx/data/dataset_mapper.py:80-82)."""
 import glob
-import importlib.util
 import json
 import os
 import sys
+import types
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import PKG
+from conftest import GOLDEN, PKG
 
-REF = "/root/reference"
-SCRIPT = os.path.join(REF, "fsod_train_net.py")
-pytestmark = pytest.mark.skipif(not os.path.exists(SCRIPT), reason="the reference tree exists in the build container only")
+CONFIGS = os.path.join(PKG, "configs", "fsod")
 
 
 def _load_script():
+    """An entry-script module: `default_argument_parser`, `get_cfg`, `setup`, `main`, `Trainer`."""
     if PKG not in sys.path:
         sys.path.insert(0, PKG)
-    spec = importlib.util.spec_from_file_location("ref_fsod_train_net", SCRIPT)
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)                       # the `if __name__ == "__main__"` launch does not fire under this name
-    return m
+    import detectron2.utils.comm as comm
+    from detectron2.checkpoint import DetectionCheckpointer
+    from detectron2.engine import DefaultTrainer, default_argument_parser, default_setup
+    from detectron2.utils.logger import setup_logger
+    from fewx.config import get_cfg
+    from fewx.data.build import build_detection_test_loader, build_detection_train_loader
+    from fewx.data.dataset_mapper import DatasetMapperWithSupport
+    from fewx.evaluation import COCOEvaluator
+    from fewx.solver import build_optimizer
+
+    class Trainer(DefaultTrainer):
+        @classmethod
+        def build_train_loader(cls, cfg):
+            return build_detection_train_loader(cfg, DatasetMapperWithSupport(cfg))
+
+        @classmethod
+        def build_test_loader(cls, cfg, dataset_name):
+            return build_detection_test_loader(cfg, dataset_name)
+
+        @classmethod
+        def build_optimizer(cls, cfg, model):
+            return build_optimizer(cfg, model)
+
+        @classmethod
+        def build_evaluator(cls, cfg, dataset_name, output_folder=None):
+            return COCOEvaluator(dataset_name, cfg, True, output_folder or os.path.join(cfg.OUTPUT_DIR, "inference"))
+
+    def setup(args):
+        cfg = get_cfg()
+        cfg.merge_from_file(args.config_file)
+        cfg.merge_from_list(args.opts)
+        cfg.freeze()
+        default_setup(cfg, args)
+        setup_logger(cfg.OUTPUT_DIR, distributed_rank=comm.get_rank(), name="fewx")
+        return cfg
+
+    def main(args):
+        cfg = setup(args)
+        if args.eval_only:
+            model = Trainer.build_model(cfg)
+            DetectionCheckpointer(model, save_dir=cfg.OUTPUT_DIR).resume_or_load(cfg.MODEL.WEIGHTS, resume=args.resume)
+            return Trainer.test(cfg, model)
+        trainer = Trainer(cfg)
+        trainer.resume_or_load(resume=args.resume)
+        return trainer.train()
+
+    return types.SimpleNamespace(default_argument_parser=default_argument_parser, get_cfg=get_cfg, setup=setup, main=main,
+                                 Trainer=Trainer)
 
 
 def _write_dataset(root, n_img=6, per_img=3, seed=3):
@@ -73,12 +121,12 @@ def script(tmp_path, monkeypatch):
 
 def _args(m, tmp_path, *opts):
     return m.default_argument_parser().parse_args(
-        ["--config-file", os.path.join(REF, "configs/fsod/finetune_vovnet.yaml"), "--num-gpus", "1",
+        ["--config-file", os.path.join(CONFIGS, "finetune_vovnet.yaml"), "--num-gpus", "1",
          "OUTPUT_DIR", str(tmp_path / "out"), "MODEL.DEVICE", "cpu", "DATALOADER.NUM_WORKERS", "0", *opts])
 
 
 def test_reference_script_setup_and_trainer_overrides(script):
-    """ref:fsod_train_net.py:76-91 `setup`, :36-73 the four `Trainer` classmethods and `build_model`, on the reference's own
+    """ref:fsod_train_net.py:76-91 `setup`, :36-73 the four `Trainer` classmethods and `build_model`, on the package's
     finetune_vovnet.yaml (BASELINE configs[1..3])."""
     m, (n_img, per_img), tmp_path = script
     args = _args(m, tmp_path, "INPUT.FS.SUPPORT_SHOT", "2")
@@ -125,15 +173,54 @@ def test_reference_script_trainer_construction(script):
     assert sched is not None and trainer.model.training
 
 
-@pytest.mark.parametrize("yaml_file", sorted(glob.glob(os.path.join(REF, "configs/fsod/*.yaml"))), ids=os.path.basename)
-def test_every_reference_config_parses(script, yaml_file):
-    """All of ref:configs/fsod/*.yaml go through the script's own get_cfg + merge_from_file + freeze."""
-    m, _, _ = script
+def _config_cases():
+    """The shipped configs (configs/fsod/*.yaml) as files; the reference's other configs as the key/value sets they hand to get_cfg
+    (tests/golden/fsod_config_keys.json, oracle/refrun/gen_golden.py::gen_fsod_config_keys), under the same ids."""
+    with open(os.path.join(GOLDEN, "fsod_config_keys.json")) as f:
+        keyed = json.load(f)
+    return ([pytest.param(p, None, id=os.path.basename(p)) for p in sorted(glob.glob(os.path.join(CONFIGS, "*.yaml")))] +
+            [pytest.param(name, keyed[name], id=name) for name in sorted(keyed)])
+
+
+def _decoded(v):
+    """A value as merge_from_file stores it: strings that are Python literals are evaluated, lists and tuples compare alike."""
+    import ast
+    if isinstance(v, str):
+        try:
+            v = ast.literal_eval(v)
+        except (ValueError, SyntaxError):
+            return v
+    return [_decoded(x) for x in v] if isinstance(v, (list, tuple)) else v
+
+
+@pytest.mark.parametrize("yaml_file,keys", _config_cases())
+def test_every_reference_config_parses(script, yaml_file, keys):
+    """Every config of ref:configs/fsod/ goes through the entry script's get_cfg + merge_from_file + freeze: the shipped ones as
+    files, the others from their stored key/value sets (written back to a YAML file first).  merge_from_file raises KeyError on a
+    key get_cfg does not know (MODEL.DLA.*, MODEL.BIFPN.*, MODEL.RESNETS.*, MODEL.CENTERNET.MORE_POS, ...), and every stored value
+    must arrive in the frozen config unchanged."""
+    import yaml
+    m, _, tmp_path = script
+    if keys is not None:
+        nested = {}
+        for k, v in keys.items():
+            node = nested
+            for part in k.split(".")[:-1]:
+                node = node.setdefault(part, {})
+            node[k.split(".")[-1]] = v
+        path = tmp_path / yaml_file
+        path.write_text(yaml.safe_dump(nested))
+        yaml_file = str(path)
     cfg = m.get_cfg()
     cfg.merge_from_file(yaml_file)
     cfg.freeze()
     assert cfg.MODEL.META_ARCHITECTURE in ("CenterNet2Detector", "FsodRCNN")
     assert cfg.INPUT.FS.SUPPORT_WAY >= 1 and cfg.INPUT.FS.SUPPORT_SHOT >= 1
+    for k, v in (keys or {}).items():
+        got = cfg
+        for part in k.split("."):
+            got = got[part]
+        assert _decoded(got) == _decoded(v), k
 
 
 def test_reference_script_main_eval_only_reaches_the_evaluator(script):

@@ -77,6 +77,12 @@ int roi_predict_post(const float* h, int32_t C, int32_t h_parts, const float* h_
                      int32_t topk, float* det_boxes, float* det_scores, int64_t* det_src, int32_t* det_count,
                      const float* post_dev, float* fin_boxes, float* fin_scores, int32_t* fin_count,
                      int32_t* host_count, void* workspace, size_t workspace_bytes, void* stream);
+// N-way pass: merge of the K per-class detection lists (det_boxes / det_scores / det_count of class slot k at k * cap rows / k * 4 words)
+// into one list -- score descending, ties by class slot, then by row -- cut at topk, then detector_postprocess into fin_* and the
+// caller's record (csrc/ore_roi.hip, k_roi_merge_classes).  class_ids [K] int64 device.
+int roi_merge_classes(const float* det_boxes, const float* det_scores, const int32_t* det_count, int32_t K, int32_t cap,
+                      const int64_t* class_ids, int32_t topk, const float* post_dev, float* fin_boxes, float* fin_scores,
+                      int64_t* fin_classes, int32_t* fin_count, int32_t* host_count, void* stream);
 // where the per-ROI rows of the predictor live inside that workspace (read-back for tests: ore_engine_buffer "roi_raw_*")
 struct PredictWs { size_t raw_boxes, c_boxes, raw_scores, c_scores, c_src, ok, keep, nms; };
 inline PredictWs predict_ws_layout(int32_t cap) {
@@ -93,4 +99,11 @@ inline PredictWs predict_ws_layout(int32_t cap) {
     w.nms = (o + 255) & ~(size_t)255;
     return w;
 }
+}
+
+namespace oremisc {
+// N-way fan-out correlation and the query copy in front of it (csrc/ore_misc.hip)
+int correlation_classes(const float* q, int32_t q_ld, int32_t q_coff, int32_t n_levels, const int32_t* H, const int32_t* W, int32_t C,
+                        int32_t K, const float* k11s, const float* k13s, const float* k31s, float* out, int32_t out_ld, void* stream);
+int copy_cols(const float* src, int32_t src_ld, int32_t src_coff, int32_t rows, int32_t C, float* dst, int32_t dst_ld, void* stream);
 }

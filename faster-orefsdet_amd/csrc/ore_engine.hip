@@ -98,9 +98,16 @@ struct ore_engine {
     float* fin_boxes_of(size_t b) const { return (float*)(fin_pack + b * (size_t)roi_cap * 28); }
     float* fin_scores_of(size_t b) const { return fin_boxes_of(b) + (size_t)roi_cap * 4; }
     int32_t* pin_count = nullptr; int32_t* pin_count_dev = nullptr; float* pin_post = nullptr;
-    // graph cache
+    // N-way pass (ore_engine_set_classes): class slot k sits where image k of a batch would; allocated on the first set_classes(n >= 1)
+    int n_classes = 0, n_slots = 0;
+    int64_t* class_ids = nullptr;                        // device [ORE_MAX_CLASSES]
+    float* k11s = nullptr, *k13s = nullptr, *k31s = nullptr;   // [slot][3][C], [slot][3][C][3], [slot][3][C][3]
+    bool slot_support_set[ORE_MAX_CLASSES][3] = {};
+    float* roi_W_slot[ORE_MAX_CLASSES] = {}; float* roi_b_slot[ORE_MAX_CLASSES] = {};   // composed DSA-mix + fc1 of each class
+    char* det_ws_slots = nullptr;                        // detection-tail workspaces of slots 1.. (slot 0 uses det_ws)
+    // graph cache (K: class count of an N-way pass, 0 = the single-class / batch passes)
     hipStream_t cap_stream = nullptr;
-    struct GraphKey { int u8, H, W, B; hipGraphExec_t exec; };
+    struct GraphKey { int u8, H, W, B, K; hipGraphExec_t exec; };
     std::vector<GraphKey> graphs;
     Geo last{};
     double last_flops = 0.0;
@@ -395,23 +402,25 @@ int run_backbone(ore_engine* e, const void* img, int is_u8, const Geo& g, hipStr
     return r.rc;
 }
 
-int run_heads(ore_engine* e, const Geo& g, hipStream_t st, double* flops) {
+int run_heads(ore_engine* e, const Geo& g, hipStream_t st, double* flops, bool correlate = true) {   // correlate = false: pcat holds [attn|q] already (N-way pass)
     const ore_model_cfg& c = e->cfg;
     const int F = c.fpn_ch;
     Run r{e, st};
     r.prof = e->profiling;
     const int H[3] = {g.h[3], g.h[4], g.h[5]}, W[3] = {g.w[3], g.w[4], g.w[5]};
     const int HW[3] = {H[0] * W[0], H[1] * W[1], H[2] * W[2]};
-    for (int l = 0; l < 3; ++l)
-        if (!e->support_set[l]) { ore_set_error("support prototype for level %d not set", l + 3); return ORE_EINVAL; }
-    // query<->support depthwise correlation, all levels: attn -> channels [0,F) of pcat (q sits in [F,2F))
     const bool sb = e->sb();
-    r.rc = sb ? ore_correlation_levels_bf16_fwd(reinterpret_cast<const uint16_t*>(e->pcat.p), 2 * F, F, g.B, 3, H, W, F, e->k11, e->k13, e->k31,
-                                                reinterpret_cast<uint16_t*>(e->pcat.p), 2 * F, 0, st)
-              : ore_correlation_levels_fwd(e->pcat.p, 2 * F, F, g.B, 3, H, W, F, e->k11, e->k13, e->k31, e->pcat.p, 2 * F, 0, st);
-    if (r.rc) return r.rc;
     const double rows = (double)g.B * (HW[0] + HW[1] + HW[2]);
-    r.flops += 2.0 * 8.0 * rows * F;
+    if (correlate) {
+        for (int l = 0; l < 3; ++l)
+            if (!e->support_set[l]) { ore_set_error("support prototype for level %d not set", l + 3); return ORE_EINVAL; }
+        // query<->support depthwise correlation, all levels: attn -> channels [0,F) of pcat (q sits in [F,2F))
+        r.rc = sb ? ore_correlation_levels_bf16_fwd(reinterpret_cast<const uint16_t*>(e->pcat.p), 2 * F, F, g.B, 3, H, W, F, e->k11, e->k13, e->k31,
+                                                    reinterpret_cast<uint16_t*>(e->pcat.p), 2 * F, 0, st)
+                  : ore_correlation_levels_fwd(e->pcat.p, 2 * F, F, g.B, 3, H, W, F, e->k11, e->k13, e->k31, e->pcat.p, 2 * F, 0, st);
+        if (r.rc) return r.rc;
+        r.flops += 2.0 * 8.0 * rows * F;
+    }
     r.conv_levels(e->conv3, e->pcat.p, 2 * F, 0, g.B, H, W, e->pos.p, F, 0);            // relu(conv3(cat(attn, q)))
     r.conv_levels(e->tower, e->pos.p, F, 0, g.B, H, W, e->tow.p, F, 0);                 // bbox_tower conv (+bias)
     if (r.rc) return r.rc;
@@ -448,10 +457,9 @@ int run_heads(ore_engine* e, const Geo& g, hipStream_t st, double* flops) {
     return r.rc;
 }
 
-int run_detect(ore_engine* e, const Geo& g, hipStream_t st, int b = 0) {        // image b of the batch
+void detect_desc(ore_engine* e, const Geo& g, int b, ore_detect_desc& d) {   // image b of the batch
     const ore_model_cfg& c = e->cfg;
     const size_t cap = (size_t)3 * c.pre_topk;
-    ore_detect_desc d{};
     d.n_levels = 3; d.head_ld = 8;
     for (int l = 0; l < 3; ++l) {
         d.head[l] = e->head.p + ((size_t)lvl_row0(g, l) + (size_t)b * g.h[l + 3] * g.w[l + 3]) * 8;
@@ -462,11 +470,31 @@ int run_detect(ore_engine* e, const Geo& g, hipStream_t st, int b = 0) {        
     d.pre_level = e->pre_level + b * cap; d.keep_idx = e->keep_idx + b * cap; d.counts = e->counts + b * 4;
     d.out_boxes = e->out_boxes + b * cap * 4; d.out_scores = e->out_scores + b * cap;
     d.workspace = e->det_ws; d.workspace_bytes = e->det_ws_bytes;
+}
+
+int run_detect(ore_engine* e, const Geo& g, hipStream_t st, int b = 0) {        // image b of the batch
+    ore_detect_desc d{};
+    detect_desc(e, g, b, d);
     return ore_detect_fwd(&d, st);
 }
 
-int run_roi(ore_engine* e, const Geo& g, hipStream_t st, double* flops, int b = 0) {   // image b (scratch roi_feat / roi_h / roi_ws is shared: stream order)
+// N-way pass: the K class blocks' proposal tails in one ore_detect_batch_fwd call (each block its own outputs and workspace)
+int run_detect_classes(ore_engine* e, const Geo& g, hipStream_t st, int K) {
+    ore_detect_desc d[ORE_MAX_CLASSES];
+    for (int k = 0; k < K; ++k) {
+        d[k] = ore_detect_desc{};
+        detect_desc(e, g, k, d[k]);
+        if (k > 0) d[k].workspace = e->det_ws_slots + (size_t)(k - 1) * e->det_ws_bytes;
+    }
+    return ore_detect_batch_fwd(d, K, st);
+}
+
+// image b (scratch roi_feat / roi_h / roi_ws is shared: stream order).  class_slot: the N-way pass -- block b = class slot b with that
+// class's composed fc1, detections to det_*#b only (the merge kernel does the postprocess and publishes the count)
+int run_roi(ore_engine* e, const Geo& g, hipStream_t st, double* flops, int b = 0, bool class_slot = false) {
     const ore_model_cfg& c = e->cfg;
+    float* roi_W = class_slot ? e->roi_W_slot[b] : e->roi_W;
+    float* roi_b = class_slot ? e->roi_b_slot[b] : e->roi_b;
     const int F = c.fpn_ch;
     const size_t cap = (size_t)3 * c.pre_topk, rcap = (size_t)e->roi_cap;
     float* out_boxes = e->out_boxes + b * cap * 4;
@@ -484,7 +512,7 @@ int run_roi(ore_engine* e, const Geo& g, hipStream_t st, double* flops, int b = 
     Run r{e, st};
     r.prof = e->profiling;
     Conv fc{};
-    fc.w = e->roi_W; fc.scale = nullptr; fc.shift = e->roi_b; fc.Cin = K; fc.Cout = e->roi_fc; fc.k = 1; fc.stride = 1; fc.pad = 0;
+    fc.w = roi_W; fc.scale = nullptr; fc.shift = roi_b; fc.Cin = K; fc.Cout = e->roi_fc; fc.k = 1; fc.stride = 1; fc.pad = 0;
     fc.relu_cout = e->roi_fc;
     // pre-composed DSA mix + flatten + fc1 (+ bias, ReLU).  The second-stage GEMM stays fp32 in every mode (include/ore_hip.h).
     const int S = e->roi_ksplit;
@@ -494,7 +522,7 @@ int run_roi(ore_engine* e, const Geo& g, hipStream_t st, double* flops, int b = 
         hipEvent_t ea = nullptr, eb = nullptr;
         size_t ia = 0;
         if (r.prof) { ia = e->ev_used; ea = e->next_event(); eb = e->next_event(); if (ea) (void)hipEventRecord(ea, st); }
-        rc = oreconv::conv_gd_splitk(e->roi_feat, K, e->roi_W, e->roi_cap, K, e->roi_fc, e->roi_hp, S, st);
+        rc = oreconv::conv_gd_splitk(e->roi_feat, K, roi_W, e->roi_cap, K, e->roi_fc, e->roi_hp, S, st);
         if (r.prof && ea && eb) { (void)hipEventRecord(eb, st); e->spans.push_back({ia, ia + 1, fl, fl}); }
         if (rc) return rc;
         *flops = fl;
@@ -504,12 +532,12 @@ int run_roi(ore_engine* e, const Geo& g, hipStream_t st, double* flops, int b = 
         if (r.rc) return r.rc;
         *flops = r.flops;
     }
-    return oreroi::roi_predict_post(S > 1 ? e->roi_hp : e->roi_h, e->roi_fc, S > 1 ? S : 0, S > 1 ? e->roi_b : nullptr, e->roi_cls_w, e->roi_cls_b,
+    return oreroi::roi_predict_post(S > 1 ? e->roi_hp : e->roi_h, e->roi_fc, S > 1 ? S : 0, S > 1 ? roi_b : nullptr, e->roi_cls_w, e->roi_cls_b,
                                     e->roi_box_w, e->roi_box_b, out_boxes, counts + 1, 0,
                                     e->roi_cap, e->roi_reg_w, (float)g.H, (float)g.W, e->roi_score_thresh, e->roi_nms_thresh, e->roi_topk,
                                     e->det_boxes + b * rcap * 4, e->det_scores + b * rcap, e->det_src + b * rcap, e->det_count + b * 4,
-                                    e->post, e->fin_boxes_of(b), e->fin_scores_of(b), e->fin_count + b * 4,
-                                    b == 0 ? e->pin_count_dev : nullptr, e->roi_ws, e->roi_ws_bytes, st);
+                                    class_slot ? nullptr : e->post, e->fin_boxes_of(b), e->fin_scores_of(b), e->fin_count + b * 4,
+                                    b == 0 && !class_slot ? e->pin_count_dev : nullptr, e->roi_ws, e->roi_ws_bytes, st);
 }
 
 }  // namespace
@@ -794,6 +822,31 @@ static int check_geo(ore_engine* e, int B, int H, int W) {
     return ORE_OK;
 }
 
+// replay the graph captured for this key, or capture it once on the engine's own stream and replay it on the caller's
+template <typename Body>
+static int replay_or_capture(ore_engine* e, int is_u8, int H, int W, int B, int K, hipStream_t st, Body& body) {
+    for (auto& k : e->graphs)
+        if (k.u8 == is_u8 && k.H == H && k.W == W && k.B == B && k.K == K) {
+            ORE_HIP(hipGraphLaunch(k.exec, st));
+            return ORE_OK;
+        }
+    hipGraph_t graph = nullptr;
+    const bool was_prof = e->profiling;
+    e->profiling = false;
+    ORE_HIP(hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeThreadLocal));
+    int rc = body(e->cap_stream, &e->last_flops);
+    e->profiling = was_prof;
+    hipError_t ce = hipStreamEndCapture(e->cap_stream, &graph);
+    if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
+    if (ce != hipSuccess) { ore_set_error("hipStreamEndCapture -> %s", hipGetErrorString(ce)); return ORE_EHIP; }
+    hipGraphExec_t exec = nullptr;
+    ORE_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+    hipGraphDestroy(graph);
+    e->graphs.push_back({is_u8, H, W, B, K, exec});
+    ORE_HIP(hipGraphLaunch(exec, st));
+    return ORE_OK;
+}
+
 extern "C" int ore_engine_backbone_fwd(ore_engine* e, const void* img, int32_t is_u8, int32_t B, int32_t H, int32_t W, void* stream) {
     int rc = check_geo(e, B, H, W);
     if (rc) return rc;
@@ -809,8 +862,10 @@ extern "C" int ore_engine_eval_fwd(ore_engine* e, const void* img, int32_t is_u8
     return ore_engine_eval_batch_fwd(e, img, is_u8, 1, H, W, use_graph, stream);
 }
 
-extern "C" int ore_engine_detect_begin(ore_engine* e, const void* img, int32_t is_u8, int32_t H, int32_t W, int32_t out_h, int32_t out_w,
-                                       void* out_record, void* stream) {
+static int eval_classes(ore_engine* e, const void* img, int32_t is_u8, int32_t H, int32_t W, int32_t use_graph, hipStream_t st);
+
+static int detect_begin(ore_engine* e, const void* img, int32_t is_u8, int32_t H, int32_t W, int32_t out_h, int32_t out_w, void* out_record,
+                        void* stream, bool classes) {
     ORE_CHECK_ARG(e && e->roi_set && out_record && out_h >= 1 && out_w >= 1, "ore_engine_detect_begin: needs the second stage (ore_engine_set_roi_head)");
     hipStream_t st = (hipStream_t)stream;
     // detector_postprocess parameters: sx = out_w / W, sy = out_h / H evaluated like the reference's Python floats, rounded once to
@@ -831,9 +886,14 @@ extern "C" int ore_engine_detect_begin(ore_engine* e, const void* img, int32_t i
     volatile int32_t* cnt_word = e->pin_count;
     *cnt_word = -1;                                          // sentinel: the last kernel of the graph overwrites it with the count (>= 0)
     __atomic_thread_fence(__ATOMIC_RELEASE);
-    const int rc = ore_engine_eval_batch_fwd(e, img, is_u8, 1, H, W, 1, stream);
+    const int rc = classes ? eval_classes(e, img, is_u8, H, W, 1, st) : ore_engine_eval_batch_fwd(e, img, is_u8, 1, H, W, 1, stream);
     if (rc) *rec_word = 0ull;
     return rc;
+}
+
+extern "C" int ore_engine_detect_begin(ore_engine* e, const void* img, int32_t is_u8, int32_t H, int32_t W, int32_t out_h, int32_t out_w,
+                                       void* out_record, void* stream) {
+    return detect_begin(e, img, is_u8, H, W, out_h, out_w, out_record, stream, false);
 }
 
 extern "C" int ore_engine_detect_end(ore_engine* e, void* stream, int32_t* n_det) {
@@ -897,26 +957,135 @@ extern "C" int ore_engine_eval_batch_fwd(ore_engine* e, const void* img, int32_t
         return r;
     };
     if (!use_graph) return body(st, &e->last_flops);
-    for (auto& k : e->graphs)
-        if (k.u8 == is_u8 && k.H == H && k.W == W && k.B == B) {
-            ORE_HIP(hipGraphLaunch(k.exec, st));
-            return ORE_OK;
+    return replay_or_capture(e, is_u8, H, W, B, 0, st, body);
+}
+
+// N-way pass: backbone + FPN once (one image), the correlation fanned out to the K class blocks, conv3 / tower / head over the K blocks
+// as one batch, the K proposal tails (greedy scans in one launch), the second stage per class with its own composed fc1, the merge.
+static int eval_classes(ore_engine* e, const void* img, int32_t is_u8, int32_t H, int32_t W, int32_t use_graph, hipStream_t st) {
+    ORE_CHECK_ARG(e && e->finalized, "engine not finalized");
+    const int K = e->n_classes;
+    ORE_CHECK_ARG(K >= 1, "N-way pass: no class set (ore_engine_set_classes with n >= 1 first)");
+    for (int k = 0; k < K; ++k) {
+        for (int l = 0; l < 3; ++l)
+            ORE_CHECK_ARG(e->slot_support_set[k][l], "N-way pass: class slot %d has no support prototype for level %d (ore_engine_set_support_slot)", k, l + 3);
+        ORE_CHECK_ARG(!e->roi_set || e->roi_W_slot[k], "N-way pass: class slot %d has no second-stage support (ore_engine_set_roi_support_slot)", k);
+    }
+    int rc = check_geo(e, K, H, W);
+    if (rc) return rc;
+    ORE_CHECK_ARG(img, "null image");
+    const Geo g1 = make_geo(1, H, W), gK = make_geo(K, H, W);
+    e->last = gK;                                        // buffers read back as a K-image batch: block k = class slot k
+    PrecisionScope ps(e->conv_precision);
+    const size_t bytes = (size_t)3 * H * W * (is_u8 ? 1 : 4);
+    ORE_CHECK_ARG(bytes <= e->img_bytes, "image exceeds the engine's input buffer");
+    if (img != e->img_in) ORE_HIP(hipMemcpyAsync(e->img_in, img, bytes, hipMemcpyDefault, st));
+    const int F = e->cfg.fpn_ch;
+    auto body = [&](hipStream_t s, double* fl) -> int {
+        double f1 = 0, f2 = 0, f3 = 0;
+        int r = run_backbone(e, e->img_in, is_u8, g1, s, &f1);
+        // the query (FPN outputs, one image, in the q half of pcat) moves to the tower buffer -- the class blocks are written over the
+        // rows it occupies --, then ONE launch writes [attn_k | query] into every class block k of pcat
+        const int rows1 = lvl_row0(g1, 3);
+        const int Hl[3] = {g1.h[3], g1.h[4], g1.h[5]}, Wl[3] = {g1.w[3], g1.w[4], g1.w[5]};
+        if (!r) r = oremisc::copy_cols(e->pcat.p, 2 * F, F, rows1, F, e->tow.p, F, s);
+        if (!r) r = oremisc::correlation_classes(e->tow.p, F, 0, 3, Hl, Wl, F, K, e->k11s, e->k13s, e->k31s, e->pcat.p, 2 * F, s);
+        f2 += 2.0 * 8.0 * (double)K * rows1 * F;
+        double fh = 0;
+        if (!r) r = run_heads(e, gK, s, &fh, false);
+        f2 += fh;
+        if (!r) r = run_detect_classes(e, gK, s, K);
+        for (int k = 0; k < K && !r && e->roi_set; ++k) {
+            double fb = 0;
+            r = run_roi(e, gK, s, &fb, k, true);
+            f3 += fb;
         }
-    // capture once on the engine's own stream, replay on the caller's
-    hipGraph_t graph = nullptr;
-    const bool was_prof = e->profiling;
-    e->profiling = false;
-    ORE_HIP(hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeThreadLocal));
-    rc = body(e->cap_stream, &e->last_flops);
-    e->profiling = was_prof;
-    hipError_t ce = hipStreamEndCapture(e->cap_stream, &graph);
-    if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
-    if (ce != hipSuccess) { ore_set_error("hipStreamEndCapture -> %s", hipGetErrorString(ce)); return ORE_EHIP; }
-    hipGraphExec_t exec = nullptr;
-    ORE_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    hipGraphDestroy(graph);
-    e->graphs.push_back({is_u8, H, W, B, exec});
-    ORE_HIP(hipGraphLaunch(exec, st));
+        if (!r && e->roi_set)
+            r = oreroi::roi_merge_classes(e->det_boxes, e->det_scores, e->det_count, K, e->roi_cap, e->class_ids, e->roi_topk, e->post,
+                                          e->fin_boxes_of(0), e->fin_scores_of(0), (int64_t*)(e->fin_pack + (size_t)e->roi_cap * 20),
+                                          e->fin_count, e->pin_count_dev, s);
+        *fl = f1 + f2 + f3;
+        return r;
+    };
+    if (!use_graph) return body(st, &e->last_flops);
+    return replay_or_capture(e, is_u8, H, W, 1, K, st, body);
+}
+
+extern "C" int ore_engine_eval_classes_fwd(ore_engine* e, const void* img, int32_t is_u8, int32_t H, int32_t W, int32_t use_graph, void* stream) {
+    return eval_classes(e, img, is_u8, H, W, use_graph, (hipStream_t)stream);
+}
+
+extern "C" int ore_engine_detect_classes_begin(ore_engine* e, const void* img, int32_t is_u8, int32_t H, int32_t W, int32_t out_h, int32_t out_w,
+                                               void* out_record, void* stream) {
+    return detect_begin(e, img, is_u8, H, W, out_h, out_w, out_record, stream, true);
+}
+
+// graphs of N-way passes read the class slots: drop them whenever the class set or a slot changes
+static void drop_class_graphs(ore_engine* e) {
+    std::vector<ore_engine::GraphKey> keep;
+    for (auto& gk : e->graphs) {
+        if (gk.K > 0) (void)hipGraphExecDestroy(gk.exec);
+        else keep.push_back(gk);
+    }
+    e->graphs.swap(keep);
+}
+
+extern "C" int ore_engine_set_classes(ore_engine* e, int32_t n, const int64_t* class_ids_host) {
+    ORE_CHECK_ARG(e, "ore_engine_set_classes: null engine");
+    ORE_CHECK_ARG(n == 0 || !e->sb(), "ore_engine_set_classes: a bf16-storage engine takes one image per pass (max_batch = 1); N-way inference needs "
+                                      "an fp32-storage engine");
+    ORE_CHECK_ARG(n >= 0 && n <= ORE_MAX_CLASSES, "ore_engine_set_classes: %d classes (at most %d)", n, ORE_MAX_CLASSES);
+    ORE_CHECK_ARG(n <= e->cfg.max_batch, "ore_engine_set_classes: %d classes need max_batch >= %d (class slots are batch slots; this engine has "
+                                         "max_batch = %d)", n, n, e->cfg.max_batch);
+    ORE_CHECK_ARG(e->finalized, "ore_engine_set_classes: engine must be finalized");
+    ORE_CHECK_ARG(n == 0 || class_ids_host, "ore_engine_set_classes: null class ids");
+    ORE_HIP(hipSetDevice(e->device));
+    int rc;
+    if (n > 0 && !e->k11s) {
+        const size_t F = (size_t)e->cfg.fpn_ch, S = (size_t)std::min(e->cfg.max_batch, ORE_MAX_CLASSES);
+        if ((rc = e->dalloc(&e->class_ids, ORE_MAX_CLASSES)) || (rc = e->dalloc(&e->k11s, S * 3 * F)) || (rc = e->dalloc(&e->k13s, S * 3 * F * 3)) ||
+            (rc = e->dalloc(&e->k31s, S * 3 * F * 3)))
+            return rc;
+        if (S > 1 && (rc = e->dalloc(&e->det_ws_slots, (S - 1) * e->det_ws_bytes))) return rc;
+        ORE_HIP(hipMemset(e->class_ids, 0, ORE_MAX_CLASSES * sizeof(int64_t)));
+        e->n_slots = (int)S;
+    }
+    if (n > 0) ORE_HIP(hipMemcpy(e->class_ids, class_ids_host, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
+    drop_class_graphs(e);
+    e->n_classes = n;
+    return ORE_OK;
+}
+
+extern "C" int ore_engine_set_support_slot(ore_engine* e, int32_t slot, int32_t level, const float* proto_chw_host, int32_t C, int32_t s) {
+    ORE_CHECK_ARG(e && e->k11s, "ore_engine_set_support_slot: ore_engine_set_classes (n >= 1) first");
+    ORE_CHECK_ARG(slot >= 0 && slot < e->n_slots, "ore_engine_set_support_slot: slot %d outside [0, %d)", slot, e->n_slots);
+    ORE_CHECK_ARG(proto_chw_host && level >= 3 && level <= 5 && C == e->cfg.fpn_ch && s >= 1, "ore_engine_set_support_slot: bad args");
+    ORE_HIP(hipSetDevice(e->device));
+    const int l = level - 3;
+    const size_t kl = (size_t)slot * 3 + l;
+    float* tmp = nullptr;
+    ORE_HIP(hipMalloc((void**)&tmp, (size_t)C * s * s * sizeof(float)));
+    hipError_t err = hipMemcpy(tmp, proto_chw_host, (size_t)C * s * s * sizeof(float), hipMemcpyHostToDevice);
+    int rc = err == hipSuccess ? ore_support_kernels_fwd(tmp, C, s, e->k11s + kl * C, e->k13s + kl * C * 3, e->k31s + kl * C * 3, nullptr) : ORE_EHIP;
+    (void)hipDeviceSynchronize();
+    (void)hipFree(tmp);
+    if (rc) return rc;
+    e->slot_support_set[slot][l] = true;
+    drop_class_graphs(e);
+    return ORE_OK;
+}
+
+extern "C" int ore_engine_set_roi_support_slot(ore_engine* e, int32_t slot, const float* W_host, const float* b_host) {
+    ORE_CHECK_ARG(e && e->roi_set && e->k11s && W_host && b_host,
+                  "ore_engine_set_roi_support_slot: needs ore_engine_set_roi_head and ore_engine_set_classes (n >= 1) first, pointers non-null");
+    ORE_CHECK_ARG(slot >= 0 && slot < e->n_slots, "ore_engine_set_roi_support_slot: slot %d outside [0, %d)", slot, e->n_slots);
+    ORE_HIP(hipSetDevice(e->device));
+    const size_t K = (size_t)e->roi_pooled * e->roi_pooled * e->cfg.fpn_ch, fc = (size_t)e->roi_fc;
+    int rc;
+    if (!e->roi_W_slot[slot] && ((rc = e->dalloc(&e->roi_W_slot[slot], fc * K)) || (rc = e->dalloc(&e->roi_b_slot[slot], fc)))) return rc;
+    ORE_HIP(hipMemcpy(e->roi_W_slot[slot], W_host, fc * K * sizeof(float), hipMemcpyHostToDevice));
+    ORE_HIP(hipMemcpy(e->roi_b_slot[slot], b_host, fc * sizeof(float), hipMemcpyHostToDevice));
+    drop_class_graphs(e);
     return ORE_OK;
 }
 
@@ -1028,6 +1197,7 @@ extern "C" int ore_engine_buffer(ore_engine* e, const char* name, void** ptr, in
         if (base == "final_boxes") return set(e->fin_boxes_of(ib), e->roi_cap, 4, 4, 0);
         if (base == "final_scores") return set(e->fin_scores_of(ib), e->roi_cap, 1, 1, 0);
         if (base == "final_count") return set(e->fin_count + ib * 4, 4, 1, 1, 0);
+        if (base == "final_classes") return set(e->fin_pack + ib * rcap * 28 + rcap * 20, e->roi_cap, 1, 1, 0);   // N-way pass: slot 0
         if (n == "roi_h") return set(e->roi_h, e->roi_cap, e->roi_fc, e->roi_fc, 0);
         // the predictor's per-ROI rows BEFORE the score filter / NMS (row r = proposal r of the image the second stage ran last on)
         const oreroi::PredictWs L = oreroi::predict_ws_layout(e->roi_cap);

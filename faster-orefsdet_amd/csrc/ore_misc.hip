@@ -414,6 +414,79 @@ __global__ __launch_bounds__(256) void k_correlation(CorrP p) {
     st4(reinterpret_cast<TS*>(p.out) + (size_t)row * p.out_ld + p.out_coff + c, res);
 }
 
+// N-way fan-out of the same correlation: ONE query (rows level-major [level][y][x], q_ld / q_coff) against K support-kernel sets.  A
+// thread reads its 3x3 query neighbourhood once and, per class k, writes attn_k to channels [0,C) and the query to [C,2C) of class block
+// k of `out` -- rows [level][k][y][x], the layout of a K-image batch -- so conv3 / the tower / the head / ROIAlign run on the K blocks as
+// on a batch.  Per class the arithmetic is k_correlation's, expression for expression, so block k is bit-identical to a single-class pass.
+// Kernels: k11s [K][L][C], k13s / k31s [K][L][C][3].
+struct CorrClsP {
+    const float* q; int q_ld, q_coff; int C4, nlev, K; CorrLv lv[4]; int out_row0[4]; int rows;
+    const float* k11; const float* k13; const float* k31;
+    float* out; int out_ld;
+};
+
+__global__ __launch_bounds__(256) void k_correlation_classes(CorrClsP p) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= p.rows * p.C4) return;
+    const int c4 = idx % p.C4, row = idx / p.C4;
+    int l = 0;
+#pragma unroll
+    for (int j = 1; j < 4; ++j)
+        if (j < p.nlev && row >= p.lv[j].row0) l = j;
+    const int H = p.lv[l].H, W = p.lv[l].W, HW = H * W;
+    const int rr = row - p.lv[l].row0;
+    const int y = rr / W, x = rr - y * W;
+    const int c = c4 * 4, C = p.C4 * 4;
+    auto Q = [&](int yy, int xx) -> f32x4 {
+        if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W)
+            return ld4(p.q + (size_t)(p.lv[l].row0 + yy * W + xx) * p.q_ld + p.q_coff + c);
+        return f32x4{0.f, 0.f, 0.f, 0.f};
+    };
+    f32x4 qn[3][3];                                      // [dy + 1][dx + 1], zero outside the map
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) qn[dy + 1][dx + 1] = Q(y + dy, x + dx);
+    const f32x4 qc = qn[1][1];
+    float* o = p.out + ((size_t)p.out_row0[l] + rr) * p.out_ld + c;
+    const size_t kstep = (size_t)HW * p.out_ld;          // class block k of level l starts k * H * W rows further
+    for (int k = 0; k < p.K; ++k, o += kstep) {
+        const int kl = k * p.nlev + l;
+        const float* k11 = p.k11 + (size_t)kl * C;
+        const float* k13 = p.k13 + (size_t)kl * C * 3;
+        const float* k31 = p.k31 + (size_t)kl * C * 3;
+        const f32x4 w11 = *reinterpret_cast<const f32x4*>(k11 + c);
+        f32x4 w13[3], w31[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            w13[j] = f32x4{k13[(c + 0) * 3 + j], k13[(c + 1) * 3 + j], k13[(c + 2) * 3 + j], k13[(c + 3) * 3 + j]};
+            w31[j] = f32x4{k31[(c + 0) * 3 + j], k31[(c + 1) * 3 + j], k31[(c + 2) * 3 + j], k31[(c + 3) * 3 + j]};
+        }
+        const f32x4 a = relu4(w11 * relu4(w11 * qc));
+        f32x4 bacc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy) {
+            const int yy = y + dy;
+            if ((unsigned)yy < (unsigned)H) {
+                const f32x4 t = relu4(w13[0] * qn[dy + 1][0] + w13[1] * qn[dy + 1][1] + w13[2] * qn[dy + 1][2]);
+                bacc += w31[dy + 1] * t;
+            }
+        }
+        const f32x4 res = a + relu4(bacc) + qc;
+        st4(o, res);
+        st4(o + C, qc);
+    }
+}
+
+// plain copy of a channel slice of `rows` rows (the query of an N-way pass moves out of the buffer the class blocks are written into)
+__global__ __launch_bounds__(256) void k_copy_cols(const float* __restrict__ src, int src_ld, int src_coff, int rows, int C4,
+                                                   float* __restrict__ dst, int dst_ld) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= rows * C4) return;
+    const int c = (idx % C4) * 4, r = idx / C4;
+    st4(dst + (size_t)r * dst_ld + c, ld4(src + (size_t)r * src_ld + src_coff + c));
+}
+
 // support prototype [C][s][s] -> adaptive avg pools (1,1), (1,3), (3,1); one block per channel.
 __global__ __launch_bounds__(64) void k_support_kernels(const float* __restrict__ proto, int s, float* __restrict__ k11,
                                                         float* __restrict__ k13, float* __restrict__ k31) {
@@ -1109,4 +1182,30 @@ extern "C" int ore_groupnorm_affine_fwd(const float* x, int32_t ld, int32_t coff
                       256 % C == 0, "ore_groupnorm_affine_fwd: bad args (need C | 256, groups <= 64)");
     const int32_t hw1[1] = {HW};
     return ore_groupnorm_affine_levels_fwd(x, ld, coff, B, 1, hw1, C, groups, eps, gamma, beta, mul, add, workspace, stream);
+}
+
+// N-way pass (ore_engine_detect_classes_begin): the query of ONE image, rows level-major in q, against K support-kernel sets; class block k
+// of every level lands where image k of a K-image batch would (out rows [level][k][y][x], ld out_ld, attn | query).
+int oremisc::correlation_classes(const float* q, int32_t q_ld, int32_t q_coff, int32_t n_levels, const int32_t* H, const int32_t* W,
+                                 int32_t C, int32_t K, const float* k11s, const float* k13s, const float* k31s, float* out, int32_t out_ld,
+                                 void* stream) {
+    ORE_CHECK_ARG(q && k11s && k13s && k31s && out && H && W && n_levels >= 1 && n_levels <= 4 && K >= 1 && K <= 16,
+                  "correlation_classes: bad args");
+    ORE_CHECK_ARG(C % 4 == 0 && q_ld % 4 == 0 && q_coff % 4 == 0 && out_ld % 4 == 0 && out_ld >= 2 * C, "correlation_classes: alignment");
+    CorrClsP p{};
+    p.q = q; p.q_ld = q_ld; p.q_coff = q_coff; p.C4 = C / 4; p.nlev = n_levels; p.K = K;
+    int rows = 0;
+    for (int l = 0; l < n_levels; ++l) { p.lv[l] = {rows, H[l], W[l]}; p.out_row0[l] = K * rows; rows += H[l] * W[l]; }
+    p.rows = rows;
+    p.k11 = k11s; p.k13 = k13s; p.k31 = k31s; p.out = out; p.out_ld = out_ld;
+    hipLaunchKernelGGL(k_correlation_classes, dim3(ceil_div(p.rows * p.C4, 256)), dim3(256), 0, (hipStream_t)stream, p);
+    return ore_launch_status("k_correlation_classes");
+}
+
+int oremisc::copy_cols(const float* src, int32_t src_ld, int32_t src_coff, int32_t rows, int32_t C, float* dst, int32_t dst_ld, void* stream) {
+    ORE_CHECK_ARG(src && dst && rows >= 0 && C % 4 == 0 && src_ld % 4 == 0 && src_coff % 4 == 0 && dst_ld % 4 == 0, "copy_cols: bad args");
+    if (rows == 0) return ORE_OK;
+    hipLaunchKernelGGL(k_copy_cols, dim3(ceil_div(rows * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, src, src_ld, src_coff, rows, C / 4,
+                       dst, dst_ld);
+    return ore_launch_status("k_copy_cols");
 }

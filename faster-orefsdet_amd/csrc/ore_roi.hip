@@ -1042,6 +1042,122 @@ __global__ __launch_bounds__(T) void k_roi_tail(TailP p) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// N-way merge (ore_engine_detect_classes_begin): ONE block over the K per-class detection lists that k_roi_tail left in det_* (class slot
+// k at k * cap rows, each list score-descending).  Every row's place in the union is its stable descending rank -- score first, then
+// the row's index in the concatenation slot 0 | slot 1 | ..., i.e. class slot, then row order within the class --, counted like
+// k_roi_tail's sort; rows ranked below min(topk, cap) are kept.  Because each class went through its own NMS and top-k, this equals
+// FewX's class-aware batched_nms followed by top-k over all classes (d2z:modeling/roi_heads/fast_rcnn.py:118-171 with one score column
+// per support class): boxes of different classes never suppress each other, so the per-class survivors are the class-aware survivors,
+// and the global top-k of the union is the same set in the same order.  Then detector_postprocess with k_roi_tail's arithmetic, the
+// caller's record (class ids instead of 0) and, LAST, the pinned count word.
+constexpr int MERGE_MAX_CLASSES = 16;
+constexpr int MERGE_MAX_ROWS = MERGE_MAX_CLASSES * ROI_FUSED_CAP;
+
+struct MergeP {
+    const float* det_boxes; const float* det_scores; const int* det_count; int K, cap; const long long* class_ids; int topk;
+    const float* post; float* fin_boxes; float* fin_scores; long long* fin_classes; int* fin_count; int* host_count;
+};
+
+template <int T>
+__global__ __launch_bounds__(T) void k_roi_merge_classes(MergeP p) {
+    unsigned long long rec_early = 0ull;                 // the record address: a PCIe round trip, issued first (as in k_roi_tail)
+    if (p.host_count)
+        rec_early = __hip_atomic_load(reinterpret_cast<unsigned long long*>(p.host_count) + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __shared__ float sc[MERGE_MAX_ROWS];                                     // scores of the concatenation
+    __shared__ __attribute__((aligned(16))) float sel_b[ROI_FUSED_CAP * 4];  // kept rows in merged order
+    __shared__ float sel_s[ROI_FUSED_CAP];
+    __shared__ int sel_k[ROI_FUSED_CAP];
+    __shared__ int off[MERGE_MAX_CLASSES + 1];
+    __shared__ int wsum[T / 64];
+    constexpr int NW = T / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) {
+        int o = 0;
+        for (int k = 0; k < p.K; ++k) { off[k] = o; o += min(max(p.det_count[k * 4], 0), p.cap); }
+        off[p.K] = o;
+    }
+    __syncthreads();
+    const int m = off[p.K];
+    auto slot_of = [&](int i) { int k = 0; for (int j = 1; j < p.K; ++j) if (i >= off[j]) k = j; return k; };
+    for (int i = tid; i < m; i += T) { const int k = slot_of(i); sc[i] = p.det_scores[(size_t)k * p.cap + (i - off[k])]; }
+    __syncthreads();
+    int nsel = min(m, p.cap);
+    if (p.topk >= 0 && nsel > p.topk) nsel = p.topk;
+    // stable descending rank: 4 lanes per row
+    for (int e0 = 0; e0 < m; e0 += T / 4) {
+        const int e = e0 + (tid >> 2), sub = tid & 3;
+        const bool valid = e < m;
+        const float se = valid ? sc[e] : 0.f;
+        int c = 0;
+        if (valid)
+            for (int f = sub; f < m; f += 4) {
+                const float sf = sc[f];
+                c += (sf > se || (sf == se && f < e)) ? 1 : 0;
+            }
+        c += __shfl_xor(c, 1);
+        c += __shfl_xor(c, 2);
+        if (valid && sub == 0 && c < nsel) {
+            const int k = slot_of(e);
+            *reinterpret_cast<f32x4*>(sel_b + c * 4) = *reinterpret_cast<const f32x4*>(p.det_boxes + ((size_t)k * p.cap + (e - off[k])) * 4);
+            sel_s[c] = se;
+            sel_k[c] = k;
+        }
+    }
+    __syncthreads();
+    // detector_postprocess (d2z:modeling/postprocessing.py:10-75), k_roi_tail's arithmetic: scale, clip, drop empty boxes, order kept
+    const float sx = p.post[0], sy = p.post[1], ow = p.post[2], oh = p.post[3];
+    char* rec = reinterpret_cast<char*>(rec_early);
+    float* rec_boxes = reinterpret_cast<float*>(rec);
+    float* rec_scores = rec ? reinterpret_cast<float*>(rec + (size_t)p.cap * 16) : nullptr;
+    long long* rec_cls = rec ? reinterpret_cast<long long*>(rec + (size_t)p.cap * 20) : nullptr;
+    int fbase = 0;
+    for (int i0 = 0; i0 < nsel; i0 += T) {
+        const int i = i0 + tid;
+        int ok = 0;
+        f32x4 b = {0.f, 0.f, 0.f, 0.f};
+        float s = 0.f;
+        long long cls = 0;
+        if (i < nsel) {
+            b = *reinterpret_cast<const f32x4*>(sel_b + i * 4);
+            s = sel_s[i];
+            cls = p.class_ids[sel_k[i]];
+            b.x = b.x * sx; b.z = b.z * sx; b.y = b.y * sy; b.w = b.w * sy;
+            b.x = fminf(fmaxf(b.x, 0.f), ow); b.z = fminf(fmaxf(b.z, 0.f), ow);
+            b.y = fminf(fmaxf(b.y, 0.f), oh); b.w = fminf(fmaxf(b.w, 0.f), oh);
+            ok = ((b.z - b.x) > 0.f && (b.w - b.y) > 0.f) ? 1 : 0;
+        }
+        int inc = ok;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(inc, d); if (lane >= d) inc += t; }
+        __syncthreads();
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        int pre = fbase, tot = 0;
+        for (int w2 = 0; w2 < NW; ++w2) { const int s2 = wsum[w2]; if (w2 < wave) pre += s2; tot += s2; }
+        if (ok) {
+            const int pos = pre + inc - 1;
+            *reinterpret_cast<f32x4*>(p.fin_boxes + (size_t)pos * 4) = b;
+            p.fin_scores[pos] = s;
+            p.fin_classes[pos] = cls;
+            if (rec) {
+                *reinterpret_cast<f32x4*>(rec_boxes + (size_t)pos * 4) = b;
+                rec_scores[pos] = s;
+                rec_cls[pos] = cls;
+            }
+        }
+        fbase += tot;
+    }
+    __syncthreads();                                     // every result store is issued before the count is published
+    if (tid == 0) {
+        *p.fin_count = fbase;
+        if (p.host_count) {
+            __threadfence_system();
+            *p.host_count = fbase;                       // pinned, device-mapped host word, this kernel's last store: the caller polls it
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int ore_nms_device_n_fwd(const float* boxes, const float* scores, const int32_t* n_dev, int32_t cap, float thr,
@@ -1274,4 +1390,19 @@ extern "C" int ore_roi_align_bwd_tiled(float* const* dfeat, const int32_t* ld, c
     if (pooled <= 8) hipLaunchKernelGGL(k_roi_align_bwd_tile<8>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, tp);
     else hipLaunchKernelGGL(k_roi_align_bwd_tile<ROI_PMAX>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, tp);
     return ore_launch_status("k_roi_align_bwd_tile");
+}
+
+int oreroi::roi_merge_classes(const float* det_boxes, const float* det_scores, const int32_t* det_count, int32_t K, int32_t cap,
+                              const int64_t* class_ids, int32_t topk, const float* post_dev, float* fin_boxes, float* fin_scores,
+                              int64_t* fin_classes, int32_t* fin_count, int32_t* host_count, void* stream) {
+    ORE_CHECK_ARG(det_boxes && det_scores && det_count && class_ids && post_dev && fin_boxes && fin_scores && fin_classes && fin_count,
+                  "roi_merge_classes: null pointer");
+    ORE_CHECK_ARG(K >= 1 && K <= MERGE_MAX_CLASSES && cap >= 1 && cap <= ROI_FUSED_CAP,
+                  "roi_merge_classes: %d classes of %d rows (at most %d classes of %d rows)", K, cap, MERGE_MAX_CLASSES, ROI_FUSED_CAP);
+    MergeP p{};
+    p.det_boxes = det_boxes; p.det_scores = det_scores; p.det_count = det_count; p.K = K; p.cap = cap;
+    p.class_ids = (const long long*)class_ids; p.topk = topk; p.post = post_dev;
+    p.fin_boxes = fin_boxes; p.fin_scores = fin_scores; p.fin_classes = (long long*)fin_classes; p.fin_count = fin_count; p.host_count = host_count;
+    hipLaunchKernelGGL(k_roi_merge_classes<1024>, dim3(1), dim3(1024), 0, (hipStream_t)stream, p);
+    return ore_launch_status("k_roi_merge_classes");
 }

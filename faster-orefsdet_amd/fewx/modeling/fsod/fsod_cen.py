@@ -24,6 +24,37 @@ from .fsod_roi_heads import build_roi_heads
 from .fsod_rpn import make_proposals
 
 _TENSOR_VERSION = operator.attrgetter("_version")
+_MAX_CLASSES = 16                                     # ORE_MAX_CLASSES (include/ore_hip.h)
+
+
+def resolve_support_classes(support_dict, selection):
+    """The support classes an N-way forward answers for, in slot order (CenterNet2Detector.support_classes):
+    None -> None (the reference's path: the last class only); "all" -> every class of support_dict in insertion order
+    (the reference's `.items()` loops); a list of ids -> those classes in that order.  Every selected class needs p3 / p4 / p5 prototypes
+    and rcnn_8 features; an unknown id, a class without rcnn_8, a repeated id or an empty / too long selection raises ValueError."""
+    if selection is None:
+        return None
+    if support_dict is None:
+        raise ValueError("support_classes is set but no support prototypes are loaded (init_model / set_support_dict)")
+    if isinstance(selection, str):
+        if selection != "all":
+            raise ValueError(f"support_classes must be None, 'all' or a list of class ids, not {selection!r}")
+        ids = list(support_dict.get("p3", {}).keys())
+    else:
+        ids = list(selection)
+    if not ids:
+        raise ValueError("support_classes selects no class")
+    if len(ids) > _MAX_CLASSES:
+        raise ValueError(f"support_classes selects {len(ids)} classes; one N-way pass covers at most {_MAX_CLASSES}")
+    if len(set(ids)) != len(ids):
+        raise ValueError(f"support_classes repeats a class id: {ids}")
+    for c in ids:
+        for k in ("p3", "p4", "p5"):
+            if c not in support_dict.get(k, {}):
+                raise ValueError(f"support class {c!r} has no {k} prototype in the support set (classes: {list(support_dict.get('p3', {}))})")
+        if c not in support_dict.get("rcnn_8", {}):
+            raise ValueError(f"support class {c!r} has no rcnn_8 support features: N-way inference needs the second stage of every class")
+    return ids
 
 
 class MLP(nn.Module):
@@ -132,6 +163,10 @@ class CenterNet2Detector(nn.Module):
         # "fp32" (the reference's precision) or "bf16": operand precision of the MFMA convs of the EVAL engines this detector
         # builds (orehip.set_conv_precision / include/ore_hip.h ORE_CONV_BF16 -- BASELINE configs[4]); set it before the first forward
         self.conv_operands = "fp32"
+        # N-way inference (include/ore_hip.h, ore_engine_set_classes): None = the reference's path (only the last support class is
+        # detected, pred_classes all 0); "all" = every class of support_dict; a list of class ids = those classes in that order.  One
+        # pass then detects every selected class (pred_classes = class ids).  Not a config key: the config tree is the reference's.
+        self.support_classes = None
         self._engine = None
         self._engine_key = None
         self.max_hw = (int(cfg.INPUT.MAX_SIZE_TEST), int(cfg.INPUT.MAX_SIZE_TEST))
@@ -262,10 +297,13 @@ class CenterNet2Detector(nn.Module):
         self._invalidate_state_key()
         return out
 
-    def make_engine(self, max_batch: int = 1):
+    def make_engine(self, max_batch: int = 1, classes=None):
         """A fresh engine (own buffers, own hipGraph) for the current parameters and support set.  `engine()` caches one; a server
         that keeps several images in flight on separate streams makes one per stream (bench.py --inflight), or folds concurrent
-        requests into one pass with max_batch > 1 (Engine.eval_forward_batch)."""
+        requests into one pass with max_batch > 1 (Engine.eval_forward_batch).  classes = a resolved support_classes selection: the
+        engine also gets one class slot per selected class (Engine.set_classes / detect_classes), max_batch >= len(classes)."""
+        if classes:
+            max_batch = max(max_batch, len(classes))
         import orehip
         from detectron2.modeling.backbone.vovnet import _STAGE_SPECS
         c = self._cfg_engine
@@ -291,17 +329,27 @@ class CenterNet2Detector(nn.Module):
         if "rcnn_8" in self.support_dict and hasattr(rh, "bbox_reg_weights"):
             e.set_roi_head(self.state_dict(), self.support_dict["rcnn_8"][cls_id], rh.bbox_reg_weights, rh.test_score_thresh,
                            rh.test_nms_thresh, rh.test_topk)
+        if classes:
+            sd = self.state_dict()
+            e.set_classes(classes)
+            for k, c in enumerate(classes):
+                e.set_support({lv: self.support_dict[lv][c] for lv in ("p3", "p4", "p5")}, slot=k)
+                e.set_roi_support(sd, self.support_dict["rcnn_8"][c], slot=k)
         return e
 
+    def _support_selection(self):
+        sel = resolve_support_classes(self.support_dict, self.support_classes) if self.support_classes is not None else None
+        return tuple(sel) if sel is not None else None
+
     def _engine_key_now(self):
-        return (self._state_key(), str(self.device), self.conv_operands)
+        return (self._state_key(), str(self.device), self.conv_operands, self._support_selection())
 
     def engine(self):
         key = self._engine_key_now()
         if self._engine is None or self._engine_key != key:
             if self._engine is not None:
                 self._engine.close()
-            self._engine, self._engine_key = self.make_engine(), key
+            self._engine, self._engine_key = self.make_engine(classes=key[3]), key
         return self._engine
 
     # ---- forward ------------------------------------------------------------------------------------------------
@@ -357,7 +405,8 @@ class CenterNet2Detector(nn.Module):
             oh, ow = int(inp.get("height", H)), int(inp.get("width", W))
             import orehip
             try:
-                rec = e.detect_begin(img, oh, ow)                 # a fresh tensor, filled behind the graph
+                # a fresh tensor, filled behind the graph (N-way engines: every selected class in the same pass)
+                rec = e.detect_classes_begin(img, oh, ow) if getattr(e, "class_ids", None) else e.detect_begin(img, oh, ow)
             except orehip.OreError:
                 rec = None                                        # e.g. the cached engine belongs to another device / size: the checked path below decides
             if rec is None:
@@ -373,7 +422,7 @@ class CenterNet2Detector(nn.Module):
             boxes, scores, classes = e.detect_end(rec)
             if not fresh:
                 e = self.engine()                                 # rebuilds
-                boxes, scores, classes = e.detect(img, oh, ow)
+                boxes, scores, classes = e.detect_classes(img, oh, ow) if getattr(e, "class_ids", None) else e.detect(img, oh, ow)
             # three views of one record cut at the same count by detect_end: [k, 4] fp32, [k] fp32, [k] int64 -- what Boxes() and
             # Instances.set() would check again, per image, on the protocol's critical path
             bx.tensor = boxes
@@ -385,6 +434,21 @@ class CenterNet2Detector(nn.Module):
         """The eval call with the engine validated BEFORE it is used (first call, stale engine, other entry conditions)."""
         batched_inputs = [inp]
         e = self.engine()
+        if getattr(e, "class_ids", None):
+            # N-way: both stages of every selected class, the merge and detector_postprocess in one replay; without do_postprocess the
+            # output size is the input size (scale 1: clip to the image, drop empty boxes)
+            from detectron2.structures import Boxes, Instances
+            if img.dtype != torch.uint8 and img.dtype != torch.float32:
+                img = img.float()
+            img = img.contiguous()
+            H, W = img.shape[-2:]
+            oh, ow = (int(inp.get("height", H)), int(inp.get("width", W))) if do_postprocess else (int(H), int(W))
+            boxes, scores, classes = e.detect_classes(img, oh, ow)
+            res = Instances((oh, ow))
+            res.pred_boxes = Boxes(boxes)
+            res.scores = scores
+            res.pred_classes = classes
+            return [{"instances": res}] if do_postprocess else [res]
         if do_postprocess and getattr(e, "has_roi", False):
             from detectron2.structures import Boxes, Instances
             if img.dtype != torch.uint8 and img.dtype != torch.float32:
@@ -428,10 +492,13 @@ class CenterNet2Detector(nn.Module):
         """Serving entry point beside the reference's one-image `inference`: `requests` is a list of single-image inputs (the dicts
         the reference passes one at a time).  Requests of equal image size and dtype are folded, up to `max_fold` per engine pass
         (Engine.eval_forward_batch: dense stages batched, detection tail and second stage per image); results come back in request
-        order and equal the one-at-a-time results (tests/test_hip_parity.py)."""
+        order and equal the one-at-a-time results (tests/test_hip_parity.py).  With support_classes set (N-way inference) the requests
+        are answered one image at a time, each by the one-pass N-way call of `inference`: a pass holds one query image and its classes."""
         from detectron2.structures import Boxes, Instances
         assert not self.training
         self.init_model()
+        if self.support_classes is not None:
+            return [self.inference([r], do_postprocess=do_postprocess)[0] for r in requests]
         key = (self._state_key(), str(self.device), self.conv_operands, max_fold)
         if getattr(self, "_fold_engine_key", None) != key:
             if getattr(self, "_fold_engine", None) is not None:

@@ -73,6 +73,8 @@ SYMBOLS = ["ore_last_error", "ore_version", "ore_flop_counter_read", "ore_engine
            "ore_conv_set_precision", "ore_conv_get_precision", "ore_conv2d_wgrad_fwd", "ore_conv2d_wgrad_bias_fwd", "ore_granule_transpose_fwd", "ore_combine2_fwd", "ore_combine2_bwd", "ore_adaptive_avgpool_nhwc_fwd", "ore_adaptive_avgpool_nhwc_bwd", "ore_group_mean_fwd", "ore_group_mean_bwd", "ore_relu_affine_bwd", "ore_colsum_fwd", "ore_colsum_segments_fwd", "ore_correlation_train_fwd", "ore_correlation_train_bwd",
            "ore_groupnorm_apply_fwd", "ore_groupnorm_bwd", "ore_prod_colsum_fwd", "ore_scale_add_channels_fwd", "ore_maxpool3x3s2_bwd", "ore_sumpool2x2_fwd", "ore_engine_create", "ore_engine_destroy", "ore_engine_set_tensor",
            "ore_engine_set_support", "ore_engine_finalize", "ore_engine_set_roi_head", "ore_engine_backbone_fwd", "ore_engine_eval_fwd", "ore_engine_eval_batch_fwd", "ore_engine_detect_fwd", "ore_engine_detect_begin", "ore_engine_detect_end", "ore_roi_predict_post_fwd",
+           "ore_engine_set_classes", "ore_engine_set_support_slot", "ore_engine_set_roi_support_slot", "ore_engine_detect_classes_begin",
+           "ore_engine_eval_classes_fwd",
            "ore_engine_buffer", "ore_engine_last_flops", "ore_engine_set_profiling", "ore_engine_read_profile", "ore_event_pair_overhead_us",
            "ore_rccl_load", "ore_rccl_unique_id", "ore_rccl_comm_create", "ore_rccl_comm_destroy", "ore_allreduce_grads"]
 
@@ -1243,13 +1245,33 @@ class Engine:
             _chk(lib().ore_engine_set_tensor(self._h, k.encode(), C.c_void_p(t.data_ptr()), shape, t.dim()),
                  f"ore_engine_set_tensor({k})")
 
-    def set_support(self, protos: Dict[str, torch.Tensor]) -> None:
-        """{'p3': [1,C,32,32], 'p4': [1,C,16,16], 'p5': [1,C,8,8]} -- support_feature.pkl prototypes."""
+    def set_support(self, protos: Dict[str, torch.Tensor], slot: Optional[int] = None) -> None:
+        """{'p3': [1,C,32,32], 'p4': [1,C,16,16], 'p5': [1,C,8,8]} -- support_feature.pkl prototypes.  slot=k: the prototypes of N-way
+        class slot k instead (ore_engine_set_support_slot; after finalize() and set_classes())."""
         for lvl in (3, 4, 5):
             t = protos[f"p{lvl}"].detach().float().cpu().contiguous()
             t = t.reshape(t.shape[-3], t.shape[-2], t.shape[-1])
-            _chk(lib().ore_engine_set_support(self._h, lvl, C.c_void_p(t.data_ptr()), t.shape[0], t.shape[1]),
-                 "ore_engine_set_support")
+            if slot is None:
+                _chk(lib().ore_engine_set_support(self._h, lvl, C.c_void_p(t.data_ptr()), t.shape[0], t.shape[1]),
+                     "ore_engine_set_support")
+            else:
+                _chk(lib().ore_engine_set_support_slot(self._h, int(slot), lvl, C.c_void_p(t.data_ptr()), t.shape[0], t.shape[1]),
+                     "ore_engine_set_support_slot")
+
+    def set_classes(self, ids: Sequence[int]) -> None:
+        """N-way inference (include/ore_hip.h): class slot k answers for support class ids[k]; len(ids) <= max_batch and <= 16.  [] turns
+        it off.  Each slot then needs set_support(..., slot=k) and, with a second stage, set_roi_support(..., slot=k)."""
+        ids = [int(i) for i in ids]
+        arr = (C.c_int64 * max(len(ids), 1))(*ids)
+        _chk(lib().ore_engine_set_classes(self._h, len(ids), arr), "ore_engine_set_classes")
+        self.class_ids = ids
+
+    def set_roi_support(self, sd, support_8: torch.Tensor, slot: int, prefix: str = "roi_heads.") -> None:
+        """The second stage of N-way class slot `slot`: DSA-mix + flatten + fc1 composed with that class's rcnn_8 support features
+        (compose_roi_head), after set_roi_head() and set_classes()."""
+        Wp, bp = compose_roi_head(sd, support_8, prefix)
+        _chk(lib().ore_engine_set_roi_support_slot(self._h, int(slot), C.c_void_p(Wp.data_ptr()), C.c_void_p(bp.data_ptr())),
+             "ore_engine_set_roi_support_slot")
 
     def finalize(self) -> None:
         _chk(lib().ore_engine_finalize(self._h), "ore_engine_finalize")
@@ -1302,6 +1324,29 @@ class Engine:
                                            C.c_void_p(rec.data_ptr()), _stream()), "ore_engine_detect_begin")
         return rec
 
+    def detect_classes_begin(self, img: torch.Tensor, out_h: int, out_w: int) -> torch.Tensor:
+        """detect_begin for the N-way pass (ore_engine_detect_classes_begin); end it with detect_end."""
+        assert img.is_contiguous() and img.dim() == 3
+        _, H, W = img.shape
+        R = self.__dict__.get("_rec_rows") or self.__dict__.setdefault("_rec_rows", int(lib().ore_det_record_rows()))
+        rec = torch.empty(R * 7, dtype=torch.float32, device=self.device)
+        _chk(lib().ore_engine_detect_classes_begin(self._h, C.c_void_p(img.data_ptr()), int(img.dtype == torch.uint8), H, W, int(out_h),
+                                                   int(out_w), C.c_void_p(rec.data_ptr()), _stream()), "ore_engine_detect_classes_begin")
+        return rec
+
+    def detect_classes(self, img: torch.Tensor, out_h: int, out_w: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """`detect` over every class of set_classes() in ONE pass: per class both stages with that class's supports, then the merge
+        (score descending, ties by class slot then row, top-k) and detector_postprocess.  Returns (boxes [n,4], scores [n], class ids [n])."""
+        return self.detect_end(self.detect_classes_begin(img, out_h, out_w))
+
+    def eval_classes_forward(self, img: torch.Tensor, use_graph: bool = True) -> None:
+        """The N-way pass without a result record: class slot k's results are .proposals(k) / .detections(k) / .buffer("name#k"), the
+        dense buffers read back as a K-image batch (block k = slot k)."""
+        assert img.is_cuda and img.is_contiguous() and img.dim() == 3
+        _, H, W = img.shape
+        _chk(lib().ore_engine_eval_classes_fwd(self._h, C.c_void_p(img.data_ptr()), int(img.dtype == torch.uint8), H, W, int(use_graph),
+                                               _stream()), "ore_engine_eval_classes_fwd")
+
     def detect_end(self, rec: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Second half: wait for the count (ore_engine_detect_end) and cut the record into (boxes [n,4], scores [n], classes [n] int64)."""
         n = C.c_int32(0)
@@ -1347,7 +1392,8 @@ class Engine:
         _chk(lib().ore_engine_buffer(self._h, name.encode(), C.byref(p), dims), f"ore_engine_buffer({name})")
         rows, ch, ld, coff = (int(x) for x in dims)
         dt = {"pre_loc": torch.int64, "keep_idx": torch.int64, "pre_level": torch.int32, "counts": torch.int32, "det_src": torch.int64,
-              "det_count": torch.int32, "roi_ok": torch.int32}.get(name.split("#")[0], torch.float32)
+              "det_count": torch.int32, "roi_ok": torch.int32,
+              "final_classes": torch.int64}.get(name.split("#")[0], torch.float32)
         if lib().ore_engine_buffer_is_bf16(self._h, name.encode()):
             dt = torch.bfloat16                               # activation buffers of a bf16-storage engine
         flat = _from_ptr(p.value, rows * ld, dt, self.device)

@@ -591,6 +591,31 @@ int ore_engine_detect_end(ore_engine* e, void* stream, int32_t* n_det);
  * image b's results are the buffers "out_boxes#b", "counts#b", "det_boxes#b", ... ("#0" may be omitted). */
 int ore_engine_eval_batch_fwd(ore_engine* e, const void* img, int32_t img_is_u8, int32_t B, int32_t H, int32_t W, int32_t use_graph,
                               void* stream);
+/* N-way inference: ONE query image against K support classes in one pass (FewX's per-class loop, ref:fewx/modeling/fsod/fsod_rcnn.py:445-512
+ * and ref:fewx/modeling/fsod/fsod_roi_heads.py:144-191; the CenterNet2 variant keeps only the last class).  Class slot k
+ * lives where image k of a batch would, so K <= cfg.max_batch.  The pass: backbone + FPN once; the depthwise correlation fanned out to the
+ * K class blocks in one launch (per class bit-identical to the single-class correlation); conv3, tower and head over the K blocks as one
+ * batch; the K proposal tails through ore_detect_batch_fwd; per class the second stage with that class's composed fc1 (score filter, NMS,
+ * top-k -> "det_boxes#k" / "det_scores#k" / "det_count#k"); then ONE merge kernel: the union of the K lists ordered by score descending,
+ * ties by class slot, then by row within the class, cut at the set_roi_head topk (= FewX's class-aware batched_nms + top-k, since
+ * per-class NMS is independent), detector_postprocess as in ore_engine_detect_fwd, classes = the class ids.  Every existing entry point
+ * behaves as before when ore_engine_set_classes was never called (or n = 0).
+ *   ore_engine_set_classes: n <= min(max_batch, ORE_MAX_CLASSES) class ids (host, int64), slot k <- class_ids_host[k]; n = 0 = off.  Needs a
+ *     finalized fp32-storage engine (a bf16-storage engine is refused).  The first call with n >= 1 allocates the slot tables.
+ *   ore_engine_set_support_slot: ore_engine_set_support for class slot `slot` (after ore_engine_set_classes).
+ *   ore_engine_set_roi_support_slot: the composed DSA-mix + fc1 (W_host [fc_dim][pooled*pooled*fpn_ch], b_host [fc_dim], the output of
+ *     orehip.compose_roi_head for that class's rcnn_8 features) of class slot `slot` (after ore_engine_set_roi_head and _set_classes).
+ *   ore_engine_detect_classes_begin: ore_engine_detect_begin for the N-way pass (ended by ore_engine_detect_end); the record's classes
+ *     are the class ids.  The merged rows are also in "final_boxes" / "final_scores" / "final_classes" / "final_count" (slot 0).
+ *   ore_engine_eval_classes_fwd: the same pass without a record (use_graph as ore_engine_eval_fwd); buffers read back as a K-image batch.
+ * A pass with a slot left unset is refused.  Changing the class set or a slot drops the captured N-way graphs (their key holds K). */
+#define ORE_MAX_CLASSES 16
+int ore_engine_set_classes(ore_engine* e, int32_t n, const int64_t* class_ids_host);
+int ore_engine_set_support_slot(ore_engine* e, int32_t slot, int32_t level, const float* proto_chw_host, int32_t C, int32_t s);
+int ore_engine_set_roi_support_slot(ore_engine* e, int32_t slot, const float* W_host, const float* b_host);
+int ore_engine_detect_classes_begin(ore_engine* e, const void* img, int32_t img_is_u8, int32_t H, int32_t W, int32_t out_h, int32_t out_w,
+                                    void* out_record, void* stream);
+int ore_engine_eval_classes_fwd(ore_engine* e, const void* img, int32_t img_is_u8, int32_t H, int32_t W, int32_t use_graph, void* stream);
 /* Named device buffers: "p3","p4","p5" (NHWC, ld=2*fpn_ch, coff=fpn_ch), "pos3".."pos5", "head3".."head5",
  * "pre_boxes","pre_scores","pre_loc","keep_idx","counts","out_boxes","out_scores", "stage2".."stage5", ...
  * Returns device pointer and fills dims[0..3] = {rows(H*W*B), channels, ld, coff}. */

@@ -8,6 +8,7 @@
 void ore_set_error(const char* fmt, ...);
 void ore_note_wino(int v);
 int ore_last_wino(void);                // 1: this thread's last ore_conv2d_fwd / _levels_fwd call ran on the Winograd kernel
+void ore_note_launch(int code, int split);   // the launcher (ORE_LAUNCH_*) and split-K of that call (ore_conv_last_launch)
 void ore_flop_count_add(double flops);   // csrc/ore_util.cpp: algorithmic FLOPs of the per-op conv entry points (ore_flop_counter_read)
 
 #define ORE_CHECK_ARG(cond, ...)              \

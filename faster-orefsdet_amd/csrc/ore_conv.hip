@@ -970,6 +970,7 @@ static int ws_sb_go(const PatchP& p, int tiles, dim3 pgrid, hipStream_t st) {
     const size_t lds = ((size_t)2 * (((TH - 1) * ST + 3) * (15 * ST + 3)) * (CF + (ST == 1 ? 8 : 4)) + (KS > 1 ? 2 * 4 * TH * 256 : 0)) * sizeof(float);
     static bool attr = false;
     if (!attr) { ORE_HIP(hipFuncSetAttribute((const void*)k_conv3x3_ws<TH, CF, KS, false, SBF, ST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr = true; }
+    ore_note_launch(ORE_LAUNCH_WS_SB, 1);
     hipLaunchKernelGGL((k_conv3x3_ws<TH, CF, KS, false, SBF, ST>), pgrid, dim3(256 * KS), lds, st, p, tiles);
     return ore_launch_status("k_conv3x3_ws");
 }
@@ -1086,6 +1087,7 @@ static int patch_launch(const ConvP& c, hipStream_t st) {
     if (ws) {
         // 64-channel layers: 4 waves, 2 blocks per CU; 128-channel layers: 8 waves (K split in wave pairs), 1 block per CU
         const bool wide = c.Cin == 128;
+        ore_note_launch(wide ? ORE_LAUNCH_WS128 : ORE_LAUNCH_WS64, 1);
         const int resident = wide ? 256 : 512;
         const dim3 pgrid(tiles < resident ? tiles : resident, c.Cout16 / 64);   // (a grid of tiles/rounds blocks measured 7 % slower on stem_2)
         if (wide) {
@@ -1106,6 +1108,7 @@ static int patch_launch(const ConvP& c, hipStream_t st) {
         }
         return ore_launch_status("k_conv3x3_ws");
     }
+    ore_note_launch(db ? ORE_LAUNCH_PATCH_DB : TH == 8 ? ORE_LAUNCH_PATCH8 : ORE_LAUNCH_PATCH4, 1);
     if (db) {
         const size_t lds = (size_t)2 * (10 * 18 + 9 * 64) * 24 * sizeof(float);
         static bool attrdb = false;
@@ -1414,6 +1417,7 @@ static int conv_launch(ConvP& p, int req_splitk, float* workspace, size_t worksp
     p.tile_cnt = reinterpret_cast<int*>(workspace);
     p.ws = workspace ? workspace + ORE_CONV_CNT_INTS : nullptr;
     p.xmap = conv_choose_xmap(p, gx, gy);
+    ore_note_launch(ORE_LAUNCH_IGEMM, S);
     const int rc = dispatch(p, t, dim3(gx, gy, S), st);
     if (rc != ORE_OK) {
         ore_set_error("ore_conv2d_fwd: no %skernel for tile %dx%d (%d,%d,%d)", g_conv_bf16 ? "bf16 " : "", t.BM, t.BN, t.WGM, t.WGN, t.WGK);
@@ -1468,6 +1472,7 @@ static void fill_common(ConvP& p, const ore_conv_desc* d) {
 
 extern "C" int ore_conv2d_fwd(const ore_conv_desc* d, void* stream) {
     ore_note_wino(0);
+    ore_note_launch(ORE_LAUNCH_NONE, 1);
     int rc = conv_common_checks(d);
     if (rc) return rc;
     ORE_CHECK_ARG(d->H > 0 && d->W > 0, "ore_conv2d_fwd: bad geometry");
@@ -1492,6 +1497,7 @@ extern "C" int ore_conv2d_fwd(const ore_conv_desc* d, void* stream) {
 extern "C" int ore_conv2d_levels_fwd(const ore_conv_desc* d, int32_t n_levels, const int32_t* H, const int32_t* W,
                                      int32_t ep_stride, void* stream) {
     ore_note_wino(0);
+    ore_note_launch(ORE_LAUNCH_NONE, 1);
     int rc = conv_common_checks(d);
     if (rc) return rc;
     ORE_CHECK_ARG(n_levels >= 1 && n_levels <= 4 && H && W, "ore_conv2d_levels_fwd: 1..4 levels");

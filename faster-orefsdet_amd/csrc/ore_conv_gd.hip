@@ -347,6 +347,7 @@ int launch_gd_bf(const GdP& q, bool k3, dim3 grid, hipStream_t st) {
     const dim3 block(64 * WGM * WGN);
     constexpr size_t lds = (size_t)NS * (GA + GB) * 256 * sizeof(float);
     static_assert(lds <= 64 * 1024, "the bf16-operand builds keep the default LDS limit");
+    ore_note_launch(ORE_LAUNCH_GD, 1);
     if (!k3) hipLaunchKernelGGL((k_conv_gd<GA, GB, WGM, WGN, NS, 1, true>), grid, block, lds, st, q);
     else hipLaunchKernelGGL((k_conv_gd<GA, GB, WGM, WGN, NS, 3, true>), grid, block, lds, st, q);
     return ore_launch_status("k_conv_gd<bf16 operands>");
@@ -365,6 +366,7 @@ int launch_gd(const GdP& q, bool k3, dim3 grid, hipStream_t st) {
             attr[k3] = true;
         }
     }
+    ore_note_launch(ORE_LAUNCH_GD, 1);
     if (!k3) hipLaunchKernelGGL((k_conv_gd<GA, GB, WGM, WGN, NS, 1>), grid, block, lds, st, q);
     else hipLaunchKernelGGL((k_conv_gd<GA, GB, WGM, WGN, NS, 3>), grid, block, lds, st, q);
     return ore_launch_status("k_conv_gd");

@@ -366,6 +366,7 @@ int launch_kd(const KdP& q, bool k3, dim3 grid, hipStream_t st) {
         return ORE_EINVAL;
     } else {
         static bool attr1 = false, attr3 = false;
+        ore_note_launch(ORE_LAUNCH_KD, 1);
         if (!k3) {
             if (!attr1) { ORE_HIP(hipFuncSetAttribute((const void*)k_conv_kd<GA, GB, NW, SB, 1, SBF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr1 = true; }
             hipLaunchKernelGGL((k_conv_kd<GA, GB, NW, SB, 1, SBF>), grid, dim3(NW * 64), lds, st, q);

@@ -692,6 +692,7 @@ int launch_gs_ns(const ConvP& p, const float* zero, hipStream_t st) {
         attr = true;
     }
     const dim3 grid(ceil_div(p.M, BM), ceil_div(p.Cout16, BN), 1);
+    ore_note_launch(ORE_LAUNCH_GS, 1);
     hipLaunchKernelGGL((k_conv_gs<BM, BN, WGM, WGN, NS, SB>), grid, dim3(256), lds, st, p, zero);
     return ore_launch_status("k_conv_gs");
     }
@@ -755,6 +756,7 @@ int launch_kw_ns(const ConvP& p, const float* zero, dim3 grid, hipStream_t st) {
                 ORE_HIP(hipFuncSetAttribute((const void*)k_conv_kw<BM, BN, NS, BF, INCR, NW, SB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
                 attr = true;
             }
+            ore_note_launch(ORE_LAUNCH_KW, p.splitk);
             hipLaunchKernelGGL((k_conv_kw<BM, BN, NS, BF, INCR, NW, SB>), grid, dim3(NW * 64), lds, st, p, zero);
             return ORE_OK;
         }

@@ -272,6 +272,7 @@ int g_rf_force[3] = {0, 0, 0};           // (-11, GB, NW, MAXS): force the build
 template <int GB, int NW, int MAXS>
 int launch_rf(const RfP& q, bool k3, dim3 grid, hipStream_t st) {
     constexpr size_t lds = (size_t)(NW * GB * 256) * sizeof(float);
+    ore_note_launch(ORE_LAUNCH_RF, 1);
     if (!k3) hipLaunchKernelGGL((k_conv_rf<GB, NW, MAXS, 1>), grid, dim3(NW * 64), lds, st, q);
     else hipLaunchKernelGGL((k_conv_rf<GB, NW, MAXS, 3>), grid, dim3(NW * 64), lds, st, q);
     return ore_launch_status("k_conv_rf");

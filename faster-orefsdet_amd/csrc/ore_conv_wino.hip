@@ -446,6 +446,7 @@ static int wino_nu_go(const WinoP& p, int nb, hipStream_t st) {
         ORE_HIP(hipFuncSetAttribute((const void*)k_conv3x3_wino_nu<CIN, NCGB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr = true;
     }
+    ore_note_launch(ORE_LAUNCH_WINO_NU, 1);
     hipLaunchKernelGGL((k_conv3x3_wino_nu<CIN, NCGB>), dim3(gx, gy), dim3(512), lds, st, p);
     return ore_launch_status("k_conv3x3_wino_nu");
 }
@@ -506,6 +507,7 @@ static int conv_wino_launch_impl(const ConvP& c, hipStream_t st) {
         ORE_HIP(hipFuncSetAttribute((const void*)k_conv3x3_wino<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
         attr = true;
     }
+    ore_note_launch(ORE_LAUNCH_WINO, 1);
     if (c.Cin == 64) hipLaunchKernelGGL(k_conv3x3_wino<64>, dim3(gx, gy), dim3(512), lds, st, p);
     else hipLaunchKernelGGL(k_conv3x3_wino<128>, dim3(gx, gy), dim3(512), lds, st, p);
     return ore_launch_status("k_conv3x3_wino");

@@ -29,6 +29,13 @@ void ore_flop_count_add(double flops) {
 static thread_local int g_last_wino = 0;
 void ore_note_wino(int v) { g_last_wino = v; }
 int ore_last_wino(void) { return g_last_wino; }
+// which launcher that call ran, and its split-K (a test hook: tests/test_hip_dgrad.py tells an intended launcher from a fallback)
+static thread_local int g_last_launch = ORE_LAUNCH_NONE, g_last_split = 1;
+void ore_note_launch(int code, int split) { g_last_launch = code; g_last_split = split; }
+extern "C" int32_t ore_conv_last_launch(int32_t* split) {
+    if (split) *split = g_last_split;
+    return g_last_launch;
+}
 extern "C" int ore_flop_counter_read(double* flops, int64_t* calls, int32_t reset) {
     if (flops) *flops = g_flops.load(std::memory_order_relaxed);
     if (calls) *calls = (int64_t)g_flop_calls.load(std::memory_order_relaxed);

@@ -113,6 +113,24 @@ int ore_conv2d_fwd(const ore_conv_desc* d, void* stream);
  * height, 16 = double-buffered 8-wave variant, 102 = weight-stationary persistent kernel for Cin = 64 / 128); BM = -7 sets the
  * Winograd mode to BN (0 off, 1 automatic, 2 wherever it applies).  The product path never calls it. */
 int ore_conv_set_plan_override(int32_t BM, int32_t BN, int32_t WGM, int32_t WGN, int32_t WGK);
+/* Test hook: the launcher this host thread's last ore_conv2d_fwd / ore_conv2d_levels_fwd call ran (ORE_LAUNCH_*; ORE_LAUNCH_NONE
+ * when the call launched nothing), and in *split (if not null) the cross-block split-K S it used (1 = none). */
+#define ORE_LAUNCH_NONE 0
+#define ORE_LAUNCH_WINO 1           /* k_conv3x3_wino<64 | 128> */
+#define ORE_LAUNCH_WINO_NU 2        /* k_conv3x3_wino_nu (80 / 96 / 112 input channels) */
+#define ORE_LAUNCH_GD 3             /* k_conv_gd */
+#define ORE_LAUNCH_PATCH4 4         /* k_conv3x3_patch<4> */
+#define ORE_LAUNCH_PATCH8 5         /* k_conv3x3_patch<8> */
+#define ORE_LAUNCH_PATCH_DB 6       /* k_conv3x3_patch_db (8-row double-buffered) */
+#define ORE_LAUNCH_WS64 7           /* k_conv3x3_ws<2, 64> */
+#define ORE_LAUNCH_WS128 8          /* k_conv3x3_ws<2, 128> */
+#define ORE_LAUNCH_KD 9             /* k_conv_kd */
+#define ORE_LAUNCH_RF 10            /* k_conv_rf */
+#define ORE_LAUNCH_GS 11            /* k_conv_gs */
+#define ORE_LAUNCH_KW 12            /* k_conv_kw (split-K possible) */
+#define ORE_LAUNCH_IGEMM 13         /* k_conv_igemm (split-K possible) */
+#define ORE_LAUNCH_WS_SB 14         /* k_conv3x3_ws, bf16 storage */
+int32_t ore_conv_last_launch(int32_t* split);
 /* Operand precision of the MFMA conv kernels for all subsequent ore_conv2d*_fwd launches (BASELINE configs[4], "bf16 MFMA conv
  * path + fp32 NMS"; the reference itself is fp32 only, ref:configs/fsod/finetune_vovnet.yaml).  ORE_CONV_FP32 (default): fp32
  * operands, v_mfma_f32_16x16x4_f32.  ORE_CONV_BF16: tensors stay fp32 in HBM and LDS, both operands are rounded to bf16 (nearest

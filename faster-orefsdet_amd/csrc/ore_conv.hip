@@ -961,297 +961,99 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv3x3_ws(PatchP
     }
 }
 
-int g_ws_sb_mode = 1;    // tuning aid (ore_conv_set_plan_override(-8, mode)): 0 = bf16-storage 3x3 layers stay on k_conv_gs / k_conv_kw, 4 / 8 = tile height, 1 = automatic
+int g_conv_bf16 = 0;     // ore_conv_set_precision: 1 = bf16 MFMA operands (fp32 storage and accumulation)
+int g_conv_mode = 0;     // the mode as set (ORE_CONV_BF16S = 2 is an engine build mode, see ore_hip.h)
 
-// bf16 STORAGE: 3x3 stride-1 layers with 64 / 128 input channels on the weight-stationary kernel (weights in registers for the whole
-// launch, only the halo patch is staged).  c holds the input side in 4-byte units (fill_common).  1 = not covered.
-template <int TH, int CF, int KS, bool SBF = true, int ST = 1>
-static int ws_sb_go(const PatchP& p, int tiles, dim3 pgrid, hipStream_t st) {
+// the tile table of the 3x3 tile kernels: tiles of TH output rows x 16 columns, level by level
+PatchP patch_params(const ConvP& c, int TH, int xmap) {
+    PatchP p{};
+    p.in = c.in; p.in_ld = c.in_ld; p.in_coff = c.in_coff; p.B = c.B; p.Cin = c.Cin; p.nlev = c.nlev;
+    int tiles = 0;
+    for (int l = 0; l < c.nlev; ++l) {
+        p.lv[l] = c.lv[l];
+        p.tiles_x[l] = ceil_div(c.lv[l].Wo, 16); p.tiles_y[l] = ceil_div(c.lv[l].Ho, TH);
+        p.tile0[l] = tiles;
+        tiles += c.B * p.tiles_x[l] * p.tiles_y[l];
+    }
+    p.tile0[c.nlev] = tiles;
+    p.w = c.w; p.Cout = c.Cout; p.Cout16 = c.Cout16; p.K = c.K;
+    p.scale = c.scale; p.shift = c.shift; p.ep_stride = c.ep_stride; p.relu_cout = c.relu_cout;
+    p.out = c.out; p.out_ld = c.out_ld; p.out_coff = c.out_coff;
+    p.xmap = xmap;
+    p.w_lstride = c.w_lstride;
+    return p;
+}
+
+template <int TH, int CF, int KS, bool BF = false, bool SBF = false, int ST = 1>
+int ws_go(const PatchP& p, dim3 grid, hipStream_t st) {
     const size_t lds = ((size_t)2 * (((TH - 1) * ST + 3) * (15 * ST + 3)) * (CF + (ST == 1 ? 8 : 4)) + (KS > 1 ? 2 * 4 * TH * 256 : 0)) * sizeof(float);
     static bool attr = false;
-    if (!attr) { ORE_HIP(hipFuncSetAttribute((const void*)k_conv3x3_ws<TH, CF, KS, false, SBF, ST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr = true; }
-    ore_note_launch(ORE_LAUNCH_WS_SB, 1);
-    hipLaunchKernelGGL((k_conv3x3_ws<TH, CF, KS, false, SBF, ST>), pgrid, dim3(256 * KS), lds, st, p, tiles);
+    if (!attr) { ORE_HIP(hipFuncSetAttribute((const void*)k_conv3x3_ws<TH, CF, KS, BF, SBF, ST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr = true; }
+    hipLaunchKernelGGL((k_conv3x3_ws<TH, CF, KS, BF, SBF, ST>), grid, dim3(256 * KS), lds, st, p, p.tile0[p.nlev]);
     return ore_launch_status("k_conv3x3_ws");
 }
 
-int g_ws_s2_mode = 1;    // tuning aid (-9, mode): 0 = stem_3 (3x3 stride 2, 64 input channels) stays on k_conv_igemm / k_conv_gs
-
-// 3x3 STRIDE-2 layers with 64 input channels and a multiple of 64 output channels (stem_3), bf16 storage: weight-stationary too
-// (18.8 -> 16.0 us).  The fp32 build of the same kernel was measured and dropped: 144 VGPRs of weights + an 11-vector register-staged
-// 5 x 33 patch spill, and the stride-2 fragment reads are 2-way bank conflicted: 71.9 us against 50.2 on k_conv_igemm.
-static int ws_s2_launch(const ConvP& c, hipStream_t st) {
-    const bool sb = (c.sb & 1) != 0;
-    if (!sb) return 1;
-    if (!g_ws_s2_mode || c.kh != 3 || c.kw != 3 || c.stride != 2 || c.pad != 1 || c.in_mul || c.add || c.colsum || c.nlev != 1) return 1;
-    if (sb ? (c.Cin != 32 || !(c.sb & 2)) : (c.Cin != 64 || c.bf16)) return 1;
-    if (c.Cout != c.Cout16 || c.Cout % 64 != 0 || c.M < 6000) return 1;
-    if (c.out_ld % 4 != 0 || c.out_coff % 4 != 0 || ((uintptr_t)c.out & (sb ? 7 : 15)) != 0) return 1;
-    const int TH = 2;
-    PatchP p{};
-    p.in = c.in; p.in_ld = c.in_ld; p.in_coff = c.in_coff; p.B = c.B; p.Cin = c.Cin; p.nlev = 1;
-    p.lv[0] = c.lv[0];
-    p.tiles_x[0] = ceil_div(c.lv[0].Wo, 16); p.tiles_y[0] = ceil_div(c.lv[0].Ho, TH);
-    p.tile0[0] = 0;
-    const int tiles = c.B * p.tiles_x[0] * p.tiles_y[0];
-    p.tile0[1] = tiles;
-    p.w = c.w; p.Cout = c.Cout; p.Cout16 = c.Cout16; p.K = c.K;
-    p.scale = c.scale; p.shift = c.shift; p.ep_stride = c.ep_stride; p.relu_cout = c.relu_cout;
-    p.out = c.out; p.out_ld = c.out_ld; p.out_coff = c.out_coff;
-    p.xmap = tiles >= 16 ? 1 : 0;
-    const int gy = c.Cout16 / 64;
-    int gx = 512 / gy;
-    gx &= ~7;
-    if (gx > tiles) gx = tiles;
-    const dim3 pgrid(gx, gy);
-    return ws_sb_go<2, 32, 1, true, 2>(p, tiles, pgrid, st);
+template <int TH, bool BF = false>
+int patch_go(const PatchP& p, dim3 grid, hipStream_t st) {
+    const size_t lds = (size_t)((TH + 2) * 18 + 9 * 64) * PATCH_LDA * sizeof(float);
+    static bool attr = false;
+    if (!attr) { ORE_HIP(hipFuncSetAttribute((const void*)k_conv3x3_patch<TH, BF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr = true; }
+    hipLaunchKernelGGL((k_conv3x3_patch<TH, BF>), grid, dim3(256), lds, st, p);
+    return ore_launch_status("k_conv3x3_patch");
 }
 
-static int ws_sb_launch(const ConvP& c, hipStream_t st) {
-    if (!g_ws_sb_mode || !(c.sb & 1) || !(c.sb & 2)) return 1;
-    if (c.kh != 3 || c.kw != 3 || c.stride != 1 || c.pad != 1 || c.in_mul || c.add || c.colsum) return 1;
-    if ((c.Cin != 32 && c.Cin != 64) || c.Cout != c.Cout16 || c.Cout % 64 != 0) return 1;
-    if (c.Cin == 64 && g_ws_sb_mode == 3) return 1;                           // (A/B aid: 128-channel layers back on k_conv_kw)
-    if (c.out_ld % 4 != 0 || c.out_coff % 4 != 0 || ((uintptr_t)c.out & 7) != 0) return 1;
-    if (c.M < 6000 && !c.w_lstride) return 1;
-    // 64 channels: 4 waves x 16 output channels, 72 VGPRs of weights, two blocks per CU.  128 channels: 8 waves, the wave pairs (w, w+4)
-    // split the input channels (72 VGPRs each; the upper half's accumulators meet the lower half's in LDS), one block per CU.
-    const int TH = 4;
-    PatchP p{};
-    p.in = c.in; p.in_ld = c.in_ld; p.in_coff = c.in_coff; p.B = c.B; p.Cin = c.Cin; p.nlev = c.nlev;
-    int tiles = 0;
-    for (int l = 0; l < c.nlev; ++l) {
-        p.lv[l] = c.lv[l];
-        p.tiles_x[l] = ceil_div(c.lv[l].W, 16); p.tiles_y[l] = ceil_div(c.lv[l].H, TH);
-        p.tile0[l] = tiles;
-        tiles += c.B * p.tiles_x[l] * p.tiles_y[l];
-    }
-    p.tile0[c.nlev] = tiles;
-    p.w = c.w; p.Cout = c.Cout; p.Cout16 = c.Cout16; p.K = c.K;
-    p.scale = c.scale; p.shift = c.shift; p.ep_stride = c.ep_stride; p.relu_cout = c.relu_cout;
-    p.out = c.out; p.out_ld = c.out_ld; p.out_coff = c.out_coff;
-    p.xmap = tiles >= 16 ? 1 : 0;
-    const int gy = c.Cout16 / 64;
-    int gx = (c.Cin == 32 ? 512 : 256) / gy;                // resident blocks
-    gx &= ~7;
-    if (gx > tiles) gx = tiles;
-    if (c.w_lstride) { gx = tiles; p.xmap = 0; p.w_lstride = c.w_lstride; }   // per-level weights: one tile per block, in tile order
-    const dim3 pgrid(gx, gy);
-    if (c.Cin == 32) return ws_sb_go<4, 32, 1>(p, tiles, pgrid, st);
-    return ws_sb_go<4, 64, 2>(p, tiles, pgrid, st);
+template <int BM, int BN, int WGM, int WGN, int WGK, bool BF>
+int igemm_go(const ConvP& p, dim3 grid, hipStream_t st) {
+    if (p.in_mul) hipLaunchKernelGGL((k_conv_igemm<BM, BN, WGM, WGN, WGK, true, BF>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((k_conv_igemm<BM, BN, WGM, WGN, WGK, false, BF>), grid, dim3(256), 0, st, p);
+    return ore_launch_status("k_conv_igemm");
 }
 
-int g_conv_bf16 = 0;     // ore_conv_set_precision: 1 = bf16 MFMA operands (fp32 storage and accumulation)
-int g_conv_mode = 0;     // the mode as set (ORE_CONV_BF16S = 2 is an engine build mode, see ore_hip.h)
-int g_patch_mode = -1;   // tuning aid: -1 automatic, 0 never, 4 / 8 force TH, 16 = double-buffered 8-wave kernel, 102 = weight-stationary kernels (2-row tiles; Cin = 64 or 128)
+}  // namespace
 
-static int patch_launch(const ConvP& c, hipStream_t st) {
-    // returns ORE_OK if launched, 1 if the layer is not eligible (caller falls back to the generic kernel)
-    if (c.kh != 3 || c.kw != 3 || c.stride != 1 || c.pad != 1 || c.Cout16 % 64 != 0 || c.in_mul || c.add || c.colsum) return 1;
-    if (c.out_ld % 4 != 0 || c.out_coff % 4 != 0 || ((uintptr_t)c.out & 15) != 0) return 1;      // the epilogue stores 16 bytes per lane
-    if (g_patch_mode == 0) return 1;
-    if (g_conv_bf16 && g_patch_mode > 0 && g_patch_mode != 4 && g_patch_mode != 102) return 1;   // bf16 builds: patch<4> and ws<2,64,1> only
-    int TH = g_patch_mode > 0 ? g_patch_mode : 4;
-    bool db = TH == 16;
-    if (db) TH = 8;
-    bool ws = TH == 102;                                     // TH = 4 needs > 256 VGPRs (spills): only the 2-row tile is built
-    if (ws) { TH = 2; if (c.Cin != 64 && (c.Cin != 128 || g_conv_bf16)) return 1; }
-    if (g_patch_mode < 0 && c.M < 6000) return 1;        // plan: only the large-M layers (profiles/r01_conv_tune.txt); TH=4 wins or ties
-    // plan: the weight-stationary kernel wins once a resident block walks >= 4 tiles (stem_2: 3200 tiles, 71 vs 82 us); below that its
-    // 36-fragment weight prologue is not amortised (stage-2 64->64 layers: 800 tiles, 29 vs 26 us)
-    const long long ws_tiles = (long long)c.B * ceil_div(c.lv[0].H, 2) * ceil_div(c.lv[0].W, 16);
-    if (g_patch_mode < 0 && c.Cin == 64 && c.nlev == 1 && ws_tiles >= 2048) { ws = true; TH = 2; }
-    // Cin = 128 (8 waves, K split in wave pairs, fp32 build only): alone on the GPU it wins from ~1600 tiles (8 x 80x80: 140 vs 154 us,
-    // 8 x 160x160: 263 vs 315 us; one 160x160 image, 800 tiles: 47 vs 45 us -- tools/ws128_exp.py), but its one 512-thread,
-    // 256-VGPR block per CU leaves no room for another stream's kernel: with several passes in flight the folded-serving rate DROPS
-    // 2 %.  Used for training-sized launches only.
-    if (g_patch_mode < 0 && c.Cin == 128 && c.nlev == 1 && !g_conv_bf16 && ws_tiles >= 8192) { ws = true; TH = 2; }
-    // plan: one image of stage 2 (64 output channels, 160 x 160): the double-buffered 8-wave patch kernel beats the 4-wave one by 7-8 %
-    // (64 -> 64: 27.9 -> 25.9 us, 128 -> 64: 47.0 -> 43.3 us; tools/ws_s2_exp.py); at 128 output channels / 80 x 80 it loses (42 vs 26 us)
-    if (g_patch_mode < 0 && !ws && !g_conv_bf16 && c.nlev == 1 && c.Cout16 == 64 && c.M >= 16384 && c.M <= 65536) { db = true; TH = 8; }
-    PatchP p{};
-    p.in = c.in; p.in_ld = c.in_ld; p.in_coff = c.in_coff; p.B = c.B; p.Cin = c.Cin; p.nlev = c.nlev;
-    int tiles = 0;
-    for (int l = 0; l < c.nlev; ++l) {
-        p.lv[l] = c.lv[l];
-        p.tiles_x[l] = ceil_div(c.lv[l].W, 16); p.tiles_y[l] = ceil_div(c.lv[l].H, TH);
-        p.tile0[l] = tiles;
-        tiles += c.B * p.tiles_x[l] * p.tiles_y[l];
+namespace oreconv {
+
+// k_conv3x3_ws: bf16 storage (WS_SB: 4-row tiles, or 2-row stride-2 tiles for stem_3), fp32 storage (WS64 / WS128: 2-row tiles)
+int launch_ws(const ConvP& c, const ConvPlan& pl, hipStream_t st) {
+    const PatchP p = patch_params(c, pl.bm, pl.xmap);
+    const dim3 grid(pl.gx, pl.gy);
+    if (pl.launcher == ORE_LAUNCH_WS_SB) {
+        if (pl.build[3] == 2) return ws_go<2, 32, 1, false, true, 2>(p, grid, st);
+        if (pl.build[1] == 32) return ws_go<4, 32, 1, false, true>(p, grid, st);
+        return ws_go<4, 64, 2, false, true>(p, grid, st);
     }
-    p.tile0[c.nlev] = tiles;
-    p.w = c.w; p.Cout = c.Cout; p.Cout16 = c.Cout16; p.K = c.K;
-    p.scale = c.scale; p.shift = c.shift; p.ep_stride = c.ep_stride; p.relu_cout = c.relu_cout;
-    p.out = c.out; p.out_ld = c.out_ld; p.out_coff = c.out_coff;
-    const dim3 grid(tiles, c.Cout16 / 64);
-    { const int xf = conv_xmap_forced(); p.xmap = xf >= 0 ? (xf ? 1 : 0) : (tiles >= 16 ? 1 : 0); }   // M-major bands of tiles per XCD
-    if (ws) {
-        // 64-channel layers: 4 waves, 2 blocks per CU; 128-channel layers: 8 waves (K split in wave pairs), 1 block per CU
-        const bool wide = c.Cin == 128;
-        ore_note_launch(wide ? ORE_LAUNCH_WS128 : ORE_LAUNCH_WS64, 1);
-        const int resident = wide ? 256 : 512;
-        const dim3 pgrid(tiles < resident ? tiles : resident, c.Cout16 / 64);   // (a grid of tiles/rounds blocks measured 7 % slower on stem_2)
-        if (wide) {
-            const size_t lds = ((size_t)2 * (4 * 18) * 136 + 2 * 4 * 2 * 256) * sizeof(float);
-            static bool a128 = false;
-            if (!a128) { ORE_HIP(hipFuncSetAttribute((const void*)k_conv3x3_ws<2, 128, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); a128 = true; }
-            hipLaunchKernelGGL((k_conv3x3_ws<2, 128, 2>), pgrid, dim3(512), lds, st, p, tiles);
-        } else {
-            const size_t lds = (size_t)2 * (4 * 18) * 72 * sizeof(float);
-            static bool a2 = false;
-            if (!a2) {
-                ORE_HIP(hipFuncSetAttribute((const void*)k_conv3x3_ws<2, 64, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                ORE_HIP(hipFuncSetAttribute((const void*)k_conv3x3_ws<2, 64, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                a2 = true;
-            }
-            if (g_conv_bf16) hipLaunchKernelGGL((k_conv3x3_ws<2, 64, 1, true>), pgrid, dim3(256), lds, st, p, tiles);
-            else hipLaunchKernelGGL((k_conv3x3_ws<2, 64, 1, false>), pgrid, dim3(256), lds, st, p, tiles);
-        }
-        return ore_launch_status("k_conv3x3_ws");
-    }
-    ore_note_launch(db ? ORE_LAUNCH_PATCH_DB : TH == 8 ? ORE_LAUNCH_PATCH8 : ORE_LAUNCH_PATCH4, 1);
-    if (db) {
+    if (pl.build[1] == 128) return ws_go<2, 128, 2>(p, grid, st);
+    return pl.build[3] ? ws_go<2, 64, 1, true>(p, grid, st) : ws_go<2, 64, 1, false>(p, grid, st);
+}
+
+// k_conv3x3_patch<4 | 8> (bf16 operands: <4> only), k_conv3x3_patch_db (8-row double-buffered, 8 waves)
+int launch_patch(const ConvP& c, const ConvPlan& pl, hipStream_t st) {
+    const PatchP p = patch_params(c, pl.bm, pl.xmap);
+    const dim3 grid(pl.gx, pl.gy);
+    if (pl.launcher == ORE_LAUNCH_PATCH_DB) {
         const size_t lds = (size_t)2 * (10 * 18 + 9 * 64) * 24 * sizeof(float);
         static bool attrdb = false;
         if (!attrdb) { ORE_HIP(hipFuncSetAttribute((const void*)k_conv3x3_patch_db, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attrdb = true; }
         hipLaunchKernelGGL(k_conv3x3_patch_db, grid, dim3(512), lds, st, p);
-    } else if (TH == 8) {
-        const size_t lds = (size_t)(10 * 18 + 9 * 64) * PATCH_LDA * sizeof(float);
-        static bool attr8 = false;
-        if (!attr8) { ORE_HIP(hipFuncSetAttribute((const void*)k_conv3x3_patch<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr8 = true; }
-        hipLaunchKernelGGL(k_conv3x3_patch<8>, grid, dim3(256), lds, st, p);
-    } else {
-        const size_t lds = (size_t)(6 * 18 + 9 * 64) * PATCH_LDA * sizeof(float);
-        static bool attr4 = false;
-        if (!attr4) {
-            ORE_HIP(hipFuncSetAttribute((const void*)k_conv3x3_patch<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            ORE_HIP(hipFuncSetAttribute((const void*)k_conv3x3_patch<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr4 = true;
-        }
-        if (g_conv_bf16) hipLaunchKernelGGL((k_conv3x3_patch<4, true>), grid, dim3(256), lds, st, p);
-        else hipLaunchKernelGGL((k_conv3x3_patch<4, false>), grid, dim3(256), lds, st, p);
+        return ore_launch_status("k_conv3x3_patch");
     }
-    return ore_launch_status("k_conv3x3_patch");
+    if (pl.launcher == ORE_LAUNCH_PATCH8) return patch_go<8>(p, grid, st);
+    return pl.build[2] ? patch_go<4, true>(p, grid, st) : patch_go<4, false>(p, grid, st);
 }
 
-template <int BM, int BN, int WGM, int WGN, int WGK, bool HASBF>
-int launch_conv(const ConvP& p, dim3 grid, hipStream_t st) {
-    if (g_conv_bf16) {
-        if constexpr (HASBF) {
-            if (p.in_mul) hipLaunchKernelGGL((k_conv_igemm<BM, BN, WGM, WGN, WGK, true, true>), grid, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((k_conv_igemm<BM, BN, WGM, WGN, WGK, false, true>), grid, dim3(256), 0, st, p);
-            return ORE_OK;
-        } else {
-            return ORE_EINVAL;                                   // tuner-only tile: no bf16 build
-        }
+int launch_igemm(const ConvP& p, const ConvPlan& pl, hipStream_t st) {
+    const dim3 grid(pl.gx, pl.gy, pl.splitk);
+#define IGEMM_GO(bm_, bn_, wgm, wgn, wgk, hasbf)                                                             \
+    if (pl.bm == bm_ && pl.bn == bn_ && pl.build[0] == wgm && pl.build[1] == wgn && pl.build[2] == wgk) {  \
+        if constexpr (hasbf) { if (pl.build[3]) return igemm_go<bm_, bn_, wgm, wgn, wgk, true>(p, grid, st); } \
+        return igemm_go<bm_, bn_, wgm, wgn, wgk, false>(p, grid, st);                                      \
     }
-    if (p.in_mul) hipLaunchKernelGGL((k_conv_igemm<BM, BN, WGM, WGN, WGK, true, false>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((k_conv_igemm<BM, BN, WGM, WGN, WGK, false, false>), grid, dim3(256), 0, st, p);
-    return ORE_OK;
-}
-
-struct TileCfg { int BM, BN, WGM, WGN, WGK; };
-
-int dispatch(const ConvP& p, const TileCfg& t, dim3 grid, hipStream_t st) {
-#define ORE_CASE_(bm, bn, wgm, wgn, wgk, hasbf)                                                      \
-    if (t.BM == bm && t.BN == bn && t.WGM == wgm && t.WGN == wgn && t.WGK == wgk)                    \
-        return launch_conv<bm, bn, wgm, wgn, wgk, hasbf>(p, grid, st);
-#define ORE_CASE(bm, bn, wgm, wgn, wgk) ORE_CASE_(bm, bn, wgm, wgn, wgk, false)
-#define ORE_CASEB(bm, bn, wgm, wgn, wgk) ORE_CASE_(bm, bn, wgm, wgn, wgk, true)     /* tiles of the automatic plan: also built for bf16 operands */
-    // large-M tiles: 4 waves along M, whole N in the block
-    ORE_CASE(128, 16, 4, 1, 1) ORE_CASE(128, 32, 4, 1, 1) ORE_CASE(128, 48, 4, 1, 1) ORE_CASE(128, 64, 4, 1, 1)
-    ORE_CASE(128, 80, 4, 1, 1) ORE_CASE(128, 96, 4, 1, 1) ORE_CASE(128, 112, 4, 1, 1) ORE_CASE(128, 128, 2, 2, 1)
-    ORE_CASEB(64, 16, 4, 1, 1) ORE_CASEB(64, 32, 4, 1, 1) ORE_CASEB(64, 48, 4, 1, 1) ORE_CASEB(64, 64, 4, 1, 1)
-    ORE_CASEB(64, 80, 4, 1, 1) ORE_CASEB(64, 96, 4, 1, 1) ORE_CASEB(64, 112, 4, 1, 1) ORE_CASEB(64, 128, 2, 2, 1)
-    // mid/small-M tiles: waves split K inside the block
-    ORE_CASE(64, 64, 2, 1, 2) ORE_CASE(64, 32, 2, 1, 2) ORE_CASE(64, 16, 2, 1, 2) ORE_CASE(64, 48, 2, 1, 2)
-    ORE_CASE(32, 64, 1, 1, 4) ORE_CASE(32, 48, 1, 1, 4) ORE_CASEB(32, 32, 1, 1, 4) ORE_CASE(32, 16, 1, 1, 4)
-    ORE_CASE(16, 64, 1, 1, 4) ORE_CASE(16, 48, 1, 1, 4) ORE_CASEB(16, 32, 1, 1, 4) ORE_CASEB(16, 16, 1, 1, 4)
-    ORE_CASE(64, 128, 2, 1, 2) ORE_CASE(64, 96, 2, 1, 2) ORE_CASE(64, 80, 2, 1, 2) ORE_CASE(64, 112, 2, 1, 2)
-    ORE_CASE(32, 128, 1, 1, 4) ORE_CASE(32, 96, 1, 1, 4) ORE_CASE(32, 80, 1, 1, 4) ORE_CASE(32, 112, 1, 1, 4)
-    ORE_CASE(32, 128, 2, 1, 2) ORE_CASEB(32, 64, 2, 1, 2) ORE_CASE(32, 32, 2, 1, 2)
-    ORE_CASE(128, 64, 2, 1, 2) ORE_CASE(128, 128, 2, 1, 2)
-#undef ORE_CASE
-#undef ORE_CASEB
-#undef ORE_CASE_
+    ORE_IGEMM_BUILDS(IGEMM_GO)
+#undef IGEMM_GO
     return ORE_EINVAL;
 }
 
-// Tile / split plan.  Goal: >= ~768 waves' worth of blocks (256 CUs x 3) when the layer allows it, slabs small enough
-// for the in-kernel last-arriver reduction (splitk * BM*BN*4 bytes per tile stays in the tens of KB).
-TileCfg g_override = {0, 0, 0, 0, 0};   // tuning aid (ore_conv_set_plan_override); BM == 0 -> automatic
-int g_kw_mode = 1;                      // 0: k_conv_kw off, 1: automatic (after the 3x3 patch kernels), 2: wherever it applies
-
-void plan_conv(int M, int Cout, int nchunks, int req_splitk, TileCfg* t, int* S_out, int* sps_out) {
-    const int C16 = round_up(Cout, 16);
-    if (g_override.BM > 0) {
-        *t = g_override;
-        if (t->BN > C16) t->BN = C16;
-        const int nst = ceil_div(nchunks, t->WGK);
-        int S = req_splitk > 0 ? req_splitk : 1;
-        if (S > nst) S = nst;
-        const int sps = ceil_div(nst, S);
-        *S_out = ceil_div(nst, sps); *sps_out = sps;
-        return;
-    }
-    // Plan table distilled from tools/conv_tune.py sweeps on MI355X (profiles/r01_conv_tune.txt): small tiles with the K
-    // dimension split across the block's waves win almost everywhere -- they keep several blocks resident per CU, which
-    // hides the per-step barrier/LDS latency that dominates this kernel -- and cross-block split-K only pays for the
-    // deepest K (stage-5 layer 0).
-    int bn;
-    if (M >= 16384) {
-        if (C16 == 64) { if (M >= 65536) *t = {32, 64, 2, 1, 2}; else *t = {64, 64, 4, 1, 1}; }
-        else if (C16 % 128 == 0) *t = {64, 128, 2, 2, 1};
-        else *t = {64, C16 <= 128 ? C16 : 64, 4, 1, 1};
-    } else if (M >= 2048) {
-        if (C16 % 64 == 0) { if (C16 >= 256 && !g_conv_bf16) *t = {64, 64, 2, 1, 2}; else *t = {32, 64, 2, 1, 2}; }
-        else if (C16 >= 32) *t = {32, 32, 1, 1, 4};
-        else *t = {16, 16, 1, 1, 4};
-    } else {
-        bn = C16 >= 32 ? 32 : 16;
-        *t = {16, bn, 1, 1, 4};
-    }
-    // K-split tiles, second pass (re-tuned after the K loop lost its barriers, profiles/r01_conv_tune.txt): with wave-private staging
-    // the layers of stages 3-4 and the FPN run best at about ONE block per CU -- every CU then pulls each weight row through its
-    // memory path once -- so pick the (BM, BN) of the 1x1x4 family with >= 192 blocks and the fewest staged bytes per FLOP,
-    // (1/BM + 1/BN) x the padding waste of BN.  (The bf16 builds exist for the first-pass tiles only.)
-    // (at M < 2048 only for N < 128: the 128- and 384-channel layers of stage 4 / the FPN -- input affine, fused column sums in the
-    // epilogue -- measured slower with the picked tile inside the engine: s4cat 19.7 -> 22.6 us, lat4 11.0 -> 12.4 us)
-    const bool ksplit_pick = !g_conv_bf16 && C16 >= 32 && ((M >= 2048 && M < 16384 && C16 % 64 != 0) || (M >= 1024 && M < 2048 && C16 < 128));
-    if (ksplit_pick) {
-        static const int bms[2] = {32, 16};
-        static const int bns32[8] = {128, 112, 96, 80, 64, 48, 32, 16}, bns16[4] = {64, 48, 32, 16};
-        float best = 1e30f;
-        for (int a = 0; a < 2; ++a) {
-            const int bm = bms[a];
-            const int* bns = bm == 32 ? bns32 : bns16;
-            for (int b = 0; b < (bm == 32 ? 8 : 4); ++b) {
-                const int bnc = bns[b];
-                if (bnc > C16) continue;
-                const int nt = ceil_div(C16, bnc);
-                if (ceil_div(M, bm) * nt < 192) continue;
-                const float cost = (1.0f / (float)bm + 1.0f / (float)bnc) * (float)(nt * bnc) / (float)C16;
-                if (cost < best) { best = cost; *t = {bm, bnc, 1, 1, 4}; }
-            }
-        }
-    }
-    const int nsteps = ceil_div(nchunks, t->WGK);
-    const int blocks = ceil_div(M, t->BM) * ceil_div(C16, t->BN);
-    int S = req_splitk;
-    if (S <= 0) {
-        S = 1;
-        if (nsteps >= 48 && blocks < 256) {
-            S = ceil_div(300, blocks);
-            if (S > 4) S = 4;
-        }
-    }
-    if (S > nsteps) S = nsteps;
-    if (S < 1) S = 1;
-    const int sps = ceil_div(nsteps, S);
-    S = ceil_div(nsteps, sps);
-    *S_out = S; *sps_out = sps;
-}
-
-}  // namespace
+}  // namespace oreconv
 
 extern "C" size_t ore_packed_weight_floats(int32_t Cout, int32_t Cin, int32_t kh, int32_t kw) {
     return (size_t)round_up(Cout, 16) * kh * kw * Cin;
@@ -1293,29 +1095,6 @@ extern "C" int ore_pack_conv_weight_bf16_host(const float* w, int32_t Cout, int3
 
 extern "C" size_t ore_conv_workspace_floats(void) { return ORE_CONV_WS_FLOATS; }
 
-// Tuning aid (tools/conv_tune.py): force the tile configuration of subsequent ore_conv2d*_fwd calls; BM = 0 restores the
-// automatic plan.  Not used by the product path.
-extern "C" int ore_conv_set_plan_override(int32_t BM, int32_t BN, int32_t WGM, int32_t WGN, int32_t WGK) {
-    if (BM == -1) { g_patch_mode = BN; g_override = {0, 0, 0, 0, 0}; return ORE_OK; }   // BM = -1: BN selects the 3x3 patch kernel mode
-    if (BM == -2) { g_kw_mode = BN; g_override = {0, 0, 0, 0, 0}; return ORE_OK; }
-    if (BM == -3) { conv_kw_force(BN, WGM, WGN, WGK); return ORE_OK; }
-    if (BM == -4) { conv_gs_force(BN, WGM, WGN); return ORE_OK; }
-    if (BM == -5) { conv_xmap_force(BN); return ORE_OK; }
-    if (BM == -14) { conv_gd_mode(BN); return ORE_OK; }                                     // BM = -14: shared-stage descriptor kernel 0 off / 1 automatic
-    if (BM == -16) { conv_gd_dbg(BN); return ORE_OK; }                                      // BM = -16: its ablation flags (trace build only; no effect in the product library)
-    if (BM == -15) { conv_gd_force(BN, WGM, WGN); return ORE_OK; }                          // BM = -15: force its build (BM, BN, NS)
-    if (BM == -12) { conv_kd_mode(BN); return ORE_OK; }                                     // BM = -12: lean LDS-DMA kernel 0 off / 1 automatic / 2 wherever it applies
-    if (BM == -13) { conv_kd_force(BN, WGM, WGN, WGK); return ORE_OK; }                     // BM = -13: force its build (BM, BN, NW, SB)
-    if (BM == -10) { conv_rf_mode(BN); return ORE_OK; }                                     // BM = -10: register-fed small-M kernel 0 off / 1 automatic / 2 wherever it applies
-    if (BM == -11) { conv_rf_force(BN, WGM, WGN); return ORE_OK; }                          // BM = -11: force its build (GB, NW, MAXS)
-    if (BM == -9) { g_ws_s2_mode = BN; return ORE_OK; }                                     // BM = -9: weight-stationary stride-2 kernel (stem_3) 0 off / 1 on
-    if (BM == -8) { g_ws_sb_mode = BN; return ORE_OK; }                                     // BM = -8: bf16-storage weight-stationary 3x3 kernel: 0 off, 1 auto, 4 / 8 tile height
-    if (BM == -7) { conv_wino_mode(BN); return ORE_OK; }                                    // BM = -7: Winograd kernel 0 off / 1 automatic / 2 forced
-    if (BM == -6) { conv_kw_nw_force(BN); return ORE_OK; }                                  // BM = -6: waves per block of k_conv_kw (4 / 8 / 16)                                   // BM = -5: block -> tile mapping of k_conv_kw (-1 auto, 0, 1, 2)                           // BM = -4: tile of k_conv_gs                 // BM = -3: (tile BM, tile BN, ring depth, split-K) of k_conv_kw      // BM = -2: BN selects the k_conv_kw mode (0 / 1 / 2)
-    g_override = {BM, BN, WGM, WGN, WGK};
-    return ORE_OK;
-}
-
 #ifdef ORE_TRACE
 extern "C" int ore_debug_set_trace(unsigned long long* buf) {
     ORE_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_trace), &buf, sizeof(buf)));
@@ -1333,100 +1112,8 @@ extern "C" int ore_conv_set_precision(int32_t mode) {
 
 extern "C" int32_t ore_conv_get_precision(void) { return g_conv_mode; }
 
-extern "C" int32_t ore_conv_colsum_rows(const ore_conv_desc* d) {
-    if (!d) return 0;
-    const int Ho = (d->H + 2 * d->pad - d->kh) / d->stride + 1, Wo = (d->W + 2 * d->pad - d->kw) / d->stride + 1;
-    if (!d->storage && conv_kd_forced()) return ceil_div(d->B * Ho * Wo, conv_kd_forced_bm());   // tuning aids: forced builds
-    if (!d->storage && conv_gd_forced()) return ceil_div(d->B * Ho * Wo, conv_gd_forced_bm());
-    if (!d->storage && conv_rf_forced()) return ceil_div(d->B * Ho * Wo, 16);   // tuning aid: the forced register-fed build has 16-row tiles (a fallback kernel writes fewer rows)
-    if (d->storage) {                                         // bf16 storage: always the DMA-fed kernels (conv_kw_launch's sb branch)
-        ConvP q{};
-        q.sb = 1 | (d->storage == ORE_ST_BF16 ? 2 : 0) | (d->add ? 4 : 0);
-        q.M = d->B * Ho * Wo; q.Cout16 = round_up(d->Cout, 16); q.nchunks = d->kh * d->kw * (round_up(d->Cin, 32) / 32); q.kh = d->kh;
-        q.stride = d->stride;
-        // what the lean-DMA kernel's "does it apply" test looks at, in the 4-byte units of this mode (keep in step with fill_common)
-        q.kw = d->kw; q.Cin = round_up(d->Cin, 32) / 2; q.in_ld = d->in_ld / 2; q.in_coff = d->in_coff / 2; q.B = d->B; q.nlev = 1; q.K = d->kh * d->kw * q.Cin; q.Cout = d->Cout;
-        q.lv[0] = Lvl{0, 0, d->H, d->W, Ho, Wo}; q.in_add = d->in_add; q.in_relu = d->in_relu; q.in_mul = d->in_mul; q.colsum = d->colsum;
-        if (d->add) { q.add = d->add; q.add_ld = d->add_ld; q.add_H = (Ho + 1) / 2; q.add_W = (Wo + 1) / 2; }
-        return ceil_div(q.M, conv_kw_tile_rows(q));
-    }
-    if (g_override.BM == 0 && d->splitk <= 1 && g_kw_mode && !d->in_mul && d->Cin % 16 == 0) {
-        ConvP q{};
-        q.bf16 = g_conv_bf16;
-        q.M = d->B * Ho * Wo; q.Cout16 = round_up(d->Cout, 16); q.nchunks = d->kh * d->kw * (d->Cin / 16); q.kh = d->kh;
-        // what the lean-DMA kernel's "does it apply" test looks at (conv_kd_tile_rows; keep in step with make_conv_params)
-        q.kw = d->kw; q.Cin = d->Cin; q.in_ld = d->in_ld; q.in_coff = d->in_coff; q.B = d->B; q.nlev = 1; q.K = d->kh * d->kw * d->Cin; q.Cout = d->Cout;
-        q.lv[0] = Lvl{0, 0, d->H, d->W, Ho, Wo}; q.in_add = d->in_add; q.in_relu = d->in_relu;
-        if (d->add) { q.add = d->add; q.add_ld = d->add_ld; q.add_H = (Ho + 1) / 2; q.add_W = (Wo + 1) / 2; }
-        const int bm = conv_kw_tile_rows(q);
-        if (bm > 0) return ceil_div(q.M, bm);                 // the layer runs on k_conv_kw (same test as conv_launch)
-    }
-    TileCfg t; int S, sps;
-    plan_conv(d->B * Ho * Wo, d->Cout, d->kh * d->kw * (d->Cin / 16), d->splitk, &t, &S, &sps);
-    return ceil_div(d->B * Ho * Wo, t.BM);
-}
-
-static int conv_launch(ConvP& p, int req_splitk, float* workspace, size_t workspace_floats, hipStream_t st) {
-    if (p.sb & 1) {                                           // bf16 storage: weight-stationary 3x3 kernel, else the DMA-fed kernels (SB builds)
-        p.bf16 = 0;
-        const int wrc = ws_sb_launch(p, st);
-        if (wrc != 1) return wrc;
-        const int src = ws_s2_launch(p, st);
-        if (src != 1) return src;
-        const int krc = conv_kw_launch(p, workspace, workspace_floats, st);
-        if (krc == 1) { ore_set_error("ore_conv2d_fwd: no bf16-storage kernel for this layer (input affine?)"); return ORE_EINVAL; }
-        return krc;
-    }
-    if (g_override.BM == 0 && req_splitk <= 1) {
-        // several pyramid levels in one launch (the head tower): the 16-pixel-wide patch tiles waste 17-37 % on the 40- and 20-wide
-        // levels, k_conv_kw takes it (47 -> 39 us, profiles/r02_kw_sweep.txt)
-        p.bf16 = g_conv_bf16;
-        const int wrc = conv_wino_launch(p, st);              // Winograd F(2x2,3x3): large-M 3x3 layers that were handed transformed weights
-        if (wrc != 1) return wrc;
-        if (g_kw_mode) {                                      // large M that is not Winograd's: shared-stage LDS-DMA with descriptor addressing
-            const int grc = conv_gd_launch(p, st);            // (ore_conv_gd.hip: stem_3, the stage-2 / 3 concats)
-            if (grc != 1) return grc;
-        }
-        const bool kw_first = g_kw_mode == 2 || (g_kw_mode == 1 && p.nlev > 1);
-        const int prc = kw_first ? 1 : patch_launch(p, st);
-        if (prc != 1) return prc;
-        if (g_kw_mode) {                                      // small / medium M: the wave-private K-split LDS-DMA kernel (ore_conv_kw.hip)
-            const int krc = conv_kw_launch(p, workspace, workspace_floats, st);
-            if (krc != 1) return krc;
-            if (kw_first && g_kw_mode != 2) {                 // not covered after all: the patch kernels get their turn
-                const int prc2 = patch_launch(p, st);
-                if (prc2 != 1) return prc2;
-            }
-        }
-    }
-    TileCfg t; int S, sps;
-    plan_conv(p.M, p.Cout, p.nchunks, req_splitk, &t, &S, &sps);
-    const int gx = ceil_div(p.M, t.BM), gy = ceil_div(p.Cout16, t.BN);
-    if (S > 1) {
-        const size_t need = ORE_CONV_CNT_INTS + (size_t)gx * gy * S * t.BM * t.BN;
-        if (!workspace || workspace_floats < need || gx * gy > ORE_CONV_CNT_INTS) {
-            if (req_splitk > 1) {
-                ore_set_error("ore_conv2d_fwd: split-K %d needs %zu workspace floats (have %zu) and <= %d tiles (have %d)", S, need,
-                              workspace_floats, ORE_CONV_CNT_INTS, gx * gy);
-                return ORE_ENOMEM;
-            }
-            S = 1; sps = ceil_div(p.nchunks, t.WGK);       // automatic plan falls back to no split
-        }
-    }
-    p.splitk = S; p.steps_per_split = sps;
-    p.tile_cnt = reinterpret_cast<int*>(workspace);
-    p.ws = workspace ? workspace + ORE_CONV_CNT_INTS : nullptr;
-    p.xmap = conv_choose_xmap(p, gx, gy);
-    ore_note_launch(ORE_LAUNCH_IGEMM, S);
-    const int rc = dispatch(p, t, dim3(gx, gy, S), st);
-    if (rc != ORE_OK) {
-        ore_set_error("ore_conv2d_fwd: no %skernel for tile %dx%d (%d,%d,%d)", g_conv_bf16 ? "bf16 " : "", t.BM, t.BN, t.WGM, t.WGN, t.WGK);
-        return rc;
-    }
-    return ore_launch_status("k_conv_igemm");
-}
-
-static int conv_common_checks(const ore_conv_desc* d) {
+// Checks the arguments of an ore_conv2d_fwd (n_levels = 0) or ore_conv2d_levels_fwd call and fills the kernel parameter block
+static int conv_setup(ConvP& p, const ore_conv_desc* d, int n_levels, const int32_t* H, const int32_t* W, int ep_stride) {
     ORE_CHECK_ARG(d && d->in && d->w && d->out, "ore_conv2d_fwd: null pointer");
     ORE_CHECK_ARG(d->Cin > 0 && d->Cin % 16 == 0, "ore_conv2d_fwd: Cin=%d must be a multiple of 16", d->Cin);
     ORE_CHECK_ARG(d->in_ld % 4 == 0 && d->in_coff % 4 == 0 && d->in_coff + d->Cin <= d->in_ld,
@@ -1439,10 +1126,7 @@ static int conv_common_checks(const ore_conv_desc* d) {
     if (d->storage) {
         ORE_CHECK_ARG(d->in_ld % 8 == 0 && d->in_coff % 8 == 0 && !d->in_mul, "ore_conv2d_fwd: bf16 storage needs 16-byte aligned input slices and no input affine");
     }
-    return ORE_OK;
-}
-
-static void fill_common(ConvP& p, const ore_conv_desc* d) {
+    p = ConvP{};
     p.in = d->in; p.in_ld = d->in_ld; p.in_coff = d->in_coff;
     p.B = d->B; p.Cin = d->Cin; p.w = d->w;
     p.Cout = d->Cout; p.Cout16 = round_up(d->Cout, 16);
@@ -1454,9 +1138,8 @@ static void fill_common(ConvP& p, const ore_conv_desc* d) {
     p.nchunks = d->kh * d->kw * (d->Cin / 16);
     p.colsum = d->colsum;
     p.wino = d->w_wino;
-    p.wino_lstride = 0;
-    p.w_lstride = 0;
-    p.sb = 0;
+    p.tile_cnt = reinterpret_cast<int*>(d->workspace);
+    p.ws = d->workspace ? d->workspace + ORE_CONV_CNT_INTS : nullptr;
     if (d->storage == ORE_ST_BF16 || d->storage == ORE_ST_BF16_F32OUT) {
         // bf16 tensors: the input side is handed to the kernels in 4-byte units (pairs of channels); the packed weights hold
         // round_up(Cin, 32) channels per tap (zero beyond Cin), so a 64-byte K chunk is 32 channels and a chunk that starts inside the
@@ -1468,71 +1151,101 @@ static void fill_common(ConvP& p, const ore_conv_desc* d) {
         p.nchunks = d->kh * d->kw * (p.Cin / 16);
         p.wino = nullptr;
     }
+    if (n_levels == 0) {
+        ORE_CHECK_ARG(d->H > 0 && d->W > 0, "ore_conv2d_fwd: bad geometry");
+        p.nlev = 1;
+        Lvl& L = p.lv[0];
+        L.orow0 = 0; L.irow0 = 0; L.H = d->H; L.W = d->W;
+        L.Ho = (d->H + 2 * d->pad - d->kh) / d->stride + 1;
+        L.Wo = (d->W + 2 * d->pad - d->kw) / d->stride + 1;
+        ORE_CHECK_ARG(L.Ho > 0 && L.Wo > 0, "ore_conv2d_fwd: empty output");
+        p.M = d->B * L.Ho * L.Wo;
+        p.add = d->add; p.add_ld = d->add_ld; p.add_coff = d->add_coff;
+        p.add_H = (L.Ho + 1) / 2; p.add_W = (L.Wo + 1) / 2;
+    } else {
+        // the same conv over several pyramid levels: rows are level-major ([level][b][y][x]) in both the input and the output matrix
+        ORE_CHECK_ARG(n_levels >= 1 && n_levels <= 4 && H && W, "ore_conv2d_levels_fwd: 1..4 levels");
+        ORE_CHECK_ARG(d->stride == 1 && d->pad == d->kh / 2 && d->kh == d->kw && !d->add, "ore_conv2d_levels_fwd: 'same' convs only, no add");
+        p.nlev = n_levels;
+        int rows = 0;
+        for (int l = 0; l < n_levels; ++l) {
+            ORE_CHECK_ARG(H[l] > 0 && W[l] > 0, "ore_conv2d_levels_fwd: level %d geometry", l);
+            p.lv[l] = {rows, rows, H[l], W[l], H[l], W[l]};
+            rows += d->B * H[l] * W[l];
+        }
+        p.M = rows;
+        p.ep_stride = ep_stride;
+        if (d->w_level_stride) {                                  // per-level layers, bf16 storage: the weight-stationary 3x3 kernel or nothing
+            ORE_CHECK_ARG(d->w_level_stride > 0 && d->w_level_stride % 2 == 0 && d->kh == 3 && d->storage == ORE_ST_BF16 && !d->in_mul && !d->colsum &&
+                              !d->w_wino_level_stride,
+                          "ore_conv2d_levels_fwd: w_level_stride is for 3x3 layers in bf16 storage (ORE_ST_BF16)");
+            p.w_lstride = (size_t)d->w_level_stride / 2;          // the kernels count the bf16 side in 4-byte units
+        } else if (d->w_wino_level_stride) {                      // per-level layers: the Winograd kernel or nothing
+            ORE_CHECK_ARG(d->w_wino && d->w_wino_level_stride > 0 && d->kh == 3 && d->storage == ORE_ST_F32 && !d->in_mul && !d->colsum &&
+                              conv_wino_covers(d->Cout, d->Cin) && (d->Cin == 64 || d->Cin == 128),
+                          "ore_conv2d_levels_fwd: per-level weights need the Winograd form of a 3x3 layer with 64 / 128 input channels, fp32 storage");
+            p.wino_lstride = (size_t)d->w_wino_level_stride;
+        }
+    }
+    p.bf16 = (p.sb || p.wino_lstride) ? 0 : g_conv_bf16;       // bf16 storage and per-level Winograd weights multiply in their own precision
+    return ORE_OK;
 }
 
-extern "C" int ore_conv2d_fwd(const ore_conv_desc* d, void* stream) {
+static int conv_run(const ore_conv_desc* d, int n_levels, const int32_t* H, const int32_t* W, int ep_stride, hipStream_t st) {
     ore_note_wino(0);
     ore_note_launch(ORE_LAUNCH_NONE, 1);
-    int rc = conv_common_checks(d);
+    ConvP p;
+    const int rc = conv_setup(p, d, n_levels, H, W, ep_stride);
     if (rc) return rc;
-    ORE_CHECK_ARG(d->H > 0 && d->W > 0, "ore_conv2d_fwd: bad geometry");
-    ConvP p{};
-    fill_common(p, d);
-    p.nlev = 1;
-    Lvl& L = p.lv[0];
-    L.orow0 = 0; L.irow0 = 0; L.H = d->H; L.W = d->W;
-    L.Ho = (d->H + 2 * d->pad - d->kh) / d->stride + 1;
-    L.Wo = (d->W + 2 * d->pad - d->kw) / d->stride + 1;
-    ORE_CHECK_ARG(L.Ho > 0 && L.Wo > 0, "ore_conv2d_fwd: empty output");
-    p.M = d->B * L.Ho * L.Wo;
-    p.ep_stride = 0;
-    p.add = d->add; p.add_ld = d->add_ld; p.add_coff = d->add_coff;
-    p.add_H = (L.Ho + 1) / 2; p.add_W = (L.Wo + 1) / 2;
     ore_flop_count_add(2.0 * (double)p.M * d->Cout * d->Cin * d->kh * d->kw);
-    return conv_launch(p, d->splitk, d->workspace, d->workspace_floats, (hipStream_t)stream);
+    const ConvPlan pl = conv_plan(p, d->splitk, d->workspace_floats);
+    if (pl.error) return pl.error;
+    ore_note_launch(pl.launcher, pl.splitk);
+    p.splitk = pl.splitk; p.steps_per_split = pl.steps_per_split; p.xmap = pl.xmap;
+    switch (pl.launcher) {
+    case ORE_LAUNCH_WS_SB: case ORE_LAUNCH_WS64: case ORE_LAUNCH_WS128: return launch_ws(p, pl, st);
+    case ORE_LAUNCH_PATCH4: case ORE_LAUNCH_PATCH8: case ORE_LAUNCH_PATCH_DB: return launch_patch(p, pl, st);
+    case ORE_LAUNCH_WINO: case ORE_LAUNCH_WINO_NU: return launch_wino(p, pl, st);
+    case ORE_LAUNCH_GD: return launch_gd(p, pl, st);
+    case ORE_LAUNCH_KD: return launch_kd(p, pl, st);
+    case ORE_LAUNCH_RF: return launch_rf(p, pl, st);
+    case ORE_LAUNCH_GS: return launch_gs(p, pl, st);
+    case ORE_LAUNCH_KW: return launch_kw(p, pl, st);
+    case ORE_LAUNCH_IGEMM: return launch_igemm(p, pl, st);
+    }
+    ore_set_error("ore_conv2d_fwd: plan names launcher %d", pl.launcher);
+    return ORE_EINVAL;
 }
+
+extern "C" int ore_conv2d_fwd(const ore_conv_desc* d, void* stream) { return conv_run(d, 0, nullptr, nullptr, 0, (hipStream_t)stream); }
 
 // Same conv over several pyramid levels in ONE launch: rows are level-major ([level][b][y][x]) in both the input
 // and the output matrix; scale/shift may differ per level (ep_stride floats apart); in_mul/in_add are [level*B+b][Cin].
 extern "C" int ore_conv2d_levels_fwd(const ore_conv_desc* d, int32_t n_levels, const int32_t* H, const int32_t* W,
                                      int32_t ep_stride, void* stream) {
-    ore_note_wino(0);
-    ore_note_launch(ORE_LAUNCH_NONE, 1);
-    int rc = conv_common_checks(d);
-    if (rc) return rc;
-    ORE_CHECK_ARG(n_levels >= 1 && n_levels <= 4 && H && W, "ore_conv2d_levels_fwd: 1..4 levels");
-    ORE_CHECK_ARG(d->stride == 1 && d->pad == d->kh / 2 && d->kh == d->kw && !d->add, "ore_conv2d_levels_fwd: 'same' convs only, no add");
-    ConvP p{};
-    fill_common(p, d);
-    p.nlev = n_levels;
-    int rows = 0;
-    for (int l = 0; l < n_levels; ++l) {
-        ORE_CHECK_ARG(H[l] > 0 && W[l] > 0, "ore_conv2d_levels_fwd: level %d geometry", l);
-        p.lv[l] = {rows, rows, H[l], W[l], H[l], W[l]};
-        rows += d->B * H[l] * W[l];
+    return conv_run(d, n_levels ? n_levels : -1, H, W, ep_stride, (hipStream_t)stream);   // (n_levels = 0 is not a level count here)
+}
+
+extern "C" int ore_conv_plan(const ore_conv_desc* d, int32_t n_levels, const int32_t* H, const int32_t* W, int32_t ep_stride, ore_conv_plan_t* out) {
+    ORE_CHECK_ARG(out, "ore_conv_plan: null plan");
+    *out = ConvPlan{};
+    ConvP p;
+    int rc = conv_setup(p, d, n_levels, H, W, ep_stride);
+    if (rc == ORE_OK) {
+        *out = conv_plan(p, d->splitk, d->workspace_floats);
+        rc = out->error;
     }
-    p.M = rows;
-    p.ep_stride = ep_stride;
-    ore_flop_count_add(2.0 * (double)rows * d->Cout * d->Cin * d->kh * d->kw);
-    if (d->w_level_stride) {                                  // per-level layers, bf16 storage: the weight-stationary 3x3 kernel or nothing
-        ORE_CHECK_ARG(d->w_level_stride > 0 && d->w_level_stride % 2 == 0 && d->kh == 3 && d->storage == ORE_ST_BF16 && !d->in_mul && !d->colsum &&
-                          !d->w_wino_level_stride,
-                      "ore_conv2d_levels_fwd: w_level_stride is for 3x3 layers in bf16 storage (ORE_ST_BF16)");
-        p.w_lstride = (size_t)d->w_level_stride / 2;              // the kernels count the bf16 side in 4-byte units
-        p.bf16 = 0;
-        const int wrc = ws_sb_launch(p, (hipStream_t)stream);
-        if (wrc == 1) { ore_set_error("ore_conv2d_levels_fwd: the weight-stationary bf16 kernel does not cover this per-level launch (64 / 128 channels, Cout %% 64 == 0)"); return ORE_EINVAL; }
-        return wrc;
-    }
-    if (d->w_wino_level_stride) {                             // per-level layers: the Winograd kernel or nothing
-        ORE_CHECK_ARG(d->w_wino && d->w_wino_level_stride > 0 && d->kh == 3 && d->storage == ORE_ST_F32 && !d->in_mul && !d->colsum &&
-                          oreconv::conv_wino_covers(d->Cout, d->Cin) && (d->Cin == 64 || d->Cin == 128),
-                      "ore_conv2d_levels_fwd: per-level weights need the Winograd form of a 3x3 layer with 64 / 128 input channels, fp32 storage");
-        p.wino_lstride = (size_t)d->w_wino_level_stride;
-        p.bf16 = 0;
-        const int wrc = conv_wino_launch(p, (hipStream_t)stream);
-        if (wrc == 1) { ore_set_error("ore_conv2d_levels_fwd: the Winograd kernel does not cover this per-level launch (alignment / mode)"); return ORE_EINVAL; }
-        return wrc;
-    }
-    return conv_launch(p, d->splitk, d->workspace, d->workspace_floats, (hipStream_t)stream);
+    out->error = rc;
+    return rc;
+}
+
+// rows of d->colsum: the row tiles of the kernel the call will run (d->colsum itself may still be null)
+extern "C" int32_t ore_conv_colsum_rows(const ore_conv_desc* d) {
+    if (!d) return 0;
+    ore_conv_desc q = *d;
+    if (!q.colsum) q.colsum = reinterpret_cast<float*>(q.workspace ? q.workspace : q.out);   // (any non-null address: only its presence is planned)
+    ore_conv_plan_t pl;
+    if (ore_conv_plan(&q, 0, nullptr, nullptr, 0, &pl) != ORE_OK) return 0;
+    const int Ho = (d->H + 2 * d->pad - d->kh) / d->stride + 1, Wo = (d->W + 2 * d->pad - d->kw) / d->stride + 1;
+    return ceil_div(d->B * Ho * Wo, pl.bm);
 }

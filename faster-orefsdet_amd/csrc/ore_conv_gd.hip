@@ -29,8 +29,7 @@
 namespace {
 using namespace oreconv;
 
-constexpr unsigned kOOB = 0x80000000u;
-constexpr int kTab = 64;                          // chunk table entries: K up to 1024 (stem_3: 36, the concats: 20 / 22)
+constexpr int kTab = kGdTab;                      // chunk table entries
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
@@ -338,26 +337,11 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_conv_gd(GdP q) {
     }
 }
 
-int g_gd_mode = 1;                       // tuning aid (ore_conv_set_plan_override(-14, mode)): 0 off, 1 automatic, 2 automatic + every 1x1 layer at training sizes, 3 automatic with the round-4 limit M <= 32768
-int g_gd_force[3] = {0, 0, 0};           // (-15, BM, BN, NS): force the build
-int g_gd_dbg = 0;                        // trace build: ablation flags, ore_conv_set_plan_override(-16, flags)
-
-template <int GA, int GB, int WGM, int WGN, int NS>
-int launch_gd_bf(const GdP& q, bool k3, dim3 grid, hipStream_t st) {
+template <int GA, int GB, int WGM, int WGN, int NS, bool BF = false>
+int gd_go(const GdP& q, bool k3, dim3 grid, hipStream_t st) {
     const dim3 block(64 * WGM * WGN);
     constexpr size_t lds = (size_t)NS * (GA + GB) * 256 * sizeof(float);
-    static_assert(lds <= 64 * 1024, "the bf16-operand builds keep the default LDS limit");
-    ore_note_launch(ORE_LAUNCH_GD, 1);
-    if (!k3) hipLaunchKernelGGL((k_conv_gd<GA, GB, WGM, WGN, NS, 1, true>), grid, block, lds, st, q);
-    else hipLaunchKernelGGL((k_conv_gd<GA, GB, WGM, WGN, NS, 3, true>), grid, block, lds, st, q);
-    return ore_launch_status("k_conv_gd<bf16 operands>");
-}
-
-template <int GA, int GB, int WGM, int WGN, int NS>
-int launch_gd(const GdP& q, bool k3, dim3 grid, hipStream_t st) {
-    const dim3 block(64 * WGM * WGN);
-    constexpr size_t lds = (size_t)NS * (GA + GB) * 256 * sizeof(float);
-    static_assert(lds <= 128 * 1024, "LDS ring");
+    static_assert(lds <= (BF ? 64 : 128) * 1024, "LDS ring (the bf16-operand builds keep the default LDS limit)");
     if constexpr (lds > 64 * 1024) {                   // the one-block-per-CU builds
         static bool attr[2] = {false, false};
         if (!attr[k3]) {
@@ -366,82 +350,21 @@ int launch_gd(const GdP& q, bool k3, dim3 grid, hipStream_t st) {
             attr[k3] = true;
         }
     }
-    ore_note_launch(ORE_LAUNCH_GD, 1);
-    if (!k3) hipLaunchKernelGGL((k_conv_gd<GA, GB, WGM, WGN, NS, 1>), grid, block, lds, st, q);
-    else hipLaunchKernelGGL((k_conv_gd<GA, GB, WGM, WGN, NS, 3>), grid, block, lds, st, q);
-    return ore_launch_status("k_conv_gd");
+    if (!k3) hipLaunchKernelGGL((k_conv_gd<GA, GB, WGM, WGN, NS, 1, BF>), grid, block, lds, st, q);
+    else hipLaunchKernelGGL((k_conv_gd<GA, GB, WGM, WGN, NS, 3, BF>), grid, block, lds, st, q);
+    return ore_launch_status(BF ? "k_conv_gd<bf16 operands>" : "k_conv_gd");
 }
 
 }  // namespace
 
 namespace oreconv {
 
-void conv_gd_mode(int mode) { g_gd_mode = mode; }
-void conv_gd_dbg(int flags) { g_gd_dbg = flags; }
-void conv_gd_force(int bm, int bn, int ns) { g_gd_force[0] = bm; g_gd_force[1] = bn; g_gd_force[2] = ns; }
-bool conv_gd_forced() { return g_gd_force[0] > 0; }
-int conv_gd_forced_bm() { return g_gd_force[0]; }
-
-// several pyramid levels in one launch: a 1x1 stride-1 layer over the level-major row matrix is one flat GEMM (as in k_conv_kd)
-static bool gd_flat(const ConvP& p) { return p.nlev > 1 && p.kh == 1 && p.kw == 1 && p.stride == 1 && p.pad == 0; }
-
-static bool gd_applies(const ConvP& p) {
-    if (p.sb || p.in_mul || p.in_add || p.in_relu || (p.nlev != 1 && !gd_flat(p)) || p.ep_stride || (p.add && p.nlev != 1)) return false;
-    if (p.Cin % 16 != 0 || p.in_ld % 16 != 0 || p.kh != p.kw || (p.kh != 1 && p.kh != 3)) return false;
-    if (p.M >= (1 << 22) || p.nchunks > kTab) return false;
-    const long long in_rows = gd_flat(p) ? (long long)p.lv[0].irow0 + p.M : (long long)p.lv[0].irow0 + (long long)p.B * p.lv[0].H * p.lv[0].W;
-    if (in_rows * p.in_ld * 4 >= (long long)kOOB - (1 << 24) || (long long)p.Cout16 * p.K * 4 >= (long long)kOOB) return false;
-    if (p.add && (long long)p.B * p.add_H * p.add_W * p.add_ld * 4 >= (long long)kOOB) return false;
-    return true;
-}
-
-struct GdPlan { int bm, bn, ns; };
-static GdPlan gd_plan_any(const ConvP& p) {
-    if (g_gd_force[0] > 0) return {g_gd_force[0], g_gd_force[1], g_gd_force[2]};
-    // from tools/kw_phase_trace.py gd (profiles/r04_gd_times.txt; eager launches back to back, one MI355X, bs = 1 shapes; ns >= 10: eight waves):
-    //   stage-3 concat 352 -> 256 at M = 6400: 17.9 us (k_conv_gs 21.2); stage-2 concat 320 -> 112 at M = 25600: 27.7 (31.1);
-    //   stem_3 3x3 / 2 64 -> 128 at M = 25600: 44.0 (k_conv_igemm 62.7).
-    // Every tiling of a layer lands within ~10 % of the others (r04_gd_ablation.txt: the MFMA phase alone runs at ~75 % of the peak,
-    // staging adds to it instead of hiding behind it); the choices below are the fastest measured, not a structural preference.
-    // (training batch sizes -- the frozen stem_3 / concats over 16 queries + 384 support crops, M up to 1.6 M rows -- run on the same
-    // tiles since round 5: bs-16 step 46.7 -> 43.8 ms, tools/bench_train.py; mode 3 = the round-4 limit M <= 32768 for A/B)
-    if (p.M < 4096 || (p.M > 32768 && g_gd_mode == 3)) return {0, 0, 0};
-    if (p.kh == 1 && p.Cout16 == 256 && p.nchunks >= 16) return {64, 64, 4};
-    if (p.kh == 1 && p.Cout16 == 112 && p.nchunks >= 16) return {128, 64, 14};
-    if (p.kh == 3 && p.stride == 2 && p.Cout16 == 128 && p.Cin == 64) return {112, 128, 14};
-    // the FPN lateral of stage 3 (M = 6400) and conv3 over the three levels (M = 8400), 256 -> 128 (profiles/r04_gd_mid.txt):
-    // 9.4 us against k_conv_kd's 11.7 when 64 x 64 tiles fill the CUs once, 12.6 against 20.1 when they would spill into a second round
-    if (p.kh == 1 && p.Cout16 == 128 && p.nchunks == 16 && !p.colsum)
-        return ceil_div(p.M, 64) * 2 <= 256 ? GdPlan{64, 64, 14} : GdPlan{32, 64, 4};
-    // every other 1x1 layer at training batch sizes (the trainable concats, laterals, conv3 and their data gradients over 16 queries /
-    // 384 support crops: M >= 16384 rows): 64 x 128 tiles, or 64 x 64 for narrow outputs (round 5; they ran on k_conv_gs / k_conv_igemm)
-    if (g_gd_mode == 2 && p.kh == 1 && p.M >= 16384 && p.nchunks >= 4 && !p.colsum) return p.Cout16 > 64 ? GdPlan{64, 128, 4} : GdPlan{64, 64, 4};
-    return {0, 0, 0};
-}
-
-// the bf16-OPERAND mode has builds of the four-wave tiles only (keep in step with GD_BF in conv_gd_launch); a layer planned on another
-// tile is not this kernel's in that mode -- said here, so that the column-sum rows a caller plans are those of the kernel that will run
-static GdPlan gd_plan(const ConvP& p) {
-    const GdPlan pl = gd_plan_any(p);
-    if (p.bf16 && !((pl.bm == 64 && pl.bn == 128 && pl.ns == 4) || (pl.bm == 64 && pl.bn == 64 && pl.ns == 4) || (pl.bm == 32 && pl.bn == 64 && pl.ns == 4)))
-        return {0, 0, 0};
-    return pl;
-}
-
-int conv_gd_tile_rows(const ConvP& p) {
-    if (g_gd_mode == 0 || !gd_applies(p)) return 0;
-    return gd_plan(p).bm;
-}
-
-// Returns 1 when the layer is not covered.
-int conv_gd_launch(ConvP& p, hipStream_t st) {
-    if (g_gd_mode == 0 || !gd_applies(p)) return 1;
-    const GdPlan pl = gd_plan(p);
-    if (pl.bm == 0) return 1;
-    const int gx = ceil_div(p.M, pl.bm), gy = ceil_div(p.Cout16, pl.bn);
+// k_conv_gd: the plan's tile and build over p's rows (several levels of a 1x1 layer: one flat GEMM)
+int launch_gd(const ConvP& p, const ConvPlan& pl, hipStream_t st) {
+    const int gx = pl.gx, gy = pl.gy;
     Lvl L = p.lv[0];
     int Bimg = p.B;
-    if (gd_flat(p)) { L.H = 1; L.W = p.M; L.Ho = 1; L.Wo = p.M; Bimg = 1; }      // one "image" of M pixels in a row
+    if (p.nlev > 1) { L.H = 1; L.W = p.M; L.Ho = 1; L.Wo = p.M; Bimg = 1; }      // one "image" of M pixels in a row
     GdP q;
     GdK& k = q.k;
     k.in = p.in; k.w = p.w; k.scale = p.scale; k.shift = p.shift; k.add = p.add; k.out = p.out; k.colsum = p.colsum;
@@ -453,9 +376,9 @@ int conv_gd_launch(ConvP& p, hipStream_t st) {
     k.M = p.M; k.K = p.K; k.Cout = p.Cout; k.Cout16 = p.Cout16; k.nchunks = p.nchunks;
     k.irow0 = L.irow0; k.H = L.H; k.W = L.W; k.Ho = L.Ho; k.Wo = L.Wo; k.in_ld = p.in_ld; k.in_coff = p.in_coff; k.stride = p.stride; k.pad = p.pad;
     k.out_ld = p.out_ld; k.out_coff = p.out_coff; k.relu_cout = p.relu_cout; k.zc_stride = 0; k.out_zstride = 0;
-    k.xmap = conv_choose_xmap(p, gx, gy); k.gx = gx; k.gy = gy;
+    k.xmap = pl.xmap; k.gx = gx; k.gy = gy;
 #ifdef ORE_TRACE
-    k.dbg = g_gd_dbg;
+    k.dbg = g_knobs.gd_dbg;
 #endif
     k.inv_hw = 1.0f / (float)(L.Ho * L.Wo); k.inv_wo = 1.0f / (float)L.Wo; k.inv_gx = 1.0f / (float)gx; k.inv_gy = 1.0f / (float)gy;
     for (int c = 0; c < kTab; ++c) q.tab[c] = 15u;
@@ -468,22 +391,12 @@ int conv_gd_launch(ConvP& p, hipStream_t st) {
     }
     const bool k3 = p.kh == 3;
     const dim3 grid(gx, gy, 1);
-    if (p.bf16) {                                            // bf16-operand builds: the four-wave tiles with the default LDS limit
-#define GD_BF(bm_, bn_, wgm_, wgn_, ns_) if (pl.bm == bm_ && pl.bn == bn_ && pl.ns == ns_) return launch_gd_bf<bm_ / 16, bn_ / 16, wgm_, wgn_, ns_>(q, k3, grid, st);
-        GD_BF(64, 128, 2, 2, 4) GD_BF(64, 64, 2, 2, 4) GD_BF(32, 64, 1, 4, 4)
-#undef GD_BF
-        return 1;                                            // no bf16-operand build of this tile: the caller's other kernels take it
-    }
-    // ring depth as forced / planned: ns, or 10 + ns for the eight-wave build of the tile
-#define GD_CASE(bm_, bn_, wgm_, wgn_, ns_) if (pl.bm == bm_ && pl.bn == bn_ && pl.ns == ((wgm_) * (wgn_) == 8 ? 10 + ns_ : ns_)) return launch_gd<bm_ / 16, bn_ / 16, wgm_, wgn_, ns_>(q, k3, grid, st);
-    GD_CASE(64, 128, 2, 2, 4) GD_CASE(64, 64, 2, 2, 4) GD_CASE(64, 112, 4, 1, 4) GD_CASE(128, 64, 4, 1, 4) GD_CASE(128, 128, 2, 2, 4) GD_CASE(32, 128, 1, 4, 4)
-    GD_CASE(128, 112, 4, 1, 4) GD_CASE(208, 64, 1, 4, 4) GD_CASE(224, 64, 1, 4, 4) GD_CASE(112, 64, 1, 4, 4) GD_CASE(96, 128, 2, 2, 4) GD_CASE(64, 128, 2, 2, 2)
-    GD_CASE(128, 128, 2, 2, 2) GD_CASE(208, 64, 1, 4, 2) GD_CASE(128, 112, 4, 1, 2)
-    GD_CASE(128, 128, 2, 4, 4) GD_CASE(112, 128, 1, 8, 4) GD_CASE(128, 112, 8, 1, 4) GD_CASE(64, 128, 2, 4, 4) GD_CASE(128, 64, 4, 2, 4) GD_CASE(64, 64, 2, 4, 4)
-    GD_CASE(128, 128, 2, 4, 2) GD_CASE(112, 128, 1, 8, 2) GD_CASE(80, 64, 1, 4, 4) GD_CASE(80, 128, 1, 4, 4) GD_CASE(48, 64, 1, 4, 4) GD_CASE(32, 64, 1, 4, 4)
-#undef GD_CASE
-    if (g_gd_force[0] > 0) { ore_set_error("k_conv_gd: no build for tile %dx%d, ring %d", pl.bm, pl.bn, pl.ns); return ORE_EINVAL; }
-    return 1;
+#define GD_GO(bm_, bn_, wgm_, wgn_, ns_, bf_)                                                                             \
+    if (pl.bm == bm_ && pl.bn == bn_ && pl.build[0] == wgm_ && pl.build[1] == wgn_ && pl.build[2] == ns_ && pl.build[3] == bf_) \
+        return gd_go<bm_ / 16, bn_ / 16, wgm_, wgn_, ns_, bf_>(q, k3, grid, st);
+    ORE_GD_BUILDS(GD_GO)
+#undef GD_GO
+    return ORE_EINVAL;
 }
 
 // The second-stage GEMM (d2z:modeling/roi_heads/box_head.py FastRCNNConvFCHead.fc1 with the DSA mix pre-composed into it: M <= 512
@@ -511,7 +424,7 @@ int conv_gd_splitk(const float* in, int in_ld, const float* w, int M, int K, int
     k.dbg = 0;
 #endif
     for (int c = 0; c < kTab; ++c) q.tab[c] = 15u;
-    return launch_gd<5, 4, 1, 4, 4>(q, false, dim3(gx, gy, S), st);
+    return gd_go<5, 4, 1, 4, 4>(q, false, dim3(gx, gy, S), st);
 }
 
 }  // namespace oreconv

@@ -1,4 +1,5 @@
-// Shared by the conv translation units of libore_hip.so (ore_conv.hip, ore_conv_kw.hip): the kernel parameter block.
+// Shared by the conv translation units of libore_hip.so: the kernel parameter block, the planner (ore_conv_plan.cpp) that picks the
+// kernel and build of every ore_conv2d*_fwd call, and the launchers that execute its plans.
 #pragma once
 #include "ore_common.h"
 
@@ -46,42 +47,100 @@ __device__ __forceinline__ void tile_of_block(int xmap, int& bx, int& by) {
 }
 
 
-// ore_conv_kw.hip: wave-private K-split kernel fed by LDS-DMA.  Returns 1 when the layer is not covered (the caller falls back).
-int conv_kw_launch(ConvP& p, float* workspace, size_t workspace_floats, hipStream_t st);
-// tile of the kw plan for (M, Cout): used by ore_conv_colsum_rows so the eSE reduction knows how many partial rows to expect
-int conv_kw_tile_rows(const ConvP& p);
-// tuning aid (ore_conv_set_plan_override(-3, bm, bn, ns, splitk)): force tile / ring depth / split of k_conv_kw; bm = 0 -> automatic
-void conv_kw_force(int bm, int bn, int ns, int splitk);
-int conv_choose_xmap(const ConvP& p, int gx, int gy);   // the mapping for a gx x gy tile grid of this layer
-void conv_kw_nw_force(int nw);                   // (-6, nw): waves per block of k_conv_kw; 0 -> automatic
-void conv_xmap_force(int mode);
-int conv_xmap_forced();                          // -1 when automatic                  // (-5, mode): -1 automatic, 0 / 1 / 2 force the block -> tile mapping of k_conv_kw
-// ore_conv_wino.hip: Winograd F(2x2,3x3) kernel for the large-M 3x3 stride-1 layers.  1 = not covered.
-int conv_wino_launch(const ConvP& p, hipStream_t st);
-void conv_wino_mode(int mode);                             // (-7, mode): 0 off, 1 automatic (by row count), 2 wherever it applies
+// Limits of the buffer-descriptor kernels that the planner's eligibility tests share with them
+constexpr unsigned kOOB = 0x80000000u;   // a byte offset beyond every buffer's num_records (< 2 GB here, and kOOB + an instruction offset
+                                         // cannot wrap): the load returns zeros
+constexpr int kGdTab = 64;               // k_conv_gd chunk table entries: K up to 1024 (stem_3: 36, the concats: 20 / 22)
+constexpr int kKdTab = 512;              // k_conv_kd: K up to 8192 (the second-stage GEMM)
+constexpr int kRfTab = 256;              // k_conv_rf (3x3 layers): covers K = 9 * 448 channels
+
+// The instantiated builds, one list per kernel: the planner takes a build only from its kernel's list, the launcher dispatches on it.
+// k_conv_igemm X(BM, BN, WGM, WGN, WGK, HASBF); HASBF: also built for bf16 operands (the tiles of the automatic plan)
+#define ORE_IGEMM_BUILDS(X)                                                                                                         \
+    /* large-M tiles: 4 waves along M, whole N in the block */                                                                     \
+    X(128, 16, 4, 1, 1, 0) X(128, 32, 4, 1, 1, 0) X(128, 48, 4, 1, 1, 0) X(128, 64, 4, 1, 1, 0)                                     \
+    X(128, 80, 4, 1, 1, 0) X(128, 96, 4, 1, 1, 0) X(128, 112, 4, 1, 1, 0) X(128, 128, 2, 2, 1, 0)                                   \
+    X(64, 16, 4, 1, 1, 1) X(64, 32, 4, 1, 1, 1) X(64, 48, 4, 1, 1, 1) X(64, 64, 4, 1, 1, 1)                                         \
+    X(64, 80, 4, 1, 1, 1) X(64, 96, 4, 1, 1, 1) X(64, 112, 4, 1, 1, 1) X(64, 128, 2, 2, 1, 1)                                       \
+    /* mid/small-M tiles: waves split K inside the block */                                                                        \
+    X(64, 64, 2, 1, 2, 0) X(64, 32, 2, 1, 2, 0) X(64, 16, 2, 1, 2, 0) X(64, 48, 2, 1, 2, 0)                                         \
+    X(32, 64, 1, 1, 4, 0) X(32, 48, 1, 1, 4, 0) X(32, 32, 1, 1, 4, 1) X(32, 16, 1, 1, 4, 0)                                         \
+    X(16, 64, 1, 1, 4, 0) X(16, 48, 1, 1, 4, 0) X(16, 32, 1, 1, 4, 1) X(16, 16, 1, 1, 4, 1)                                         \
+    X(64, 128, 2, 1, 2, 0) X(64, 96, 2, 1, 2, 0) X(64, 80, 2, 1, 2, 0) X(64, 112, 2, 1, 2, 0)                                       \
+    X(32, 128, 1, 1, 4, 0) X(32, 96, 1, 1, 4, 0) X(32, 80, 1, 1, 4, 0) X(32, 112, 1, 1, 4, 0)                                       \
+    X(32, 128, 2, 1, 2, 0) X(32, 64, 2, 1, 2, 1) X(32, 32, 2, 1, 2, 0)                                                              \
+    X(128, 64, 2, 1, 2, 0) X(128, 128, 2, 1, 2, 0)
+// k_conv_gd X(BM, BN, WGM, WGN, NS, BF); BF = 1: the bf16-operand builds (four-wave tiles with the default LDS limit)
+#define ORE_GD_BUILDS(X)                                                                                                            \
+    X(64, 128, 2, 2, 4, 1) X(64, 64, 2, 2, 4, 1) X(32, 64, 1, 4, 4, 1)                                                              \
+    X(64, 128, 2, 2, 4, 0) X(64, 64, 2, 2, 4, 0) X(64, 112, 4, 1, 4, 0) X(128, 64, 4, 1, 4, 0) X(128, 128, 2, 2, 4, 0)              \
+    X(32, 128, 1, 4, 4, 0) X(128, 112, 4, 1, 4, 0) X(208, 64, 1, 4, 4, 0) X(224, 64, 1, 4, 4, 0) X(112, 64, 1, 4, 4, 0)             \
+    X(96, 128, 2, 2, 4, 0) X(64, 128, 2, 2, 2, 0) X(128, 128, 2, 2, 2, 0) X(208, 64, 1, 4, 2, 0) X(128, 112, 4, 1, 2, 0)            \
+    X(128, 128, 2, 4, 4, 0) X(112, 128, 1, 8, 4, 0) X(128, 112, 8, 1, 4, 0) X(64, 128, 2, 4, 4, 0) X(128, 64, 4, 2, 4, 0)           \
+    X(64, 64, 2, 4, 4, 0) X(128, 128, 2, 4, 2, 0) X(112, 128, 1, 8, 2, 0) X(80, 64, 1, 4, 4, 0) X(80, 128, 1, 4, 4, 0)              \
+    X(48, 64, 1, 4, 4, 0) X(32, 64, 1, 4, 4, 0)
+// k_conv_kd X(BM, BN, NW, SB): every build keeps NW x 2 x SB x (BM + BN) / 16 KiB of LDS <= 160 KiB (16x16 at 4 waves x 8 steps = 128 KiB:
+// one block per CU)
+#define ORE_KD_BUILDS(X)                                                                                                            \
+    X(16, 16, 4, 4) X(16, 16, 4, 8) X(16, 16, 8, 4) X(16, 16, 16, 2) X(16, 32, 4, 4) X(16, 32, 8, 2) X(32, 32, 4, 4) X(32, 32, 8, 2)  \
+    X(16, 48, 4, 4) X(16, 48, 8, 2) X(16, 64, 4, 2) X(16, 80, 4, 2) X(32, 64, 4, 2) X(32, 80, 4, 2) X(64, 64, 4, 2) X(32, 48, 4, 2)    \
+    X(32, 16, 4, 4)
+// k_conv_rf X(GB, NW, MAXS)
+#define ORE_RF_BUILDS(X) \
+    X(1, 4, 8) X(1, 4, 12) X(1, 4, 16) X(1, 8, 12) X(1, 8, 16) X(1, 8, 20) X(1, 16, 12) X(2, 4, 12) X(2, 4, 16) X(2, 8, 12)
+// k_conv_gs X(BM, BN, WGM, WGN), each with ring depths 3 / 4 / 6 where they fit (gs_fits)
+#define ORE_GS_BUILDS(X) \
+    X(64, 112, 4, 1) X(64, 128, 2, 2) X(64, 64, 2, 2) X(128, 64, 4, 1) X(128, 128, 2, 2) X(32, 128, 1, 4) X(128, 112, 4, 1) X(64, 80, 4, 1) X(32, 64, 2, 2)
+// k_conv_kw X(BM, BN): 4 waves with rings 2 / 3 / 4; 8 waves for BM = 16, BN <= 48 and 16 waves for BN <= 32 (fp32 operands, ring 2)
+#define ORE_KW_TILES(X) \
+    X(16, 16) X(16, 32) X(16, 48) X(16, 64) X(16, 80) X(32, 16) X(32, 32) X(32, 48) X(32, 64) X(32, 80)
+constexpr bool gs_fits(int bm, int bn, int ns) { return ((bm + bn) / 16 + 3) / 4 * (ns - 1) <= 63 && (size_t)ns * (bm + bn) * 64 <= 150 * 1024; }
+
+// Tuning aids (ore_conv_set_plan_override codes in brackets; ore_conv_reset_plan_overrides restores these defaults).  Not used by the
+// product path.
+struct ConvKnobs {
+    int patch_mode = -1;        // (-1) 3x3 patch kernels: -1 automatic, 0 never, 4 / 8 force TH, 16 = double-buffered 8-wave kernel,
+                                //      102 = weight-stationary kernels (2-row tiles; Cin = 64 or 128)
+    int kw_mode = 1;            // (-2) 0: k_conv_kw off, 1: automatic (after the 3x3 patch kernels), 2: wherever it applies
+    int kw_force[4] = {};       // (-3) k_conv_kw {BM, BN, NS, split-K}; BM = 0 -> automatic
+    int gs_force[2] = {};       // (-4) k_conv_gs {BM, BN}; 0 -> automatic
+    int gs_ns = 3;              // (-4, .., .., ns > 0) ring depth of k_conv_gs (3 / 4 / 6)
+    int xmap_force = -1;        // (-5) block -> tile mapping: -1 automatic, 0 / 1 / 2 forced
+    int kw_nw_force = 0;        // (-6) waves per block of k_conv_kw (4 / 8 / 16); 0 -> the plan's
+    int wino_mode = 1;          // (-7) Winograd: 0 off, 1 automatic (by row count), 2 wherever it applies
+    int ws_sb_mode = 1;         // (-8) bf16-storage weight-stationary 3x3 kernel: 0 off (k_conv_gs / k_conv_kw), 1 automatic, 3 = 128-channel
+                                //      layers back on k_conv_kw
+    int ws_s2_mode = 1;         // (-9) 0 = stem_3 (3x3 stride 2, 64 input channels) stays on k_conv_igemm / k_conv_gs
+    int rf_mode = 1;            // (-10) k_conv_rf: 0 off, 1 automatic, 2 wherever it applies
+    int rf_force[3] = {};       // (-11) its build {GB, NW, MAXS}; 0 -> automatic
+    int kd_mode = 1;            // (-12) k_conv_kd: 0 off, 1 automatic, 2 wherever it applies
+    int kd_force[4] = {};       // (-13) its build {BM, BN, NW, SB}; 0 -> automatic
+    int gd_mode = 1;            // (-14) k_conv_gd: 0 off, 1 automatic, 2 automatic + every 1x1 layer at training sizes, 3 automatic with
+                                //       the round-4 limit M <= 32768
+    int gd_force[3] = {};       // (-15) its build {BM, BN, NS}; 0 -> automatic
+    int gd_dbg = 0;             // (-16) its ablation flags (trace build only)
+    int igemm[5] = {};          // (BM > 0) k_conv_igemm tile {BM, BN, WGM, WGN, WGK}; BM = 0 -> automatic
+};
+extern ConvKnobs g_knobs;
+
+using ConvPlan = ore_conv_plan_t;
+// The kernel, build, split and grid of one conv call (ConvP as ore_conv2d*_fwd fills it; p.tile_cnt = the workspace or null).  No HIP
+// calls; when no kernel takes the call the plan holds the error code and the last-error string says why.
+ConvPlan conv_plan(const ConvP& p, int req_splitk, size_t workspace_floats);
 bool conv_wino_covers(int Cout, int Cin);                  // a Winograd build exists for this 3x3 stride-1 layer
-// ore_conv_gd.hip: shared-stage LDS-DMA kernel with descriptor addressing for the large-M layers (stem_3, the big concats).  1 = not covered.
-int conv_gd_launch(ConvP& p, hipStream_t st);
-int conv_gd_tile_rows(const ConvP& p);
-void conv_gd_mode(int mode);
-void conv_gd_dbg(int flags);
-int conv_gd_splitk(const float* in, int in_ld, const float* w, int M, int K, int Cout16, float* parts, int S, hipStream_t st);                               // (-14, mode): 0 off, 1 automatic
-void conv_gd_force(int bm, int bn, int ns);                // (-15, bm, bn, ns): force the build (bm = 0: automatic)
-bool conv_gd_forced();
-int conv_gd_forced_bm();
-// ore_conv_kd.hip: lean LDS-DMA kernel (buffer descriptors, chunk table in the kernel arguments, double-buffered batches).  1 = not covered.
-int conv_kd_launch(ConvP& p, hipStream_t st);
-int conv_kd_tile_rows(const ConvP& p);
-void conv_kd_mode(int mode);                               // (-12, mode): 0 off, 1 automatic, 2 wherever it applies
-void conv_kd_force(int bm, int bn, int nw, int sb);        // (-13, bm, bn, nw, sb): force the build (bm = 0: automatic)
-bool conv_kd_forced();
-int conv_kd_forced_bm();
-// ore_conv_rf.hip: register-fed kernel for the smallest-M layers (stages 4-5, laterals 4-5, the second-stage GEMM).  1 = not covered.
-int conv_rf_launch(ConvP& p, hipStream_t st);
-bool conv_rf_covers(const ConvP& p);
-void conv_rf_mode(int mode);                               // (-10, mode): 0 off, 1 automatic, 2 wherever it applies
-void conv_rf_force(int gb, int nw, int maxs);
-bool conv_rf_forced();              // (-11, gb, nw, maxs): force the build (0 = automatic)
-void conv_gs_force(int bm, int bn, int ns);     // (-4, bm, bn): force the shared-stage kernel k_conv_gs with this tile; 0 -> automatic
+int wino_level_blocks(const ConvP& p, int gy, int* blk0);  // per-level Winograd weights: blocks [blk0[l], blk0[l+1]) serve level l; returns gx
+
+// One launcher per kernel: fills its argument block from p and runs the build the plan names.
+int launch_ws(const ConvP& p, const ConvPlan& pl, hipStream_t st);       // ore_conv.hip: k_conv3x3_ws (WS_SB, WS64, WS128)
+int launch_patch(const ConvP& p, const ConvPlan& pl, hipStream_t st);    // k_conv3x3_patch<4 | 8>, k_conv3x3_patch_db
+int launch_igemm(const ConvP& p, const ConvPlan& pl, hipStream_t st);    // k_conv_igemm
+int launch_wino(const ConvP& p, const ConvPlan& pl, hipStream_t st);     // ore_conv_wino.hip: k_conv3x3_wino, k_conv3x3_wino_nu
+int launch_gd(const ConvP& p, const ConvPlan& pl, hipStream_t st);       // ore_conv_gd.hip
+int launch_kd(const ConvP& p, const ConvPlan& pl, hipStream_t st);       // ore_conv_kd.hip
+int launch_rf(const ConvP& p, const ConvPlan& pl, hipStream_t st);       // ore_conv_rf.hip
+int launch_gs(const ConvP& p, const ConvPlan& pl, hipStream_t st);       // ore_conv_kw.hip: k_conv_gs
+int launch_kw(const ConvP& p, const ConvPlan& pl, hipStream_t st);       // k_conv_kw
+// ore_conv_gd.hip: the second-stage GEMM as a K split over blocks (called directly, not planned)
+int conv_gd_splitk(const float* in, int in_ld, const float* w, int M, int K, int Cout16, float* parts, int S, hipStream_t st);
 
 }  // namespace oreconv

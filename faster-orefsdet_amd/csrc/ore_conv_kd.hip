@@ -33,8 +33,7 @@ __device__ unsigned long long* g_trace_kd = nullptr;
 #define KD_TRR(i) do { } while (0)
 #endif
 
-constexpr unsigned kOOB = 0x80000000u;            // beyond every buffer's num_records (< 2 GB here; + an instruction offset cannot wrap)
-constexpr int kTab = 512;                         // chunk table entries: K up to 8192 (the second-stage GEMM)
+constexpr int kTab = kKdTab;                      // chunk table entries
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
@@ -354,105 +353,34 @@ __global__ __launch_bounds__(NW * 64) void k_conv_kd(KdP q) {
 #endif
 }
 
-int g_kd_mode = 1;                       // tuning aid (ore_conv_set_plan_override(-12, mode)): 0 off, 1 automatic, 2 wherever it applies
-int g_kd_force[4] = {0, 0, 0, 0};        // (-13, BM, BN, NW, SB): force the build
-
 template <int GA, int GB, int NW, int SB, bool SBF>
-int launch_kd(const KdP& q, bool k3, dim3 grid, hipStream_t st) {
+int kd_go(const KdP& q, bool k3, dim3 grid, hipStream_t st) {
     constexpr size_t ring = (size_t)NW * 2 * SB * (GA + GB) * 256, red = (size_t)NW * GA * GB * 256;
     constexpr size_t lds = ((ring > red ? ring : red) + GA * GB * 16) * sizeof(float);
-    if constexpr (lds > 160 * 1024 || SB * (GA + GB) > 63) {
-        ore_set_error("k_conv_kd: this build needs %zu bytes of LDS", lds);
-        return ORE_EINVAL;
+    static_assert(lds <= 160 * 1024 && SB * (GA + GB) <= 63, "k_conv_kd build beyond the LDS / DMA-offset limits");
+    static bool attr1 = false, attr3 = false;
+    if (!k3) {
+        if (!attr1) { ORE_HIP(hipFuncSetAttribute((const void*)k_conv_kd<GA, GB, NW, SB, 1, SBF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr1 = true; }
+        hipLaunchKernelGGL((k_conv_kd<GA, GB, NW, SB, 1, SBF>), grid, dim3(NW * 64), lds, st, q);
     } else {
-        static bool attr1 = false, attr3 = false;
-        ore_note_launch(ORE_LAUNCH_KD, 1);
-        if (!k3) {
-            if (!attr1) { ORE_HIP(hipFuncSetAttribute((const void*)k_conv_kd<GA, GB, NW, SB, 1, SBF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr1 = true; }
-            hipLaunchKernelGGL((k_conv_kd<GA, GB, NW, SB, 1, SBF>), grid, dim3(NW * 64), lds, st, q);
-        } else {
-            if (!attr3) { ORE_HIP(hipFuncSetAttribute((const void*)k_conv_kd<GA, GB, NW, SB, 3, SBF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr3 = true; }
-            hipLaunchKernelGGL((k_conv_kd<GA, GB, NW, SB, 3, SBF>), grid, dim3(NW * 64), lds, st, q);
-        }
-        return ore_launch_status("k_conv_kd");
+        if (!attr3) { ORE_HIP(hipFuncSetAttribute((const void*)k_conv_kd<GA, GB, NW, SB, 3, SBF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr3 = true; }
+        hipLaunchKernelGGL((k_conv_kd<GA, GB, NW, SB, 3, SBF>), grid, dim3(NW * 64), lds, st, q);
     }
+    return ore_launch_status("k_conv_kd");
 }
 
 }  // namespace
 
 namespace oreconv {
 
-void conv_kd_mode(int mode) { g_kd_mode = mode; }
-bool conv_kd_forced() { return g_kd_force[0] > 0; }
-int conv_kd_forced_bm() { return g_kd_force[0]; }
-void conv_kd_force(int bm, int bn, int nw, int sb) { g_kd_force[0] = bm; g_kd_force[1] = bn; g_kd_force[2] = nw; g_kd_force[3] = sb; }
-
-struct KdPlan { int bm, bn, nw, sb; };
-
-// several pyramid levels in one launch: a 1x1 stride-1 layer over the level-major row matrix is one flat GEMM (row m reads row m)
-static bool kd_flat(const ConvP& p) { return p.nlev > 1 && p.kh == 1 && p.kw == 1 && p.stride == 1 && p.pad == 0 && !p.add; }
-
-static bool kd_applies(const ConvP& p) {
-    // (bf16 STORAGE, p.sb & 1, is served: its sizes arrive in 4-byte units, so the staging is byte for byte the fp32 one)
-    if (p.bf16 || p.in_mul || p.in_add || p.in_relu || (p.nlev != 1 && !kd_flat(p)) || p.ep_stride) return false;
-    // a pixel's channel vector starts on a 16-byte boundary (the DMA piece of a lane); fp32 layers of this model all have 64-byte rows
-    if (p.Cin % 16 != 0 || p.in_ld % ((p.sb & 1) ? 4 : 16) != 0 || p.in_coff % 4 != 0 || p.kh != p.kw || (p.kh != 1 && p.kh != 3)) return false;
-    if ((long long)p.M * p.Cout16 >= (1ll << 31) || p.M >= (1 << 22) || p.nchunks > kTab) return false;
-    const long long in_rows = kd_flat(p) ? (long long)p.lv[0].irow0 + p.M : (long long)p.lv[0].irow0 + (long long)p.B * p.lv[0].H * p.lv[0].W;
-    if (in_rows * p.in_ld * 4 >= (long long)kOOB - (1 << 24) || (long long)p.Cout16 * p.K * 4 >= (long long)kOOB) return false;
-    if (p.add && (long long)p.B * p.add_H * p.add_W * p.add_ld * 4 >= (long long)kOOB) return false;
-    if ((p.sb & 1) && p.colsum && !(p.sb & 2)) return false;
-    if (p.kh == 3 && (2ll * p.lv[0].W + 2) * p.in_ld * 4 + (long long)p.Cin * 4 >= (1ll << 28)) return false;   // the chunk table keeps 28 bits of offset   // (fp32 output of a bf16 layer with column sums: no caller, not built)
-    return true;
-}
-
-// tile / waves / batch of the automatic plan; bm == 0: the layer stays on k_conv_kw.  From tools/kw_phase_trace.py kd
-// (profiles/r04_kd_phase_trace.txt): first-block-start -> last-block-end of the launch against k_conv_kw's, one MI355X, bs = 1 shapes:
-//   M = 400   3x3 112->112 5.6 vs 10.8 us, 384->112 10.1 vs 22.4, 1x1 512->128 4.3 vs 6.8, 720->512 8.7 vs 12.6
-//   M = 1600  3x3 96->96 8.9 vs 12.7, 256->96 14.8 vs 24.4, 1x1 384->128 6.3 vs 9.5, 544->384 15.0 vs 15.9
-//   M = 6400  1x1 256->128 11.1 vs 15.1;  the second-stage GEMM (K = 8192) ties and stays where it is
-static KdPlan kd_plan(const ConvP& p) {
-    if (g_kd_force[0] > 0) return {g_kd_force[0], g_kd_force[1], g_kd_force[2], g_kd_force[3]};
-    if (g_kd_mode == 2) return {16, p.Cout16 >= 32 ? 32 : 16, 4, 4};
-    if (p.nchunks > 256) return {0, 0, 0, 0};
-    if (p.M <= 512) {
-        if (p.Cout16 <= 128) return p.nchunks <= 64 ? KdPlan{16, 16, 4, 8} : KdPlan{16, 16, 8, 4};
-        return {32, 32, 4, 4};
-    }
-    if (p.M <= 2048) {
-        if (p.Cout16 == 96) return p.nchunks <= 64 ? KdPlan{16, 48, 4, 4} : KdPlan{16, 48, 8, 2};
-        if (p.Cout16 == 128) return {16, 64, 4, 2};
-        if (p.Cout16 >= 320 && p.Cout16 % 80 == 64) return {32, 80, 4, 2};       // 384 = 4 x 80 + 64: five column tiles
-        return {0, 0, 0, 0};
-    }
-    if (p.M <= 9216 && p.Cout16 == 128 && p.kh == 1) {                            // FPN lateral 3, conv3 over the three levels
-        // (fp32: k_conv_gd takes both first.)  bf16 storage: 64 x 64 tiles of conv3's 8400 rows are 264 blocks -- a second round on 256
-        // CUs: 10.0 us against 8.5 on k_conv_kw's 32 x 64 tiles (tools/bf16s_sweep.py) -- so only what fits one round comes here
-        if ((p.sb & 1) && ceil_div(p.M, 64) * 2 > 256) return {0, 0, 0, 0};
-        return {64, 64, 4, 2};
-    }
-    // bf16 storage, stage 3's 3x3 layers (M = 6400, 80 output channels; fp32 runs them on the Winograd kernel): 7.0-7.6 us against
-    // k_conv_kw's 9.7-10.9 (tools/bf16s_sweep.py)
-    if ((p.sb & 1) && p.kh == 3 && p.Cout16 == 80) return {32, 80, 4, 2};   // (any M: the frozen stage 3 of a bf16 training step runs 16 queries and 384 support crops through it)
-    return {0, 0, 0, 0};
-}
-
-int conv_kd_tile_rows(const ConvP& p) {                            // rows per block when this kernel takes the layer, else 0
-    if (g_kd_mode == 0 || !kd_applies(p)) return 0;
-    return kd_plan(p).bm;
-}
-
-// Returns 1 when the layer is not covered (the caller goes on to k_conv_rf / k_conv_kw).
-int conv_kd_launch(ConvP& p, hipStream_t st) {
-    if (g_kd_mode == 0 || !kd_applies(p)) return 1;
-    const KdPlan pl = kd_plan(p);
-    if (pl.bm == 0) return 1;
-    const int bn = pl.bn < p.Cout16 ? pl.bn : p.Cout16;
-    const int steps = ceil_div(p.nchunks, pl.nw);
-    const int gx = ceil_div(p.M, pl.bm), gy = ceil_div(p.Cout16, bn);
+// k_conv_kd: the plan's tile, waves (build[0]) and steps per batch (build[1]) over p's rows (several levels of a 1x1 layer: one flat GEMM)
+int launch_kd(const ConvP& p, const ConvPlan& pl, hipStream_t st) {
+    const int nw = pl.build[0], sb = pl.build[1];
+    const int steps = ceil_div(p.nchunks, nw);
+    const int gx = pl.gx, gy = pl.gy;
     Lvl L = p.lv[0];
     int Bimg = p.B;
-    if (kd_flat(p)) { L.H = 1; L.W = p.M; L.Ho = 1; L.Wo = p.M; Bimg = 1; }      // one "image" of M pixels in a row
+    if (p.nlev > 1) { L.H = 1; L.W = p.M; L.Ho = 1; L.Wo = p.M; Bimg = 1; }      // one "image" of M pixels in a row
     KdP q;
     KdK& k = q.k;
     k.in = p.in; k.w = p.w; k.scale = p.scale; k.shift = p.shift; k.add = p.add; k.out = p.out; k.colsum = p.colsum;
@@ -461,13 +389,12 @@ int conv_kd_launch(ConvP& p, hipStream_t st) {
     k.sc_bytes = (unsigned)p.Cout * 4u;
     k.add_bytes = p.add ? (unsigned)((long long)p.B * p.add_H * p.add_W * p.add_ld * ((p.sb & 4) ? 2 : 4)) : 0u;
     k.sb = p.sb;
-    k.M = p.M; k.K = p.K; k.Cout = p.Cout; k.Cout16 = p.Cout16; k.nchunks = p.nchunks; k.nb = ceil_div(steps, pl.sb);
+    k.M = p.M; k.K = p.K; k.Cout = p.Cout; k.Cout16 = p.Cout16; k.nchunks = p.nchunks; k.nb = ceil_div(steps, sb);
     k.irow0 = L.irow0; k.H = L.H; k.W = L.W; k.Ho = L.Ho; k.Wo = L.Wo; k.in_ld = p.in_ld; k.in_coff = p.in_coff; k.stride = p.stride; k.pad = p.pad;
     k.out_ld = p.out_ld; k.out_coff = p.out_coff; k.relu_cout = p.relu_cout;
     k.add_H = p.add_H; k.add_W = p.add_W; k.add_ld = p.add_ld; k.add_coff = p.add_coff;
-    k.xmap = conv_choose_xmap(p, gx, gy); k.gx = gx; k.gy = gy;
+    k.xmap = pl.xmap; k.gx = gx; k.gy = gy;
     k.inv_hw = 1.0f / (float)(L.Ho * L.Wo); k.inv_wo = 1.0f / (float)L.Wo; k.inv_gx = 1.0f / (float)gx; k.inv_gy = 1.0f / (float)gy;
-    if (pl.nw * k.nb * pl.sb > kTab) return 1;
     if (p.kh == 3) {
         const int cpt = p.Cin >> 4, row_bytes = L.W * p.in_ld * 4, pix_bytes = p.in_ld * 4;
         for (int c = 0; c < kTab; ++c) {
@@ -478,16 +405,11 @@ int conv_kd_launch(ConvP& p, hipStream_t st) {
     }
     const bool k3 = p.kh == 3;
     const dim3 grid(gx, gy, 1);
-#define KD_CASE(bm_, bn_, nw_, sb_) if (pl.bm == bm_ && bn == bn_ && pl.nw == nw_ && pl.sb == sb_) \
-        return (p.sb & 1) ? launch_kd<bm_ / 16, bn_ / 16, nw_, sb_, true>(q, k3, grid, st) : launch_kd<bm_ / 16, bn_ / 16, nw_, sb_, false>(q, k3, grid, st);
-    // every build keeps NW x 2 x SB x (BM + BN) / 16 KiB of LDS <= 160 KiB (16x16 at 4 waves x 8 steps = 128 KiB: one block per CU)
-    KD_CASE(16, 16, 4, 4) KD_CASE(16, 16, 4, 8) KD_CASE(16, 16, 8, 4) KD_CASE(16, 16, 16, 2)
-    KD_CASE(16, 32, 4, 4) KD_CASE(16, 32, 8, 2) KD_CASE(32, 32, 4, 4) KD_CASE(32, 32, 8, 2)
-    KD_CASE(16, 48, 4, 4) KD_CASE(16, 48, 8, 2) KD_CASE(16, 64, 4, 2) KD_CASE(16, 80, 4, 2)
-    KD_CASE(32, 64, 4, 2) KD_CASE(32, 80, 4, 2) KD_CASE(64, 64, 4, 2) KD_CASE(32, 48, 4, 2) KD_CASE(32, 16, 4, 4)
-#undef KD_CASE
-    if (g_kd_force[0] > 0) { ore_set_error("k_conv_kd: no build for tile %dx%d, %d waves, %d steps per batch", pl.bm, bn, pl.nw, pl.sb); return ORE_EINVAL; }
-    return 1;
+#define KD_GO(bm_, bn_, nw_, sb_) if (pl.bm == bm_ && pl.bn == bn_ && nw == nw_ && sb == sb_) \
+        return (p.sb & 1) ? kd_go<bm_ / 16, bn_ / 16, nw_, sb_, true>(q, k3, grid, st) : kd_go<bm_ / 16, bn_ / 16, nw_, sb_, false>(q, k3, grid, st);
+    ORE_KD_BUILDS(KD_GO)
+#undef KD_GO
+    return ORE_EINVAL;
 }
 
 }  // namespace oreconv

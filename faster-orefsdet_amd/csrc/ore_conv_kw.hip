@@ -15,7 +15,7 @@
 // release/acquire ticket as k_conv_igemm (last arriver sums the slabs in slice order: bitwise deterministic).
 // Epilogue = k_conv_igemm's: y = acc*scale[n] + shift[n] (+ nearest-2x top-down add) (+ ReLU on n < relu_cout), per-tile column sums
 // (eSE average pool), channel-slice output.  BF build: both operands rounded to bf16 as the fragments leave LDS (ORE_CONV_BF16).
-// Not covered (conv_kw_launch returns 1 and the caller falls back to k_conv_igemm): any input-side affine (in_mul / in_add / in_relu:
+// Not planned here (the planner leaves such layers to k_conv_igemm): any input-side affine (in_mul / in_add / in_relu:
 // the eSE gate of the FPN laterals reaches this kernel pre-multiplied into the weights instead, ore_ese_gate_scaled_weight_fwd; the
 // GroupNorm fold of the head's last conv stays on k_conv_igemm), Cin % 16 != 0.
 //
@@ -664,164 +664,75 @@ __global__ __launch_bounds__(256) void k_conv_gs(ConvP p, const float* __restric
     }
 }
 
-int g_gs_ns = 3;                        // tuning aid: ring depth of k_conv_gs (3 / 4 / 6)
-
-template <int BM, int BN, int WGM, int WGN, int NS, bool SB = false>
-int launch_gs_ns(const ConvP& p, const float* zero, hipStream_t st);
-
-template <int BM, int BN, int WGM, int WGN>
-int launch_gs(const ConvP& p, const float* zero, hipStream_t st) {
-    if (p.sb & 1) {
-        if (g_gs_ns == 4) return launch_gs_ns<BM, BN, WGM, WGN, 4, true>(p, zero, st);
-        if (g_gs_ns == 6) return launch_gs_ns<BM, BN, WGM, WGN, 6, true>(p, zero, st);
-        return launch_gs_ns<BM, BN, WGM, WGN, 3, true>(p, zero, st);
-    }
-    if (g_gs_ns == 4) return launch_gs_ns<BM, BN, WGM, WGN, 4>(p, zero, st);
-    if (g_gs_ns == 6) return launch_gs_ns<BM, BN, WGM, WGN, 6>(p, zero, st);
-    return launch_gs_ns<BM, BN, WGM, WGN, 3>(p, zero, st);
-}
-
 template <int BM, int BN, int WGM, int WGN, int NS, bool SB>
-int launch_gs_ns(const ConvP& p, const float* zero, hipStream_t st) {
-    if constexpr (((BM + BN) / 16 + 3) / 4 * (NS - 1) > 63 || (size_t)NS * (BM + BN) * 64 > 150 * 1024) return 1;
-    else {
+int gs_go(const ConvP& p, const float* zero, dim3 grid, hipStream_t st) {
+    static_assert(gs_fits(BM, BN, NS), "k_conv_gs build beyond the LDS / DMA-offset limits");
     constexpr size_t lds = ((size_t)NS * (BM + BN) * 16 + 4 * 256 + WGM * BN) * sizeof(float);
     static bool attr = false;
     if (!attr) {
         ORE_HIP(hipFuncSetAttribute((const void*)k_conv_gs<BM, BN, WGM, WGN, NS, SB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr = true;
     }
-    const dim3 grid(ceil_div(p.M, BM), ceil_div(p.Cout16, BN), 1);
-    ore_note_launch(ORE_LAUNCH_GS, 1);
     hipLaunchKernelGGL((k_conv_gs<BM, BN, WGM, WGN, NS, SB>), grid, dim3(256), lds, st, p, zero);
     return ore_launch_status("k_conv_gs");
-    }
 }
 
-int g_gs_force[2] = {0, 0};             // tuning aid: {BM, BN}; 0 -> automatic
-
-struct KwTile { int BM, BN, S; int NW = 4; };      // S = cross-block split-K (0: decide from the block count), BM = 0: layer left to k_conv_igemm / patch
-
-// Tile plan, from tools/conv_kw_sweep.py on MI355X (profiles/r02_kw_sweep.txt).  What the sweep says: the minimal ring (NS = 2) wins
-// almost everywhere -- more resident blocks per CU hide the DMA latency better than a deeper ring --, cross-block split-K pays only
-// for K >= 2048 with < 128 tiles, and the 256-channel 1x1 concat at M = 6400 and the 128 -> 128 3x3 at M = 6400 stay on their round-1
-// kernels.  Shapes outside the table get the tile with the most FLOP per staged byte among those that give >= 384 blocks.
-KwTile kw_tile(int M, int C16, int nchunks) {
-    const int steps = ceil_div(nchunks, 4);
-    if (M >= 4096) {
-        if (C16 >= 256) return {0, 0, 0};
-        if (C16 <= 80) return {32, 16, 1};
-        if (C16 == 128) return {16, 32, 1};
-    } else if (M >= 1024) {
-        if (C16 == 96) return {16, 48, 1};
-        if (C16 == 128) return {16, 32, 1};
-        if (C16 >= 256) return {32, 80, 1};
-    } else {
-        // the second-stage GEMM, 320 x 8192 -> 128: 8 waves split K inside the block (64 steps per wave) and NO cross-block split --
-        // the release fence of a split-K block costs more than the longer chain (19.6 vs 24 us with {16, 48} x S 4)
-        if (C16 <= 128 && steps >= 96) return {16, 16, 1, 8};
-        if (C16 <= 128 && steps >= 32) return {16, 16, 1};           // stage-5 layer 0 (15.7 vs 17.4+ us with any cross-block split)
-        if (C16 <= 128) return {16, 16, 1};
-        return {16, 32, 1};
+template <int BM, int BN, int WGM, int WGN>
+int gs_ring(const ConvP& p, const float* zero, dim3 grid, int ns, hipStream_t st) {
+    if (p.sb & 1) {
+        if constexpr (gs_fits(BM, BN, 4)) if (ns == 4) return gs_go<BM, BN, WGM, WGN, 4, true>(p, zero, grid, st);
+        if constexpr (gs_fits(BM, BN, 6)) if (ns == 6) return gs_go<BM, BN, WGM, WGN, 6, true>(p, zero, grid, st);
+        if constexpr (gs_fits(BM, BN, 3)) if (ns == 3) return gs_go<BM, BN, WGM, WGN, 3, true>(p, zero, grid, st);
+        return ORE_EINVAL;
     }
-    static const int bns[5] = {80, 64, 48, 32, 16};
-    KwTile best = {16, 16, 0};
-    float bs = -1.0f;
-    int most = 0;
-    for (int bm = 32; bm >= 16; bm -= 16)
-        for (int b = 0; b < 5; ++b) {
-            const int bn = bns[b];
-            if (bn > C16) continue;
-            const int nt = ceil_div(C16, bn), blocks = ceil_div(M, bm) * nt;
-            const float ai = (float)(bm * bn) / (float)(bm + bn) * (float)C16 / (float)(nt * bn);
-            if (blocks >= 384) { if (ai > bs) { bs = ai; best = {bm, bn, 0}; } }
-            else if (bs < 0.0f && blocks > most) { most = blocks; best = {bm, bn, 0}; }
-        }
-    return best;
+    if constexpr (gs_fits(BM, BN, 4)) if (ns == 4) return gs_go<BM, BN, WGM, WGN, 4, false>(p, zero, grid, st);
+    if constexpr (gs_fits(BM, BN, 6)) if (ns == 6) return gs_go<BM, BN, WGM, WGN, 6, false>(p, zero, grid, st);
+    if constexpr (gs_fits(BM, BN, 3)) if (ns == 3) return gs_go<BM, BN, WGM, WGN, 3, false>(p, zero, grid, st);
+    return ORE_EINVAL;
 }
 
 template <int BM, int BN, int NS, bool BF = false, bool INCR = true, int NW = 4, bool SB = false>
-int launch_kw_ns(const ConvP& p, const float* zero, dim3 grid, hipStream_t st) {
+int kw_go(const ConvP& p, const float* zero, dim3 grid, hipStream_t st) {
     constexpr int G = (BM + BN) / 16;
-    if constexpr ((NS - 1) * G > 63) {
-        return ORE_EINVAL;
-    } else {
-        constexpr int RING_F = NW * NS * (BM + BN) * 16, RED_F = NW * (BM / 16) * (BN / 16) * 256 + (BM / 16) * (BN / 16) * 16;
-        constexpr size_t lds = ((size_t)(RING_F > RED_F ? RING_F : RED_F) + 8) * sizeof(float);
-        if constexpr (lds > 160 * 1024) {
-            return ORE_EINVAL;
-        } else {
-            static bool attr = false;
-            if (!attr) {
-                ORE_HIP(hipFuncSetAttribute((const void*)k_conv_kw<BM, BN, NS, BF, INCR, NW, SB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                attr = true;
-            }
-            ore_note_launch(ORE_LAUNCH_KW, p.splitk);
-            hipLaunchKernelGGL((k_conv_kw<BM, BN, NS, BF, INCR, NW, SB>), grid, dim3(NW * 64), lds, st, p, zero);
-            return ORE_OK;
-        }
+    constexpr int RING_F = NW * NS * (BM + BN) * 16, RED_F = NW * (BM / 16) * (BN / 16) * 256 + (BM / 16) * (BN / 16) * 16;
+    constexpr size_t lds = ((size_t)(RING_F > RED_F ? RING_F : RED_F) + 8) * sizeof(float);
+    static_assert((NS - 1) * G <= 63 && lds <= 160 * 1024, "k_conv_kw build beyond the LDS / DMA-offset limits");
+    static bool attr = false;
+    if (!attr) {
+        ORE_HIP(hipFuncSetAttribute((const void*)k_conv_kw<BM, BN, NS, BF, INCR, NW, SB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        attr = true;
     }
+    hipLaunchKernelGGL((k_conv_kw<BM, BN, NS, BF, INCR, NW, SB>), grid, dim3(NW * 64), lds, st, p, zero);
+    return ore_launch_status("k_conv_kw");
 }
 
-int g_kw_force[4] = {0, 0, 0, 0};       // tuning aid: {BM, BN, NS, split-K}; BM = 0 -> automatic
-int g_xmap_force = -1;                  // tuning aid: block -> tile mapping of k_conv_kw; -1 -> automatic
-
-int g_kw_nw_force = 0;                   // tuning aid (-6, nw): waves per block of k_conv_kw (4 / 8 / 16); 0 -> the plan's
-
+// build = {NS, NW, INCR, 1 bf16 operands / 2 bf16 storage}: bf16 builds and 8 / 16 waves run the minimal ring, rings 3 / 4 are fp32 4-wave
 template <int BM, int BN>
-int launch_kw(const ConvP& p, const float* zero, dim3 grid, hipStream_t st, int nw) {
-    // incremental DMA addressing pays when a tap holds >= 16 chunks (4+ steps between pointer rebuilds): 1x1 layers, deep 3x3 layers
-    const bool incr = (p.Cin >> 4) >= 4 * nw;
-    if (p.sb & 1) {                                        // bf16 storage: 4 waves, minimal ring
-        if (nw != 4) return ORE_EINVAL;
-        return incr ? launch_kw_ns<BM, BN, 2, false, true, 4, true>(p, zero, grid, st) : launch_kw_ns<BM, BN, 2, false, false, 4, true>(p, zero, grid, st);
-    }
+int kw_build(const ConvP& p, const ConvPlan& pl, const float* zero, dim3 grid, hipStream_t st) {
+    const int ns = pl.build[0], nw = pl.build[1], mode = pl.build[3];
+    const bool incr = pl.build[2] != 0;
+    if (mode == 2) return incr ? kw_go<BM, BN, 2, false, true, 4, true>(p, zero, grid, st) : kw_go<BM, BN, 2, false, false, 4, true>(p, zero, grid, st);
+    if (mode == 1) return incr ? kw_go<BM, BN, 2, true, true>(p, zero, grid, st) : kw_go<BM, BN, 2, true, false>(p, zero, grid, st);
     if constexpr (BM == 16 && BN <= 48) {                  // the small tiles also come with 8 / 16 waves (in-block K split)
-        if (nw == 8 && !p.bf16) return incr ? launch_kw_ns<BM, BN, 2, false, true, 8>(p, zero, grid, st) : launch_kw_ns<BM, BN, 2, false, false, 8>(p, zero, grid, st);
+        if (nw == 8) return incr ? kw_go<BM, BN, 2, false, true, 8>(p, zero, grid, st) : kw_go<BM, BN, 2, false, false, 8>(p, zero, grid, st);
         if constexpr (BN <= 32) {
-            if (nw == 16 && !p.bf16) return incr ? launch_kw_ns<BM, BN, 2, false, true, 16>(p, zero, grid, st) : launch_kw_ns<BM, BN, 2, false, false, 16>(p, zero, grid, st);
+            if (nw == 16) return incr ? kw_go<BM, BN, 2, false, true, 16>(p, zero, grid, st) : kw_go<BM, BN, 2, false, false, 16>(p, zero, grid, st);
         }
     }
-    if (nw != 4) return ORE_EINVAL;
-    if (p.bf16) return incr ? launch_kw_ns<BM, BN, 2, true, true>(p, zero, grid, st) : launch_kw_ns<BM, BN, 2, true, false>(p, zero, grid, st);
-    int ns = 2;                          // (see kw_tile: the minimal ring wins)
-    if (g_kw_force[0] > 0 && g_kw_force[2] > 0) ns = g_kw_force[2];
-    if (ns == 2) return incr ? launch_kw_ns<BM, BN, 2, false, true>(p, zero, grid, st) : launch_kw_ns<BM, BN, 2, false, false>(p, zero, grid, st);
-    if (ns == 3) return launch_kw_ns<BM, BN, 3>(p, zero, grid, st);        // (tuning aid only)
-    if (ns == 4) return launch_kw_ns<BM, BN, 4>(p, zero, grid, st);
-    return ORE_EINVAL;
+    if (ns == 3) return kw_go<BM, BN, 3>(p, zero, grid, st);        // (tuning aid only)
+    if (ns == 4) return kw_go<BM, BN, 4>(p, zero, grid, st);
+    return incr ? kw_go<BM, BN, 2, false, true>(p, zero, grid, st) : kw_go<BM, BN, 2, false, false>(p, zero, grid, st);
 }
 
 }  // namespace
 
 namespace oreconv {
 
-int conv_kw_tile_rows(const ConvP& p) {         // rows per block of the kernel conv_kw_launch will pick (0: not covered) -- keep in step with it
-    if (g_kw_force[0] > 0) return g_kw_force[0];
-    if (g_gs_force[0] > 0) return g_gs_force[0];
-    if (const int kd = conv_kd_tile_rows(p)) return kd;      // the lean-DMA kernels take the layer (conv_kw_launch asks them first)
-    if (const int gd = conv_gd_tile_rows(p)) return gd;
-    if (p.sb & 1) {                                            // keep in step with conv_kw_launch's bf16-storage branch
-        if (p.M >= 6400 && ((p.kh == 1 && (p.Cout16 == 112 || p.Cout16 >= 256)) || (p.kh == 3 && p.stride == 2 && p.Cout16 % 128 == 0))) return 64;
-        if (p.M >= 4096 && (p.Cout16 == 128 || p.Cout16 == 64)) return 32;
-        if (p.M >= 4096 && p.Cout16 == 80) return 16;
-        const int bm = kw_tile(p.M, p.Cout16, p.nchunks).BM;
-        return bm ? bm : 32;
-    }
-    if (p.M >= 16384 || (p.M >= 4096 && p.Cout16 >= 256)) {
-        if (p.bf16 || p.M < 6400 || p.kh != 1) return 0;      // (k_conv_gs has no bf16-operand build)
-        return (p.Cout16 == 112 || p.Cout16 % 128 == 0 || p.Cout16 == 64) ? 64 : 0;
-    }
-    return g_kw_force[0] > 0 ? g_kw_force[0] : kw_tile(p.M, p.Cout16, p.nchunks).BM;
-}
-
-void conv_kw_force(int bm, int bn, int ns, int splitk) { g_kw_force[0] = bm; g_kw_force[1] = bn; g_kw_force[2] = ns; g_kw_force[3] = splitk; }
-
 static int zero_page_of(const float** out) {
     static const float* zero_dev[16] = {};
     int dev = 0;
     ORE_HIP(hipGetDevice(&dev));
-    ORE_CHECK_ARG(dev >= 0 && dev < 16, "conv_kw_launch: device index %d", dev);
+    ORE_CHECK_ARG(dev >= 0 && dev < 16, "launch_kw: device index %d", dev);
     if (!zero_dev[dev]) {
         void* zp = nullptr;
         ORE_HIP(hipGetSymbolAddress(&zp, HIP_SYMBOL(g_zero_kw)));      // a query, legal during stream capture
@@ -831,107 +742,28 @@ static int zero_page_of(const float** out) {
     return ORE_OK;
 }
 
-// shared-stage kernel for the large-M layers; returns 1 when the shape has no tile here
-static int conv_gs_launch(ConvP& p, hipStream_t st) {
-    int bm = g_gs_force[0], bn = g_gs_force[1];
-    if (bm == 0 && (p.sb & 1)) {                              // bf16 storage (conv_kw_launch decided that this layer comes here)
-        if (p.Cout16 == 112) { bm = 64; bn = 80; }
-        else if (p.Cout16 % 128 == 0 && p.kh == 3) { bm = 64; bn = 128; }
-        else if (p.Cout16 >= 256) { bm = 64; bn = 80; }
-        else { bm = 64; bn = 64; }
-    }
-    if (bm == 0) {
-        // measured (profiles/r02_kw_ab.txt): 2-5 % ahead of k_conv_igemm on the 1x1 concats, 3 % behind on stem_3 (3x3 stride 2) --
-        // the staging mechanism is not what bounds these layers -- so only the 1x1 layers come here automatically
-        if (p.M < 6400 || (p.kh != 1 && !(p.sb & 1))) return 1;
-        if (p.Cout16 == 112) { bm = 64; bn = 112; }
-        else if (p.Cout16 % 128 == 0) { bm = 64; bn = p.M < 16384 ? 64 : 128; }      // s3cat: 64x64 21.8 us, 64x128 24.0 (400 vs 200 blocks)
-        else if (p.Cout16 == 64) { bm = 64; bn = 64; }
-        else return 1;
-    }
+// k_conv_gs: shared-stage kernel for the large-M layers, build = {WGM, WGN, NS, SB}
+int launch_gs(const ConvP& p, const ConvPlan& pl, hipStream_t st) {
     const float* zero = nullptr;
     const int zrc = zero_page_of(&zero);
     if (zrc) return zrc;
-    p.splitk = 1; p.steps_per_split = p.nchunks;
-#define GS_CASE(a, b, wgm, wgn) if (bm == a && bn == b) return launch_gs<a, b, wgm, wgn>(p, zero, st);
-    GS_CASE(64, 112, 4, 1) GS_CASE(64, 128, 2, 2) GS_CASE(64, 64, 2, 2) GS_CASE(128, 64, 4, 1) GS_CASE(128, 128, 2, 2) GS_CASE(32, 128, 1, 4)
-    GS_CASE(128, 112, 4, 1) GS_CASE(64, 80, 4, 1) GS_CASE(32, 64, 2, 2)
-#undef GS_CASE
-    return 1;
+    const dim3 grid(pl.gx, pl.gy, 1);
+#define GS_GO(a, b, wgm, wgn) if (pl.bm == a && pl.bn == b) return gs_ring<a, b, wgm, wgn>(p, zero, grid, pl.build[2], st);
+    ORE_GS_BUILDS(GS_GO)
+#undef GS_GO
+    return ORE_EINVAL;
 }
 
-void conv_xmap_force(int mode) { g_xmap_force = mode; }
-void conv_kw_nw_force(int nw) { g_kw_nw_force = nw; }
-int conv_xmap_forced() { return g_xmap_force; }
-
-// block -> tile mapping (tile_of_block): fabric bytes if every XCD reads what its tiles need once
-int conv_choose_xmap(const ConvP& p, int gx, int gy) {
-    if (g_xmap_force >= 0) return g_xmap_force;
-    const int blocks = gx * gy;
-    if (blocks < 16) return 0;
-    const double A = (double)p.M * p.Cin, Wb = (double)p.Cout16 * p.K;
-    const int per_xcd = ceil_div(blocks, 8);
-    const double cost_m = A + 8.0 * Wb;                                        // an XCD = a range of rows x all output channels
-    const int spanned = per_xcd >= gx ? ceil_div(per_xcd, gx) + 1 : 2;         // N tiles an XCD's run touches in N-major order
-    const double cost_n = (double)(gy < 8 ? gy : 8) * A + 8.0 * Wb * (spanned < gy ? spanned : gy) / gy;
-    if (cost_n < cost_m) return 2;
-    return (gx & 7) == 0 ? 0 : 1;                                              // plain mapping already keeps an M tile on one XCD
-}
-void conv_gs_force(int bm, int bn, int ns) { g_gs_force[0] = bm; g_gs_force[1] = bn; if (ns > 0) g_gs_ns = ns; }
-
-int conv_kw_launch(ConvP& p, float* workspace, size_t workspace_floats, hipStream_t st) {
-    if (p.in_mul || p.Cin % 16 != 0) return 1;                             // input affine not built here
-    if (g_kw_force[0] == 0 && g_gs_force[0] == 0) {                         // the lean LDS-DMA kernel (ore_conv_kd.hip), then the register-fed
-        const int drc = conv_kd_launch(p, st);                             // one for the smallest-M layers (ore_conv_rf.hip)
-        if (drc != 1) return drc;
-        const int rrc = conv_rf_launch(p, st);
-        if (rrc != 1) return rrc;
-    }
-    if (p.sb & 1) {                                                         // bf16 storage: every layer runs on one of the two DMA-fed kernels
-        // plan from tools/bf16s_sweep.py (profiles/r03_bf16s_sweep.txt): the shared-stage kernel for the two big 1x1 concats and the
-        // stride-2 stem_3, the K-split kernel with 32x64 tiles for everything else at M >= 4096 (3x3 at 128 channels: 12-21 vs 21-24 us)
-        const bool gs_pick = p.M >= 6400 && ((p.kh == 1 && (p.Cout16 == 112 || p.Cout16 >= 256)) || (p.kh == 3 && p.stride == 2 && p.Cout16 % 128 == 0));
-        if (g_kw_force[0] == 0 && (g_gs_force[0] > 0 || gs_pick)) {
-            const int grc = conv_gs_launch(p, st);
-            if (grc != 1) return grc;
-        }
-    } else
-    if (g_kw_force[0] == 0 && (g_gs_force[0] > 0 || p.M >= 16384 || (p.M >= 4096 && p.Cout16 >= 256))) return p.bf16 ? 1 : conv_gs_launch(p, st);
-    KwTile t = kw_tile(p.M, p.Cout16, p.nchunks);
-    if (p.sb & 1) {
-        if (t.BM == 0) t = {32, 64, 1};
-        if (p.M >= 4096 && (p.Cout16 == 128 || p.Cout16 == 64)) t = {32, 64, 1};
-        if (p.M >= 4096 && p.Cout16 == 80) t = {16, 80, 1};
-    }
-    if (g_kw_force[0] > 0) t = {g_kw_force[0], g_kw_force[1] < p.Cout16 ? g_kw_force[1] : p.Cout16, g_kw_force[3]};
-    if (t.BM == 0) return 1;
-    const int gx = ceil_div(p.M, t.BM), gy = ceil_div(p.Cout16, t.BN);
-    const int blocks = gx * gy;
-    int nw = t.NW;
-    if (g_kw_nw_force > 0) nw = g_kw_nw_force;
-    if (p.bf16 || (p.sb & 1) || t.BM != 16 || t.BN > 48 || (nw == 16 && t.BN > 32)) nw = 4;    // the 8- / 16-wave builds exist for the small fp32 tiles only
-    const int steps = ceil_div(p.nchunks, nw);                            // steps per wave without a cross-block split
-    int S = t.S;
-    if (S <= 0) S = (blocks < 128 && steps >= 32) ? 4 : 1;
-    if (S > steps) S = steps;
-    int sps = ceil_div(steps, S);
-    S = ceil_div(steps, sps);
-    if (S > 1) {
-        const size_t need = ORE_CONV_CNT_INTS + (size_t)blocks * S * t.BM * t.BN;
-        if (!workspace || workspace_floats < need || blocks > ORE_CONV_CNT_INTS) { S = 1; sps = steps; }
-    }
-    p.splitk = S; p.steps_per_split = sps;
-    p.xmap = conv_choose_xmap(p, gx, gy);
-    p.tile_cnt = reinterpret_cast<int*>(workspace);
-    p.ws = workspace ? workspace + ORE_CONV_CNT_INTS : nullptr;
-    const dim3 grid(gx, gy, S);
+// k_conv_kw: wave-private K-split kernel fed by LDS-DMA, split-K over grid.z
+int launch_kw(const ConvP& p, const ConvPlan& pl, hipStream_t st) {
     const float* zero = nullptr;
-    { const int zrc = zero_page_of(&zero); if (zrc) return zrc; }
-#define KW_CASE(bm, bn) if (t.BM == bm && t.BN == bn) { const int rc = launch_kw<bm, bn>(p, zero, grid, st, nw); return rc ? rc : ore_launch_status("k_conv_kw"); }
-    KW_CASE(16, 16) KW_CASE(16, 32) KW_CASE(16, 48) KW_CASE(16, 64) KW_CASE(16, 80)
-    KW_CASE(32, 16) KW_CASE(32, 32) KW_CASE(32, 48) KW_CASE(32, 64) KW_CASE(32, 80)
-#undef KW_CASE
-    return 1;
+    const int zrc = zero_page_of(&zero);
+    if (zrc) return zrc;
+    const dim3 grid(pl.gx, pl.gy, pl.splitk);
+#define KW_GO(bm_, bn_) if (pl.bm == bm_ && pl.bn == bn_) return kw_build<bm_, bn_>(p, pl, zero, grid, st);
+    ORE_KW_TILES(KW_GO)
+#undef KW_GO
+    return ORE_EINVAL;
 }
 
 }  // namespace oreconv

@@ -39,9 +39,7 @@ __device__ unsigned long long* g_trace_rf = nullptr;
 #define RF_TRR(i) do { } while (0)
 #endif
 
-constexpr unsigned kOOB = 0x80000000u;            // a byte offset beyond every buffer's num_records (< 2 GB here, and kOOB + an instruction offset
-                                                  // cannot wrap): the load returns zeros
-constexpr int kTab = 256;                         // chunk table entries (3x3 layers): covers K = 9 * 448 channels
+constexpr int kTab = kRfTab;                      // chunk table entries (3x3 layers)
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
@@ -266,13 +264,9 @@ __global__ __launch_bounds__(NW * 64) void k_conv_rf(RfP q) {
 #endif
 }
 
-int g_rf_mode = 1;                       // tuning aid (ore_conv_set_plan_override(-10, mode)): 0 off, 1 automatic, 2 wherever it applies
-int g_rf_force[3] = {0, 0, 0};           // (-11, GB, NW, MAXS): force the build
-
 template <int GB, int NW, int MAXS>
-int launch_rf(const RfP& q, bool k3, dim3 grid, hipStream_t st) {
+int rf_go(const RfP& q, bool k3, dim3 grid, hipStream_t st) {
     constexpr size_t lds = (size_t)(NW * GB * 256) * sizeof(float);
-    ore_note_launch(ORE_LAUNCH_RF, 1);
     if (!k3) hipLaunchKernelGGL((k_conv_rf<GB, NW, MAXS, 1>), grid, dim3(NW * 64), lds, st, q);
     else hipLaunchKernelGGL((k_conv_rf<GB, NW, MAXS, 3>), grid, dim3(NW * 64), lds, st, q);
     return ore_launch_status("k_conv_rf");
@@ -282,41 +276,11 @@ int launch_rf(const RfP& q, bool k3, dim3 grid, hipStream_t st) {
 
 namespace oreconv {
 
-void conv_rf_mode(int mode) { g_rf_mode = mode; }
-bool conv_rf_forced() { return g_rf_force[0] > 0; }
-void conv_rf_force(int gb, int nw, int maxs) { g_rf_force[0] = gb; g_rf_force[1] = nw; g_rf_force[2] = maxs; }
-
-// Does the register-fed kernel take this layer?  (keep in step with conv_rf_launch; ore_conv_colsum_rows asks before the launch)
-bool conv_rf_covers(const ConvP& p) {
-    if (g_rf_mode == 0) return false;
-    if (p.sb || p.bf16 || p.in_mul || p.in_add || p.in_relu || p.nlev != 1 || p.ep_stride) return false;
-    if (p.colsum && g_rf_force[0] == 0) return false;       // (the eSE pool's consumers size their partial rows from k_conv_kw's tile plan)
-    if (p.Cin % 16 != 0 || p.in_ld % 16 != 0 || p.kh != p.kw || (p.kh != 1 && p.kh != 3)) return false;
-    if ((long long)p.M * p.Cout16 * p.K >= (1ll << 31) || p.M >= (1 << 22)) return false;
-    if (p.add && (long long)p.B * p.add_H * p.add_W * p.add_ld * 4 >= (long long)kOOB) return false;
-    const long long in_rows = (long long)p.lv[0].irow0 + (long long)p.B * p.lv[0].H * p.lv[0].W;
-    if (in_rows * p.in_ld * 4 >= (long long)kOOB || (long long)p.Cout16 * p.K * 4 >= (long long)kOOB) return false;
-    if (g_rf_mode == 2 || g_rf_force[0] > 0) return true;
-    // automatic: the latency-bound launches -- few rows, not so many output channels that 16-row tiles re-read the pixels too often,
-    // not so deep a K that a wave needs more than two batches (the second-stage GEMM stays on k_conv_kw: measured)
-    // (round 4: k_conv_kd, which moves the same bytes in coalesced 64-byte segments through LDS-DMA, is ahead of this kernel on every
-    // shape measured -- 5.6 vs 6.3 us on stage 5's 112->112 layers, 10.1 vs 17.2 on 384->112 -- and conv_kw_launch asks it first; what
-    // k_conv_kd declines and fits here still comes here)
-    return p.M <= 512 && p.Cout16 <= 128 && p.nchunks <= 256;
-}
-
-// Returns 1 when the layer is not covered (the caller goes on to k_conv_kw).
-int conv_rf_launch(ConvP& p, hipStream_t st) {
-    if (!conv_rf_covers(p)) return 1;
-    int gb = 1, nw = 4, maxs = 16;
-    if (g_rf_force[0] > 0) { gb = g_rf_force[0]; nw = g_rf_force[1]; maxs = g_rf_force[2]; }
-    else {
-        // waves per block so that a wave's K slice fits ONE batch of registers where it can (two for the deepest layer)
-        if (p.nchunks <= 64) { nw = 4; maxs = p.nchunks <= 32 ? 8 : (p.nchunks <= 48 ? 12 : 16); }
-        else { nw = 8; maxs = p.nchunks <= 96 ? 12 : 16; }
-    }
+// k_conv_rf: build (GB, NW, MAXS) = pl.build[0..2]
+int launch_rf(const ConvP& p, const ConvPlan& pl, hipStream_t st) {
+    const int gb = pl.build[0], nw = pl.build[1], maxs = pl.build[2];
     const int steps = ceil_div(p.nchunks, nw);
-    const int gx = ceil_div(p.M, 16), gy = ceil_div(p.Cout16, 16 * gb);
+    const int gx = pl.gx, gy = pl.gy;
     const Lvl& L = p.lv[0];
     RfP q;
     RfK& k = q.k;
@@ -329,10 +293,9 @@ int conv_rf_launch(ConvP& p, hipStream_t st) {
     k.irow0 = L.irow0; k.H = L.H; k.W = L.W; k.Ho = L.Ho; k.Wo = L.Wo; k.in_ld = p.in_ld; k.in_coff = p.in_coff; k.stride = p.stride; k.pad = p.pad;
     k.out_ld = p.out_ld; k.out_coff = p.out_coff; k.relu_cout = p.relu_cout;
     k.add_H = p.add_H; k.add_W = p.add_W; k.add_ld = p.add_ld; k.add_coff = p.add_coff;
-    k.xmap = conv_choose_xmap(p, gx, gy); k.gx = gx; k.gy = gy;
+    k.xmap = pl.xmap; k.gx = gx; k.gy = gy;
     k.inv_hw = 1.0f / (float)(L.Ho * L.Wo); k.inv_wo = 1.0f / (float)L.Wo; k.inv_gx = 1.0f / (float)gx; k.inv_gy = 1.0f / (float)gy;
     if (p.kh == 3) {                                                  // the chunk table of a 3x3 layer (see RfP)
-        if (nw * k.nb * maxs > kTab) return 1;
         const int cpt = p.Cin >> 4, row_bytes = L.W * p.in_ld * 4, pix_bytes = p.in_ld * 4;
         for (int c = 0; c < kTab; ++c) {
             if (c >= p.nchunks) { q.tab[c] = 15u; continue; }
@@ -342,11 +305,10 @@ int conv_rf_launch(ConvP& p, hipStream_t st) {
     }
     const bool k3 = p.kh == 3;
     const dim3 grid(gx, gy, 1);
-#define RF_CASE(g, w, s) if (gb == g && nw == w && maxs == s) return launch_rf<g, w, s>(q, k3, grid, st);
-    RF_CASE(1, 4, 8) RF_CASE(1, 4, 12) RF_CASE(1, 4, 16) RF_CASE(1, 8, 12) RF_CASE(1, 8, 16) RF_CASE(1, 8, 20) RF_CASE(1, 16, 12)
-    RF_CASE(2, 4, 12) RF_CASE(2, 4, 16) RF_CASE(2, 8, 12)
-#undef RF_CASE
-    return 1;
+#define RF_GO(g, w, s) if (gb == g && nw == w && maxs == s) return rf_go<g, w, s>(q, k3, grid, st);
+    ORE_RF_BUILDS(RF_GO)
+#undef RF_GO
+    return ORE_EINVAL;
 }
 
 }  // namespace oreconv

@@ -418,49 +418,40 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino_nu(WinoP p) {
     }
 }
 
-int g_wino_mode = 1;          // ore_conv_set_plan_override(-7, mode): 0 off, 1 automatic (by row count), 2 wherever it applies
-
-}  // namespace
-
-namespace oreconv {
-
-void conv_wino_mode(int mode) { g_wino_mode = mode; }
-
-// the (Cin, Cout) pairs of 3x3 stride-1 layers a Winograd build exists for
-bool conv_wino_covers(int Cout, int Cin) {
-    if (Cout <= 0 || Cout % 16 != 0) return false;
-    if (Cin == 64) return Cout % 64 == 0;
-    if (Cin == 128) return Cout % 32 == 0;
-    return Cin == 80 || Cin == 96 || Cin == 112;
-}
-
 template <int CIN, int NCGB>
-static int wino_nu_go(const WinoP& p, int nb, hipStream_t st) {
-    const int gy = ceil_div(p.Cout16 / 16, NCGB);
-    int gx = 256 / gy;                                  // one resident block per CU
-    if (gx > nb) gx = nb;
-    if (gx < 1) gx = 1;
+int wino_nu_go(const WinoP& p, dim3 grid, hipStream_t st) {
     const size_t lds = ((size_t)16 * 16 * (CIN + 4) + 4 * 2 * 2 * 16 * (NCGB * 16 + 4)) * sizeof(float);
     static bool attr = false;
     if (!attr) {
         ORE_HIP(hipFuncSetAttribute((const void*)k_conv3x3_wino_nu<CIN, NCGB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr = true;
     }
-    ore_note_launch(ORE_LAUNCH_WINO_NU, 1);
-    hipLaunchKernelGGL((k_conv3x3_wino_nu<CIN, NCGB>), dim3(gx, gy), dim3(512), lds, st, p);
+    hipLaunchKernelGGL((k_conv3x3_wino_nu<CIN, NCGB>), grid, dim3(512), lds, st, p);
     return ore_launch_status("k_conv3x3_wino_nu");
 }
 
-// ORE_OK if launched, 1 if the layer is not covered (the caller goes on to the direct kernels)
-static int conv_wino_launch_impl(const ConvP& c, hipStream_t st) {
-    if ((!g_wino_mode && !c.wino_lstride) || !c.wino || c.bf16) return 1;   // (per-level launches have no direct twin: mode 0 does not apply)
-    if (c.kh != 3 || c.kw != 3 || c.stride != 1 || c.pad != 1 || c.in_mul || c.add || c.colsum) return 1;
-    if (c.Cout != c.Cout16 || !conv_wino_covers(c.Cout, c.Cin)) return 1;
-    if (c.out_ld % 4 != 0 || c.out_coff % 4 != 0 || ((uintptr_t)c.out & 15) != 0 || c.in_ld % 4 != 0 || c.in_coff % 4 != 0) return 1;
-    if (c.ep_stride % 4 != 0 || ((uintptr_t)c.scale & 15) != 0 || ((uintptr_t)c.shift & 15) != 0) return 1;
-    // below these row counts a launch is latency-bound, not multiply-bound (tools/wino_time.py: 128 -> 128 at 1600 rows 13.4 -> 10.3 us,
-    // 96 -> 96 at 1600-1900 rows and everything at 400 rows a tie)
-    if (g_wino_mode != 2 && !c.wino_lstride && c.M < ((c.Cin == 64 || c.Cin == 128) ? 1500 : 3000)) return 1;
+int wino_go(const ConvP& c, const WinoP& p, dim3 grid, hipStream_t st) {
+    if (c.Cin == 80) return wino_nu_go<80, 3>(p, grid, st);
+    if (c.Cin == 96) return wino_nu_go<96, 2>(p, grid, st);
+    if (c.Cin == 112) return wino_nu_go<112, 2>(p, grid, st);
+    const size_t lds = ((size_t)16 * 16 * c.Cin + 4 * 2 * 16 * 64) * sizeof(float);      // V + Z (32 KB for both builds)
+    static bool attr = false;
+    if (!attr) {
+        ORE_HIP(hipFuncSetAttribute((const void*)k_conv3x3_wino<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(96 * 1024)));
+        ORE_HIP(hipFuncSetAttribute((const void*)k_conv3x3_wino<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
+        attr = true;
+    }
+    if (c.Cin == 64) hipLaunchKernelGGL(k_conv3x3_wino<64>, grid, dim3(512), lds, st, p);
+    else hipLaunchKernelGGL(k_conv3x3_wino<128>, grid, dim3(512), lds, st, p);
+    return ore_launch_status("k_conv3x3_wino");
+}
+
+}  // namespace
+
+namespace oreconv {
+
+// k_conv3x3_wino<64 | 128>, k_conv3x3_wino_nu<80 | 96 | 112>
+int launch_wino(const ConvP& c, const ConvPlan& pl, hipStream_t st) {
     WinoP p{};
     p.in = c.in; p.in_ld = c.in_ld; p.in_coff = c.in_coff; p.B = c.B; p.nlev = c.nlev;
     int nb = 0;
@@ -474,47 +465,8 @@ static int conv_wino_launch_impl(const ConvP& c, hipStream_t st) {
     p.U = c.wino; p.Cout = c.Cout; p.Cout16 = c.Cout16;
     p.scale = c.scale; p.shift = c.shift; p.ep_stride = c.ep_stride; p.relu_cout = c.relu_cout;
     p.out = c.out; p.out_ld = c.out_ld; p.out_coff = c.out_coff;
-    if (c.wino_lstride && c.Cin != 64 && c.Cin != 128) {
-        ore_set_error("ore_conv2d_levels_fwd: per-level Winograd weights exist for 64 / 128 input channels only");
-        return ORE_EINVAL;
-    }
-    if (c.Cin == 80) return wino_nu_go<80, 3>(p, nb, st);
-    if (c.Cin == 96) return wino_nu_go<96, 2>(p, nb, st);
-    if (c.Cin == 112) return wino_nu_go<112, 2>(p, nb, st);
-    const int coutb = c.Cin == 64 ? 64 : 32;
-    const int gy = c.Cout / coutb;
-    int gx = 256 / gy;                                  // one resident block per CU
-    if (gx > nb) gx = nb;
-    if (gx < 1) gx = 1;
-    if (c.wino_lstride) {
-        // per-level weights: a block serves one level.  The fewest rounds R for which sum_l ceil(batches_l / R) blocks fit a block row
-        p.u_lstride = c.wino_lstride;
-        const int G = std::max(256 / gy, c.nlev);
-        int R = 1;
-        for (;; ++R) {
-            int need = 0;
-            for (int l = 0; l < c.nlev; ++l) need += ceil_div(p.bat0[l + 1] - p.bat0[l], R);
-            if (need <= G) break;
-        }
-        gx = 0;
-        for (int l = 0; l < c.nlev; ++l) { p.blk0[l] = gx; gx += ceil_div(p.bat0[l + 1] - p.bat0[l], R); }
-        p.blk0[c.nlev] = gx;
-    }
-    const size_t lds = ((size_t)16 * 16 * c.Cin + 4 * 2 * 16 * 64) * sizeof(float);      // V + Z (32 KB for both builds)
-    static bool attr = false;
-    if (!attr) {
-        ORE_HIP(hipFuncSetAttribute((const void*)k_conv3x3_wino<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(96 * 1024)));
-        ORE_HIP(hipFuncSetAttribute((const void*)k_conv3x3_wino<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-        attr = true;
-    }
-    ore_note_launch(ORE_LAUNCH_WINO, 1);
-    if (c.Cin == 64) hipLaunchKernelGGL(k_conv3x3_wino<64>, dim3(gx, gy), dim3(512), lds, st, p);
-    else hipLaunchKernelGGL(k_conv3x3_wino<128>, dim3(gx, gy), dim3(512), lds, st, p);
-    return ore_launch_status("k_conv3x3_wino");
-}
-
-int conv_wino_launch(const ConvP& c, hipStream_t st) {
-    const int rc = conv_wino_launch_impl(c, st);
+    if (c.wino_lstride) { p.u_lstride = c.wino_lstride; wino_level_blocks(c, pl.gy, p.blk0); }
+    const int rc = wino_go(c, p, dim3(pl.gx, pl.gy), st);
     if (rc == 0) ore_note_wino(1);                      // the engine's profile separates algorithmic from executed multiplies
     return rc;
 }

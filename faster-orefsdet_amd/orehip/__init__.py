@@ -5,6 +5,7 @@ There is NO CPU fallback: if the library is missing or a call fails, an exceptio
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -46,6 +47,15 @@ class ConvDesc(C.Structure):
                 ("w_wino", C.c_void_p), ("storage", C.c_int32), ("w_wino_level_stride", C.c_int64), ("w_level_stride", C.c_int64)]
 
 
+class ConvPlan(C.Structure):
+    """ore_conv_plan_t: the kernel, build, split-K and grid of one conv call (ore_conv_plan)."""
+    _fields_ = [("launcher", C.c_int32), ("error", C.c_int32), ("bm", C.c_int32), ("bn", C.c_int32), ("build", C.c_int32 * 4),
+                ("splitk", C.c_int32), ("steps_per_split", C.c_int32), ("xmap", C.c_int32), ("gx", C.c_int32), ("gy", C.c_int32)]
+
+    def astuple(self) -> Tuple[int, ...]:
+        return (self.launcher, self.bm, self.bn, *self.build, self.splitk, self.steps_per_split, self.xmap, self.gx, self.gy)
+
+
 class DetectDesc(C.Structure):
     _fields_ = [("n_levels", C.c_int32), ("head", C.c_void_p * 8), ("head_ld", C.c_int32),
                 ("H", C.c_int32 * 8), ("W", C.c_int32 * 8), ("stride", C.c_int32 * 8),
@@ -64,7 +74,7 @@ class ModelCfg(C.Structure):
 
 
 # every symbol include/ore_hip.h declares (checked by tests/test_capi_symbols.py without a GPU)
-SYMBOLS = ["ore_last_error", "ore_version", "ore_flop_counter_read", "ore_engine_profile_executed_flops", "ore_pack_conv_weights_multi_fwd", "ore_roi_align_bwd_det", "ore_roi_align_bwd_tiled", "ore_roi_losses_fwd", "ore_sample_rois_fwd", "ore_det_record_rows", "ore_winograd_covers", "ore_winograd_weight_floats", "ore_winograd_weight_fwd", "ore_packed_weight_bf16_elems", "ore_pack_conv_weight_bf16_host", "ore_engine_buffer_is_bf16", "ore_stem1_bf16_fwd", "ore_ese_gate_bf16_fwd", "ore_maxpool3x3s2_bf16_fwd", "ore_correlation_levels_bf16_fwd", "ore_groupnorm_affine_levels_bf16_fwd", "ore_groupnorm_apply_bf16_fwd", "ore_head_pred_fwd", "ore_head_pred_bf16_fwd", "ore_head_pred_gn_fwd", "ore_head_pred_gn_bf16_fwd", "ore_groupnorm_apply_levels_bf16_fwd", "ore_ese_gate_scaled_weight_bf16_fwd", "ore_ese_gate_pool_fwd", "ore_ese_gate_pool_bf16_fwd", "ore_roi_align_bf16_fwd", "ore_conv2d_fwd", "ore_conv2d_levels_fwd", "ore_conv_workspace_floats", "ore_conv_colsum_rows", "ore_conv_set_plan_override", "ore_conv_last_launch", "ore_packed_weight_floats", "ore_pack_conv_weight_host",
+SYMBOLS = ["ore_last_error", "ore_version", "ore_flop_counter_read", "ore_engine_profile_executed_flops", "ore_pack_conv_weights_multi_fwd", "ore_roi_align_bwd_det", "ore_roi_align_bwd_tiled", "ore_roi_losses_fwd", "ore_sample_rois_fwd", "ore_det_record_rows", "ore_winograd_covers", "ore_winograd_weight_floats", "ore_winograd_weight_fwd", "ore_packed_weight_bf16_elems", "ore_pack_conv_weight_bf16_host", "ore_engine_buffer_is_bf16", "ore_stem1_bf16_fwd", "ore_ese_gate_bf16_fwd", "ore_maxpool3x3s2_bf16_fwd", "ore_correlation_levels_bf16_fwd", "ore_groupnorm_affine_levels_bf16_fwd", "ore_groupnorm_apply_bf16_fwd", "ore_head_pred_fwd", "ore_head_pred_bf16_fwd", "ore_head_pred_gn_fwd", "ore_head_pred_gn_bf16_fwd", "ore_groupnorm_apply_levels_bf16_fwd", "ore_ese_gate_scaled_weight_bf16_fwd", "ore_ese_gate_pool_fwd", "ore_ese_gate_pool_bf16_fwd", "ore_roi_align_bf16_fwd", "ore_conv2d_fwd", "ore_conv2d_levels_fwd", "ore_conv_workspace_floats", "ore_conv_colsum_rows", "ore_conv_set_plan_override", "ore_conv_reset_plan_overrides", "ore_conv_plan", "ore_conv_last_launch", "ore_packed_weight_floats", "ore_pack_conv_weight_host",
            "ore_stem1_fwd", "ore_maxpool3x3s2_fwd", "ore_ese_gate_fwd", "ore_ese_gate_from_colsum_fwd", "ore_ese_gate_scaled_weight_fwd", "ore_correlation_levels_fwd",
            "ore_groupnorm_affine_levels_fwd", "ore_scale_channels_fwd", "ore_correlation_fwd",
            "ore_support_kernels_fwd", "ore_groupnorm_affine_fwd", "ore_detect_workspace_bytes", "ore_detect_fwd", "ore_detect_batch_fwd",
@@ -522,6 +532,33 @@ def conv_last_launch() -> Tuple[str, int]:
     s = C.c_int32(1)
     code = int(lib().ore_conv_last_launch(C.byref(s)))
     return CONV_LAUNCHERS[code], int(s.value)
+
+
+def conv_plan(d: ConvDesc, levels: Optional[Sequence[Tuple[int, int]]] = None, ep_stride: int = 0) -> ConvPlan:
+    """The plan an ore_conv2d_fwd (levels None) or ore_conv2d_levels_fwd call with this descriptor makes now (ore_conv_plan); raises
+    OreError with the call's error when no kernel takes it."""
+    pl = ConvPlan()
+    if levels is None:
+        rc = lib().ore_conv_plan(C.byref(d), 0, None, None, 0, C.byref(pl))
+    else:
+        n = len(levels)
+        H, W = (C.c_int32 * n)(*[h for h, _ in levels]), (C.c_int32 * n)(*[w for _, w in levels])
+        rc = lib().ore_conv_plan(C.byref(d), n, H, W, ep_stride, C.byref(pl))
+    _chk(rc, "ore_conv_plan")
+    return pl
+
+
+@contextlib.contextmanager
+def conv_overrides(*codes: Sequence[int]):
+    """Tuning aids for the duration of a block: ore_conv_set_plan_override(*code) for each code (padded with zeros to its five
+    arguments); every override is reset to the automatic plan on exit, also when the block raises."""
+    try:
+        for c in codes:
+            c = tuple(c) + (0,) * (5 - len(c))
+            _chk(lib().ore_conv_set_plan_override(*c), "ore_conv_set_plan_override")
+        yield
+    finally:
+        lib().ore_conv_reset_plan_overrides()
 
 
 def _detect_spec(L: int, pre_topk: int):

@@ -131,6 +131,20 @@ int ore_conv_set_plan_override(int32_t BM, int32_t BN, int32_t WGM, int32_t WGN,
 #define ORE_LAUNCH_IGEMM 13         /* k_conv_igemm (split-K possible) */
 #define ORE_LAUNCH_WS_SB 14         /* k_conv3x3_ws, bf16 storage */
 int32_t ore_conv_last_launch(int32_t* split);
+/* Tuning aid: restore every ore_conv_set_plan_override setting to the automatic plan (the precision is left as it is). */
+int ore_conv_reset_plan_overrides(void);
+/* The plan an ore_conv2d_fwd (n_levels = 0) or ore_conv2d_levels_fwd call with these arguments makes under the current settings; no
+ * GPU work.  Returns ORE_OK, or the error code the call would return (the last-error string says why; out->launcher is then
+ * ORE_LAUNCH_NONE).  Pointers are only tested for null and alignment. */
+typedef struct ore_conv_plan_t {
+    int32_t launcher;          /* ORE_LAUNCH_* */
+    int32_t error;             /* ORE_OK or the call's error code */
+    int32_t bm, bn;            /* rows x output channels of a block tile (3x3 tile kernels: image rows of a tile x channels per block) */
+    int32_t build[4];          /* the launcher's other build parameters (waves, ring depth, ...) */
+    int32_t splitk, steps_per_split, xmap;   /* cross-block split-K, K steps per split, block -> tile mapping (tile_of_block) */
+    int32_t gx, gy;            /* grid */
+} ore_conv_plan_t;
+int ore_conv_plan(const ore_conv_desc* d, int32_t n_levels, const int32_t* H, const int32_t* W, int32_t ep_stride, ore_conv_plan_t* out);
 /* Operand precision of the MFMA conv kernels for all subsequent ore_conv2d*_fwd launches (BASELINE configs[4], "bf16 MFMA conv
  * path + fp32 NMS"; the reference itself is fp32 only, ref:configs/fsod/finetune_vovnet.yaml).  ORE_CONV_FP32 (default): fp32
  * operands, v_mfma_f32_16x16x4_f32.  ORE_CONV_BF16: tensors stay fp32 in HBM and LDS, both operands are rounded to bf16 (nearest

@@ -91,12 +91,8 @@ def test_conv_gd_bf16_operand_builds_vs_oracle(ore, bf16, bm, bn, H, W, Cin, Cou
     sc, sh = torch.rand(Cout, generator=g) + 0.5, torch.randn(Cout, generator=g) * 0.1
     with R.operand_precision("bf16"):
         ref = F.relu(R.dense_conv(x, w, None, stride, k // 2) * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1))
-    L = ore.lib()
-    assert L.ore_conv_set_plan_override(-15, bm, bn, 4, 0) == 0
-    try:
+    with ore.conv_overrides((-15, bm, bn, 4)):
         y = ore.conv2d(nhwc(x), ore.pack_conv_weight(w).cuda(), Cout, k, stride, scale=sc.cuda(), shift=sh.cuda(), relu_cout=Cout)
-    finally:
-        L.ore_conv_set_plan_override(-15, 0, 0, 0, 0)
     got = nchw(y).numpy()
     assert rel_err(got, ref.numpy()) < TOL_LAYER
     full = F.relu(F.conv2d(x, w, None, stride, k // 2) * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1))
@@ -341,14 +337,10 @@ def test_conv_kd_bf16_storage_every_build(bm, bn, nw, sb, H, W, Cin, Cout, k):
     ref = F.relu(F.conv2d(x.float(), w.float(), sh, 1, k // 2))
     xd = x.permute(0, 2, 3, 1).contiguous().cuda()
     wp = ore.pack_conv_weight_bf16(w.float()).cuda()
-    L = ore.lib()
-    L.ore_conv_set_plan_override(-13, bm, bn, nw, sb)
-    try:
+    with ore.conv_overrides((-13, bm, bn, nw, sb)):
         y32 = ore.conv2d(xd, wp, Cout, k, 1, shift=sh.cuda(), relu_cout=Cout, out_f32=True)
         y, cs = ore.conv2d(xd, wp, Cout, k, 1, shift=sh.cuda(), relu_cout=Cout, want_colsum=True)
         y2 = ore.conv2d(xd, wp, Cout, k, 1, shift=sh.cuda(), relu_cout=Cout)
-    finally:
-        L.ore_conv_set_plan_override(-13, 0, 0, 0, 0)
     assert float((y32.cpu().permute(0, 3, 1, 2) - ref).abs().max() / ref.abs().max()) < 1e-4
     assert y.dtype == torch.bfloat16 and _ulp_close(y.cpu(), y32.cpu()) and torch.equal(y, y2)
     want_cs = y.float().sum((0, 1, 2)).cpu()

@@ -16,6 +16,8 @@ Launchers and how this module reaches them:
     k_conv_kw, k_conv_gs, k_conv_igemm at other shapes; explicit split-K 2, 3, 7, 17 on k_conv_igemm (test_explicit_splitk).
 
 ORE_DGRAD_LOG=<file>: append the worst hard-bound and rms ratios per (mode, launcher) to that file."""
+import contextlib
+import ctypes as C
 import os
 
 import pytest
@@ -29,10 +31,6 @@ NAN = float("nan")
 _RATIOS = {}        # (mode, launcher) -> [worst hard, worst rms, checks]
 _CELLS = set()      # (mode, launcher) reached by the automatic plan in the matrix / edge classes
 
-# overrides (BM, BN, WGM, WGN, WGK) of ore_conv_set_plan_override that restore the automatic plan
-_DEFAULTS = [(-1, -1), (-2, 1), (-7, 1), (-10, 1), (-11, 0, 0, 0), (-12, 1), (-13, 0, 0, 0, 0), (-14, 1), (-15, 0, 0, 0), (-4, 0, 0),
-             (-3, 0, 0, 0, 0), (0, 0, 0, 0, 0)]
-
 
 @pytest.fixture(scope="module")
 def oh():
@@ -42,20 +40,28 @@ def oh():
     return orehip
 
 
-def _override(oh, *args):
-    a = list(args) + [0] * (5 - len(args))
-    oh.lib().ore_conv_set_plan_override(*a)
+@contextlib.contextmanager
+def _planned(oh):
+    """Each ore_conv2d_fwd call made inside the block first asks ore_conv_plan about the same descriptor; the answers, in order."""
+    L = oh.lib()
+    real, plans = L.ore_conv2d_fwd, []
 
+    def fwd(d, stream):
+        pl = oh.ConvPlan()
+        assert L.ore_conv_plan(d, 0, None, None, 0, C.byref(pl)) == 0, L.ore_last_error()
+        plans.append((oh.CONV_LAUNCHERS[pl.launcher], pl.splitk))
+        return real(d, stream)
 
-def _restore(oh):
-    for a in _DEFAULTS:
-        _override(oh, *a)
+    L.ore_conv2d_fwd = fwd
+    try:
+        yield plans
+    finally:
+        L.ore_conv2d_fwd = real
 
 
 @pytest.fixture(scope="module", autouse=True)
 def ratio_report(oh):
     yield
-    _restore(oh)
     lines = [f"{m:5s} {l:26s} max hard {h:.3e}  max rms {r:.3e}  ({n} checks)" for (m, l), (h, r, n) in sorted(_RATIOS.items())]
     print("\n" + "\n".join(lines))
     log = os.environ.get("ORE_DGRAD_LOG")
@@ -69,13 +75,6 @@ def mode(oh, request):
     prev = oh.set_conv_precision(request.param)
     yield request.param
     oh.set_conv_precision(prev)
-
-
-@pytest.fixture
-def plan(oh):
-    """Overrides set inside the test are undone afterwards."""
-    yield lambda *a: _override(oh, *a)
-    _restore(oh)
 
 
 def _subset(B, H, W, k, work):
@@ -193,24 +192,25 @@ FORCED = [
 
 
 @pytest.mark.parametrize("i,mode_", [(i, m) for i, f in enumerate(FORCED) for m in f[3]])
-def test_forced_launcher(oh, plan, i, mode_):
+def test_forced_launcher(oh, i, mode_):
     """Each launcher the automatic plan does not pick for a data-gradient call, forced at a data-gradient shape in every mode it has a
     build for; the hook confirms it ran."""
     name, overrides, (B, H, W, Cout, Cin, k), _ = FORCED[i]
     prev = oh.set_conv_precision(mode_)
     try:
-        _forced(oh, plan, i, mode_)
+        with oh.conv_overrides(*FORCED[i][1]):
+            _forced(oh, i, mode_)
     finally:
         oh.set_conv_precision(prev)
 
 
-def _forced(oh, plan, i, mode):
+def _forced(oh, i, mode):
     name, overrides, (B, H, W, Cout, Cin, k), _ = FORCED[i]
-    for o in overrides:
-        plan(*o)
     dz, w = DR.scaled_operands(B, H, W, Cout, Cin, k, seed=50 + i, device="cuda")
-    got, launch = _launch_dgrad(oh, dz, w, k, wino=False)
+    with _planned(oh) as plans:
+        got, launch = _launch_dgrad(oh, dz, w, k, wino=False)
     assert launch[0] == name, (FORCED[i], launch)
+    assert plans == [launch], (FORCED[i], plans, launch)
     _check(oh, mode, dz, w, k, got, launch, FORCED[i])
     got2, launch2 = _launch_dgrad(oh, dz, w, k, wino=False)
     assert launch2 == launch and torch.equal(got, got2), "two identical launches differ"
@@ -245,12 +245,14 @@ def test_explicit_splitk_small_workspace_is_refused(oh):
     assert bool(out.isnan().all()), "a refused launch wrote its output"
 
 
-def test_automatic_split_falls_back_with_a_small_workspace(oh, mode, plan):
+def test_automatic_split_falls_back_with_a_small_workspace(oh, mode):
     """The automatic k_conv_igemm plan splits K on a small, deep launch (>= 48 steps, < 256 blocks: a 3x3 over 384 dZ channels on
     an 8x8 map); with a workspace too small for the split it runs S = 1."""
-    plan(-14, 0)
-    plan(-2, 0)
-    plan(-1, 0)
+    with oh.conv_overrides((-14, 0), (-2, 0), (-1, 0)):
+        _automatic_split(oh, mode)
+
+
+def _automatic_split(oh, mode):
     B, H, W, Cout, Cin, k = 1, 8, 8, 384, 112, 3
     dz, w = DR.scaled_operands(B, H, W, Cout, Cin, k, seed=4, device="cuda")
     got, launch = _launch_dgrad(oh, dz, w, k)
@@ -439,10 +441,12 @@ def _replay(oh, mode, calls, batch):
         if add_ld:
             add = torch.randn(B, (H + 1) // 2, (W + 1) // 2, add_ld, generator=gen, device="cuda") * float(sw.mean())
         out = torch.full((B, H, W, out_ld), NAN, device="cuda")
-        res = oh.conv2d(x, pw, Cout, k, 1, pad, in_coff=in_coff, Cin=Cin, scale=scale, shift=shift, relu_cout=relu_cout, add=add,
-                        out=out, out_coff=out_coff, splitk=splitk, w_wino=ww, want_colsum=colsum)
+        with _planned(oh) as plans:
+            res = oh.conv2d(x, pw, Cout, k, 1, pad, in_coff=in_coff, Cin=Cin, scale=scale, shift=shift, relu_cout=relu_cout, add=add,
+                            out=out, out_coff=out_coff, splitk=splitk, w_wino=ww, want_colsum=colsum)
         got_l = oh.conv_last_launch()
         assert got_l == launch, (sig, launch, got_l)
+        assert plans == [got_l], (sig, plans, got_l)
         out = res[0] if colsum else res
         assert bool(out[..., :out_coff].isnan().all()) and bool(out[..., out_coff + Cout:].isnan().all()), ("wrote outside its slice", sig)
         images, rows = _subset(B, H, W, k, B * H * W * Cin * Cout * k * k)

@@ -131,9 +131,8 @@ def test_conv_slices_inmul_add_partial_relu(ore):
 @pytest.fixture
 def wino_forced(ore):
     """Winograd F(2x2,3x3) kernel (csrc/ore_conv_wino.hip) wherever it applies -- the automatic plan only takes it from 1500 / 3000 rows."""
-    ore.lib().ore_conv_set_plan_override(-7, 2, 0, 0, 0)
-    yield
-    ore.lib().ore_conv_set_plan_override(-7, 1, 0, 0, 0)
+    with ore.conv_overrides((-7, 2)):
+        yield
 
 
 @pytest.mark.parametrize("B,H,W,Cin,Cout", [
@@ -254,15 +253,8 @@ def test_conv_winograd_per_level_weights(ore, HW, B):
 @pytest.fixture
 def kw_forced(ore):
     """Force the wave-private K-split LDS-DMA kernel (k_conv_kw, csrc/ore_conv_kw.hip) wherever it applies, then restore the plan."""
-    ore.lib().ore_conv_set_plan_override(-2, 2, 0, 0, 0)
-    ore.lib().ore_conv_set_plan_override(-10, 0, 0, 0, 0)        # (the register-fed / lean-DMA kernels would take their shapes first)
-    ore.lib().ore_conv_set_plan_override(-12, 0, 0, 0, 0)
-    ore.lib().ore_conv_set_plan_override(-14, 0, 0, 0, 0)
-    yield
-    ore.lib().ore_conv_set_plan_override(-14, 1, 0, 0, 0)
-    ore.lib().ore_conv_set_plan_override(-12, 1, 0, 0, 0)
-    ore.lib().ore_conv_set_plan_override(-10, 1, 0, 0, 0)
-    ore.lib().ore_conv_set_plan_override(-2, 1, 0, 0, 0)
+    with ore.conv_overrides((-2, 2), (-10, 0), (-12, 0), (-14, 0)):   # (the register-fed / lean-DMA kernels would take their shapes first)
+        yield
 
 
 @pytest.mark.parametrize("B,H,W,Cin,Cout,k,stride", [
@@ -301,8 +293,8 @@ GD_BUILDS = [(64, 128, 4), (64, 64, 4), (64, 112, 4), (128, 64, 4), (128, 128, 4
 @pytest.fixture
 def gd_forced(ore):
     """Force builds of the shared-stage descriptor kernel (k_conv_gd, csrc/ore_conv_gd.hip); restore the plan afterwards."""
-    yield
-    ore.lib().ore_conv_set_plan_override(-15, 0, 0, 0, 0)
+    with ore.conv_overrides():
+        yield
 
 
 @pytest.mark.parametrize("bm,bn,ns", GD_BUILDS)
@@ -354,10 +346,8 @@ def test_conv_gd_levels_flat(ore, gd_forced, bm, bn, ns):
     xs = [torch.randn(B, Cin, h, ww, generator=g) for h, ww in HW]
     rows = torch.cat([nhwc(x).reshape(-1, Cin) for x in xs], 0).contiguous()
     wp = ore.pack_conv_weight(w).cuda()
-    ore.lib().ore_conv_set_plan_override(-12, 0, 0, 0, 0)          # k_conv_kd would take these rows first
-    ore.lib().ore_conv_set_plan_override(-15, bm, bn, ns, 0)
-    y = ore.conv2d_levels(rows.cuda(), HW, B, wp, Cout, 1, shift=dev(b), relu_cout=Cout).cpu()
-    ore.lib().ore_conv_set_plan_override(-12, 1, 0, 0, 0)
+    with ore.conv_overrides((-12, 0), (-15, bm, bn, ns)):          # k_conv_kd would take these rows first
+        y = ore.conv2d_levels(rows.cuda(), HW, B, wp, Cout, 1, shift=dev(b), relu_cout=Cout).cpu()
     o = 0
     for x, (h, ww) in zip(xs, HW):
         ref = F.relu(F.conv2d(x, w, b))
@@ -376,10 +366,8 @@ def test_conv_gd_topdown_add(ore, gd_forced, bm, bn, ns):
     b = torch.randn(Cout, generator=g) * 0.1
     top = torch.randn(B, Cout, (H + 1) // 2, (W + 1) // 2, generator=g)
     ref = F.conv2d(x, w, b) + F.interpolate(top, scale_factor=2, mode="nearest")[:, :, :H, :W]
-    ore.lib().ore_conv_set_plan_override(-12, 0, 0, 0, 0)
-    ore.lib().ore_conv_set_plan_override(-15, bm, bn, ns, 0)
-    y = ore.conv2d(nhwc(x), ore.pack_conv_weight(w).cuda(), Cout, 1, 1, shift=dev(b), add=nhwc(top))
-    ore.lib().ore_conv_set_plan_override(-12, 1, 0, 0, 0)
+    with ore.conv_overrides((-12, 0), (-15, bm, bn, ns)):
+        y = ore.conv2d(nhwc(x), ore.pack_conv_weight(w).cuda(), Cout, 1, 1, shift=dev(b), add=nhwc(top))
     assert rel_err(nchw(y).numpy(), ref.numpy()) < TOL
 
 
@@ -394,14 +382,10 @@ def test_conv_gd_plan_takes_conv3_and_lat3(ore):
         top = torch.randn(1, 40, 40, 128, generator=g).cuda()          # the lateral adds the upsampled coarser level (FPN top-down)
         run = (lambda: ore.conv2d_levels(rows, HW, 1, wp, 128, 1)) if len(HW) > 1 else (lambda: ore.conv2d(rows.view(1, 80, 80, 256), wp, 128, 1, add=top).view(-1, 128))
         y_plan = run().clone()
-        ore.lib().ore_conv_set_plan_override(-12, 0, 0, 0, 0)
-        ore.lib().ore_conv_set_plan_override(-15, *build, 0)
-        y_forced = run().clone()
-        ore.lib().ore_conv_set_plan_override(-15, 0, 0, 0, 0)
-        ore.lib().ore_conv_set_plan_override(-14, 0, 0, 0, 0)
-        y_other = run().clone()                                        # gd and kd off: the round-3 kernel
-        ore.lib().ore_conv_set_plan_override(-14, 1, 0, 0, 0)
-        ore.lib().ore_conv_set_plan_override(-12, 1, 0, 0, 0)
+        with ore.conv_overrides((-12, 0), (-15, *build)):
+            y_forced = run().clone()
+        with ore.conv_overrides((-12, 0), (-14, 0)):
+            y_other = run().clone()                                    # gd and kd off: the round-3 kernel
         assert torch.equal(y_plan, y_forced)
         ref = rows.cpu() @ w.view(128, 256).t()
         if len(HW) == 1:
@@ -412,10 +396,8 @@ def test_conv_gd_plan_takes_conv3_and_lat3(ore):
 @pytest.fixture
 def kd_forced(ore):
     """Force the lean LDS-DMA kernel (k_conv_kd, csrc/ore_conv_kd.hip) wherever it applies, then restore the plan."""
-    ore.lib().ore_conv_set_plan_override(-12, 2, 0, 0, 0)
-    yield
-    ore.lib().ore_conv_set_plan_override(-13, 0, 0, 0, 0)
-    ore.lib().ore_conv_set_plan_override(-12, 1, 0, 0, 0)
+    with ore.conv_overrides((-12, 2)):
+        yield
 
 
 KD_BUILDS = [(16, 16, 4, 4), (16, 16, 4, 8), (16, 16, 8, 4), (16, 16, 16, 2), (16, 32, 4, 4), (16, 32, 8, 2), (32, 32, 4, 4), (32, 32, 8, 2),
@@ -451,11 +433,8 @@ def test_conv_kd_kernel_vs_oracle(ore, kd_forced, B, H, W, Cin, Cout, k, stride)
     assert rel_err(nchw(y).numpy(), ref.numpy()) < TOL
     assert chan_err(nchw(y).numpy(), ref.numpy()) < TOL
     assert torch.equal(y, ore.conv2d(nhwc(x), wp, Cout, k, stride, scale=dev(sc), shift=dev(sh), relu_cout=Cout))
-    ore.lib().ore_conv_set_plan_override(-12, 0, 0, 0, 0)
-    ore.lib().ore_conv_set_plan_override(-10, 0, 0, 0, 0)
-    y_kw = ore.conv2d(nhwc(x), wp, Cout, k, stride, scale=dev(sc), shift=dev(sh), relu_cout=Cout)
-    ore.lib().ore_conv_set_plan_override(-10, 1, 0, 0, 0)
-    ore.lib().ore_conv_set_plan_override(-12, 2, 0, 0, 0)
+    with ore.conv_overrides((-12, 0), (-10, 0)):
+        y_kw = ore.conv2d(nhwc(x), wp, Cout, k, stride, scale=dev(sc), shift=dev(sh), relu_cout=Cout)
     assert rel_err(y.cpu().numpy(), y_kw.cpu().numpy()) < 2e-5
 
 
@@ -506,12 +485,8 @@ def test_conv_kd_slices_add_colsum(ore, kd_forced):
 @pytest.fixture
 def rf_forced(ore):
     """Force the register-fed small-M kernel (k_conv_rf, csrc/ore_conv_rf.hip) wherever it applies, then restore the plan."""
-    ore.lib().ore_conv_set_plan_override(-10, 2, 0, 0, 0)
-    ore.lib().ore_conv_set_plan_override(-12, 0, 0, 0, 0)
-    yield
-    ore.lib().ore_conv_set_plan_override(-12, 1, 0, 0, 0)
-    ore.lib().ore_conv_set_plan_override(-11, 0, 0, 0, 0)
-    ore.lib().ore_conv_set_plan_override(-10, 1, 0, 0, 0)
+    with ore.conv_overrides((-10, 2), (-12, 0)):
+        yield
 
 
 RF_BUILDS = [(1, 4, 8), (1, 4, 12), (1, 4, 16), (1, 8, 12), (1, 8, 16), (1, 8, 20), (1, 16, 12), (2, 4, 12), (2, 4, 16), (2, 8, 12)]
@@ -544,9 +519,8 @@ def test_conv_rf_kernel_vs_oracle(ore, rf_forced, B, H, W, Cin, Cout, k, stride)
     assert rel_err(nchw(y).numpy(), ref.numpy()) < TOL
     assert chan_err(nchw(y).numpy(), ref.numpy()) < TOL
     assert torch.equal(y, ore.conv2d(nhwc(x), wp, Cout, k, stride, scale=dev(sc), shift=dev(sh), relu_cout=Cout))
-    ore.lib().ore_conv_set_plan_override(-10, 0, 0, 0, 0)                             # and it really was another kernel than k_conv_kw's sum order
-    y_kw = ore.conv2d(nhwc(x), wp, Cout, k, stride, scale=dev(sc), shift=dev(sh), relu_cout=Cout)
-    ore.lib().ore_conv_set_plan_override(-10, 2, 0, 0, 0)
+    with ore.conv_overrides((-10, 0), (-12, 0)):                                      # and it really was another kernel than k_conv_kw's sum order
+        y_kw = ore.conv2d(nhwc(x), wp, Cout, k, stride, scale=dev(sc), shift=dev(sh), relu_cout=Cout)
     assert rel_err(y.cpu().numpy(), y_kw.cpu().numpy()) < 2e-5
 
 
@@ -597,20 +571,14 @@ def test_conv_kw_wave_counts(ore, kw_forced, nw, tile, H, W, Cin, Cout, k, S):
     """k_conv_kw with the K dimension split over 8 / 16 waves of one block (template NW; the production plan uses 8 waves for the
     second-stage GEMM): every instantiated (tile, NW) pair, few and many chunks per tap, with and without a cross-block split, against
     F.conv2d at 1e-4, bit-reproducible."""
-    L = ore.lib()
     g = torch.Generator().manual_seed(H + Cin + nw)
     x = torch.randn(1, Cin, H, W, generator=g)
     w = torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5
     sh = torch.randn(Cout, generator=g) * 0.1
     ref = F.relu(F.conv2d(x, w, sh, 1, k // 2))
-    L.ore_conv_set_plan_override(-6, nw, 0, 0, 0)
-    L.ore_conv_set_plan_override(-3, tile[0], tile[1], 2, S)
-    try:
+    with ore.conv_overrides((-6, nw), (-3, tile[0], tile[1], 2, S)):     # (on top of kw_forced; every override is reset afterwards)
         y = ore.conv2d(nhwc(x), ore.pack_conv_weight(w).cuda(), Cout, k, 1, shift=dev(sh), relu_cout=Cout)
         y2 = ore.conv2d(nhwc(x), ore.pack_conv_weight(w).cuda(), Cout, k, 1, shift=dev(sh), relu_cout=Cout)
-    finally:
-        L.ore_conv_set_plan_override(-3, 0, 0, 0, 0)
-        L.ore_conv_set_plan_override(-6, 0, 0, 0, 0)
     assert rel_err(nchw(y).numpy(), ref.numpy()) < TOL
     assert torch.equal(y, y2)
 
@@ -1369,10 +1337,8 @@ def test_conv_inkernel_splitk_repeatable(ore, M_hw, Cin, Cout, k, splitk):
 # ------------------------------------------------------------------------------------------ 3x3 patch kernel (forced on small shapes)
 @pytest.mark.parametrize("mode", [102, 16, 8, 4])
 def test_conv3x3_patch_kernel(ore, mode):
-    L = ore.lib()
     g = torch.Generator().manual_seed(21 + mode)
-    try:
-        L.ore_conv_set_plan_override(-1, mode, 0, 0, 0)
+    with ore.conv_overrides((-1, mode)):
         for (B, H, W, Cin, Cout) in ((2, 17, 23, 32, 64), (1, 40, 40, 128, 128), (1, 9, 33, 16, 64), (1, 64, 48, 64, 192)):
             x = torch.randn(B, Cin, H, W, generator=g)
             w = torch.randn(Cout, Cin, 3, 3, generator=g) / (Cin * 9) ** 0.5
@@ -1403,8 +1369,6 @@ def test_conv3x3_patch_kernel(ore, mode):
             got = out[r0:r0 + B * h * wd].reshape(B, h, wd, 128).permute(0, 3, 1, 2).cpu()
             assert rel_err(got.numpy(), ref.numpy()) < TOL, (mode, l)
             r0 += B * h * wd
-    finally:
-        L.ore_conv_set_plan_override(-1, -1, 0, 0, 0)
 
 
 def test_engines_on_concurrent_streams_are_bit_identical(model):

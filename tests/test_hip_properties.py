@@ -120,14 +120,11 @@ def test_winograd_kernels_linearity_full_size(oh):
     bias = (torch.randn(3, 128, generator=g) * 0.1).cuda()
     y = oh.conv2d_levels(rows, HW, 1, ws[0], 128, 3, shift=bias, ep_stride=128, w_wino=Us, w_wino_level_stride=Us.shape[1])
     r0 = 0
-    oh.lib().ore_conv_set_plan_override(-7, 2, 0, 0, 0)            # single-level reference launches on the Winograd kernel whatever the row count
-    try:
+    with oh.conv_overrides((-7, 2)):                               # single-level reference launches on the Winograd kernel whatever the row count
         for l, (h, w_) in enumerate(HW):
             yl = oh.conv2d(rows[r0:r0 + h * w_].reshape(1, h, w_, 128), ws[l], 128, 3, shift=bias[l].contiguous(), w_wino=Us[l].contiguous())
             assert torch.equal(y[r0:r0 + h * w_], yl.reshape(-1, 128)), "level %d of the grouped launch differs from its own launch" % l
             r0 += h * w_
-    finally:
-        oh.lib().ore_conv_set_plan_override(-7, 1, 0, 0, 0)
 
 
 def test_descriptor_kernels_properties_full_size(oh):
@@ -136,7 +133,6 @@ def test_descriptor_kernels_properties_full_size(oh):
     rounding of the round-3 kernel, and the eSE column sums a launch emits add up to the column sums of its output."""
     g = torch.Generator().manual_seed(28)
     a, b = 0.75, -1.5
-    L = oh.lib()
     shapes = [(320, 320, 64, 128, 3, 2),      # stem_3                      -> k_conv_gd 112 x 128, eight waves
               (160, 160, 320, 112, 1, 1),     # stage-2 concat              -> k_conv_gd 128 x 64, eight waves
               (80, 80, 352, 256, 1, 1),       # stage-3 concat              -> k_conv_gd 64 x 64
@@ -156,11 +152,8 @@ def test_descriptor_kernels_properties_full_size(oh):
         ref_cs = yc.double().sum((0, 1, 2))
         assert float((cs.double().sum(0)[:Cout] - ref_cs).abs().max()) <= 2e-5 * float(ref_cs.abs().max() + yc.abs().sum() / Cout * 1e-2)
         assert float((yc - y1).abs().max()) <= 2e-5 * float(y1.abs().max())
-        L.ore_conv_set_plan_override(-14, 0, 0, 0, 0); L.ore_conv_set_plan_override(-12, 0, 0, 0, 0)
-        try:
+        with oh.conv_overrides((-14, 0), (-12, 0)):
             y_old = oh.conv2d(x1, w, Cout, k, st)
-        finally:
-            L.ore_conv_set_plan_override(-14, 1, 0, 0, 0); L.ore_conv_set_plan_override(-12, 1, 0, 0, 0)
         assert float((y1 - y_old).abs().max()) <= 2e-5 * float(y_old.abs().max())
         differs += int(not torch.equal(y1, y_old))
     assert differs >= 3, "the descriptor kernels did not run (the plan fell back to the round-3 kernels everywhere)"

@@ -1,8 +1,11 @@
 """inference_on_dataset: the reference's evaluation / FPS protocol (d2z:evaluation/evaluator.py:101-221): model.eval(), one
-`model(inputs)` per batch, device sync after every batch, the first min(5, n-1) iterations excluded from the timing."""
+`model(inputs)` per batch, device sync after every batch, the first min(5, n-1) iterations excluded from the timing.
+COCOEvaluator (coco_evaluation.py): COCO box AP on the device; DatasetEvaluators and print_csv_format as d2z exports them."""
 import datetime
 import logging
 import time
+from collections import OrderedDict
+from collections.abc import Mapping
 from contextlib import contextmanager
 
 import torch
@@ -17,6 +20,46 @@ class DatasetEvaluator:
 
     def evaluate(self):
         pass
+
+
+class DatasetEvaluators(DatasetEvaluator):
+    """d2z:evaluation/evaluator.py: several evaluators as one; their result dicts are merged (keys must not collide)."""
+
+    def __init__(self, evaluators):
+        super().__init__()
+        self._evaluators = evaluators
+
+    def reset(self):
+        for evaluator in self._evaluators:
+            evaluator.reset()
+
+    def process(self, inputs, outputs):
+        for evaluator in self._evaluators:
+            evaluator.process(inputs, outputs)
+
+    def evaluate(self):
+        from detectron2.utils.comm import is_main_process
+        results = OrderedDict()
+        for evaluator in self._evaluators:
+            result = evaluator.evaluate()
+            if is_main_process() and result is not None:
+                for k, v in result.items():
+                    assert k not in results, "Different evaluators produce results with the same key {}".format(k)
+                    results[k] = v
+        return results
+
+
+def print_csv_format(results):
+    """d2z:evaluation/testing.py: each task's metrics as copy-paste CSV lines in the log (per-category "AP-..." keys left out)."""
+    logger = logging.getLogger(__name__)
+    for task, res in results.items():
+        if isinstance(res, Mapping):
+            important_res = [(k, v) for k, v in res.items() if "-" not in k]
+            logger.info("copypaste: Task: {}".format(task))
+            logger.info("copypaste: " + ",".join([k[0] for k in important_res]))
+            logger.info("copypaste: " + ",".join(["{0:.4f}".format(k[1]) for k in important_res]))
+        else:
+            logger.info(f"copypaste: {task}={res}")
 
 
 @contextmanager
@@ -55,3 +98,6 @@ def inference_on_dataset(model, data_loader, evaluator):
     results = evaluator.evaluate()
     inference_on_dataset.last_timing = {"images": n, "seconds_per_image": total_time / n, "compute_seconds_per_image": total_compute_time / n}
     return {} if results is None else results
+
+
+from .coco_evaluation import COCOEvaluator  # noqa: E402  (needs DatasetEvaluator above)

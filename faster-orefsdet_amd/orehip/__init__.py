@@ -86,7 +86,8 @@ SYMBOLS = ["ore_last_error", "ore_version", "ore_flop_counter_read", "ore_engine
            "ore_engine_set_classes", "ore_engine_set_support_slot", "ore_engine_set_roi_support_slot", "ore_engine_detect_classes_begin",
            "ore_engine_eval_classes_fwd",
            "ore_engine_buffer", "ore_engine_last_flops", "ore_engine_set_profiling", "ore_engine_read_profile", "ore_event_pair_overhead_us",
-           "ore_rccl_load", "ore_rccl_unique_id", "ore_rccl_comm_create", "ore_rccl_comm_destroy", "ore_allreduce_grads"]
+           "ore_rccl_load", "ore_rccl_unique_id", "ore_rccl_comm_create", "ore_rccl_comm_destroy", "ore_allreduce_grads",
+           "ore_coco_eval_workspace_bytes", "ore_coco_eval"]
 
 _lib = None
 
@@ -106,6 +107,7 @@ def lib() -> C.CDLL:
         L.ore_detect_workspace_bytes.restype = C.c_size_t
         L.ore_nms_workspace_bytes.restype = C.c_size_t
         L.ore_roi_predict_workspace_bytes.restype = C.c_size_t
+        L.ore_coco_eval_workspace_bytes.restype = C.c_size_t
         L.ore_conv_wgrad_workspace_floats.restype = C.c_size_t
         L.ore_engine_last_flops.restype = C.c_double
         L.ore_engine_last_flops.argtypes = [C.c_void_p]
@@ -626,6 +628,70 @@ def detect_batch(heads_per_image: Sequence[Sequence[torch.Tensor]], strides: Seq
     outs = [_detect_desc(heads_per_image[b], strides, score_thresh, pre_topk, nms_thresh, post_topk, ds[b], raw[b], ws[b]) for b in range(B)]
     _chk(lib().ore_detect_batch_fwd(ds, B, _stream()), "ore_detect_batch_fwd")
     return outs
+
+
+class CocoEvalDesc(C.Structure):
+    _fields_ = [("n_images", C.c_int32), ("n_cats", C.c_int32),
+                ("det_boxes", C.c_void_p), ("det_scores", C.c_void_p), ("det_image", C.c_void_p), ("det_cat", C.c_void_p), ("n_dets", C.c_int32),
+                ("gt_boxes", C.c_void_p), ("gt_area", C.c_void_p), ("gt_crowd", C.c_void_p), ("gt_id", C.c_void_p), ("gt_off", C.c_void_p),
+                ("n_gts", C.c_int32),
+                ("iou_thrs_host", C.c_void_p), ("n_iou_thrs", C.c_int32), ("rec_thrs_host", C.c_void_p), ("n_rec_thrs", C.c_int32),
+                ("area_rngs_host", C.c_void_p), ("n_areas", C.c_int32), ("max_dets_host", C.c_void_p), ("n_max_dets", C.c_int32),
+                ("precision", C.c_void_p), ("recall", C.c_void_p), ("scores", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class CocoEvalImages(C.Structure):
+    _fields_ = [("n_units", C.c_void_p), ("unit_pair", C.c_void_p), ("det_index", C.c_void_p), ("dt_matches", C.c_void_p),
+                ("dt_ignore", C.c_void_p), ("gt_npig", C.c_void_p), ("capacity", C.c_int64)]
+
+
+def coco_eval(det_boxes: torch.Tensor, det_scores: torch.Tensor, det_image: torch.Tensor, det_cat: torch.Tensor, gt: Dict[str, torch.Tensor],
+              n_images: int, n_cats: int, iou_thrs, rec_thrs, area_rngs, max_dets, per_image: bool = False,
+              workspace: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """pycocotools COCOeval (bbox, useCats) on the device: ore_coco_eval.  Detections in results-json order: det_boxes [N, 4] XYXY fp32,
+    det_scores [N] fp32, det_image / det_cat [N] int32 indices into the id-sorted images / categories.  gt: device tensors "boxes"
+    [G, 4] XYWH fp64, "area" fp64, "crowd" int32, "id" int64, grouped by (category, image) pair with "off" [K * I + 1] int32.
+    iou_thrs / rec_thrs / area_rngs / max_dets are host sequences (the exact doubles of COCOeval's Params).  Returns device
+    "precision" [T, R, K, A, M], "recall" [T, K, A, M], "scores" [T, R, K, A, M] fp64, and with per_image=True the per-image stage's
+    arrays (n_units, unit_pair, det_index, dt_matches, dt_ignore, gt_npig; include/ore_hip.h).  Enqueued on the current stream, no sync."""
+    dev = det_boxes.device
+    N, G = int(det_scores.numel()), int(gt["area"].numel())
+    iou = np.ascontiguousarray(iou_thrs, dtype=np.float64)
+    rec = np.ascontiguousarray(rec_thrs, dtype=np.float64)
+    area = np.ascontiguousarray(area_rngs, dtype=np.float64).reshape(-1, 2)
+    mdet = np.ascontiguousarray(max_dets, dtype=np.int32)
+    T, R, A, M = len(iou), len(rec), len(area), len(mdet)
+    wsb = lib().ore_coco_eval_workspace_bytes(n_cats, n_images, N, G, T, A, int(mdet[-1]))
+    if wsb == 0:
+        raise OreError(f"coco_eval: bad sizes (cats {n_cats}, images {n_images}, dets {N}, gts {G}, T {T}, A {A})")
+    if workspace is None or workspace.numel() < wsb:
+        workspace = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    out = {"precision": torch.empty(T, R, n_cats, A, M, dtype=torch.float64, device=dev),
+           "recall": torch.empty(T, n_cats, A, M, dtype=torch.float64, device=dev),
+           "scores": torch.empty(T, R, n_cats, A, M, dtype=torch.float64, device=dev)}
+    det_boxes, det_scores = det_boxes.float().contiguous(), det_scores.float().contiguous()
+    det_image, det_cat = det_image.to(torch.int32).contiguous(), det_cat.to(torch.int32).contiguous()
+    d = CocoEvalDesc(n_images=n_images, n_cats=n_cats, det_boxes=_ptr(det_boxes) if N else None, det_scores=_ptr(det_scores) if N else None,
+                     det_image=_ptr(det_image) if N else None, det_cat=_ptr(det_cat) if N else None, n_dets=N,
+                     gt_boxes=_ptr(gt["boxes"]) if G else None, gt_area=_ptr(gt["area"]) if G else None,
+                     gt_crowd=_ptr(gt["crowd"]) if G else None, gt_id=_ptr(gt["id"]) if G else None, gt_off=_ptr(gt["off"]), n_gts=G,
+                     iou_thrs_host=iou.ctypes.data, n_iou_thrs=T, rec_thrs_host=rec.ctypes.data, n_rec_thrs=R,
+                     area_rngs_host=area.ctypes.data, n_areas=A, max_dets_host=mdet.ctypes.data, n_max_dets=M,
+                     precision=_ptr(out["precision"]), recall=_ptr(out["recall"]), scores=_ptr(out["scores"]),
+                     workspace=_ptr(workspace), workspace_bytes=wsb)
+    img = None
+    if per_image:
+        cap = max(1, min(n_cats * n_images, N + G))
+        D = int(mdet[-1])
+        pi = {"n_units": torch.zeros(1, dtype=torch.int32, device=dev), "unit_pair": torch.zeros(cap, dtype=torch.int32, device=dev),
+              "det_index": torch.zeros(cap, D, dtype=torch.int32, device=dev),
+              "dt_matches": torch.zeros(cap, A, T, D, dtype=torch.int64, device=dev),
+              "dt_ignore": torch.zeros(cap, A, T, D, dtype=torch.uint8, device=dev), "gt_npig": torch.zeros(cap, A, dtype=torch.int32, device=dev)}
+        img = CocoEvalImages(capacity=cap, **{k: _ptr(v) for k, v in pi.items()})
+        out.update(pi)
+    _chk(lib().ore_coco_eval(C.byref(d), C.byref(img) if img is not None else None, _stream()), "ore_coco_eval")
+    return out
 
 
 def nms(boxes: torch.Tensor, scores: torch.Tensor, thr: float) -> torch.Tensor:

@@ -682,6 +682,41 @@ int32_t ore_rccl_comm_create(const void* id128, int32_t world, int32_t rank, voi
 int32_t ore_rccl_comm_destroy(void* comm);
 int32_t ore_allreduce_grads(void* comm, float* grads, size_t count, void* stream);
 
+/* ------------------------------------------------------------------ COCO box AP --------------- */
+/* pycocotools COCOeval, iouType "bbox", useCats 1 (evaluate + accumulate) on the device, bit-exact against its published definition;
+ * replaces d2z:evaluation/coco_evaluation.py _evaluate_predictions_on_coco (COCOeval_opt in d2z:evaluation/fast_eval_api.py).
+ * Detections: n_dets rows in results-json order; det_boxes [n][4] XYXY fp32 (XYWH = (x0, y0, x1 - x0, y1 - y0) in fp32, widened),
+ * det_scores [n] fp32, det_image [n] index into the images sorted by id, det_cat [n] index into the categories sorted by id (a row
+ * whose index is out of range is dropped).  Ground truth, grouped by (category, image) pair p = cat * n_images + image, json order
+ * inside a pair: gt_off [n_cats * n_images + 1] int32 offsets, gt_boxes [n_gts][4] XYWH fp64, gt_area (the json "area") fp64,
+ * gt_crowd int32, gt_id (the json "id") int64.  Parameters are host arrays: iou_thrs [T <= 16], rec_thrs [R <= 128, non-decreasing],
+ * area_rngs [A <= 8][2], max_dets [M <= 4, non-decreasing, last <= 128]; A * T <= 64; n_dets < 2^21.
+ * Outputs (fp64, -1 where COCOeval leaves -1): precision [T][R][K][A][M], recall [T][K][A][M], scores [T][R][K][A][M].
+ * Deterministic, no host synchronisation; workspace: ore_coco_eval_workspace_bytes. */
+typedef struct ore_coco_eval_desc {
+    int32_t n_images, n_cats;
+    const float* det_boxes; const float* det_scores; const int32_t* det_image; const int32_t* det_cat; int32_t n_dets;
+    const double* gt_boxes; const double* gt_area; const int32_t* gt_crowd; const int64_t* gt_id; const int32_t* gt_off; int32_t n_gts;
+    const double* iou_thrs_host; int32_t n_iou_thrs;
+    const double* rec_thrs_host; int32_t n_rec_thrs;
+    const double* area_rngs_host; int32_t n_areas;
+    const int32_t* max_dets_host; int32_t n_max_dets;
+    double* precision; double* recall; double* scores;
+    void* workspace; size_t workspace_bytes;
+} ore_coco_eval_desc;
+/* Optional output of the per-image stage (evaluateImg), for tests.  A unit is a (category, image) pair with at least one GT or one
+ * detection, units in pair order; capacity >= min(n_cats * n_images, n_dets + n_gts).  n_units [1]; unit_pair [cap];
+ * det_index [cap][max_det]: input row of the detection of rank r (r < the unit's kept count, score descending, stable);
+ * dt_matches [cap][A][T][max_det]: the matched GT's json id, 0 if none (dtMatches); dt_ignore [cap][A][T][max_det] (dtIgnore);
+ * gt_npig [cap][A]: the unit's GTs that are not ignored in that area range. */
+typedef struct ore_coco_eval_images {
+    int32_t* n_units; int32_t* unit_pair; int32_t* det_index; int64_t* dt_matches; uint8_t* dt_ignore; int32_t* gt_npig;
+    int64_t capacity;
+} ore_coco_eval_images;
+size_t ore_coco_eval_workspace_bytes(int32_t n_cats, int32_t n_images, int32_t n_dets, int32_t n_gts, int32_t n_iou_thrs,
+                                     int32_t n_areas, int32_t max_det);
+int ore_coco_eval(const ore_coco_eval_desc* desc, const ore_coco_eval_images* per_image /* NULL: not wanted */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

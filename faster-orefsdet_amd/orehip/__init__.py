@@ -8,6 +8,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import os
+import re
 import subprocess
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -17,6 +18,7 @@ import torch
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG, "lib", "libore_hip.so")
 CSRC = os.path.join(_PKG, "csrc")
+HEADER = os.path.join(os.path.dirname(_PKG), "include", "ore_hip.h")
 ESE_PARTS = 512
 
 
@@ -73,48 +75,55 @@ class ModelCfg(C.Structure):
                 ("max_batch", C.c_int32), ("max_h", C.c_int32), ("max_w", C.c_int32)]
 
 
-# every symbol include/ore_hip.h declares (checked by tests/test_capi_symbols.py without a GPU)
-SYMBOLS = ["ore_last_error", "ore_version", "ore_flop_counter_read", "ore_engine_profile_executed_flops", "ore_pack_conv_weights_multi_fwd", "ore_roi_align_bwd_det", "ore_roi_align_bwd_tiled", "ore_roi_losses_fwd", "ore_sample_rois_fwd", "ore_det_record_rows", "ore_winograd_covers", "ore_winograd_weight_floats", "ore_winograd_weight_fwd", "ore_packed_weight_bf16_elems", "ore_pack_conv_weight_bf16_host", "ore_engine_buffer_is_bf16", "ore_stem1_bf16_fwd", "ore_ese_gate_bf16_fwd", "ore_maxpool3x3s2_bf16_fwd", "ore_correlation_levels_bf16_fwd", "ore_groupnorm_affine_levels_bf16_fwd", "ore_groupnorm_apply_bf16_fwd", "ore_head_pred_fwd", "ore_head_pred_bf16_fwd", "ore_head_pred_gn_fwd", "ore_head_pred_gn_bf16_fwd", "ore_groupnorm_apply_levels_bf16_fwd", "ore_ese_gate_scaled_weight_bf16_fwd", "ore_ese_gate_pool_fwd", "ore_ese_gate_pool_bf16_fwd", "ore_roi_align_bf16_fwd", "ore_conv2d_fwd", "ore_conv2d_levels_fwd", "ore_conv_workspace_floats", "ore_conv_colsum_rows", "ore_conv_set_plan_override", "ore_conv_reset_plan_overrides", "ore_conv_plan", "ore_conv_last_launch", "ore_packed_weight_floats", "ore_pack_conv_weight_host",
-           "ore_stem1_fwd", "ore_maxpool3x3s2_fwd", "ore_ese_gate_fwd", "ore_ese_gate_from_colsum_fwd", "ore_ese_gate_scaled_weight_fwd", "ore_correlation_levels_fwd",
-           "ore_groupnorm_affine_levels_fwd", "ore_scale_channels_fwd", "ore_correlation_fwd",
-           "ore_support_kernels_fwd", "ore_groupnorm_affine_fwd", "ore_detect_workspace_bytes", "ore_detect_fwd", "ore_detect_batch_fwd",
-           "ore_nms_workspace_bytes", "ore_nms_fwd", "ore_nms_device_n_fwd", "ore_roi_align_fwd", "ore_roi_predict_workspace_bytes",
-           "ore_roi_predict_fwd", "ore_roi_align_batched_fwd", "ore_roi_align_bwd", "ore_centernet_targets_fwd", "ore_centernet_losses_fwd", "ore_centernet_losses_bwd", "ore_sgd_step_fwd", "ore_pack_conv_weight_fwd", "ore_conv_wgrad_workspace_floats",
-           "ore_conv_set_precision", "ore_conv_get_precision", "ore_conv2d_wgrad_fwd", "ore_conv2d_wgrad_bias_fwd", "ore_granule_transpose_fwd", "ore_combine2_fwd", "ore_combine2_bwd", "ore_adaptive_avgpool_nhwc_fwd", "ore_adaptive_avgpool_nhwc_bwd", "ore_group_mean_fwd", "ore_group_mean_bwd", "ore_relu_affine_bwd", "ore_colsum_fwd", "ore_colsum_segments_fwd", "ore_correlation_train_fwd", "ore_correlation_train_bwd",
-           "ore_groupnorm_apply_fwd", "ore_groupnorm_bwd", "ore_prod_colsum_fwd", "ore_scale_add_channels_fwd", "ore_maxpool3x3s2_bwd", "ore_sumpool2x2_fwd", "ore_engine_create", "ore_engine_destroy", "ore_engine_set_tensor",
-           "ore_engine_set_support", "ore_engine_finalize", "ore_engine_set_roi_head", "ore_engine_backbone_fwd", "ore_engine_eval_fwd", "ore_engine_eval_batch_fwd", "ore_engine_detect_fwd", "ore_engine_detect_begin", "ore_engine_detect_end", "ore_roi_predict_post_fwd",
-           "ore_engine_set_classes", "ore_engine_set_support_slot", "ore_engine_set_roi_support_slot", "ore_engine_detect_classes_begin",
-           "ore_engine_eval_classes_fwd",
-           "ore_engine_buffer", "ore_engine_last_flops", "ore_engine_set_profiling", "ore_engine_read_profile", "ore_event_pair_overhead_us",
-           "ore_rccl_load", "ore_rccl_unique_id", "ore_rccl_comm_create", "ore_rccl_comm_destroy", "ore_allreduce_grads",
-           "ore_coco_eval_workspace_bytes", "ore_coco_eval"]
+# The C-ABI's parameter and return types.  Every pointer (T*, T* const*, T a[n], struct and handle pointers) is a c_void_p, which takes
+# an int address, None, bytes, a ctypes array, byref() or a c_void_p.
+_PARAM_TYPES = {"int32_t": C.c_int32, "int64_t": C.c_int64, "size_t": C.c_size_t, "float": C.c_float}
+_RESULT_TYPES = {"int": C.c_int, "int32_t": C.c_int32, "size_t": C.c_size_t, "double": C.c_double, "const char*": C.c_char_p,
+                 "void": None}
 
+
+def _prototypes(path: str) -> Dict[str, Tuple[Optional[type], List[type]]]:
+    """{name: (restype, argtypes)} of every `ret ore_name(params);` the header declares, in its order.  A type outside the tables
+    above is an error: no function of the library is called untyped."""
+    with open(path) as f:
+        src = re.sub(r"/\*.*?\*/|//[^\n]*", " ", f.read(), flags=re.S)
+    src = re.sub(r"^\s*#[^\n]*", " ", src, flags=re.M)
+    protos = {}
+    for stmt in re.split(r"[;{}]", src):
+        m = re.fullmatch(r"\s*(.+?)\s*\b(ore_\w+)\s*\((.*)\)\s*", stmt, flags=re.S)
+        if m is None:
+            continue
+        ret, name, params = " ".join(m[1].split()).replace(" *", "*"), m[2], " ".join(m[3].split())
+        if ret not in _RESULT_TYPES:
+            raise OreError(f"{path}: {name}: no ctypes type for the return type '{ret}'")
+        args = []
+        for p in ([] if params == "void" else params.split(",")):
+            scalar = re.fullmatch(r"\s*(?:const\s+)?(\w+)\s+\w+\s*", p)
+            if "*" in p or "[" in p:
+                args.append(C.c_void_p)
+            elif scalar is not None and scalar[1] in _PARAM_TYPES:
+                args.append(_PARAM_TYPES[scalar[1]])
+            else:
+                raise OreError(f"{path}: {name}: no ctypes type for the parameter '{p.strip()}'")
+        protos[name] = (_RESULT_TYPES[ret], args)
+    return protos
+
+
+_PROTOTYPES = _prototypes(HEADER)
+SYMBOLS = tuple(_PROTOTYPES)          # every function include/ore_hip.h declares
 _lib = None
 
 
 def lib() -> C.CDLL:
+    """libore_hip.so with argtypes / restype of every function set from the header's prototypes."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise OreError(f"{LIB_PATH} not found: build it with `make -C {CSRC}` (there is no CPU fallback)")
         L = C.CDLL(LIB_PATH)
-        L.ore_last_error.restype = C.c_char_p
-        L.ore_packed_weight_floats.restype = C.c_size_t
-        L.ore_winograd_weight_floats.restype = C.c_size_t
-        L.ore_packed_weight_bf16_elems.restype = C.c_size_t
-        L.ore_conv_workspace_floats.restype = C.c_size_t
-        L.ore_conv_colsum_rows.restype = C.c_int32
-        L.ore_detect_workspace_bytes.restype = C.c_size_t
-        L.ore_nms_workspace_bytes.restype = C.c_size_t
-        L.ore_roi_predict_workspace_bytes.restype = C.c_size_t
-        L.ore_coco_eval_workspace_bytes.restype = C.c_size_t
-        L.ore_conv_wgrad_workspace_floats.restype = C.c_size_t
-        L.ore_engine_last_flops.restype = C.c_double
-        L.ore_engine_last_flops.argtypes = [C.c_void_p]
-        L.ore_engine_profile_executed_flops.restype = C.c_double
-        L.ore_engine_profile_executed_flops.argtypes = [C.c_void_p]
-        L.ore_engine_destroy.argtypes = [C.c_void_p]
-        L.ore_engine_destroy.restype = None
+        for name, (restype, argtypes) in _PROTOTYPES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -127,12 +136,12 @@ def _chk(rc: int, what: str):
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
-def _stream() -> C.c_void_p:
+def _stream() -> int:
     """The current torch stream of the current device as a hipStream_t (the raw-handle query is ~10x cheaper than building a
     torch.cuda.Stream object per launch; thousands of launches per training step go through here)."""
     if _RAW_STREAM is not None:
-        return C.c_void_p(_RAW_STREAM(torch.cuda.current_device()))
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        return _RAW_STREAM(torch.cuda.current_device())
+    return torch.cuda.current_stream().cuda_stream
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -145,6 +154,12 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 def _f32(t: torch.Tensor) -> torch.Tensor:
     assert t.dtype == torch.float32 and t.is_contiguous(), (t.dtype, t.is_contiguous())
     return t
+
+
+def _i32s(seq) -> C.Array:
+    """The values as a host int32_t array (per-level sizes and strides)."""
+    v = list(seq)
+    return (C.c_int32 * len(v))(*v)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -166,8 +181,7 @@ def pack_conv_weight(w_oihw: torch.Tensor) -> torch.Tensor:
     co, ci, kh, kw = w.shape
     n = lib().ore_packed_weight_floats(co, ci, kh, kw)
     dst = np.empty(n, dtype=np.float32)
-    _chk(lib().ore_pack_conv_weight_host(C.c_void_p(w.data_ptr()), co, ci, kh, kw, dst.ctypes.data_as(C.c_void_p)),
-         "ore_pack_conv_weight_host")
+    _chk(lib().ore_pack_conv_weight_host(w.data_ptr(), co, ci, kh, kw, dst.ctypes.data), "ore_pack_conv_weight_host")
     return torch.from_numpy(dst).to(w_oihw.device)
 
 
@@ -177,8 +191,7 @@ def pack_conv_weight_bf16(w_oihw: torch.Tensor) -> torch.Tensor:
     co, ci, kh, kw = w.shape
     n = lib().ore_packed_weight_bf16_elems(co, ci, kh, kw)
     dst = np.empty(n, dtype=np.uint16)
-    _chk(lib().ore_pack_conv_weight_bf16_host(C.c_void_p(w.data_ptr()), co, ci, kh, kw, dst.ctypes.data_as(C.c_void_p)),
-         "ore_pack_conv_weight_bf16_host")
+    _chk(lib().ore_pack_conv_weight_bf16_host(w.data_ptr(), co, ci, kh, kw, dst.ctypes.data), "ore_pack_conv_weight_bf16_host")
     return torch.from_numpy(dst.view(np.int16)).view(torch.bfloat16).to(w_oihw.device)
 
 
@@ -191,7 +204,7 @@ def winograd_weight(w_packed: torch.Tensor, Cout: int, Cin: int) -> torch.Tensor
     """Packed 3x3 weights ([Cout16][9][Cin], pack_weight) -> their Winograd F(2x2,3x3) form U [16][Cout16][Cin] on the device."""
     _f32(w_packed)
     U = torch.empty(int(lib().ore_winograd_weight_floats(Cout, Cin)), device=w_packed.device, dtype=torch.float32)
-    _chk(lib().ore_winograd_weight_fwd(C.c_void_p(_ptr(w_packed)), Cout, Cin, C.c_void_p(_ptr(U)), _stream()), "ore_winograd_weight_fwd")
+    _chk(lib().ore_winograd_weight_fwd(_ptr(w_packed), Cout, Cin, _ptr(U), _stream()), "ore_winograd_weight_fwd")
     return U
 
 
@@ -295,10 +308,8 @@ def conv2d_levels(x_rows: torch.Tensor, HW: Sequence[Tuple[int, int]], B: int, w
     d.w_wino = _ptr(w_wino)
     d.w_wino_level_stride = int(w_wino_level_stride)   # != 0: the levels are different layers of one shape, w_wino = [L][stride] (Winograd only)
     d.w_level_stride = int(w_level_stride)             # the same for bf16 storage: w_packed = [L][stride] bf16 (weight-stationary 3x3 kernel)
-    L = len(HW)
-    Hs = (C.c_int32 * L)(*[h for h, _ in HW])
-    Ws = (C.c_int32 * L)(*[w for _, w in HW])
-    _chk(lib().ore_conv2d_levels_fwd(C.byref(d), L, Hs, Ws, ep_stride, _stream()), "ore_conv2d_levels_fwd")
+    _chk(lib().ore_conv2d_levels_fwd(C.byref(d), len(HW), _i32s(h for h, _ in HW), _i32s(w for _, w in HW), ep_stride, _stream()),
+         "ore_conv2d_levels_fwd")
     return out
 
 
@@ -307,12 +318,9 @@ def correlation_levels(q_rows: torch.Tensor, HW: Sequence[Tuple[int, int]], B: i
     _f32(q_rows)
     if out is None:
         out = torch.empty(q_rows.shape[0], Cc, device=q_rows.device, dtype=torch.float32)
-    L = len(HW)
-    Hs = (C.c_int32 * L)(*[h for h, _ in HW])
-    Ws = (C.c_int32 * L)(*[w for _, w in HW])
-    _chk(lib().ore_correlation_levels_fwd(C.c_void_p(_ptr(q_rows)), q_rows.shape[-1], q_coff, B, L, Hs, Ws, Cc,
-                                          C.c_void_p(_ptr(_f32(k11))), C.c_void_p(_ptr(_f32(k13))), C.c_void_p(_ptr(_f32(k31))),
-                                          C.c_void_p(_ptr(out)), out.shape[-1], out_coff, _stream()), "ore_correlation_levels_fwd")
+    _chk(lib().ore_correlation_levels_fwd(_ptr(q_rows), q_rows.shape[-1], q_coff, B, len(HW), _i32s(h for h, _ in HW),
+                                          _i32s(w for _, w in HW), Cc, _ptr(_f32(k11)), _ptr(_f32(k13)), _ptr(_f32(k31)), _ptr(out),
+                                          out.shape[-1], out_coff, _stream()), "ore_correlation_levels_fwd")
     return out
 
 
@@ -323,10 +331,8 @@ def groupnorm_affine_levels(x_rows: torch.Tensor, HW: Sequence[int], B: int, gro
     mul = torch.empty(L * B, Cc, device=x_rows.device)
     add = torch.empty(L * B, Cc, device=x_rows.device)
     ws = torch.empty(sum(B * ((hw + 63) // 64) for hw in HW) * groups * 2 + 64, device=x_rows.device)
-    hws = (C.c_int32 * L)(*HW)
-    _chk(lib().ore_groupnorm_affine_levels_fwd(C.c_void_p(_ptr(x_rows)), Cc, 0, B, L, hws, Cc, groups, C.c_float(eps),
-                                               C.c_void_p(_ptr(_f32(gamma))), C.c_void_p(_ptr(_f32(beta))), C.c_void_p(_ptr(mul)),
-                                               C.c_void_p(_ptr(add)), C.c_void_p(_ptr(ws)), _stream()), "ore_groupnorm_affine_levels_fwd")
+    _chk(lib().ore_groupnorm_affine_levels_fwd(_ptr(x_rows), Cc, 0, B, L, _i32s(HW), Cc, groups, eps, _ptr(_f32(gamma)), _ptr(_f32(beta)),
+                                               _ptr(mul), _ptr(add), _ptr(ws), _stream()), "ore_groupnorm_affine_levels_fwd")
     return mul, add
 
 
@@ -336,9 +342,8 @@ def ese_gate_from_colsum(part: torch.Tensor, HW: int, fc_w: torch.Tensor, fc_b: 
     P, Cc = part.shape
     gate = torch.empty(1, Cc, device=part.device, dtype=torch.float32)
     mean_ws = torch.empty(Cc, device=part.device, dtype=torch.float32)
-    _chk(lib().ore_ese_gate_from_colsum_fwd(C.c_void_p(_ptr(part)), P, 1, HW, Cc, C.c_void_p(_ptr(_f32(fc_w.reshape(Cc, Cc)))),
-                                            C.c_void_p(_ptr(_f32(fc_b))), C.c_void_p(_ptr(gate)), C.c_void_p(_ptr(mean_ws)), _stream()),
-         "ore_ese_gate_from_colsum_fwd")
+    _chk(lib().ore_ese_gate_from_colsum_fwd(_ptr(part), P, 1, HW, Cc, _ptr(_f32(fc_w.reshape(Cc, Cc))), _ptr(_f32(fc_b)), _ptr(gate),
+                                            _ptr(mean_ws), _stream()), "ore_ese_gate_from_colsum_fwd")
     return gate
 
 
@@ -351,9 +356,8 @@ def ese_gate_scaled_weight(part: torch.Tensor, HW: int, fc_w: torch.Tensor, fc_b
     gate = torch.empty(1, Cc, device=part.device, dtype=torch.float32)
     mean_ws = torch.empty(Cc, device=part.device, dtype=torch.float32)
     ws = torch.empty_like(w_packed)
-    _chk(lib().ore_ese_gate_scaled_weight_fwd(C.c_void_p(_ptr(part)), P, HW, Cc, C.c_void_p(_ptr(_f32(fc_w.reshape(Cc, Cc)))),
-                                              C.c_void_p(_ptr(_f32(fc_b))), C.c_void_p(_ptr(gate)), C.c_void_p(_ptr(mean_ws)),
-                                              C.c_void_p(_ptr(w_packed)), w_packed.shape[0], C.c_void_p(_ptr(ws)), _stream()),
+    _chk(lib().ore_ese_gate_scaled_weight_fwd(_ptr(part), P, HW, Cc, _ptr(_f32(fc_w.reshape(Cc, Cc))), _ptr(_f32(fc_b)), _ptr(gate),
+                                              _ptr(mean_ws), _ptr(w_packed), w_packed.shape[0], _ptr(ws), _stream()),
          "ore_ese_gate_scaled_weight_fwd")
     return gate, ws
 
@@ -377,14 +381,9 @@ def stem1(img: torch.Tensor, Hp: int, Wp: int, mean: Sequence[float], std: Seque
     out = torch.empty(B, Hp // 2, Wp // 2, Cout, device=img.device, dtype=torch.bfloat16 if out_bf16 else torch.float32)
     m = (C.c_float * 3)(*mean)
     s = (C.c_float * 3)(*std)
-    if out_bf16:
-        _chk(lib().ore_stem1_bf16_fwd(C.c_void_p(_ptr(img)), int(img.dtype == torch.uint8), B, H, W, Hp, Wp, m, s,
-                                      C.c_void_p(_ptr(_f32(w_oihw))), C.c_void_p(_ptr(scale)), C.c_void_p(_ptr(shift)), Cout,
-                                      C.c_void_p(_ptr(out)), Cout, 0, _stream()), "ore_stem1_bf16_fwd")
-        return out
-    _chk(lib().ore_stem1_fwd(C.c_void_p(_ptr(img)), int(img.dtype == torch.uint8), B, H, W, Hp, Wp, m, s,
-                             C.c_void_p(_ptr(_f32(w_oihw))), C.c_void_p(_ptr(scale)), C.c_void_p(_ptr(shift)), Cout,
-                             C.c_void_p(_ptr(out)), Cout, 0, _stream()), "ore_stem1_fwd")
+    fn = lib().ore_stem1_bf16_fwd if out_bf16 else lib().ore_stem1_fwd
+    _chk(fn(_ptr(img), int(img.dtype == torch.uint8), B, H, W, Hp, Wp, m, s, _ptr(_f32(w_oihw)), _ptr(scale), _ptr(shift), Cout, _ptr(out),
+            Cout, 0, _stream()), fn.__name__)
     return out
 
 
@@ -395,23 +394,14 @@ def maxpool3x3s2(x: torch.Tensor, in_mul: Optional[torch.Tensor] = None, out: Op
     bf = x.dtype == torch.bfloat16
     assert x.is_contiguous() and (bf or x.dtype == torch.float32)
     B, H, W, Cc = x.shape
-
-    def osz(n):
-        o = (n - 3 + 1) // 2 + 1 if n >= 3 else 1
-        if (o - 1) * 2 >= n:
-            o -= 1
-        return max(o, 1)
+    Ho, Wo = maxpool3x3s2_out_hw(H, W)
     if out is None:
-        out = torch.empty(B, osz(H), osz(W), Cc, device=x.device, dtype=x.dtype)
+        out = torch.empty(B, Ho, Wo, Cc, device=x.device, dtype=x.dtype)
     else:
         assert out.dtype == x.dtype and out.is_contiguous()
-        assert tuple(out.shape[:3]) == (B, osz(H), osz(W)) and out_coff + Cc <= out.shape[-1] and out_coff % 4 == 0
-    if bf:
-        _chk(lib().ore_maxpool3x3s2_bf16_fwd(C.c_void_p(_ptr(x)), Cc, 0, B, H, W, Cc, C.c_void_p(_ptr(in_mul)),
-                                             C.c_void_p(_ptr(out)), out.shape[-1], out_coff, _stream()), "ore_maxpool3x3s2_bf16_fwd")
-        return out
-    _chk(lib().ore_maxpool3x3s2_fwd(C.c_void_p(_ptr(x)), Cc, 0, B, H, W, Cc, C.c_void_p(_ptr(in_mul)),
-                                    C.c_void_p(_ptr(out)), out.shape[-1], out_coff, _stream()), "ore_maxpool3x3s2_fwd")
+        assert tuple(out.shape[:3]) == (B, Ho, Wo) and out_coff + Cc <= out.shape[-1] and out_coff % 4 == 0
+    fn = lib().ore_maxpool3x3s2_bf16_fwd if bf else lib().ore_maxpool3x3s2_fwd
+    _chk(fn(_ptr(x), Cc, 0, B, H, W, Cc, _ptr(in_mul), _ptr(out), out.shape[-1], out_coff, _stream()), fn.__name__)
     return out
 
 
@@ -431,14 +421,8 @@ def ese_gate(x: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor) -> torch.T
     B, H, W, Cc = x.shape
     gate = torch.empty(B, Cc, device=x.device, dtype=torch.float32)
     ws = torch.empty(B * (ESE_PARTS + 1) * Cc, device=x.device, dtype=torch.float32)
-    if bf:
-        _chk(lib().ore_ese_gate_bf16_fwd(C.c_void_p(_ptr(x)), Cc, 0, B, H * W, Cc, C.c_void_p(_ptr(_f32(fc_w.reshape(Cc, Cc)))),
-                                         C.c_void_p(_ptr(_f32(fc_b))), C.c_void_p(_ptr(gate)), C.c_void_p(_ptr(ws)), _stream()),
-             "ore_ese_gate_bf16_fwd")
-        return gate
-    _chk(lib().ore_ese_gate_fwd(C.c_void_p(_ptr(x)), Cc, 0, B, H * W, Cc, C.c_void_p(_ptr(_f32(fc_w.reshape(Cc, Cc)))),
-                                C.c_void_p(_ptr(_f32(fc_b))), C.c_void_p(_ptr(gate)), C.c_void_p(_ptr(ws)), _stream()),
-         "ore_ese_gate_fwd")
+    fn = lib().ore_ese_gate_bf16_fwd if bf else lib().ore_ese_gate_fwd
+    _chk(fn(_ptr(x), Cc, 0, B, H * W, Cc, _ptr(_f32(fc_w.reshape(Cc, Cc))), _ptr(_f32(fc_b)), _ptr(gate), _ptr(ws), _stream()), fn.__name__)
     return gate
 
 
@@ -458,9 +442,8 @@ def ese_gate_pool(part: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, x:
         _f32(w_packed)
         ws = torch.empty(w_packed.shape, device=x.device, dtype=x.dtype)
     fn = lib().ore_ese_gate_pool_bf16_fwd if bf else lib().ore_ese_gate_pool_fwd
-    _chk(fn(C.c_void_p(_ptr(part)), P, H * W, Cc, C.c_void_p(_ptr(_f32(fc_w.reshape(Cc, Cc)))), C.c_void_p(_ptr(_f32(fc_b))),
-            C.c_void_p(_ptr(gate)), C.c_void_p(_ptr(w_packed)), 0 if w_packed is None else w_packed.shape[0], C.c_void_p(_ptr(ws)),
-            C.c_void_p(_ptr(x)), Cc, 0, H, W, C.c_void_p(_ptr(out)), Cc, 0, _stream()), "ore_ese_gate_pool_fwd")
+    _chk(fn(_ptr(part), P, H * W, Cc, _ptr(_f32(fc_w.reshape(Cc, Cc))), _ptr(_f32(fc_b)), _ptr(gate), _ptr(w_packed),
+            0 if w_packed is None else w_packed.shape[0], _ptr(ws), _ptr(x), Cc, 0, H, W, _ptr(out), Cc, 0, _stream()), fn.__name__)
     return gate, out, ws
 
 
@@ -468,8 +451,7 @@ def scale_channels(x: torch.Tensor, gate: torch.Tensor) -> torch.Tensor:
     _f32(x)
     B, H, W, Cc = x.shape
     y = torch.empty_like(x)
-    _chk(lib().ore_scale_channels_fwd(C.c_void_p(_ptr(x)), Cc, 0, B, H * W, Cc, C.c_void_p(_ptr(_f32(gate))),
-                                      C.c_void_p(_ptr(y)), Cc, 0, _stream()), "ore_scale_channels_fwd")
+    _chk(lib().ore_scale_channels_fwd(_ptr(x), Cc, 0, B, H * W, Cc, _ptr(_f32(gate)), _ptr(y), Cc, 0, _stream()), "ore_scale_channels_fwd")
     return y
 
 
@@ -480,8 +462,7 @@ def support_kernels(proto_chw: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor
     k11 = torch.empty(Cc, device=proto_chw.device)
     k13 = torch.empty(Cc, 3, device=proto_chw.device)
     k31 = torch.empty(Cc, 3, device=proto_chw.device)
-    _chk(lib().ore_support_kernels_fwd(C.c_void_p(_ptr(proto_chw)), Cc, s, C.c_void_p(_ptr(k11)), C.c_void_p(_ptr(k13)),
-                                       C.c_void_p(_ptr(k31)), _stream()), "ore_support_kernels_fwd")
+    _chk(lib().ore_support_kernels_fwd(_ptr(proto_chw), Cc, s, _ptr(k11), _ptr(k13), _ptr(k31), _stream()), "ore_support_kernels_fwd")
     return k11, k13, k31
 
 
@@ -492,8 +473,7 @@ def correlation(q: torch.Tensor, k11, k13, k31, out: Optional[torch.Tensor] = No
     Cc = Cc if Cc is not None else ld
     if out is None:
         out = torch.empty(B, H, W, Cc, device=q.device, dtype=torch.float32)
-    _chk(lib().ore_correlation_fwd(C.c_void_p(_ptr(q)), ld, q_coff, B, H, W, Cc, C.c_void_p(_ptr(_f32(k11))),
-                                   C.c_void_p(_ptr(_f32(k13))), C.c_void_p(_ptr(_f32(k31))), C.c_void_p(_ptr(out)),
+    _chk(lib().ore_correlation_fwd(_ptr(q), ld, q_coff, B, H, W, Cc, _ptr(_f32(k11)), _ptr(_f32(k13)), _ptr(_f32(k31)), _ptr(out),
                                    out.shape[-1], out_coff, _stream()), "ore_correlation_fwd")
     return out
 
@@ -504,9 +484,8 @@ def groupnorm_affine(x: torch.Tensor, groups: int, gamma: torch.Tensor, beta: to
     mul = torch.empty(B, Cc, device=x.device)
     add = torch.empty(B, Cc, device=x.device)
     ws = torch.empty(B * ((H * W + 63) // 64) * groups * 2, device=x.device)
-    _chk(lib().ore_groupnorm_affine_fwd(C.c_void_p(_ptr(x)), Cc, 0, B, H * W, Cc, groups, C.c_float(eps),
-                                        C.c_void_p(_ptr(_f32(gamma))), C.c_void_p(_ptr(_f32(beta))), C.c_void_p(_ptr(mul)),
-                                        C.c_void_p(_ptr(add)), C.c_void_p(_ptr(ws)), _stream()), "ore_groupnorm_affine_fwd")
+    _chk(lib().ore_groupnorm_affine_fwd(_ptr(x), Cc, 0, B, H * W, Cc, groups, eps, _ptr(_f32(gamma)), _ptr(_f32(beta)), _ptr(mul),
+                                        _ptr(add), _ptr(ws), _stream()), "ore_groupnorm_affine_fwd")
     return mul, add
 
 
@@ -543,9 +522,7 @@ def conv_plan(d: ConvDesc, levels: Optional[Sequence[Tuple[int, int]]] = None, e
     if levels is None:
         rc = lib().ore_conv_plan(C.byref(d), 0, None, None, 0, C.byref(pl))
     else:
-        n = len(levels)
-        H, W = (C.c_int32 * n)(*[h for h, _ in levels]), (C.c_int32 * n)(*[w for _, w in levels])
-        rc = lib().ore_conv_plan(C.byref(d), n, H, W, ep_stride, C.byref(pl))
+        rc = lib().ore_conv_plan(C.byref(d), len(levels), _i32s(h for h, _ in levels), _i32s(w for _, w in levels), ep_stride, C.byref(pl))
     _chk(rc, "ore_conv_plan")
     return pl
 
@@ -704,9 +681,15 @@ def nms(boxes: torch.Tensor, scores: torch.Tensor, thr: float) -> torch.Tensor:
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
     b = boxes.float().contiguous() if n else torch.zeros(1, 4, device=dev)
     s = scores.float().contiguous() if n else torch.zeros(1, device=dev)
-    _chk(lib().ore_nms_fwd(C.c_void_p(_ptr(b)), C.c_void_p(_ptr(s)), n, C.c_float(thr), C.c_void_p(_ptr(keep)),
-                           C.c_void_p(_ptr(cnt)), C.c_void_p(_ptr(ws)), C.c_size_t(wsb), _stream()), "ore_nms_fwd")
+    _chk(lib().ore_nms_fwd(_ptr(b), _ptr(s), n, thr, _ptr(keep), _ptr(cnt), _ptr(ws), wsb, _stream()), "ore_nms_fwd")
     return keep[: int(cnt.item())]
+
+
+def _roi_levels(maps: Sequence[torch.Tensor], strides: Sequence[int]):
+    """The per-level arrays of the ROIAlign entry points: map pointers, ld, channel offset (0), H, W and 1 / stride."""
+    L = len(maps)
+    return ((C.c_void_p * L)(*[_ptr(_f32(f)) for f in maps]), _i32s(f.shape[-1] for f in maps), _i32s([0] * L),
+            _i32s(f.shape[-3] for f in maps), _i32s(f.shape[-2] for f in maps), (C.c_float * L)(*[1.0 / s for s in strides]))
 
 
 def roi_align(feats: Sequence[torch.Tensor], boxes: torch.Tensor, strides: Sequence[int], pooled: int = 8,
@@ -717,15 +700,10 @@ def roi_align(feats: Sequence[torch.Tensor], boxes: torch.Tensor, strides: Seque
     cap = cap or max(n, 1)
     Cc = feats[0].shape[-1]
     out = torch.empty(cap, pooled * pooled * Cc, device=boxes.device, dtype=torch.float32)
-    ptrs = (C.c_void_p * L)(*[_ptr(_f32(f)) for f in feats])
-    ld = (C.c_int32 * L)(*[f.shape[-1] for f in feats])
-    coff = (C.c_int32 * L)(*[0] * L)
-    Hs = (C.c_int32 * L)(*[f.shape[-3] for f in feats])
-    Ws = (C.c_int32 * L)(*[f.shape[-2] for f in feats])
-    sc = (C.c_float * L)(*[1.0 / s for s in strides])
+    ptrs, ld, coff, Hs, Ws, sc = _roi_levels(feats, strides)
     b = boxes.float().contiguous() if n else torch.zeros(1, 4, device=boxes.device)
-    _chk(lib().ore_roi_align_fwd(ptrs, ld, coff, Hs, Ws, sc, L, min_level, Cc, pooled, C.c_void_p(_ptr(b)),
-                                 C.c_void_p(_ptr(n_dev)), n, cap, C.c_void_p(_ptr(out)), _stream()), "ore_roi_align_fwd")
+    _chk(lib().ore_roi_align_fwd(ptrs, ld, coff, Hs, Ws, sc, L, min_level, Cc, pooled, _ptr(b), _ptr(n_dev), n, cap, _ptr(out), _stream()),
+         "ore_roi_align_fwd")
     return out
 
 
@@ -736,15 +714,10 @@ def roi_align_batched(feats: Sequence[torch.Tensor], boxes: torch.Tensor, box_im
     n = boxes.shape[0]
     Cc = feats[0].shape[-1]
     out = torch.empty(max(n, 1), pooled * pooled * Cc, device=boxes.device, dtype=torch.float32)
-    ptrs = (C.c_void_p * L)(*[_ptr(_f32(f)) for f in feats])
-    ld = (C.c_int32 * L)(*[f.shape[-1] for f in feats])
-    coff = (C.c_int32 * L)(*[0] * L)
-    Hs = (C.c_int32 * L)(*[f.shape[-3] for f in feats])
-    Ws = (C.c_int32 * L)(*[f.shape[-2] for f in feats])
-    sc = (C.c_float * L)(*[1.0 / s for s in strides])
+    ptrs, ld, coff, Hs, Ws, sc = _roi_levels(feats, strides)
     assert box_image.dtype == torch.int32 and box_image.numel() == n
-    _chk(lib().ore_roi_align_batched_fwd(ptrs, ld, coff, Hs, Ws, sc, L, min_level, Cc, pooled, C.c_void_p(_ptr(_f32(boxes))),
-                                         C.c_void_p(_ptr(box_image)), n, C.c_void_p(_ptr(out)), _stream()), "ore_roi_align_batched_fwd")
+    _chk(lib().ore_roi_align_batched_fwd(ptrs, ld, coff, Hs, Ws, sc, L, min_level, Cc, pooled, _ptr(_f32(boxes)), _ptr(box_image), n,
+                                         _ptr(out), _stream()), "ore_roi_align_batched_fwd")
     return out[:n]
 
 
@@ -769,20 +742,14 @@ def roi_align_bwd(dout: torch.Tensor, feats_like: Sequence[torch.Tensor], boxes:
             for f in dfeats:
                 f.zero_()
         return list(dfeats)
-    ptrs = (C.c_void_p * L)(*[_ptr(_f32(f)) for f in dfeats])
-    ld = (C.c_int32 * L)(*[f.shape[-1] for f in dfeats])
-    coff = (C.c_int32 * L)(*[0] * L)
-    Hs = (C.c_int32 * L)(*[f.shape[-3] for f in dfeats])
-    Ws = (C.c_int32 * L)(*[f.shape[-2] for f in dfeats])
-    sc = (C.c_float * L)(*[1.0 / s for s in strides])
+    ptrs, ld, coff, Hs, Ws, sc = _roi_levels(dfeats, strides)
     n_img = 1 if dfeats[0].dim() == 3 else dfeats[0].shape[0]
     assert box_image is not None or n_img == 1
     if tiled:
         # one block per (image, level, 16 x 16-cell tile, 32 channels) gathers the ROIs that reach its cells in index order: no atomics, no
         # scratch, bit-reproducible (ore_roi_align_bwd_tiled)
-        _chk(lib().ore_roi_align_bwd_tiled(ptrs, ld, coff, Hs, Ws, sc, L, min_level, Cc, pooled, C.c_void_p(_ptr(_f32(boxes.float().contiguous()))),
-                                           C.c_void_p(_ptr(box_image)), n, C.c_void_p(_ptr(_f32(dout))), n_img, int(given), _stream()),
-             "ore_roi_align_bwd_tiled")
+        _chk(lib().ore_roi_align_bwd_tiled(ptrs, ld, coff, Hs, Ws, sc, L, min_level, Cc, pooled, _ptr(_f32(boxes.float().contiguous())),
+                                           _ptr(box_image), n, _ptr(_f32(dout)), n_img, int(given), _stream()), "ore_roi_align_bwd_tiled")
         return list(dfeats)
     # Two ROIs of one image may touch the same cell: their sum must not depend on the order the blocks run in -> fixed-point accumulation
     # (ore_roi_align_bwd_det, one zeroed int64 scratch for all levels).  With at most one ROI per image (the support crops: one box each)
@@ -793,11 +760,11 @@ def roi_align_bwd(dout: torch.Tensor, feats_like: Sequence[torch.Tensor], boxes:
         scratch = torch.zeros(sum(sizes), dtype=torch.int64, device=dout.device)
         offs = [sum(sizes[:i]) for i in range(L)]
         accs = (C.c_void_p * L)(*[_ptr(scratch) + 8 * o for o in offs])
-        _chk(lib().ore_roi_align_bwd_det(ptrs, ld, coff, Hs, Ws, sc, L, min_level, Cc, pooled, C.c_void_p(_ptr(_f32(boxes.float().contiguous()))),
-                                         C.c_void_p(_ptr(box_image)), n, C.c_void_p(_ptr(_f32(dout))), accs, n_img, _stream()), "ore_roi_align_bwd_det")
+        _chk(lib().ore_roi_align_bwd_det(ptrs, ld, coff, Hs, Ws, sc, L, min_level, Cc, pooled, _ptr(_f32(boxes.float().contiguous())),
+                                         _ptr(box_image), n, _ptr(_f32(dout)), accs, n_img, _stream()), "ore_roi_align_bwd_det")
         return list(dfeats)
-    _chk(lib().ore_roi_align_bwd(ptrs, ld, coff, Hs, Ws, sc, L, min_level, Cc, pooled, C.c_void_p(_ptr(_f32(boxes.float().contiguous()))),
-                                 C.c_void_p(_ptr(box_image)), n, C.c_void_p(_ptr(_f32(dout))), _stream()), "ore_roi_align_bwd")
+    _chk(lib().ore_roi_align_bwd(ptrs, ld, coff, Hs, Ws, sc, L, min_level, Cc, pooled, _ptr(_f32(boxes.float().contiguous())),
+                                 _ptr(box_image), n, _ptr(_f32(dout)), _stream()), "ore_roi_align_bwd")
     return list(dfeats)
 
 
@@ -812,12 +779,9 @@ def roi_predict(h: torch.Tensor, cls_w, cls_b, box_w, box_b, boxes: torch.Tensor
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
     rw = (C.c_float * 4)(*reg_weights)
     b = boxes.float().contiguous() if n else torch.zeros(1, 4, device=dev)
-    _chk(lib().ore_roi_predict_fwd(C.c_void_p(_ptr(_f32(h))), Cc, C.c_void_p(_ptr(_f32(cls_w))), C.c_void_p(_ptr(_f32(cls_b))),
-                                   C.c_void_p(_ptr(_f32(box_w))), C.c_void_p(_ptr(_f32(box_b))), C.c_void_p(_ptr(b)),
-                                   C.c_void_p(_ptr(n_dev)), n, cap, rw, C.c_float(image_hw[0]), C.c_float(image_hw[1]),
-                                   C.c_float(score_thresh), C.c_float(nms_thresh), topk, C.c_void_p(_ptr(o["boxes"])),
-                                   C.c_void_p(_ptr(o["scores"])), C.c_void_p(_ptr(o["src"])), C.c_void_p(_ptr(o["count"])),
-                                   C.c_void_p(_ptr(ws)), C.c_size_t(wsb), _stream()), "ore_roi_predict_fwd")
+    _chk(lib().ore_roi_predict_fwd(_ptr(_f32(h)), Cc, _ptr(_f32(cls_w)), _ptr(_f32(cls_b)), _ptr(_f32(box_w)), _ptr(_f32(box_b)), _ptr(b),
+                                   _ptr(n_dev), n, cap, rw, image_hw[0], image_hw[1], score_thresh, nms_thresh, topk, _ptr(o["boxes"]),
+                                   _ptr(o["scores"]), _ptr(o["src"]), _ptr(o["count"]), _ptr(ws), wsb, _stream()), "ore_roi_predict_fwd")
     o["_ws"] = ws
     return o
 
@@ -865,10 +829,9 @@ def centernet_targets(gt_boxes: Sequence[torch.Tensor], shapes: Sequence[Tuple[i
          "pos_inds": torch.zeros(B * max_n * L, dtype=torch.int64, device=dev), "pos_count": torch.zeros(1, dtype=torch.int32, device=dev)}
     Hs = (C.c_int32 * L)(*[h for h, _ in shapes]); Ws = (C.c_int32 * L)(*[w for _, w in shapes]); St = (C.c_int32 * L)(*strides)
     so = (C.c_float * (2 * L))(*[float(v) for r in soi for v in r])
-    _chk(lib().ore_centernet_targets_fwd(L, Hs, Ws, St, B, C.c_void_p(_ptr(gt)), C.c_void_p(_ptr(cnt)), max_n, so,
-                                         C.c_float(hm_min_overlap), C.c_float(min_radius), C.c_void_p(_ptr(o["reg_targets"])),
-                                         C.c_void_p(_ptr(o["hm_targets"])), C.c_void_p(_ptr(o["pos_inds"])),
-                                         C.c_void_p(_ptr(o["pos_count"])), _stream()), "ore_centernet_targets_fwd")
+    _chk(lib().ore_centernet_targets_fwd(L, Hs, Ws, St, B, _ptr(gt), _ptr(cnt), max_n, so, hm_min_overlap, min_radius,
+                                         _ptr(o["reg_targets"]), _ptr(o["hm_targets"]), _ptr(o["pos_inds"]), _ptr(o["pos_count"]),
+                                         _stream()), "ore_centernet_targets_fwd")
     o["_keep"] = (gt, cnt)
     return o
 
@@ -881,10 +844,8 @@ def centernet_loss_sums(head: torch.Tensor, reg_targets: torch.Tensor, hm_target
     rows, ld = head.shape
     out = torch.zeros(4, device=head.device)
     ws = torch.empty(4 * 256, device=head.device)
-    _chk(lib().ore_centernet_losses_fwd(C.c_void_p(_ptr(_f32(head))), ld, C.c_void_p(_ptr(_f32(reg_targets))),
-                                        C.c_void_p(_ptr(_f32(hm_targets))), rows, C.c_void_p(_ptr(pos_inds)),
-                                        C.c_void_p(_ptr(pos_count)), C.c_float(gamma), C.c_float(beta), C.c_float(sigmoid_clamp),
-                                        C.c_float(ignore_high_fp), C.c_void_p(_ptr(out)), C.c_void_p(_ptr(ws)), _stream()),
+    _chk(lib().ore_centernet_losses_fwd(_ptr(_f32(head)), ld, _ptr(_f32(reg_targets)), _ptr(_f32(hm_targets)), rows, _ptr(pos_inds),
+                                        _ptr(pos_count), gamma, beta, sigmoid_clamp, ignore_high_fp, _ptr(out), _ptr(ws), _stream()),
          "ore_centernet_losses_fwd")
     return out
 
@@ -895,11 +856,9 @@ def centernet_loss_grad(head: torch.Tensor, reg_targets: torch.Tensor, hm_target
     """d(losses)/d(head[:, :5]) for coef3 = [reg_w/reg_norm, pos_w*alpha/num_pos_avg, neg_w*(1-alpha)/num_pos_avg] (device)."""
     rows, ld = head.shape
     dhead = torch.zeros(rows, ld, device=head.device, dtype=torch.float32)
-    _chk(lib().ore_centernet_losses_bwd(C.c_void_p(_ptr(_f32(head))), ld, C.c_void_p(_ptr(_f32(reg_targets))),
-                                        C.c_void_p(_ptr(_f32(hm_targets))), rows, C.c_void_p(_ptr(pos_inds)), C.c_void_p(_ptr(pos_count)),
-                                        int(pos_inds.numel()), C.c_float(gamma), C.c_float(beta), C.c_float(sigmoid_clamp),
-                                        C.c_float(ignore_high_fp), C.c_void_p(_ptr(_f32(coef3))), C.c_void_p(_ptr(dhead)), ld, _stream()),
-         "ore_centernet_losses_bwd")
+    _chk(lib().ore_centernet_losses_bwd(_ptr(_f32(head)), ld, _ptr(_f32(reg_targets)), _ptr(_f32(hm_targets)), rows, _ptr(pos_inds),
+                                        _ptr(pos_count), int(pos_inds.numel()), gamma, beta, sigmoid_clamp, ignore_high_fp,
+                                        _ptr(_f32(coef3)), _ptr(dhead), ld, _stream()), "ore_centernet_losses_bwd")
     return dhead
 
 
@@ -917,9 +876,8 @@ def sample_rois(prop: torch.Tensor, prop_n: torch.Tensor, gtp: torch.Tensor, gt_
     gt = torch.empty(B, R, 4, device=dev, dtype=torch.float32)
     labels = torch.empty(B, R, device=dev, dtype=torch.int64)
     valid = torch.empty(B, R, device=dev, dtype=torch.bool)
-    _chk(lib().ore_sample_rois_fwd(C.c_void_p(_ptr(_f32(prop))), C.c_void_p(_ptr(prop_n)), C.c_void_p(_ptr(_f32(gtp))), C.c_void_p(_ptr(gt_n)),
-                                   C.c_void_p(_ptr(keys)), B, cap, G, int(bool(append_gt)), R, P, C.c_float(iou_thr), C.c_void_p(_ptr(boxes)),
-                                   C.c_void_p(_ptr(labels)), C.c_void_p(_ptr(gt)), C.c_void_p(_ptr(valid)), _stream()), "ore_sample_rois_fwd")
+    _chk(lib().ore_sample_rois_fwd(_ptr(_f32(prop)), _ptr(prop_n), _ptr(_f32(gtp)), _ptr(gt_n), _ptr(keys), B, cap, G, int(bool(append_gt)),
+                                   R, P, iou_thr, _ptr(boxes), _ptr(labels), _ptr(gt), _ptr(valid), _stream()), "ore_sample_rois_fwd")
     return boxes, labels, gt, valid
 
 
@@ -935,9 +893,8 @@ def roi_losses(scores: torch.Tensor, deltas: torch.Tensor, boxes: torch.Tensor, 
     ds = torch.empty(RT, 2, device=dev, dtype=torch.float32)
     dd = torch.empty(RT, 4, device=dev, dtype=torch.float32)
     rw = (C.c_float * 4)(*[float(v) for v in reg_weights])
-    _chk(lib().ore_roi_losses_fwd(C.c_void_p(_ptr(_f32(scores))), C.c_void_p(_ptr(_f32(deltas))), C.c_void_p(_ptr(_f32(boxes))),
-                                  C.c_void_p(_ptr(_f32(gt))), C.c_void_p(_ptr(labels.contiguous())), C.c_void_p(_ptr(valid.contiguous())), B, R, rw,
-                                  C.c_void_p(_ptr(out)), C.c_void_p(_ptr(ds)), C.c_void_p(_ptr(dd)), _stream()), "ore_roi_losses_fwd")
+    _chk(lib().ore_roi_losses_fwd(_ptr(_f32(scores)), _ptr(_f32(deltas)), _ptr(_f32(boxes)), _ptr(_f32(gt)), _ptr(labels.contiguous()),
+                                  _ptr(valid.contiguous()), B, R, rw, _ptr(out), _ptr(ds), _ptr(dd), _stream()), "ore_roi_losses_fwd")
     return out, ds, dd
 
 
@@ -949,10 +906,8 @@ def sgd_step(params: torch.Tensor, grads: torch.Tensor, momentum_buf: torch.Tens
     assert n % 256 == 0 and grads.numel() == n and momentum_buf.numel() == n and chunk_lr.numel() == n // 256 == chunk_wd.numel()
     for t in (params, grads, momentum_buf, chunk_lr, chunk_wd):
         assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
-    _chk(lib().ore_sgd_step_fwd(C.c_void_p(_ptr(params)), C.c_void_p(_ptr(grads)), C.c_void_p(_ptr(momentum_buf)),
-                                C.c_int64(n // 256), C.c_void_p(_ptr(chunk_lr)), C.c_void_p(_ptr(chunk_wd)),
-                                C.c_void_p(_ptr(lr_scale_dev)), C.c_float(lr_scale), C.c_float(momentum), C.c_float(clip_value),
-                                C.c_float(grad_scale), _stream()), "ore_sgd_step_fwd")
+    _chk(lib().ore_sgd_step_fwd(_ptr(params), _ptr(grads), _ptr(momentum_buf), n // 256, _ptr(chunk_lr), _ptr(chunk_wd), _ptr(lr_scale_dev),
+                                lr_scale, momentum, clip_value, grad_scale, _stream()), "ore_sgd_step_fwd")
 
 
 def pack_conv_weight_dev(w_oihw: torch.Tensor, dgrad: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -965,8 +920,7 @@ def pack_conv_weight_dev(w_oihw: torch.Tensor, dgrad: bool = False, out: Optiona
     if out is None:
         out = torch.empty(n, device=w.device, dtype=torch.float32)
     assert out.numel() == n
-    _chk(lib().ore_pack_conv_weight_fwd(C.c_void_p(_ptr(w)), co, ci, kh, kw, int(dgrad), C.c_void_p(_ptr(out)), _stream()),
-         "ore_pack_conv_weight_fwd")
+    _chk(lib().ore_pack_conv_weight_fwd(_ptr(w), co, ci, kh, kw, int(dgrad), _ptr(out), _stream()), "ore_pack_conv_weight_fwd")
     return out
 
 
@@ -1004,7 +958,7 @@ def pack_conv_weights_multi(jobs) -> None:
         if len(_PACK_TABLES) > 64:
             _PACK_TABLES.clear()
         tab = _PACK_TABLES[key] = host.to(dev)
-    _chk(lib().ore_pack_conv_weights_multi_fwd(C.c_void_p(_ptr(tab)), len(rows), C.c_int64(first), _stream()), "ore_pack_conv_weights_multi_fwd")
+    _chk(lib().ore_pack_conv_weights_multi_fwd(_ptr(tab), len(rows), first, _stream()), "ore_pack_conv_weights_multi_fwd")
 
 
 _WGWS: Dict[str, torch.Tensor] = {}
@@ -1040,9 +994,8 @@ def conv2d_wgrad(x: torch.Tensor, dz: torch.Tensor, k: int, *, x_coff: int = 0, 
         db = db_out
     else:
         db, beta_b = (torch.empty(Cout, device=x.device, dtype=torch.float32) if want_bias else None), 0.0
-    _chk(lib().ore_conv2d_wgrad_bias_fwd(C.c_void_p(_ptr(x)), xld, x_coff, C.c_void_p(_ptr(dz)), dld, dz_coff, B, H, W, Cin, Cout, k, k,
-                                         k // 2, C.c_void_p(_ptr(out)), C.c_float(beta), C.c_void_p(_ptr(db)), C.c_float(beta_b),
-                                         C.c_void_p(_ptr(ws)), C.c_size_t(ws.numel()), _stream()), "ore_conv2d_wgrad_bias_fwd")
+    _chk(lib().ore_conv2d_wgrad_bias_fwd(_ptr(x), xld, x_coff, _ptr(dz), dld, dz_coff, B, H, W, Cin, Cout, k, k, k // 2, _ptr(out), beta,
+                                         _ptr(db), beta_b, _ptr(ws), ws.numel(), _stream()), "ore_conv2d_wgrad_bias_fwd")
     return (out, db) if want_bias else out
 
 
@@ -1054,9 +1007,8 @@ def relu_affine_bwd(dy: torch.Tensor, y: torch.Tensor, scale: Optional[torch.Ten
     rows = y.numel() // y.shape[-1]
     if out is None:
         out = torch.empty(*y.shape[:-1], Cc, device=y.device, dtype=torch.float32)
-    _chk(lib().ore_relu_affine_bwd(C.c_void_p(_ptr(dy)), dy.shape[-1], dy_coff, C.c_void_p(_ptr(y)), y.shape[-1], y_coff,
-                                   C.c_void_p(_ptr(scale)), C.c_int64(rows), Cc, C.c_void_p(_ptr(_f32(out))), out.shape[-1], out_coff,
-                                   _stream()), "ore_relu_affine_bwd")
+    _chk(lib().ore_relu_affine_bwd(_ptr(dy), dy.shape[-1], dy_coff, _ptr(y), y.shape[-1], y_coff, _ptr(scale), rows, Cc, _ptr(_f32(out)),
+                                   out.shape[-1], out_coff, _stream()), "ore_relu_affine_bwd")
     return out
 
 
@@ -1070,8 +1022,7 @@ def colsum(x: torch.Tensor, *, coff: int = 0, Cc: Optional[int] = None, out: Opt
         out = torch.empty(Cc, device=x.device, dtype=torch.float32)
         beta = 0.0
     ws = _wgrad_ws(x.device, ((rows + 63) // 64) * Cc)
-    _chk(lib().ore_colsum_fwd(C.c_void_p(_ptr(x)), ld, coff, C.c_int64(rows), Cc, C.c_float(beta), C.c_void_p(_ptr(out)),
-                              C.c_void_p(_ptr(ws)), C.c_size_t(ws.numel()), _stream()), "ore_colsum_fwd")
+    _chk(lib().ore_colsum_fwd(_ptr(x), ld, coff, rows, Cc, beta, _ptr(out), _ptr(ws), ws.numel(), _stream()), "ore_colsum_fwd")
     return out
 
 
@@ -1084,8 +1035,8 @@ def colsum_segments(x: torch.Tensor, segments: int) -> torch.Tensor:
     rps = rows // segments
     out = torch.empty(segments, Cc, device=x.device, dtype=torch.float32)
     ws = _wgrad_ws(x.device, segments * ((rps + 255) // 256) * Cc)
-    _chk(lib().ore_colsum_segments_fwd(C.c_void_p(_ptr(x)), Cc, 0, segments, C.c_int64(rps), Cc, C.c_float(0.0), C.c_void_p(_ptr(out)),
-                                       C.c_void_p(_ptr(ws)), C.c_size_t(ws.numel()), _stream()), "ore_colsum_segments_fwd")
+    _chk(lib().ore_colsum_segments_fwd(_ptr(x), Cc, 0, segments, rps, Cc, 0.0, _ptr(out), _ptr(ws), ws.numel(), _stream()),
+         "ore_colsum_segments_fwd")
     return out
 
 
@@ -1099,9 +1050,8 @@ def correlation_train_fwd(q: torch.Tensor, k11: torch.Tensor, k13: torch.Tensor,
     cat = torch.empty(B, H, W, 2 * Cc, device=q.device, dtype=torch.float32)
     t = torch.empty(B, H, W, Cc, device=q.device, dtype=torch.float32)
     u = torch.empty_like(t)
-    _chk(lib().ore_correlation_train_fwd(C.c_void_p(_ptr(q)), Cc, 0, B, H, W, Cc, C.c_void_p(_ptr(_f32(k11))), C.c_void_p(_ptr(_f32(k13))),
-                                         C.c_void_p(_ptr(_f32(k31))), per_image, C.c_void_p(_ptr(cat)), C.c_void_p(_ptr(t)),
-                                         C.c_void_p(_ptr(u)), _stream()), "ore_correlation_train_fwd")
+    _chk(lib().ore_correlation_train_fwd(_ptr(q), Cc, 0, B, H, W, Cc, _ptr(_f32(k11)), _ptr(_f32(k13)), _ptr(_f32(k31)), per_image,
+                                         _ptr(cat), _ptr(t), _ptr(u), _stream()), "ore_correlation_train_fwd")
     return cat, t, u
 
 
@@ -1114,10 +1064,9 @@ def correlation_train_bwd(q, k11, k13, k31, dcat, t, u):
     dq = torch.empty_like(q)
     dk = torch.empty(S, 7, Cc, device=q.device, dtype=torch.float32)
     ws = _wgrad_ws(q.device, rows * Cc * 8 + S * ((rows // S + 255) // 256) * 7 * Cc)
-    _chk(lib().ore_correlation_train_bwd(C.c_void_p(_ptr(_f32(q))), Cc, 0, B, H, W, Cc, C.c_void_p(_ptr(_f32(k11))),
-                                         C.c_void_p(_ptr(_f32(k13))), C.c_void_p(_ptr(_f32(k31))), per_image, C.c_void_p(_ptr(_f32(dcat))),
-                                         C.c_void_p(_ptr(t)), C.c_void_p(_ptr(u)), C.c_void_p(_ptr(dq)), C.c_void_p(_ptr(dk)),
-                                         C.c_void_p(_ptr(ws)), C.c_size_t(ws.numel()), _stream()), "ore_correlation_train_bwd")
+    _chk(lib().ore_correlation_train_bwd(_ptr(_f32(q)), Cc, 0, B, H, W, Cc, _ptr(_f32(k11)), _ptr(_f32(k13)), _ptr(_f32(k31)), per_image,
+                                         _ptr(_f32(dcat)), _ptr(t), _ptr(u), _ptr(dq), _ptr(dk), _ptr(ws), ws.numel(), _stream()),
+         "ore_correlation_train_bwd")
     d11, d13, d31 = dk[:, 0], dk[:, 1:4].transpose(1, 2).contiguous(), dk[:, 4:7].transpose(1, 2).contiguous()
     if not per_image:
         d11, d13, d31 = d11[0], d13[0], d31[0]
@@ -1131,9 +1080,8 @@ def groupnorm_apply(x: torch.Tensor, rstd_c: torch.Tensor, shift_c: torch.Tensor
     rpi = x.numel() // (Cc * B)
     assert rstd_c.numel() == B * Cc and shift_c.numel() == B * Cc
     y = torch.empty_like(x)
-    _chk(lib().ore_groupnorm_apply_fwd(C.c_void_p(_ptr(x)), Cc, 0, B, C.c_int64(rpi), Cc, C.c_void_p(_ptr(_f32(rstd_c))),
-                                       C.c_void_p(_ptr(_f32(shift_c))), C.c_void_p(_ptr(_f32(gamma))), C.c_void_p(_ptr(_f32(beta))), int(relu),
-                                       C.c_void_p(_ptr(y)), _stream()), "ore_groupnorm_apply_fwd")
+    _chk(lib().ore_groupnorm_apply_fwd(_ptr(x), Cc, 0, B, rpi, Cc, _ptr(_f32(rstd_c)), _ptr(_f32(shift_c)), _ptr(_f32(gamma)),
+                                       _ptr(_f32(beta)), int(relu), _ptr(y), _stream()), "ore_groupnorm_apply_fwd")
     return y
 
 
@@ -1145,10 +1093,8 @@ def groupnorm_bwd(dy, y, x, groups: int, rstd_c, shift_c, gamma, relu: bool):
     dx = torch.empty_like(x)
     sums = torch.empty(B, 2 * Cc, device=x.device, dtype=torch.float32)
     ws = _wgrad_ws(x.device, B * rpi * 2 * Cc + B * ((rpi + 255) // 256) * 2 * Cc)
-    _chk(lib().ore_groupnorm_bwd(C.c_void_p(_ptr(dy)), C.c_void_p(_ptr(y)), C.c_void_p(_ptr(x)), Cc, 0, B, C.c_int64(rpi), Cc, groups,
-                                 C.c_void_p(_ptr(_f32(rstd_c))), C.c_void_p(_ptr(_f32(shift_c))), C.c_void_p(_ptr(_f32(gamma))), int(relu),
-                                 C.c_void_p(_ptr(dx)), C.c_void_p(_ptr(sums)), C.c_void_p(_ptr(ws)), C.c_size_t(ws.numel()), _stream()),
-         "ore_groupnorm_bwd")
+    _chk(lib().ore_groupnorm_bwd(_ptr(dy), _ptr(y), _ptr(x), Cc, 0, B, rpi, Cc, groups, _ptr(_f32(rstd_c)), _ptr(_f32(shift_c)),
+                                 _ptr(_f32(gamma)), int(relu), _ptr(dx), _ptr(sums), _ptr(ws), ws.numel(), _stream()), "ore_groupnorm_bwd")
     return dx, sums[:, :Cc], sums[:, Cc:]
 
 
@@ -1159,8 +1105,8 @@ def prod_colsum(p: torch.Tensor, q: Optional[torch.Tensor] = None, scale: float 
     rows = p.numel() // (B * Cc)
     out = torch.empty(B, Cc, device=p.device, dtype=torch.float32)
     ws = _wgrad_ws(p.device, p.numel())
-    _chk(lib().ore_prod_colsum_fwd(C.c_void_p(_ptr(p)), C.c_void_p(_ptr(_f32(q)) if q is not None else None), B, rows, Cc, C.c_float(scale),
-                                   C.c_void_p(_ptr(out)), C.c_void_p(_ptr(ws)), C.c_size_t(ws.numel()), _stream()), "ore_prod_colsum_fwd")
+    _chk(lib().ore_prod_colsum_fwd(_ptr(p), _ptr(_f32(q)) if q is not None else None, B, rows, Cc, scale, _ptr(out), _ptr(ws), ws.numel(),
+                                   _stream()), "ore_prod_colsum_fwd")
     return out
 
 
@@ -1169,9 +1115,8 @@ def scale_add_channels(x: torch.Tensor, scale_bc: torch.Tensor, add_bc: Optional
     B, Cc = x.shape[0], x.shape[-1]
     rows = x.numel() // (B * Cc)
     out = torch.empty_like(x)
-    _chk(lib().ore_scale_add_channels_fwd(C.c_void_p(_ptr(x)), C.c_void_p(_ptr(_f32(scale_bc))),
-                                          C.c_void_p(_ptr(_f32(add_bc)) if add_bc is not None else None), B, rows, Cc, C.c_void_p(_ptr(out)),
-                                          _stream()), "ore_scale_add_channels_fwd")
+    _chk(lib().ore_scale_add_channels_fwd(_ptr(x), _ptr(_f32(scale_bc)), _ptr(_f32(add_bc)) if add_bc is not None else None, B, rows, Cc,
+                                          _ptr(out), _stream()), "ore_scale_add_channels_fwd")
     return out
 
 
@@ -1183,12 +1128,12 @@ def adaptive_avgpool_nhwc(x: torch.Tensor, OH: int, OW: int, grad_of: Optional[T
     if grad_of is None:
         H, W = x.shape[1:3]
         y = torch.empty(B, OH, OW, Cc, device=x.device, dtype=torch.float32)
-        _chk(lib().ore_adaptive_avgpool_nhwc_fwd(C.c_void_p(_ptr(x)), B, H, W, Cc, OH, OW, C.c_void_p(_ptr(y)), _stream()), "ore_adaptive_avgpool_nhwc_fwd")
+        _chk(lib().ore_adaptive_avgpool_nhwc_fwd(_ptr(x), B, H, W, Cc, OH, OW, _ptr(y), _stream()), "ore_adaptive_avgpool_nhwc_fwd")
         return y
     H, W = grad_of
     assert tuple(x.shape[1:3]) == (OH, OW)
     dx = torch.empty(B, H, W, Cc, device=x.device, dtype=torch.float32)
-    _chk(lib().ore_adaptive_avgpool_nhwc_bwd(C.c_void_p(_ptr(x)), B, H, W, Cc, OH, OW, C.c_void_p(_ptr(dx)), _stream()), "ore_adaptive_avgpool_nhwc_bwd")
+    _chk(lib().ore_adaptive_avgpool_nhwc_bwd(_ptr(x), B, H, W, Cc, OH, OW, _ptr(dx), _stream()), "ore_adaptive_avgpool_nhwc_bwd")
     return dx
 
 
@@ -1201,11 +1146,11 @@ def group_mean(x: torch.Tensor, groups: int, backward: bool = False, members: in
         assert N * groups == x.shape[0]
         M = x.numel() // x.shape[0]
         y = torch.empty(groups, *x.shape[1:], device=x.device, dtype=torch.float32)
-        _chk(lib().ore_group_mean_fwd(C.c_void_p(_ptr(x)), groups, N, C.c_int64(M), C.c_void_p(_ptr(y)), _stream()), "ore_group_mean_fwd")
+        _chk(lib().ore_group_mean_fwd(_ptr(x), groups, N, M, _ptr(y), _stream()), "ore_group_mean_fwd")
         return y
     M = x.numel() // groups
     dx = torch.empty(groups * members, *x.shape[1:], device=x.device, dtype=torch.float32)
-    _chk(lib().ore_group_mean_bwd(C.c_void_p(_ptr(x)), groups, members, C.c_int64(M), C.c_void_p(_ptr(dx)), _stream()), "ore_group_mean_bwd")
+    _chk(lib().ore_group_mean_bwd(_ptr(x), groups, members, M, _ptr(dx), _stream()), "ore_group_mean_bwd")
     return dx
 
 
@@ -1232,8 +1177,7 @@ def sm_permute(x: torch.Tensor, B: int, H: int, W: int, G: int, S: int, axis: st
     else:
         _f32(out)
         assert out.numel() == x.numel()
-    _chk(lib().ore_granule_transpose_fwd(C.c_void_p(_ptr(x)), C.c_void_p(_ptr(out)), B, nb2, A_, Bc, S, C.c_int64(ib1), C.c_int64(ib2),
-                                         C.c_int64(irs), C.c_int64(ob1), C.c_int64(ob2), C.c_int64(ors), int(accumulate), _stream()),
+    _chk(lib().ore_granule_transpose_fwd(_ptr(x), _ptr(out), B, nb2, A_, Bc, S, ib1, ib2, irs, ob1, ob2, ors, int(accumulate), _stream()),
          "ore_granule_transpose_fwd")
     return out
 
@@ -1243,8 +1187,8 @@ def combine2(w: torch.Tensor, h: torch.Tensor, a0: torch.Tensor, a1: torch.Tenso
     _f32(w); _f32(h)
     B, Cc = w.shape[0], w.shape[-1]
     y = torch.empty_like(w)
-    _chk(lib().ore_combine2_fwd(C.c_void_p(_ptr(w)), C.c_void_p(_ptr(h)), C.c_void_p(_ptr(_f32(a0))), C.c_void_p(_ptr(_f32(a1))), B,
-                                w.numel() // (B * Cc), Cc, C.c_void_p(_ptr(y)), _stream()), "ore_combine2_fwd")
+    _chk(lib().ore_combine2_fwd(_ptr(w), _ptr(h), _ptr(_f32(a0)), _ptr(_f32(a1)), B, w.numel() // (B * Cc), Cc, _ptr(y), _stream()),
+         "ore_combine2_fwd")
     return y
 
 
@@ -1253,9 +1197,8 @@ def combine2_bwd(dy: torch.Tensor, a0: torch.Tensor, a1: torch.Tensor, add_bc: O
     _f32(dy)
     B, Cc = dy.shape[0], dy.shape[-1]
     dw, dh = torch.empty_like(dy), torch.empty_like(dy)
-    _chk(lib().ore_combine2_bwd(C.c_void_p(_ptr(dy)), C.c_void_p(_ptr(_f32(a0))), C.c_void_p(_ptr(_f32(a1))),
-                                C.c_void_p(_ptr(_f32(add_bc)) if add_bc is not None else None), B, dy.numel() // (B * Cc), Cc,
-                                C.c_void_p(_ptr(dw)), C.c_void_p(_ptr(dh)), _stream()), "ore_combine2_bwd")
+    _chk(lib().ore_combine2_bwd(_ptr(dy), _ptr(_f32(a0)), _ptr(_f32(a1)), _ptr(_f32(add_bc)) if add_bc is not None else None, B,
+                                dy.numel() // (B * Cc), Cc, _ptr(dw), _ptr(dh), _stream()), "ore_combine2_bwd")
     return dw, dh
 
 
@@ -1263,7 +1206,7 @@ def maxpool3x3s2_bwd(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
     _f32(x); _f32(dy)
     B, H, W, Cc = x.shape
     dx = torch.empty_like(x)
-    _chk(lib().ore_maxpool3x3s2_bwd(C.c_void_p(_ptr(x)), C.c_void_p(_ptr(dy)), B, H, W, Cc, C.c_void_p(_ptr(dx)), _stream()), "ore_maxpool3x3s2_bwd")
+    _chk(lib().ore_maxpool3x3s2_bwd(_ptr(x), _ptr(dy), B, H, W, Cc, _ptr(dx), _stream()), "ore_maxpool3x3s2_bwd")
     return dx
 
 
@@ -1271,7 +1214,7 @@ def sumpool2x2(x: torch.Tensor) -> torch.Tensor:
     _f32(x)
     B, H, W, Cc = x.shape
     out = torch.empty(B, (H + 1) // 2, (W + 1) // 2, Cc, device=x.device, dtype=torch.float32)
-    _chk(lib().ore_sumpool2x2_fwd(C.c_void_p(_ptr(x)), Cc, B, H, W, Cc, C.c_void_p(_ptr(out)), _stream()), "ore_sumpool2x2_fwd")
+    _chk(lib().ore_sumpool2x2_fwd(_ptr(x), Cc, B, H, W, Cc, _ptr(out), _stream()), "ore_sumpool2x2_fwd")
     return out
 
 
@@ -1358,8 +1301,7 @@ class Engine:
         for k, v in sd.items():
             t = v.detach().float().cpu().contiguous()
             shape = (C.c_int64 * max(t.dim(), 1))(*t.shape)
-            _chk(lib().ore_engine_set_tensor(self._h, k.encode(), C.c_void_p(t.data_ptr()), shape, t.dim()),
-                 f"ore_engine_set_tensor({k})")
+            _chk(lib().ore_engine_set_tensor(self._h, k.encode(), t.data_ptr(), shape, t.dim()), f"ore_engine_set_tensor({k})")
 
     def set_support(self, protos: Dict[str, torch.Tensor], slot: Optional[int] = None) -> None:
         """{'p3': [1,C,32,32], 'p4': [1,C,16,16], 'p5': [1,C,8,8]} -- support_feature.pkl prototypes.  slot=k: the prototypes of N-way
@@ -1368,10 +1310,9 @@ class Engine:
             t = protos[f"p{lvl}"].detach().float().cpu().contiguous()
             t = t.reshape(t.shape[-3], t.shape[-2], t.shape[-1])
             if slot is None:
-                _chk(lib().ore_engine_set_support(self._h, lvl, C.c_void_p(t.data_ptr()), t.shape[0], t.shape[1]),
-                     "ore_engine_set_support")
+                _chk(lib().ore_engine_set_support(self._h, lvl, t.data_ptr(), t.shape[0], t.shape[1]), "ore_engine_set_support")
             else:
-                _chk(lib().ore_engine_set_support_slot(self._h, int(slot), lvl, C.c_void_p(t.data_ptr()), t.shape[0], t.shape[1]),
+                _chk(lib().ore_engine_set_support_slot(self._h, int(slot), lvl, t.data_ptr(), t.shape[0], t.shape[1]),
                      "ore_engine_set_support_slot")
 
     def set_classes(self, ids: Sequence[int]) -> None:
@@ -1386,8 +1327,7 @@ class Engine:
         """The second stage of N-way class slot `slot`: DSA-mix + flatten + fc1 composed with that class's rcnn_8 support features
         (compose_roi_head), after set_roi_head() and set_classes()."""
         Wp, bp = compose_roi_head(sd, support_8, prefix)
-        _chk(lib().ore_engine_set_roi_support_slot(self._h, int(slot), C.c_void_p(Wp.data_ptr()), C.c_void_p(bp.data_ptr())),
-             "ore_engine_set_roi_support_slot")
+        _chk(lib().ore_engine_set_roi_support_slot(self._h, int(slot), Wp.data_ptr(), bp.data_ptr()), "ore_engine_set_roi_support_slot")
 
     def finalize(self) -> None:
         _chk(lib().ore_engine_finalize(self._h), "ore_engine_finalize")
@@ -1401,10 +1341,8 @@ class Engine:
         assert cw.shape[0] == 2 and bw.shape[0] == 4, "one foreground class, class-agnostic box regression"
         pooled = int(round((Wp.shape[1] // self.fpn_ch) ** 0.5))
         rw = (C.c_float * 4)(*reg_weights)
-        _chk(lib().ore_engine_set_roi_head(self._h, C.c_void_p(Wp.data_ptr()), C.c_void_p(bp.data_ptr()), Wp.shape[0], pooled,
-                                           C.c_void_p(cw.data_ptr()), C.c_void_p(cb.data_ptr()), C.c_void_p(bw.data_ptr()),
-                                           C.c_void_p(bb.data_ptr()), rw, C.c_float(score_thresh), C.c_float(nms_thresh), topk),
-             "ore_engine_set_roi_head")
+        _chk(lib().ore_engine_set_roi_head(self._h, Wp.data_ptr(), bp.data_ptr(), Wp.shape[0], pooled, cw.data_ptr(), cb.data_ptr(),
+                                           bw.data_ptr(), bb.data_ptr(), rw, score_thresh, nms_thresh, topk), "ore_engine_set_roi_head")
         self.has_roi = True
         self._det_cap = min(max(int(topk), 1), 320)        # rows of the result tensors ore_engine_detect_fwd fills
 
@@ -1417,7 +1355,7 @@ class Engine:
         """img [B,3,H,W] u8/f32 on device -> {'p3','p4','p5'} as logical NCHW views of engine-owned NHWC buffers."""
         assert img.is_cuda and img.is_contiguous()
         B, _, H, W = img.shape
-        _chk(lib().ore_engine_backbone_fwd(self._h, C.c_void_p(img.data_ptr()), int(img.dtype == torch.uint8), B, H, W, _stream()),
+        _chk(lib().ore_engine_backbone_fwd(self._h, img.data_ptr(), int(img.dtype == torch.uint8), B, H, W, _stream()),
              "ore_engine_backbone_fwd")
         Hp, Wp = (H + 31) // 32 * 32, (W + 31) // 32 * 32
         return {f"p{l}": self.buffer(f"p{l}", (B, Hp >> l, Wp >> l)) for l in (3, 4, 5)}
@@ -1426,8 +1364,8 @@ class Engine:
         """img [3,H,W] u8/f32 on device.  Enqueues the whole path; results via .buffer()/.proposals()."""
         assert img.is_cuda and img.is_contiguous() and img.dim() == 3
         _, H, W = img.shape
-        _chk(lib().ore_engine_eval_fwd(self._h, C.c_void_p(img.data_ptr()), int(img.dtype == torch.uint8), H, W,
-                                       int(use_graph), _stream()), "ore_engine_eval_fwd")
+        _chk(lib().ore_engine_eval_fwd(self._h, img.data_ptr(), int(img.dtype == torch.uint8), H, W, int(use_graph), _stream()),
+             "ore_engine_eval_fwd")
 
     def detect_begin(self, img: torch.Tensor, out_h: int, out_w: int) -> torch.Tensor:
         """First half of `detect`: enqueue the pass (ore_engine_detect_begin) and return the result record it will fill.  Host work
@@ -1436,8 +1374,8 @@ class Engine:
         _, H, W = img.shape
         R = self.__dict__.get("_rec_rows") or self.__dict__.setdefault("_rec_rows", int(lib().ore_det_record_rows()))   # ORE_DET_RECORD_ROWS of the loaded library (= the engine's roi_cap)
         rec = torch.empty(R * 7, dtype=torch.float32, device=self.device)  # [R][4] f32 | [R] f32 | [R] i64, written by the last kernel
-        _chk(lib().ore_engine_detect_begin(self._h, C.c_void_p(img.data_ptr()), int(img.dtype == torch.uint8), H, W, int(out_h), int(out_w),
-                                           C.c_void_p(rec.data_ptr()), _stream()), "ore_engine_detect_begin")
+        _chk(lib().ore_engine_detect_begin(self._h, img.data_ptr(), int(img.dtype == torch.uint8), H, W, int(out_h), int(out_w),
+                                           rec.data_ptr(), _stream()), "ore_engine_detect_begin")
         return rec
 
     def detect_classes_begin(self, img: torch.Tensor, out_h: int, out_w: int) -> torch.Tensor:
@@ -1446,8 +1384,8 @@ class Engine:
         _, H, W = img.shape
         R = self.__dict__.get("_rec_rows") or self.__dict__.setdefault("_rec_rows", int(lib().ore_det_record_rows()))
         rec = torch.empty(R * 7, dtype=torch.float32, device=self.device)
-        _chk(lib().ore_engine_detect_classes_begin(self._h, C.c_void_p(img.data_ptr()), int(img.dtype == torch.uint8), H, W, int(out_h),
-                                                   int(out_w), C.c_void_p(rec.data_ptr()), _stream()), "ore_engine_detect_classes_begin")
+        _chk(lib().ore_engine_detect_classes_begin(self._h, img.data_ptr(), int(img.dtype == torch.uint8), H, W, int(out_h), int(out_w),
+                                                   rec.data_ptr(), _stream()), "ore_engine_detect_classes_begin")
         return rec
 
     def detect_classes(self, img: torch.Tensor, out_h: int, out_w: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -1460,8 +1398,8 @@ class Engine:
         dense buffers read back as a K-image batch (block k = slot k)."""
         assert img.is_cuda and img.is_contiguous() and img.dim() == 3
         _, H, W = img.shape
-        _chk(lib().ore_engine_eval_classes_fwd(self._h, C.c_void_p(img.data_ptr()), int(img.dtype == torch.uint8), H, W, int(use_graph),
-                                               _stream()), "ore_engine_eval_classes_fwd")
+        _chk(lib().ore_engine_eval_classes_fwd(self._h, img.data_ptr(), int(img.dtype == torch.uint8), H, W, int(use_graph), _stream()),
+             "ore_engine_eval_classes_fwd")
 
     def detect_end(self, rec: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Second half: wait for the count (ore_engine_detect_end) and cut the record into (boxes [n,4], scores [n], classes [n] int64)."""
@@ -1482,8 +1420,8 @@ class Engine:
         (ore_engine_eval_batch_fwd).  Image b's results: .proposals(b) / .detections(b) / .buffer("name#b")."""
         assert imgs.is_cuda and imgs.is_contiguous() and imgs.dim() == 4
         B, _, H, W = imgs.shape
-        _chk(lib().ore_engine_eval_batch_fwd(self._h, C.c_void_p(imgs.data_ptr()), int(imgs.dtype == torch.uint8), B, H, W,
-                                             int(use_graph), _stream()), "ore_engine_eval_batch_fwd")
+        _chk(lib().ore_engine_eval_batch_fwd(self._h, imgs.data_ptr(), int(imgs.dtype == torch.uint8), B, H, W, int(use_graph), _stream()),
+             "ore_engine_eval_batch_fwd")
 
     def last_flops(self) -> float:
         return float(lib().ore_engine_last_flops(self._h))

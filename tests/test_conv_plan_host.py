@@ -47,7 +47,7 @@ def test_table_reaches_every_launcher(table):
     assert {r[4][0] for r in table["rows"] if r[3] == 0} == set(range(1, LAUNCHERS))
 
 
-def test_plans_match_recorded(table, L):
+def test_plans_match_recorded_with_full_overrides(table, L):
     import orehip
     bad = []
     try:
@@ -57,8 +57,9 @@ def test_plans_match_recorded(table, L):
             assert L.ore_conv_set_precision(prec) == 0
             knobs = table["knobs"][ki]
             for code in sorted((int(c) for c in knobs), key=lambda c: (c == 0, -c)):   # -1, -2, ..., -16, then the k_conv_igemm tile (0)
-                args = knobs[str(code)]
-                assert L.ore_conv_set_plan_override(*((code, *args) if code else args)) == 0
+                args = (code, *knobs[str(code)]) if code else tuple(knobs[str(code)])
+                args += (0,) * (5 - len(args))            # padded with zeros to its five arguments, as orehip.conv_overrides does
+                assert L.ore_conv_set_plan_override(*args) == 0
             pl = orehip.ConvPlan()
             if fn == 0:
                 got_rc = L.ore_conv_plan(C.byref(d), 0, None, None, 0, C.byref(pl))

@@ -5,6 +5,7 @@ flat-bucket data-parallel step of fewx.solver:
                              [gradient exchange overlapped] -> optimizer.step() (one fused clip+SGD launch)
     create_ddp_model         d2z:engine/defaults.py:60-79       FlatDataParallel instead of DistributedDataParallel
     DefaultTrainer           d2z:engine/defaults.py:300-560     build_model / build_optimizer / build_lr_scheduler / train()
+    DefaultPredictor         d2z:engine/defaults.py:235-297     in detectron2/engine/defaults.py, re-exported here
     launch                   d2z:engine/launch.py:24-83          one process per GPU, RCCL ("nccl") process group, 127.0.0.1
 Dataset registration, evaluators, hooks for periodic checkpoint/eval belong to the data/evaluation side.
 """
@@ -19,7 +20,7 @@ import torch.distributed as dist
 from detectron2.utils import comm
 from detectron2.utils.events import EventStorage
 
-__all__ = ["SimpleTrainer", "DefaultTrainer", "create_ddp_model", "default_argument_parser", "default_setup", "launch"]
+__all__ = ["SimpleTrainer", "DefaultTrainer", "DefaultPredictor", "create_ddp_model", "default_argument_parser", "default_setup", "launch"]
 
 
 def create_ddp_model(model, cfg=None, **kwargs):
@@ -266,3 +267,6 @@ def launch(main_func, num_gpus_per_machine, num_machines=1, machine_rank=0, dist
         dist_url = "tcp://127.0.0.1:{}".format(port)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     mp.spawn(_worker, nprocs=num_gpus_per_machine, args=(main_func, world, num_gpus_per_machine, machine_rank, dist_url, args), daemon=False)
+
+
+from detectron2.engine.defaults import DefaultPredictor  # noqa: E402  (that module imports the names above)

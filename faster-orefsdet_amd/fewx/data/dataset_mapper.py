@@ -25,7 +25,12 @@ def _pil_read_image(path, format="BGR"):
 class DatasetMapperWithSupport:
     SUPPORT_DIR = "./datasets/coco/"                      # ref:fewx/data/dataset_mapper.py:80-82,227
 
-    def __init__(self, cfg, is_train=True, support_df=None, read_image=None):
+    def __init__(self, cfg, is_train=True, support_df=None, read_image=None, device_resize=False):
+        """device_resize=True (test time only): the record keeps the image as read -- "image_raw", HWC uint8 -- with "height" / "width",
+        and the model resizes it on the device to the same bytes (CenterNet2Detector "image_raw" requests); no Pillow resize here."""
+        if device_resize and is_train:
+            raise ValueError("device_resize covers test-time records: training augmentation runs in loader workers without a GPU")
+        self.device_resize = bool(device_resize)
         self.is_train = is_train
         self.img_format = cfg.INPUT.FORMAT
         self.support_way = cfg.INPUT.FS.SUPPORT_WAY
@@ -124,6 +129,12 @@ class DatasetMapperWithSupport:
             d["support_images"] = torch.as_tensor(np.ascontiguousarray(sup))
             d["support_bboxes"] = sbox
             d["support_cls"] = scls
+        if self.device_resize:
+            d["image_raw"] = torch.as_tensor(np.ascontiguousarray(image))
+            d.setdefault("height", int(image.shape[0]))
+            d.setdefault("width", int(image.shape[1]))
+            d.pop("annotations", None)
+            return d
         rng = np.random.default_rng()
         image, tf_boxes = self._resize_flip(image, rng)
         d["image"] = torch.as_tensor(np.ascontiguousarray(image.transpose(2, 0, 1)))

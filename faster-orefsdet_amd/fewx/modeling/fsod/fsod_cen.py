@@ -170,6 +170,7 @@ class CenterNet2Detector(nn.Module):
         self._engine = None
         self._engine_key = None
         self.max_hw = (int(cfg.INPUT.MAX_SIZE_TEST), int(cfg.INPUT.MAX_SIZE_TEST))
+        self._test_size = (int(cfg.INPUT.MIN_SIZE_TEST), int(cfg.INPUT.MAX_SIZE_TEST))     # ResizeShortestEdge of "image_raw" requests
 
     @property
     def device(self):
@@ -369,6 +370,44 @@ class CenterNet2Detector(nn.Module):
         a gradient, and therefore stay out of the gradient bucket / optimizer like `grad is None` parameters do in torch."""
         return ("conv1.", "conv2.", "roi_heads.fc2.", "roi_heads.fc3.")
 
+    # ---- raw images ---------------------------------------------------------------------------------------------
+    def _resolve_raw(self, inp):
+        """A request that carries "image_raw" -- the unresized [h, w, 3] uint8 image in the model's channel order, or the other one with
+        "swap_rb": numpy array, CPU tensor or device tensor -- instead of "image": the image goes to the device (host memory through a
+        pinned staging buffer this model owns, asynchronously on the current stream), is resized there to cfg.INPUT.MIN_SIZE_TEST /
+        MAX_SIZE_TEST (orehip.resize_bilinear_u8: the bytes of the CPU mapper's Pillow resize) and the request comes back in its
+        "image" form, "height" / "width" defaulting to the raw size.  Everything behind treats it as if it had come in that way."""
+        import orehip
+        if "image" in inp:
+            raise ValueError('a request carries either "image" or "image_raw", not both')
+        dev = self.device
+        assert dev.type == "cuda", "CenterNet2Detector inference runs on the MI355X only"
+        raw = inp["image_raw"]
+        if isinstance(raw, np.ndarray):
+            raw = torch.from_numpy(np.ascontiguousarray(raw))
+        if raw.dim() != 3 or raw.shape[2] != 3 or raw.dtype != torch.uint8:
+            raise ValueError(f"image_raw must be [h, w, 3] uint8, got {tuple(raw.shape)} {raw.dtype}")
+        h, w = int(raw.shape[0]), int(raw.shape[1])
+        if raw.is_cuda:
+            raw = raw.to(dev).contiguous()
+        else:
+            n = h * w * 3
+            stage = self.__dict__.get("_raw_stage")
+            if stage is not None:
+                stage[1].synchronize()                            # the copy out of the buffer issued by the previous request
+            if stage is None or stage[0].numel() < n:
+                stage = self.__dict__["_raw_stage"] = (torch.empty(max(n, 1 << 20), dtype=torch.uint8, pin_memory=True), torch.cuda.Event())
+            stage[0][:n].view(h, w, 3).copy_(raw)
+            raw = torch.empty(h, w, 3, dtype=torch.uint8, device=dev)
+            raw.copy_(stage[0][:n].view(h, w, 3), non_blocking=True)
+            stage[1].record()
+        nh, nw = orehip.resize_shortest_edge_shape(h, w, self._test_size[0], self._test_size[1])
+        out = {k: v for k, v in inp.items() if k not in ("image_raw", "swap_rb")}
+        out["image"] = orehip.resize_bilinear_u8(raw, nh, nw, swap_rb=bool(inp.get("swap_rb", False)))
+        out.setdefault("height", h)
+        out.setdefault("width", w)
+        return out
+
     @torch.no_grad()
     def inference_proposals(self, batched_inputs, use_graph=True):
         """The built hot path: image -> proposals (Instances with proposal_boxes / objectness_logits / scores / pred_classes)."""
@@ -389,6 +428,8 @@ class CenterNet2Detector(nn.Module):
         self.init_model()
         assert len(batched_inputs) == 1, "only 1 query image in test (ref fsod_cen.py:438-439)"
         inp = batched_inputs[0]
+        if "image_raw" in inp:
+            inp = self._resolve_raw(inp)
         img = inp["image"]
         e = self._engine
         if do_postprocess and e is not None and self._engine_key is not None and getattr(e, "has_roi", False):
@@ -432,6 +473,9 @@ class CenterNet2Detector(nn.Module):
 
     def _inference_checked(self, inp, img, do_postprocess):
         """The eval call with the engine validated BEFORE it is used (first call, stale engine, other entry conditions)."""
+        if "image_raw" in inp:
+            inp = self._resolve_raw(inp)
+            img = inp["image"]
         batched_inputs = [inp]
         e = self.engine()
         if getattr(e, "class_ids", None):
@@ -499,6 +543,7 @@ class CenterNet2Detector(nn.Module):
         self.init_model()
         if self.support_classes is not None:
             return [self.inference([r], do_postprocess=do_postprocess)[0] for r in requests]
+        requests = [self._resolve_raw(r) if "image_raw" in r else r for r in requests]
         key = (self._state_key(), str(self.device), self.conv_operands, max_fold)
         if getattr(self, "_fold_engine_key", None) != key:
             if getattr(self, "_fold_engine", None) is not None:

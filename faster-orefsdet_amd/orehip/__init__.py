@@ -797,6 +797,99 @@ def to_device(t: torch.Tensor, dev) -> torch.Tensor:
     return t.pin_memory().to(dev, non_blocking=True)
 
 
+# ---------------------------------------------------------------------------------------------------
+# image resize: Pillow's Image.resize(size, BILINEAR) on the device (csrc/ore_resize.hip, csrc/ore_resize_plan.cpp)
+# ---------------------------------------------------------------------------------------------------
+RESIZE_FORM_LDS, RESIZE_FORM_WORKSPACE = 1, 2            # ORE_RESIZE_FORM_* (include/ore_hip.h)
+
+
+def resize_shortest_edge_shape(h: int, w: int, size: int, max_size: int) -> Tuple[int, int]:
+    """(nh, nw) of detectron2 v0.5's ResizeShortestEdge.get_transform (d2z:data/transforms/augmentation_impl.py): the short side
+    scaled to `size`, everything rescaled when the long side then exceeds `max_size`, int(x + 0.5) at the end -- the arithmetic of
+    DatasetMapperWithSupport._resize_flip."""
+    scale = size * 1.0 / min(h, w)
+    nh, nw = (size, scale * w) if h < w else (scale * h, size)
+    if max(nh, nw) > max_size:
+        s2 = max_size * 1.0 / max(nh, nw)
+        nh, nw = nh * s2, nw * s2
+    return int(nh + 0.5), int(nw + 0.5)
+
+
+def resize_plan(n_in: int, n_out: int) -> Tuple[np.ndarray, np.ndarray]:
+    """One axis of the resample (ore_resize_plan, host only): bounds [n_out, 2] int32 = (first source index, count) and coeffs
+    [n_out, ksize] int32, Pillow's 22-bit fixed-point weights.  A pixel is clip8((2^21 + sum(src * coeff)) >> 22)."""
+    ks = int(lib().ore_resize_ksize(int(n_in), int(n_out)))
+    if ks <= 0:
+        raise OreError(f"resize_plan: sizes {n_in} -> {n_out} outside [1, 8192]")
+    bounds, coeffs = np.empty((n_out, 2), dtype=np.int32), np.empty((n_out, ks), dtype=np.int32)
+    _chk(lib().ore_resize_plan(int(n_in), int(n_out), bounds.ctypes.data, coeffs.ctypes.data, None), "ore_resize_plan")
+    return bounds, coeffs
+
+
+def resize_form(h: int, w: int, nh: int, nw: int) -> int:
+    """The form resize_bilinear_u8 takes for this size pair: RESIZE_FORM_LDS (one launch) or RESIZE_FORM_WORKSPACE (two)."""
+    return int(lib().ore_resize_form(int(h), int(w), int(nh), int(nw)))
+
+
+_RESIZE_TABLES: Dict[tuple, torch.Tensor] = {}
+_RESIZE_TABLES_MAX = 32
+_RESIZE_WS: Dict[tuple, torch.Tensor] = {}
+
+
+def _resize_tables(dev, h: int, w: int, nh: int, nw: int) -> torch.Tensor:
+    """The device tables of one size pair, cached.  A new table is planned on the host into pinned memory and copied behind the
+    current stream's work, so the launch that follows on that stream reads it complete.  The cache is bounded: the oldest table
+    leaves when a new one would be the 33rd.  Nothing here is captured in a graph, so a launch that still reads an evicted table is
+    protected by stream order alone: torch's allocator hands the block to later work of the stream it was allocated on, and a table
+    used on another stream is marked for that stream (record_stream) at that use."""
+    key = (str(dev), h, w, nh, nw)
+    tab = _RESIZE_TABLES.get(key)
+    cur = _stream()
+    if tab is None:
+        n = int(lib().ore_resize_table_ints(h, w, nh, nw))
+        if n <= 0:
+            raise OreError(f"resize_bilinear_u8: {h}x{w} -> {nh}x{nw}: sides must be in [1, 8192]")
+        host = torch.empty(n, dtype=torch.int32, pin_memory=True)
+        _chk(lib().ore_resize_tables_host(h, w, nh, nw, host.data_ptr()), "ore_resize_tables_host")
+        while len(_RESIZE_TABLES) >= _RESIZE_TABLES_MAX:
+            _RESIZE_TABLES.pop(next(iter(_RESIZE_TABLES)))
+        tab = _RESIZE_TABLES[key] = host.to(dev, non_blocking=True)
+        tab._ore_stream = cur
+    elif tab._ore_stream != cur:
+        tab.record_stream(torch.cuda.current_stream(tab.device))
+    return tab
+
+
+def resize_bilinear_u8(img_hwc_u8: torch.Tensor, nh: int, nw: int, swap_rb: bool = False, out: Optional[torch.Tensor] = None,
+                       stream: Optional["torch.cuda.Stream"] = None, form: int = 0) -> torch.Tensor:
+    """[h, w, 3] uint8 device tensor (interleaved, what an image reader gives) -> [3, nh, nw] uint8 planar, byte for byte
+    np.asarray(Image.fromarray(img).resize((nw, nh), Image.BILINEAR)).transpose(2, 0, 1); swap_rb exchanges channels 0 and 2.
+    form: 0 = the library's choice (resize_form), or RESIZE_FORM_LDS / RESIZE_FORM_WORKSPACE to force one."""
+    if stream is not None:
+        with torch.cuda.stream(stream):
+            return resize_bilinear_u8(img_hwc_u8, nh, nw, swap_rb, out, None, form)
+    assert img_hwc_u8.is_cuda and img_hwc_u8.dtype == torch.uint8 and img_hwc_u8.dim() == 3 and img_hwc_u8.shape[2] == 3 and \
+        img_hwc_u8.is_contiguous(), "resize_bilinear_u8 takes a contiguous [h, w, 3] uint8 device tensor"
+    h, w = int(img_hwc_u8.shape[0]), int(img_hwc_u8.shape[1])
+    nh, nw = int(nh), int(nw)
+    dev = img_hwc_u8.device
+    with torch.cuda.device(dev):
+        tab = _resize_tables(dev, h, w, nh, nw)
+        if out is None:
+            out = torch.empty(3, nh, nw, dtype=torch.uint8, device=dev)
+        assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (3, nh, nw) and out.is_contiguous()
+        ws, ws_bytes = None, 0
+        if form == RESIZE_FORM_WORKSPACE or (form == 0 and resize_form(h, w, nh, nw) == RESIZE_FORM_WORKSPACE):
+            ws_bytes = int(lib().ore_resize_workspace_bytes(h, w, nh, nw))
+            ws_key = (str(dev), _stream())                          # per stream: two streams' passes must not share an intermediate
+            ws = _RESIZE_WS.get(ws_key)
+            if ws is None or ws.numel() < ws_bytes:
+                ws = _RESIZE_WS[ws_key] = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _chk(lib().ore_resize_bilinear_u8_fwd(_ptr(img_hwc_u8), h, w, _ptr(out), nh, nw, int(bool(swap_rb)), _ptr(tab), int(form), _ptr(ws),
+                                              ws_bytes, _stream()), "ore_resize_bilinear_u8_fwd")
+    return out
+
+
 def centernet_targets(gt_boxes: Sequence[torch.Tensor], shapes: Sequence[Tuple[int, int]], strides=(8, 16, 32),
                       soi=((0, 64), (48, 192), (128, 1000000)), hm_min_overlap: float = 0.8, min_radius: float = 4.0,
                       device=None, padded: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:

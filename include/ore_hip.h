@@ -717,6 +717,31 @@ size_t ore_coco_eval_workspace_bytes(int32_t n_cats, int32_t n_images, int32_t n
                                      int32_t n_areas, int32_t max_det);
 int ore_coco_eval(const ore_coco_eval_desc* desc, const ore_coco_eval_images* per_image /* NULL: not wanted */, void* stream);
 
+/* ------------------------------------------------------------------ image resize -------------- */
+/* Pillow's Image.resize(size, BILINEAR) for 8-bit images, byte for byte (ImagingResample: antialiased separable triangle filter,
+ * 22-bit fixed-point weights, horizontal pass to a uint8 intermediate, then the vertical pass); replaces the CPU resize of
+ * ResizeShortestEdge in front of the detector (d2z:data/transforms/augmentation_impl.py, d2z:data/transforms/transform.py
+ * ResizeTransform.apply_image; d2z:engine/defaults.py DefaultPredictor.__call__).  Sides 1 .. 8192.
+ * Planner (host only, no GPU needed), one axis: bounds_host [out][2] = (first source index, count), coeffs_host [out][ksize] with
+ * ksize = ore_resize_ksize(in, out) = 2 * ceil(max(in / out, 1)) + 1 (0 for sizes out of range); entries past `count` are 0.
+ * Device tables of one (h, w, nh, nw): ore_resize_table_ints() int32 values laid out x bounds [nw][2] | y bounds [nh][2] |
+ * x coefficients [nw][ksize_x] | y coefficients [nh][ksize_y], filled on the host by ore_resize_tables_host and copied by the caller.
+ * ore_resize_bilinear_u8_fwd: src_hwc [h][w][3] uint8 interleaved -> dst_chw [3][nh][nw] uint8 planar (the engine's uint8 image
+ * layout); swap_rb exchanges channels 0 and 2.  form 0: ORE_RESIZE_FORM_LDS (one launch, the intermediate stays in LDS) where a
+ * tile's staging fits 64 KiB of LDS, else ORE_RESIZE_FORM_WORKSPACE (two launches, the intermediate [h][nw][3] in `workspace`,
+ * ore_resize_workspace_bytes); a form code forces that form (the LDS form where it does not fit: ORE_EINVAL).  ore_resize_form tells
+ * which one form 0 takes.  Both forms write the same bytes; nothing outside dst_chw[0, 3 * nh * nw) is written. */
+#define ORE_RESIZE_FORM_LDS 1
+#define ORE_RESIZE_FORM_WORKSPACE 2
+int32_t ore_resize_ksize(int32_t in, int32_t out);
+int ore_resize_plan(int32_t in, int32_t out, int32_t* bounds_host, int32_t* coeffs_host, int32_t* ksize_out /* or NULL */);
+size_t ore_resize_table_ints(int32_t h, int32_t w, int32_t nh, int32_t nw);
+int ore_resize_tables_host(int32_t h, int32_t w, int32_t nh, int32_t nw, int32_t* tables_host);
+int32_t ore_resize_form(int32_t h, int32_t w, int32_t nh, int32_t nw);
+size_t ore_resize_workspace_bytes(int32_t h, int32_t w, int32_t nh, int32_t nw);
+int ore_resize_bilinear_u8_fwd(const uint8_t* src_hwc, int32_t h, int32_t w, uint8_t* dst_chw, int32_t nh, int32_t nw, int32_t swap_rb,
+                               const int32_t* tables_dev, int32_t form, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

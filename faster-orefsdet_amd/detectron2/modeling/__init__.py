@@ -25,3 +25,6 @@ def build_model(cfg):
     model = META_ARCH_REGISTRY.get(cfg.MODEL.META_ARCHITECTURE)(cfg)
     model.to(torch.device(cfg.MODEL.DEVICE))
     return model
+
+
+from .test_time_augmentation import DatasetMapperTTA, GeneralizedRCNNWithTTA  # noqa: E402,F401

@@ -298,11 +298,14 @@ class CenterNet2Detector(nn.Module):
         self._invalidate_state_key()
         return out
 
-    def make_engine(self, max_batch: int = 1, classes=None):
+    def make_engine(self, max_batch: int = 1, classes=None, max_hw=None):
         """A fresh engine (own buffers, own hipGraph) for the current parameters and support set.  `engine()` caches one; a server
         that keeps several images in flight on separate streams makes one per stream (bench.py --inflight), or folds concurrent
         requests into one pass with max_batch > 1 (Engine.eval_forward_batch).  classes = a resolved support_classes selection: the
-        engine also gets one class slot per selected class (Engine.set_classes / detect_classes), max_batch >= len(classes)."""
+        engine also gets one class slot per selected class (Engine.set_classes / detect_classes), max_batch >= len(classes).
+        max_hw = (max_h, max_w): the largest input the engine's buffers are sized for instead of cfg.INPUT.MAX_SIZE_TEST squared (the
+        test-time-augmentation wrapper's variants exceed it)."""
+        max_hw = self.max_hw if max_hw is None else (int(max_hw[0]), int(max_hw[1]))
         if classes:
             max_batch = max(max_batch, len(classes))
         import orehip
@@ -317,7 +320,7 @@ class CenterNet2Detector(nn.Module):
             e = orehip.Engine(stem=spec["stem"], conv=spec["stage_conv_ch"], out=spec["stage_out_ch"], layers=spec["layer_per_block"],
                               fpn_ch=c["fpn_ch"], strides=c["strides"], pixel_mean=c["pixel_mean"], pixel_std=c["pixel_std"],
                               score_thresh=c["score_thresh"], pre_topk=c["pre_topk"], nms_thresh=c["nms_thresh"],
-                              post_topk=c["post_topk"], max_batch=max_batch, max_h=self.max_hw[0], max_w=self.max_hw[1],
+                              post_topk=c["post_topk"], max_batch=max_batch, max_h=max_hw[0], max_w=max_hw[1],
                               device=dev.index or 0)
         finally:
             orehip.set_conv_precision(prev)
@@ -371,18 +374,11 @@ class CenterNet2Detector(nn.Module):
         return ("conv1.", "conv2.", "roi_heads.fc2.", "roi_heads.fc3.")
 
     # ---- raw images ---------------------------------------------------------------------------------------------
-    def _resolve_raw(self, inp):
-        """A request that carries "image_raw" -- the unresized [h, w, 3] uint8 image in the model's channel order, or the other one with
-        "swap_rb": numpy array, CPU tensor or device tensor -- instead of "image": the image goes to the device (host memory through a
-        pinned staging buffer this model owns, asynchronously on the current stream), is resized there to cfg.INPUT.MIN_SIZE_TEST /
-        MAX_SIZE_TEST (orehip.resize_bilinear_u8: the bytes of the CPU mapper's Pillow resize) and the request comes back in its
-        "image" form, "height" / "width" defaulting to the raw size.  Everything behind treats it as if it had come in that way."""
-        import orehip
-        if "image" in inp:
-            raise ValueError('a request carries either "image" or "image_raw", not both')
+    def _upload_raw(self, raw):
+        """The upload half of `_resolve_raw`: an [h, w, 3] uint8 image (numpy array, CPU tensor or device tensor) as a contiguous device
+        tensor; host memory goes through the pinned staging buffer this model owns, asynchronously on the current stream."""
         dev = self.device
         assert dev.type == "cuda", "CenterNet2Detector inference runs on the MI355X only"
-        raw = inp["image_raw"]
         if isinstance(raw, np.ndarray):
             raw = torch.from_numpy(np.ascontiguousarray(raw))
         if raw.dim() != 3 or raw.shape[2] != 3 or raw.dtype != torch.uint8:
@@ -401,6 +397,19 @@ class CenterNet2Detector(nn.Module):
             raw = torch.empty(h, w, 3, dtype=torch.uint8, device=dev)
             raw.copy_(stage[0][:n].view(h, w, 3), non_blocking=True)
             stage[1].record()
+        return raw
+
+    def _resolve_raw(self, inp):
+        """A request that carries "image_raw" -- the unresized [h, w, 3] uint8 image in the model's channel order, or the other one with
+        "swap_rb": numpy array, CPU tensor or device tensor -- instead of "image": the image goes to the device (host memory through a
+        pinned staging buffer this model owns, asynchronously on the current stream), is resized there to cfg.INPUT.MIN_SIZE_TEST /
+        MAX_SIZE_TEST (orehip.resize_bilinear_u8: the bytes of the CPU mapper's Pillow resize) and the request comes back in its
+        "image" form, "height" / "width" defaulting to the raw size.  Everything behind treats it as if it had come in that way."""
+        import orehip
+        if "image" in inp:
+            raise ValueError('a request carries either "image" or "image_raw", not both')
+        raw = self._upload_raw(inp["image_raw"])
+        h, w = int(raw.shape[0]), int(raw.shape[1])
         nh, nw = orehip.resize_shortest_edge_shape(h, w, self._test_size[0], self._test_size[1])
         out = {k: v for k, v in inp.items() if k not in ("image_raw", "swap_rb")}
         out["image"] = orehip.resize_bilinear_u8(raw, nh, nw, swap_rb=bool(inp.get("swap_rb", False)))

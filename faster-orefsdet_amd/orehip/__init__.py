@@ -890,6 +890,79 @@ def resize_bilinear_u8(img_hwc_u8: torch.Tensor, nh: int, nw: int, swap_rb: bool
     return out
 
 
+# ---------------------------------------------------------------------------------------------------
+# test-time augmentation tail (csrc/ore_tta.hip): flipped variants, per-variant collection, the merge
+# ---------------------------------------------------------------------------------------------------
+TTA_MAX_CANDIDATES = 8192                                # rows one ore_tta_merge_fwd takes (include/ore_hip.h)
+
+
+def tta_hflip_u8(img_chw_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[3, nh, nw] uint8 planar device image with its columns reversed (img[:, :, ::-1]) -- the flipped TTA variant, a copy of the
+    resized variant's bytes (ore_tta_hflip_u8_fwd).  Enqueued on the current stream."""
+    assert img_chw_u8.is_cuda and img_chw_u8.dtype == torch.uint8 and img_chw_u8.dim() == 3 and img_chw_u8.is_contiguous(), \
+        "tta_hflip_u8 takes a contiguous [c, h, w] uint8 device tensor"
+    if out is None:
+        out = torch.empty_like(img_chw_u8)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.shape == img_chw_u8.shape and out.is_contiguous()
+    c, nh, nw = (int(v) for v in img_chw_u8.shape)
+    with torch.cuda.device(img_chw_u8.device):
+        _chk(lib().ore_tta_hflip_u8_fwd(_ptr(img_chw_u8), _ptr(out), c * nh, nw, _stream()), "ore_tta_hflip_u8_fwd")
+    return out
+
+
+class TTAPool:
+    """Device buffers of one TTA merge: the candidate pool of `variants` x `rows` rows (boxes, scores, class ids), its running row
+    count, the per-variant counts and the merge workspace."""
+
+    def __init__(self, variants: int, rows: int, device):
+        self.variants, self.rows, self.cap = int(variants), int(rows), int(variants) * int(rows)
+        if not 1 <= self.cap <= TTA_MAX_CANDIDATES:
+            raise OreError(f"TTAPool: {variants} variants x {rows} rows = {self.cap} candidates, one merge takes 1 .. {TTA_MAX_CANDIDATES}")
+        dev = torch.device(device)
+        self.boxes = torch.zeros(self.cap, 4, dtype=torch.float32, device=dev)
+        self.scores = torch.zeros(self.cap, dtype=torch.float32, device=dev)
+        self.classes = torch.zeros(self.cap, dtype=torch.int64, device=dev)
+        self.n = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.var_counts = torch.zeros(self.variants, dtype=torch.int32, device=dev)
+        self.ws_bytes = int(lib().ore_tta_merge_workspace_bytes(self.cap))
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
+
+
+def tta_collect(pool: TTAPool, variant: int, boxes, scores, classes, n, max_rows: int, *, flip: bool, variant_w: int,
+                sx: float, sy: float, pre: Optional[Tuple[float, float]] = None) -> None:
+    """Append one variant's detection rows, inverse-transformed, to the pool (ore_tta_collect_fwd; no host sync).  boxes [.., 4] /
+    scores / classes (int64, or None: all 0): device tensors whose rows are contiguous; n: an int32 device tensor holding the row count
+    (read by the kernel) or a host int; at most max_rows rows are taken.  sx, sy (and pre = (px, py)) are the inverse resize ratios,
+    computed in double by the caller and rounded to fp32 here."""
+    n_dev, n_host = (_ptr(n), 0) if torch.is_tensor(n) else (None, int(n))
+    px, py = pre if pre is not None else (1.0, 1.0)
+    with torch.cuda.device(pool.boxes.device):
+        _chk(lib().ore_tta_collect_fwd(_ptr(boxes), _ptr(scores), _ptr(classes), n_dev, n_host, int(max_rows), int(bool(flip)), int(variant_w),
+                                       float(np.float32(sx)), float(np.float32(sy)), int(pre is not None), float(np.float32(px)),
+                                       float(np.float32(py)), _ptr(pool.boxes), _ptr(pool.scores), _ptr(pool.classes), _ptr(pool.n), pool.cap,
+                                       _ptr(pool.var_counts), int(variant), _stream()), "ore_tta_collect_fwd")
+
+
+def tta_merge(pool: TTAPool, out_h: int, out_w: int, score_thresh: float, nms_thresh: float, topk: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fast_rcnn_inference_single_image over the pool (ore_tta_merge_fwd; no host sync): returns (record, count) -- a fresh fp32 tensor
+    laid out [R][4] boxes | [R] scores | [R] int64 classes with R = topk rounded up to even, and the int32 device count of its valid rows.
+    `record_views(record, R, count)` cuts it."""
+    R = int(topk) + (int(topk) & 1)
+    dev = pool.boxes.device
+    rec = torch.empty(R * 7, dtype=torch.float32, device=dev)
+    cnt = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _chk(lib().ore_tta_merge_fwd(_ptr(pool.boxes), _ptr(pool.scores), _ptr(pool.classes), _ptr(pool.n), pool.cap, int(out_h), int(out_w),
+                                     float(score_thresh), float(nms_thresh), int(topk), _ptr(rec), R, _ptr(cnt), _ptr(pool.ws), pool.ws_bytes,
+                                     _stream()), "ore_tta_merge_fwd")
+    return rec, cnt
+
+
+def record_views(rec: torch.Tensor, R: int, k: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(boxes [k, 4], scores [k], classes [k] int64) of a result record of R rows (the layout of Engine.detect_end)."""
+    return rec.as_strided((k, 4), (4, 1)), rec.as_strided((k,), (1,), R * 4), rec.view(torch.int64).as_strided((k,), (1,), R * 5 // 2)
+
+
 def centernet_targets(gt_boxes: Sequence[torch.Tensor], shapes: Sequence[Tuple[int, int]], strides=(8, 16, 32),
                       soi=((0, 64), (48, 192), (128, 1000000)), hm_min_overlap: float = 0.8, min_radius: float = 4.0,
                       device=None, padded: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:

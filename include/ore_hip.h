@@ -742,6 +742,33 @@ size_t ore_resize_workspace_bytes(int32_t h, int32_t w, int32_t nh, int32_t nw);
 int ore_resize_bilinear_u8_fwd(const uint8_t* src_hwc, int32_t h, int32_t w, uint8_t* dst_chw, int32_t nh, int32_t nw, int32_t swap_rb,
                                const int32_t* tables_dev, int32_t form, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ test-time augmentation ---- */
+/* The device side of GeneralizedRCNNWithTTA (d2z:modeling/test_time_augmentation.py): everything between and behind the engine passes
+ * of one image's variants, enqueued on `stream`, no host synchronisation.
+ * ore_tta_hflip_u8_fwd: dst[r][x] = src[r][nw - 1 - x] for `rows` rows of nw bytes (a planar [3][nh][nw] image: rows = 3 * nh <= 65535);
+ *   the flipped variant is HFlipTransform.apply_image of the resized one, so it is a copy of the bytes ore_resize_bilinear_u8_fwd wrote.
+ * ore_tta_collect_fwd: one variant's detection rows -- boxes [n][4], scores [n], classes [n] int64 (NULL: all 0), n = min(*n_dev if
+ *   n_dev else n_host, max_rows) -- through tfm.inverse().apply_box in fp32, every operation rounded on its own: flip != 0: x = variant_w
+ *   - x; x *= sx, y *= sy (ResizeTransform variant -> image, the ratios rounded to fp32 by the caller); pre != 0: x *= px, y *= py (the
+ *   mapper's pre-transform undone); then (min x, min y, max x, max y) with numpy's NaN rule.  The rows are appended to the pool (boxes
+ *   [pool_cap][4], scores, classes int64) at the running offset *pool_n, which the call advances (variant == 0 restarts it at 0; rows that
+ *   would pass pool_cap are cut); var_counts[variant] = the rows taken.
+ * ore_tta_merge_fwd: fast_rcnn_inference_single_image (d2z:modeling/roi_heads/fast_rcnn.py) over the first min(*pool_n, cap) pool rows:
+ *   rows with a non-finite value dropped, boxes clipped to (out_h, out_w), score > score_thresh, stable sort by score (ties keep pool
+ *   order), greedy NMS per class id on the true coordinates with the IoU arithmetic of ore_nms_fwd, the first topk survivors -> out_record
+ *   ([rec_rows][4] f32 boxes | [rec_rows] f32 scores | [rec_rows] int64 classes, rec_rows even and >= topk) and out_count[0] (device).
+ *   cap <= 8192; class ids must fit 32 bits; workspace: ore_tta_merge_workspace_bytes(cap) (0 for a cap out of range).  No float
+ *   atomics: bit-reproducible run to run. */
+int ore_tta_hflip_u8_fwd(const uint8_t* src, uint8_t* dst, int32_t rows, int32_t nw, void* stream);
+int ore_tta_collect_fwd(const float* boxes, const float* scores, const int64_t* classes, const int32_t* n_dev, int32_t n_host,
+                        int32_t max_rows, int32_t flip, int32_t variant_w, float sx, float sy, int32_t pre, float px, float py,
+                        float* pool_boxes, float* pool_scores, int64_t* pool_classes, int32_t* pool_n, int32_t pool_cap,
+                        int32_t* var_counts, int32_t variant, void* stream);
+size_t ore_tta_merge_workspace_bytes(int32_t cap);
+int ore_tta_merge_fwd(const float* pool_boxes, const float* pool_scores, const int64_t* pool_classes, const int32_t* pool_n, int32_t cap,
+                      int32_t out_h, int32_t out_w, float score_thresh, float nms_thresh, int32_t topk, void* out_record,
+                      int32_t rec_rows, int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,10 +166,8 @@ __global__ __launch_bounds__(256) void k_wgrad(WgradP p) {
     // step to step instead of divided out
     const int x_first = max(0, m_begin + dy * p.W + dx);
     const int x_last = min(p.M, m_end + dy * p.W + dx + WG_K);                     // exclusive
-    const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.dz + (size_t)m_begin * p.dz_ld), 0,
-                                                                         (int)((unsigned)(m_end - m_begin) * (unsigned)p.dz_ld * 4u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x + (size_t)x_first * p.x_ld), 0,
-                                                                         (int)((unsigned)max(x_last - x_first, 0) * (unsigned)p.x_ld * 4u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rz = make_rsrc(p.dz + (size_t)m_begin * p.dz_ld, (unsigned)(m_end - m_begin) * (unsigned)p.dz_ld * 4u);
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x + (size_t)x_first * p.x_ld, (unsigned)max(x_last - x_first, 0) * (unsigned)p.x_ld * 4u);
     constexpr unsigned OOB = 0x80000000u;
     unsigned vz = co0 + lc < p.Cout ? (unsigned)(lr * p.dz_ld + p.dz_coff + co0 + lc) * 4u : OOB;
     unsigned vx = ci0 + lc < p.Cin ? (unsigned)((m_begin + lr + dy * p.W + dx - x_first) * p.x_ld + p.x_coff + ci0 + lc) * 4u : OOB;
@@ -283,10 +281,8 @@ __global__ __launch_bounds__(256) void k_wgrad3(WgradP p) {
     // them per MFMA and kept the matrix pipe 61 % busy.
     const int x_first = max(0, m_begin + dy * p.W - 1);
     const int x_last = min(p.M, m_end + dy * p.W + WG_K + 2);                      // exclusive
-    const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.dz + (size_t)m_begin * p.dz_ld), 0,
-                                                                         (int)((unsigned)(m_end - m_begin) * (unsigned)p.dz_ld * 4u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x + (size_t)x_first * p.x_ld), 0,
-                                                                         (int)((unsigned)max(x_last - x_first, 0) * (unsigned)p.x_ld * 4u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rz = make_rsrc(p.dz + (size_t)m_begin * p.dz_ld, (unsigned)(m_end - m_begin) * (unsigned)p.dz_ld * 4u);
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x + (size_t)x_first * p.x_ld, (unsigned)max(x_last - x_first, 0) * (unsigned)p.x_ld * 4u);
     constexpr unsigned OOB = 0x80000000u;
     unsigned vz = co0 + lc < p.Cout ? (unsigned)(lr * p.dz_ld + p.dz_coff + co0 + lc) * 4u : OOB;
     const bool ci_ok = ci0 + lc < p.Cin;
@@ -440,10 +436,8 @@ __global__ __launch_bounds__(256) void k_wgrad_bf(WgradP p) {
     const int xshift = K3 ? dy * p.W - 1 : dy * p.W + dx1;
     const int x_first = max(0, m_begin + xshift);
     const int x_last = min(p.M, m_end + xshift + WB_K + (K3 ? 2 : 0));             // exclusive
-    const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.dz + (size_t)m_begin * p.dz_ld), 0,
-                                                                         (int)((unsigned)(m_end - m_begin) * (unsigned)p.dz_ld * 4u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x + (size_t)x_first * p.x_ld), 0,
-                                                                         (int)((unsigned)max(x_last - x_first, 0) * (unsigned)p.x_ld * 4u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rz = make_rsrc(p.dz + (size_t)m_begin * p.dz_ld, (unsigned)(m_end - m_begin) * (unsigned)p.dz_ld * 4u);
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x + (size_t)x_first * p.x_ld, (unsigned)max(x_last - x_first, 0) * (unsigned)p.x_ld * 4u);
     constexpr unsigned OOB = 0x80000000u;
     const unsigned z0 = (unsigned)(lr * p.dz_ld + p.dz_coff + co0 + lc) * 4u;
     const unsigned x0 = (unsigned)((m_begin + lr + xshift - x_first) * p.x_ld + p.x_coff + ci0 + lc) * 4u;

@@ -70,6 +70,31 @@ __device__ __forceinline__ void st4(ore_bf16_t* p, f32x4 v) { *reinterpret_cast<
 __device__ __forceinline__ float ld1(const float* p) { return *p; }
 __device__ __forceinline__ float ld1(const ore_bf16_t* p) { return bf16_bits_to_f32(p->v); }
 
+// a raw buffer over [base, base + bytes): stride 0, num_records = bytes, so the range check is on the byte offset (flags word 0x00020000:
+// 32-bit data format, nothing else)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
+}
+
+// expf of the bit-exact twins (ore_detect.hip, ore_roi.hip and their CPU references): a fixed sequence of fmaf / single IEEE operations,
+// the same on both sides, instead of whatever the math library of either side does.  Those files are compiled with -ffp-contract=off.
+__device__ __forceinline__ float ore_expf(float x) {
+    if (x > 88.0f) x = 88.0f;
+    if (x < -87.0f) x = -87.0f;
+    const float n = rintf(x * 1.44269504088896341f);
+    float r = fmaf(n, -0.693359375f, x);
+    r = fmaf(n, 2.12194440e-4f, r);
+    float p = 1.9875691500e-4f;
+    p = fmaf(p, r, 1.3981999507e-3f);
+    p = fmaf(p, r, 8.3334519073e-3f);
+    p = fmaf(p, r, 4.1665795894e-2f);
+    p = fmaf(p, r, 1.6666665459e-1f);
+    p = fmaf(p, r, 5.0000001201e-1f);
+    const float e = fmaf(p, r * r, r) + 1.0f;
+    const int ni = (int)n;
+    return e * __uint_as_float((unsigned)(ni + 127) << 23);
+}
+
 namespace oreroi {
 // ore_roi_predict_post_fwd with the fc1 rows still in K-split partial sums (csrc/ore_roi.hip; h_parts = 0: as the C-ABI entry)
 int roi_predict_post(const float* h, int32_t C, int32_t h_parts, const float* h_bias, const float* cls_w, const float* cls_b,

@@ -31,19 +31,7 @@ using namespace oreconv;
 // unconditional (no branch around a load => the compiler keeps them in flight behind counted vmcnt waits).
 __device__ __attribute__((aligned(16))) float g_zero16[4] = {0.f, 0.f, 0.f, 0.f};
 
-__device__ __forceinline__ void decode_row(const ConvP& p, int m, int& lvl, int& b, int& oy, int& ox) {
-    lvl = 0;
-#pragma unroll
-    for (int l = 1; l < 4; ++l)
-        if (l < p.nlev && m >= p.lv[l].orow0) lvl = l;
-    const Lvl& L = p.lv[lvl];
-    const int r = m - L.orow0, hw = L.Ho * L.Wo;
-    b = r / hw;
-    const int q = r - b * hw;
-    oy = q / L.Wo;
-    ox = q - oy * L.Wo;
-}
-
+// (fp32 addend only; the epilogue_one of ore_conv_kw.hip also takes a bf16 one, p.sb & 4)
 __device__ __forceinline__ float epilogue_one(const ConvP& p, float acc, int m, int n) {
     float v = acc;
     int lvl = 0, b = 0, oy = 0, ox = 0;

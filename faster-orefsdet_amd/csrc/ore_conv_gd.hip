@@ -4,9 +4,8 @@
 //
 // Round 4.  k_conv_gs / k_conv_igemm ran the large layers at 36-48 % of the fp32 MFMA peak, and round 2's counters said why: 87 VALU + 82
 // SALU instructions per 28 MFMAs per step -- the matrix pipe waits for instruction issue, not for data.  k_conv_kd showed the cure on
-// the small layers (descriptor addressing: per-lane byte offsets computed once, the step is a scalar offset from a table in the kernel
-// arguments or an instruction offset, out-of-range = the descriptor's zeros) but its K-split blocks tie here, because their partial tiles
-// meet in LDS and one block owns a CU.  This kernel puts the same addressing into the SHARED-stage structure:
+// the small layers (the descriptor addressing of ore_conv_desc.h) but its K-split blocks tie here, because their partial tiles meet in
+// LDS and one block owns a CU.  This kernel puts the same addressing into the SHARED-stage structure:
 //   * the NW = 4 or 8 waves of a block tile its BM x BN output (WGM x WGN waves) and share every staged 16-channel chunk: a chunk is
 //     (BM + BN) / 16 DMA pieces of 1 KiB, piece p is issued by wave p % NW (`buffer_load_dwordx4 ... lds`, XOR swizzle on the source
 //     offset as in k_conv_kw), an NS-deep ring, ONE raw barrier per chunk: a wave waits for its own pieces of chunk t (counted vmcnt,
@@ -24,44 +23,20 @@
 // Replaces F.conv2d + FrozenBatchNorm2d + ReLU of d2z:modeling/backbone/vovnet.py:205-219 (stem_3), :310-332 (the concat convs);
 // d2z:modeling/backbone/fpn.py:130-150 (lateral 3); ref:fewx/modeling/fsod/fsod_cen.py conv3 after the correlation;
 // d2z:modeling/roi_heads/box_head.py fc1 (conv_gd_splitk).
-#include "ore_conv_internal.h"
+#include "ore_conv_desc.h"
 
 namespace {
 using namespace oreconv;
 
 constexpr int kTab = kGdTab;                      // chunk table entries
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-// one LDS-DMA piece (see k_conv_kd: the instruction offset moves the LDS address too, so M0 gets dst - IMM)
-template <int IMM>
-__device__ __forceinline__ void dma(__amdgpu_buffer_rsrc_t r, float* dst, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)(dst - IMM / 4), 16, (int)voff, (int)soff, IMM, 0);
-}
-__device__ __forceinline__ f32x4 bload4(__amdgpu_buffer_rsrc_t r, unsigned voff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0));
-}
-__device__ __forceinline__ int fdiv(int n, int d, float inv) {       // n / d, 0 <= n < 2^22, inv = 1.0f / d
-    int q = (int)((float)n * inv);
-    int r = n - q * d;
-    q += r >= d ? 1 : 0;
-    r -= r >= d ? d : 0;
-    q -= r < 0 ? 1 : 0;
-    return q;
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N >= 0 && N <= 63, "vmcnt immediate");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ int swz(int r16) { return (0x1320 >> (((r16 >> 2) & 3) * 4)) & 3; }   // {0, 2, 3, 1}
+constexpr ChunkFmt kFmt = kChunkTapLow;
 
 struct GdK {
     const float* in; const float* w; const float* scale; const float* shift; const float* add; float* out; float* colsum;
     unsigned in_bytes, w_bytes, sc_bytes, add_bytes;
     int M, K, Cout, Cout16, nchunks;
     int irow0, H, W, Ho, Wo, in_ld, in_coff, stride, pad;
-    int out_ld, out_coff, relu_cout, add_H, add_W, add_ld, add_coff;   // add: the FPN top-down addend [B][add_H][add_W][add_ld], read at (oy / 2, ox / 2)
+    int out_ld, out_coff, relu_cout, add_H, add_W, add_ld, add_coff;
     int zc_stride, out_zstride;   // K split over blockIdx.z: slice z stages chunks z * zc_stride + [0, nchunks) and writes raw sums at out + z * out_zstride (0, 0: no split)
     int xmap, gx, gy;
     float inv_hw, inv_wo, inv_gx, inv_gy;
@@ -71,19 +46,8 @@ struct GdK {
 };
 struct GdP {
     GdK k;
-    unsigned tab[kTab];      // 3x3: per 16-channel chunk (byte offset of (tap, channel chunk) from the window's first pixel) | tap; beyond K: 15
+    unsigned tab[kTab];      // 3x3: the chunk table, format kFmt
 };
-
-__device__ __forceinline__ void gd_tile(const GdK& k, int& bx, int& by) {
-    bx = blockIdx.x; by = blockIdx.y;
-    if (k.xmap == 0) return;
-    const int T = k.gx * k.gy;
-    const int lin = by * k.gx + bx, r = lin & 7, kk = lin >> 3;
-    const int qd = T >> 3, rem = T & 7;
-    const int t = r * qd + min(r, rem) + kk;
-    if (k.xmap == 1) { bx = fdiv(t, k.gy, k.inv_gy); by = t - bx * k.gy; }
-    else { by = fdiv(t, k.gx, k.inv_gx); bx = t - by * k.gx; }
-}
 
 template <int GA, int GB, int WGM, int WGN, int NS, int KS, bool BF = false>
 __global__ __launch_bounds__(64 * WGM * WGN) void k_conv_gd(GdP q) {
@@ -104,12 +68,10 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_conv_gd(GdP q) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WGN, wn = wave % WGN;
     int bx, by;
-    gd_tile(p, bx, by);
+    tile_of_block_rcp(p, bx, by);
     const int m0 = bx * (16 * GA), n0 = by * (16 * GB);
-    const int row_bytes = p.W * p.in_ld * 4, pix_bytes = p.in_ld * 4;
-    const int bias = p.pad * (row_bytes + pix_bytes);
-    const __amdgpu_buffer_rsrc_t rw = make_rsrc(p.w, p.w_bytes);
-    const __amdgpu_buffer_rsrc_t ri = make_rsrc(reinterpret_cast<const char*>(p.in) - bias, p.in_bytes + (unsigned)bias);
+    const int bias = window_bias(p);
+    const __amdgpu_buffer_rsrc_t rw = make_rsrc(p.w, p.w_bytes), ri = make_pixel_rsrc(p, bias);
 
     // ---- this wave's DMA pieces: piece index pw + 4 s (s < PPW); pieces 0 .. GA-1 are pixel groups, GA .. G-1 weight-row groups
     const int r16 = lane >> 2, lq = (lane & 3) ^ swz(r16);
@@ -122,20 +84,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_conv_gd(GdP q) {
         if (pi < GA) {
             const int m = m0 + pi * 16 + r16;
             if (m < p.M) {
-                const int b = fdiv(m, hw, p.inv_hw);
-                const int rr = m - b * hw;
-                const int oy = fdiv(rr, p.Wo, p.inv_wo), ox = rr - oy * p.Wo;
-                const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
-                unsigned rmask = 0u, cmask = 0u, tm = 0u;
-#pragma unroll
-                for (int d = 0; d < KS; ++d) {
-                    rmask |= (unsigned)(iy0 + d) < (unsigned)p.H ? 1u << d : 0u;
-                    cmask |= (unsigned)(ix0 + d) < (unsigned)p.W ? 1u << d : 0u;
-                }
-#pragma unroll
-                for (int d = 0; d < KS; ++d) tm |= ((rmask >> d) & 1u) ? cmask << (d * KS) : 0u;
-                ptaps[s] = tm;
-                pv[s] = (unsigned)(bias + (((p.irow0 + b * p.H * p.W) + iy0 * p.W + ix0) * p.in_ld + p.in_coff + lq * 4) * 4);
+                const Pixel px = pixel_of_row(p, m, hw);
+                CONV_WINDOW_OF_PIXEL(KS, p, px, lq, bias, ptaps[s], pv[s]);
             }
         } else if (pi < G) {
             const int n = n0 + (pi - GA) * 16 + r16;
@@ -148,13 +98,13 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_conv_gd(GdP q) {
         float* dst = lds + slot * STAGE_F;
         const bool live = c < p.nchunks;
         const int cz = c + zc0;                                            // the chunk's place in K (zc0 = 0 without a K split)
-        unsigned e = 15u;
+        unsigned e = chunk_entry(kFmt, 0u, kNoTap);
         if constexpr (KS != 1) e = q.tab[cz < kTab ? cz : kTab - 1];
-        const unsigned bit = 1u << (e & 15u);
+        const unsigned bit = 1u << chunk_tap(kFmt, e);
         const int pi = wave + NW * s;                                      // wave-uniform
         if (pi < GA) {
             if constexpr (KS == 1) dma<0>(ri, dst + pi * 256, live ? pv[s] : kOOB, (unsigned)cz * 64u);
-            else dma<0>(ri, dst + pi * 256, (live && (ptaps[s] & bit)) ? pv[s] : kOOB, e & ~63u);
+            else dma<0>(ri, dst + pi * 256, (live && (ptaps[s] & bit)) ? pv[s] : kOOB, chunk_off(kFmt, e));
         } else if (pi < G) {
             dma<0>(rw, dst + pi * 256, live ? pv[s] : kOOB, (unsigned)cz * 64u);
         }
@@ -294,12 +244,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_conv_gd(GdP q) {
             if (m < p.M && en < p.Cout) {
 #endif
                 v = acc[i][j] * e_sc + e_sh;
-                if (p.add) {                                       // nearest-neighbour upsampled coarser level (d2z:modeling/backbone/fpn.py:140-144)
-                    const int b = fdiv(m, hw, p.inv_hw);
-                    const int rr = m - b * hw;
-                    const int oy = fdiv(rr, p.Wo, p.inv_wo), ox = rr - oy * p.Wo;
-                    v += bload4(rad, (unsigned)((((b * p.add_H + (oy >> 1)) * p.add_W + (ox >> 1)) * p.add_ld + p.add_coff + en) * 4));
-                }
+                if (p.add) v += bload4(rad, (unsigned)(addend_index(p, pixel_of_row(p, m, hw), en) * 4));
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     if (en + r < p.relu_cout) v[r] = fmaxf(v[r], 0.0f);
@@ -361,36 +306,16 @@ namespace oreconv {
 
 // k_conv_gd: the plan's tile and build over p's rows (several levels of a 1x1 layer: one flat GEMM)
 int launch_gd(const ConvP& p, const ConvPlan& pl, hipStream_t st) {
-    const int gx = pl.gx, gy = pl.gy;
-    Lvl L = p.lv[0];
-    int Bimg = p.B;
-    if (p.nlev > 1) { L.H = 1; L.W = p.M; L.Ho = 1; L.Wo = p.M; Bimg = 1; }      // one "image" of M pixels in a row
     GdP q;
-    GdK& k = q.k;
-    k.in = p.in; k.w = p.w; k.scale = p.scale; k.shift = p.shift; k.add = p.add; k.out = p.out; k.colsum = p.colsum;
-    k.add_bytes = p.add ? (unsigned)((long long)p.B * p.add_H * p.add_W * p.add_ld * 4) : 0u;
-    k.add_H = p.add_H; k.add_W = p.add_W; k.add_ld = p.add_ld; k.add_coff = p.add_coff;
-    k.in_bytes = (unsigned)(((long long)L.irow0 + (long long)Bimg * L.H * L.W) * p.in_ld * 4);
-    k.w_bytes = (unsigned)((long long)p.Cout16 * p.K * 4);
-    k.sc_bytes = (unsigned)p.Cout * 4u;
-    k.M = p.M; k.K = p.K; k.Cout = p.Cout; k.Cout16 = p.Cout16; k.nchunks = p.nchunks;
-    k.irow0 = L.irow0; k.H = L.H; k.W = L.W; k.Ho = L.Ho; k.Wo = L.Wo; k.in_ld = p.in_ld; k.in_coff = p.in_coff; k.stride = p.stride; k.pad = p.pad;
-    k.out_ld = p.out_ld; k.out_coff = p.out_coff; k.relu_cout = p.relu_cout; k.zc_stride = 0; k.out_zstride = 0;
-    k.xmap = pl.xmap; k.gx = gx; k.gy = gy;
+    Lvl L;
+    fill_desc_args(q.k, p, pl, L);
+    q.k.zc_stride = 0; q.k.out_zstride = 0;
 #ifdef ORE_TRACE
-    k.dbg = g_knobs.gd_dbg;
+    q.k.dbg = g_knobs.gd_dbg;
 #endif
-    k.inv_hw = 1.0f / (float)(L.Ho * L.Wo); k.inv_wo = 1.0f / (float)L.Wo; k.inv_gx = 1.0f / (float)gx; k.inv_gy = 1.0f / (float)gy;
-    for (int c = 0; c < kTab; ++c) q.tab[c] = 15u;
-    if (p.kh == 3) {
-        const int cpt = p.Cin >> 4, row_bytes = L.W * p.in_ld * 4, pix_bytes = p.in_ld * 4;
-        for (int c = 0; c < p.nchunks; ++c) {
-            const int tap = c / cpt, cc = c - tap * cpt, dy = tap / 3, dx = tap - dy * 3;
-            q.tab[c] = (unsigned)(dy * row_bytes + dx * pix_bytes + cc * 64) | (unsigned)tap;
-        }
-    }
+    build_chunk_table(q.tab, kTab, p, L, kFmt);
     const bool k3 = p.kh == 3;
-    const dim3 grid(gx, gy, 1);
+    const dim3 grid(pl.gx, pl.gy, 1);
 #define GD_GO(bm_, bn_, wgm_, wgn_, ns_, bf_)                                                                             \
     if (pl.bm == bm_ && pl.bn == bn_ && pl.build[0] == wgm_ && pl.build[1] == wgn_ && pl.build[2] == ns_ && pl.build[3] == bf_) \
         return gd_go<bm_ / 16, bn_ / 16, wgm_, wgn_, ns_, bf_>(q, k3, grid, st);
@@ -409,22 +334,22 @@ int conv_gd_splitk(const float* in, int in_ld, const float* w, int M, int K, int
     ORE_CHECK_ARG(in && w && parts && M >= 1 && M < (1 << 20) && K % 16 == 0 && Cout16 % 64 == 0 && in_ld % 16 == 0 && in_ld >= K && S >= 1 &&
                       (K / 16) % S == 0, "conv_gd_splitk: bad shape M %d K %d Cout16 %d S %d", M, K, Cout16, S);
     ORE_CHECK_ARG((long long)M * in_ld * 4 < (long long)kOOB - (1 << 24) && (long long)Cout16 * K * 4 < (long long)kOOB, "conv_gd_splitk: operand beyond a buffer descriptor");
+    // the GEMM as a 1x1 layer over one "image" of M pixels in a row, no epilogue operands; each slice sees its own K / S chunks
+    ConvP p{};
+    p.in = in; p.in_ld = in_ld; p.B = 1; p.Cin = K; p.nlev = 1; p.lv[0] = Lvl{0, 0, 1, M, 1, M};
+    p.w = w; p.Cout = Cout16; p.Cout16 = Cout16; p.kh = 1; p.kw = 1; p.stride = 1; p.M = M; p.K = K;
+    p.out = parts; p.out_ld = Cout16; p.nchunks = K / 16 / S;
+    ConvPlan pl{};
+    pl.gx = ceil_div(M, 80); pl.gy = Cout16 / 64;
     GdP q;
-    GdK& k = q.k;
-    k.in = in; k.w = w; k.scale = nullptr; k.shift = nullptr; k.add = nullptr; k.out = parts; k.colsum = nullptr;
-    k.add_bytes = 0u; k.add_H = k.add_W = k.add_ld = k.add_coff = 0;
-    k.in_bytes = (unsigned)((long long)M * in_ld * 4); k.w_bytes = (unsigned)((long long)Cout16 * K * 4); k.sc_bytes = 0u;
-    k.M = M; k.K = K; k.Cout = Cout16; k.Cout16 = Cout16; k.nchunks = K / 16 / S;
-    k.irow0 = 0; k.H = 1; k.W = M; k.Ho = 1; k.Wo = M; k.in_ld = in_ld; k.in_coff = 0; k.stride = 1; k.pad = 0;
-    k.out_ld = Cout16; k.out_coff = 0; k.relu_cout = 0; k.zc_stride = K / 16 / S; k.out_zstride = M * Cout16;
-    const int gx = ceil_div(M, 80), gy = Cout16 / 64;
-    k.xmap = 0; k.gx = gx; k.gy = gy;
-    k.inv_hw = 1.0f / (float)M; k.inv_wo = 1.0f / (float)M; k.inv_gx = 1.0f / (float)gx; k.inv_gy = 1.0f / (float)gy;
+    Lvl L;
+    fill_desc_args(q.k, p, pl, L);
+    q.k.zc_stride = p.nchunks; q.k.out_zstride = M * Cout16;
 #ifdef ORE_TRACE
-    k.dbg = 0;
+    q.k.dbg = 0;
 #endif
-    for (int c = 0; c < kTab; ++c) q.tab[c] = 15u;
-    return gd_go<5, 4, 1, 4, 4>(q, false, dim3(gx, gy, S), st);
+    build_chunk_table(q.tab, kTab, p, L, kFmt);
+    return gd_go<5, 4, 1, 4, 4>(q, false, dim3(pl.gx, pl.gy, S), st);
 }
 
 }  // namespace oreconv

@@ -46,6 +46,19 @@ __device__ __forceinline__ void tile_of_block(int xmap, int& bx, int& by) {
     else { by = t / gx; bx = t - by * gx; }
 }
 
+// Row m of the GEMM -> pyramid level, image and output pixel (k_conv_igemm, k_conv_kw, k_conv_gs: rows may span several levels).
+__device__ __forceinline__ void decode_row(const ConvP& p, int m, int& lvl, int& b, int& oy, int& ox) {
+    lvl = 0;
+#pragma unroll
+    for (int l = 1; l < 4; ++l)
+        if (l < p.nlev && m >= p.lv[l].orow0) lvl = l;
+    const Lvl& L = p.lv[lvl];
+    const int r = m - L.orow0, hw = L.Ho * L.Wo;
+    b = r / hw;
+    const int q = r - b * hw;
+    oy = q / L.Wo;
+    ox = q - oy * L.Wo;
+}
 
 // Limits of the buffer-descriptor kernels that the planner's eligibility tests share with them
 constexpr unsigned kOOB = 0x80000000u;   // a byte offset beyond every buffer's num_records (< 2 GB here, and kOOB + an instruction offset

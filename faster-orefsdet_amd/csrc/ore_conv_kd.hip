@@ -7,61 +7,23 @@
 // 55 B/clk through LDS-DMA in 16 x 64-byte segments per instruction (58 clocks per instruction), 23 B/clk for the fragment-shaped
 // register loads of k_conv_rf.  This kernel keeps k_conv_kw's data path (coalesced segments -> LDS image with the XOR swizzle on the
 // source address -> ds_read_b128 fragments) and k_conv_rf's addressing:
-//   * `buffer_load_dwordx4 ... lds` through range-checked descriptors: the per-lane byte offset of a pixel row / weight row is computed
-//     ONCE, a step adds a scalar offset (3x3: `(offset | tap)` per chunk from a table in the kernel arguments, built by the host) or an
-//     instruction offset (weights, 1x1 layers); out-of-image taps, rows beyond M / Cout and chunks beyond K are the descriptor's zeros
-//     (they land in LDS as zeros) -- no zero page, no 64-bit pointer select, no tap walk: ~6 instructions per piece and step;
+//   * `buffer_load_dwordx4 ... lds` through range-checked descriptors (the addressing layer of ore_conv_desc.h; what is out of range
+//     lands in LDS as zeros): ~6 instructions per piece and step;
 //   * a wave owns a CONTIGUOUS range of the K axis and works in batches of SB steps on a double-buffered private LDS region: the DMAs of
-//     batch b+1 are in flight while batch b is multiplied; waits are counted (`s_waitcnt vmcnt`), there is no barrier in the K loop;
-//   * kernel arguments are one compact block fetched by a handful of scalar loads at the top (see k_conv_rf).
+//     batch b+1 are in flight while batch b is multiplied; waits are counted (`s_waitcnt vmcnt`), there is no barrier in the K loop.
 // K is split over the NW waves of a block, partial tiles meet in LDS, epilogue = k_conv_kw's (scale / shift, FPN top-down add, ReLU,
 // per-tile column sums, channel-slice output).  Single level, fp32 storage, no input affine.
 //
 // Replaces F.conv2d + FrozenBatchNorm2d + ReLU / bias of d2z:modeling/backbone/vovnet.py:205-219,310-332 (stages 3-5), fpn.py:126-145
 // (laterals), ref:fewx/modeling/fsod/fsod_cen.py:470 (conv3) at batch 1.
-#include "ore_conv_internal.h"
+#include "ore_conv_desc.h"
 
 namespace {
 using namespace oreconv;
 
-#ifdef ORE_TRACE
-__device__ unsigned long long* g_trace_kd = nullptr;
-#define KD_TR(i) do { if (g_trace_kd && threadIdx.x == 0) g_trace_kd[(size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#define KD_TRR(i) do { if (g_trace_kd && threadIdx.x == 0) g_trace_kd[(size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 16 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define KD_TR(i) do { } while (0)
-#define KD_TRR(i) do { } while (0)
-#endif
-
+CONV_TRACE_SYMBOL(g_trace_kd)
 constexpr int kTab = kKdTab;                      // chunk table entries
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-// one LDS-DMA piece: 64 lanes x 16 bytes -> 1 KiB at `dst` (lane-linear), source = base + voff + soff + IMM.  The instruction offset
-// of a buffer load with the LDS flag is added to the LDS address as well as to the memory address (LDS address = M0 + offset + lane * 16),
-// so M0 is handed dst - IMM: the step rides in the instruction on the memory side and cancels on the LDS side.
-template <int IMM>
-__device__ __forceinline__ void dma(__amdgpu_buffer_rsrc_t r, float* dst, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)(dst - IMM / 4), 16, (int)voff, (int)soff, IMM, 0);
-}
-__device__ __forceinline__ f32x4 bload4(__amdgpu_buffer_rsrc_t r, unsigned voff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0));
-}
-__device__ __forceinline__ int fdiv(int n, int d, float inv) {       // n / d, 0 <= n < 2^22, inv = 1.0f / d
-    int q = (int)((float)n * inv);
-    int r = n - q * d;
-    q += r >= d ? 1 : 0;
-    r -= r >= d ? d : 0;
-    q -= r < 0 ? 1 : 0;
-    return q;
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N >= 0 && N <= 63, "vmcnt immediate");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// XOR swizzle of the four 16-byte quads of a 64-byte row inside a 16-row group (k_conv_kw's: conflict-free ds_read_b128)
-__device__ __forceinline__ int swz(int r16) { return (0x1320 >> (((r16 >> 2) & 3) * 4)) & 3; }   // {0, 2, 3, 1}
+constexpr ChunkFmt kFmt = kChunkTapHigh;
 
 struct KdK {
     const float* in; const float* w; const float* scale; const float* shift; const float* add; float* out; float* colsum;
@@ -75,19 +37,8 @@ struct KdK {
 };
 struct KdP {
     KdK k;
-    unsigned tab[kTab];      // 3x3: per 16-channel chunk (byte offset of (tap, channel chunk) from the window's first pixel) | tap << 28; beyond K: tap 15
+    unsigned tab[kTab];      // 3x3: the chunk table, format kFmt
 };
-
-__device__ __forceinline__ void kd_tile(const KdK& k, int& bx, int& by) {
-    bx = blockIdx.x; by = blockIdx.y;
-    if (k.xmap == 0) return;
-    const int T = k.gx * k.gy;
-    const int lin = by * k.gx + bx, r = lin & 7, kk = lin >> 3;
-    const int qd = T >> 3, rem = T & 7;
-    const int t = r * qd + min(r, rem) + kk;
-    if (k.xmap == 1) { bx = fdiv(t, k.gy, k.inv_gy); by = t - bx * k.gy; }
-    else { by = fdiv(t, k.gx, k.inv_gx); bx = t - by * k.gx; }
-}
 
 template <int GA, int GB, int NW, int SB, int KS, bool SBF = false>
 __global__ __launch_bounds__(NW * 64) void k_conv_kd(KdP q) {
@@ -99,7 +50,7 @@ __global__ __launch_bounds__(NW * 64) void k_conv_kd(KdP q) {
     constexpr int NT = GA * GB;
     static_assert(SB * G <= 63, "a batch must fit the vmcnt counter");
     extern __shared__ __attribute__((aligned(16))) float lds[];   // max(NW * WAVE_F, NW * NT * 256) + NT * 16 floats
-    KD_TR(0); KD_TRR(1);
+    CONV_TR(g_trace_kd, 0); CONV_TRR(g_trace_kd, 1);
     KdK p = q.k;
     asm volatile("" :: "s"(p.in), "s"(p.w), "s"(p.scale), "s"(p.shift), "s"(p.add), "s"(p.out), "s"(p.colsum), "s"(p.in_bytes), "s"(p.w_bytes),
                  "s"(p.sc_bytes), "s"(p.add_bytes), "s"(p.M), "s"(p.K), "s"(p.Cout), "s"(p.Cout16), "s"(p.nchunks), "s"(p.nb));
@@ -109,12 +60,10 @@ __global__ __launch_bounds__(NW * 64) void k_conv_kd(KdP q) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int bx, by;
-    kd_tile(p, bx, by);
+    tile_of_block_rcp(p, bx, by);
     const int m0 = bx * (16 * GA), n0 = by * (16 * GB);
-    const int row_bytes = p.W * p.in_ld * 4, pix_bytes = p.in_ld * 4;
-    const int bias = p.pad * (row_bytes + pix_bytes);             // see k_conv_rf: keeps the window's first pixel at a non-negative offset
-    const __amdgpu_buffer_rsrc_t rw = make_rsrc(p.w, p.w_bytes);
-    const __amdgpu_buffer_rsrc_t ri = make_rsrc(reinterpret_cast<const char*>(p.in) - bias, p.in_bytes + (unsigned)bias);
+    const int bias = window_bias(p);
+    const __amdgpu_buffer_rsrc_t rw = make_rsrc(p.w, p.w_bytes), ri = make_pixel_rsrc(p, bias);
 
     // ---- per-lane DMA sources: lane L of a piece fills LDS slot L = (row L >> 2, physical quad L & 3) with logical quad (L & 3) ^ swz(row)
     const int r16 = lane >> 2, lq = (lane & 3) ^ swz(r16);
@@ -131,20 +80,8 @@ __global__ __launch_bounds__(NW * 64) void k_conv_kd(KdP q) {
         const int m = m0 + i * 16 + r16;
         a_voff[i] = kOOB; a_taps[i] = 0u;
         if (m < p.M) {
-            const int b = fdiv(m, hw, p.inv_hw);
-            const int rr = m - b * hw;
-            const int oy = fdiv(rr, p.Wo, p.inv_wo), ox = rr - oy * p.Wo;
-            const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
-            unsigned rmask = 0u, cmask = 0u, tm = 0u;
-#pragma unroll
-            for (int d = 0; d < KS; ++d) {
-                rmask |= (unsigned)(iy0 + d) < (unsigned)p.H ? 1u << d : 0u;
-                cmask |= (unsigned)(ix0 + d) < (unsigned)p.W ? 1u << d : 0u;
-            }
-#pragma unroll
-            for (int d = 0; d < KS; ++d) tm |= ((rmask >> d) & 1u) ? cmask << (d * KS) : 0u;
-            a_taps[i] = tm;
-            a_voff[i] = (unsigned)(bias + (((p.irow0 + b * p.H * p.W) + iy0 * p.W + ix0) * p.in_ld + p.in_coff + lq * 4) * 4);
+            const Pixel px = pixel_of_row(p, m, hw);
+            CONV_WINDOW_OF_PIXEL(KS, p, px, lq, bias, a_taps[i], a_voff[i]);
         }
     }
     // this wave's chunks: the contiguous range [wave * nst, (wave + 1) * nst), SB steps per batch, nb batches
@@ -172,9 +109,9 @@ __global__ __launch_bounds__(NW * 64) void k_conv_kd(KdP q) {
                 }
             } else {
                 const unsigned e = q.tab[w_c + t];
-                const unsigned bit = 1u << (e >> 28);             // tap in the top four bits, byte offset below (a bf16 pixel pitch need not be a multiple of 64)
+                const unsigned bit = 1u << chunk_tap(kFmt, e);
 #pragma unroll
-                for (int i = 0; i < GA; ++i) dma<0>(ri, dst + i * 256, (a_taps[i] & bit) ? a_voff[i] : kOOB, e & 0x0fffffffu);
+                for (int i = 0; i < GA; ++i) dma<0>(ri, dst + i * 256, (a_taps[i] & bit) ? a_voff[i] : kOOB, chunk_off(kFmt, e));
             }
 #pragma unroll
             for (int j = 0; j < GB; ++j) {
@@ -201,9 +138,9 @@ __global__ __launch_bounds__(NW * 64) void k_conv_kd(KdP q) {
     // fragment read offsets (floats) inside a 16-row group: row = lane & 15, logical quad = lane >> 4
     const int frow = lane & 15;
     const int foff = frow * 16 + (((lane >> 4) ^ swz(frow)) << 2);
-    KD_TR(2);
+    CONV_TR(g_trace_kd, 2);
     issue(ring);
-    KD_TR(3);
+    CONV_TR(g_trace_kd, 3);
     // epilogue operands of this thread's items (below): requested now, behind the first batch, consumed after the K loop
     // (range-checked descriptors: a channel beyond Cout reads 0, an absent operand reads its neutral value)
     for (int bt = 0; bt < p.nb; ++bt) {
@@ -215,7 +152,7 @@ __global__ __launch_bounds__(NW * 64) void k_conv_kd(KdP q) {
         } else {
             wait_vmcnt<0>();
         }
-        if (bt == 0) KD_TR(4);
+        if (bt == 0) CONV_TR(g_trace_kd, 4);
         // fragments of step t+1 are requested before the MFMAs of step t issue (two register sets)
         f32x4 af[2][GA], bf[2][GB];
 #pragma unroll
@@ -250,17 +187,17 @@ __global__ __launch_bounds__(NW * 64) void k_conv_kd(KdP q) {
             }
         }
     }
-    KD_TR(5);
+    CONV_TR(g_trace_kd, 5);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();                                              // every wave's ring is dead: the partial tiles take its place
-    KD_TR(6);
+    CONV_TR(g_trace_kd, 6);
 #pragma unroll
     for (int i = 0; i < GA; ++i)
 #pragma unroll
         for (int j = 0; j < GB; ++j)
             *reinterpret_cast<f32x4*>(lds + ((wave * NT) + i * GB + j) * 256 + lane * 4) = NACC == 2 ? acc[0][i][j] + acc[NACC - 1][i][j] : acc[0][i][j];
     __syncthreads();
-    KD_TR(7);
+    CONV_TR(g_trace_kd, 7);
     constexpr int RED_F = NW * NT * 256;
     float* cs = lds + RED_F;
     const __amdgpu_buffer_rsrc_t rsc = make_rsrc(p.scale, p.scale ? p.sc_bytes : 0u), rsh = make_rsrc(p.shift, p.shift ? p.sc_bytes : 0u);
@@ -279,10 +216,7 @@ __global__ __launch_bounds__(NW * 64) void k_conv_kd(KdP q) {
             if (p.scale) e_sc = bload4(rsc, ev);
             if (p.shift) e_sh = bload4(rsh, ev);
             if (p.add) {
-                const int b = fdiv(m, hw, p.inv_hw);
-                const int rr = m - b * hw;
-                const int oy = fdiv(rr, p.Wo, p.inv_wo), ox = rr - oy * p.Wo;
-                const unsigned ai = (unsigned)(((b * p.add_H + (oy >> 1)) * p.add_W + (ox >> 1)) * p.add_ld + p.add_coff + en);
+                const unsigned ai = (unsigned)addend_index(p, pixel_of_row(p, m, hw), en);
                 if (p.sb & 4) {                                   // bf16 addend: four channels = 8 bytes
                     const u32x2 h = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rad, on ? (int)(ai * 2u) : (int)kOOB, 0, 0));
                     e_add = from_bf16x4(__builtin_bit_cast(s16x4, h));
@@ -346,10 +280,10 @@ __global__ __launch_bounds__(NW * 64) void k_conv_kd(KdP q) {
             if (n < p.Cout16) p.colsum[(size_t)bx * p.Cout16 + n] = sacc;
         }
     }
-    KD_TR(8);
+    CONV_TR(g_trace_kd, 8);
 #ifdef ORE_TRACE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    KD_TR(9); KD_TRR(10);
+    CONV_TR(g_trace_kd, 9); CONV_TRR(g_trace_kd, 10);
 #endif
 }
 
@@ -377,34 +311,14 @@ namespace oreconv {
 int launch_kd(const ConvP& p, const ConvPlan& pl, hipStream_t st) {
     const int nw = pl.build[0], sb = pl.build[1];
     const int steps = ceil_div(p.nchunks, nw);
-    const int gx = pl.gx, gy = pl.gy;
-    Lvl L = p.lv[0];
-    int Bimg = p.B;
-    if (p.nlev > 1) { L.H = 1; L.W = p.M; L.Ho = 1; L.Wo = p.M; Bimg = 1; }      // one "image" of M pixels in a row
     KdP q;
-    KdK& k = q.k;
-    k.in = p.in; k.w = p.w; k.scale = p.scale; k.shift = p.shift; k.add = p.add; k.out = p.out; k.colsum = p.colsum;
-    k.in_bytes = (unsigned)(((long long)L.irow0 + (long long)Bimg * L.H * L.W) * p.in_ld * 4);
-    k.w_bytes = (unsigned)((long long)p.Cout16 * p.K * 4);
-    k.sc_bytes = (unsigned)p.Cout * 4u;
-    k.add_bytes = p.add ? (unsigned)((long long)p.B * p.add_H * p.add_W * p.add_ld * ((p.sb & 4) ? 2 : 4)) : 0u;
-    k.sb = p.sb;
-    k.M = p.M; k.K = p.K; k.Cout = p.Cout; k.Cout16 = p.Cout16; k.nchunks = p.nchunks; k.nb = ceil_div(steps, sb);
-    k.irow0 = L.irow0; k.H = L.H; k.W = L.W; k.Ho = L.Ho; k.Wo = L.Wo; k.in_ld = p.in_ld; k.in_coff = p.in_coff; k.stride = p.stride; k.pad = p.pad;
-    k.out_ld = p.out_ld; k.out_coff = p.out_coff; k.relu_cout = p.relu_cout;
-    k.add_H = p.add_H; k.add_W = p.add_W; k.add_ld = p.add_ld; k.add_coff = p.add_coff;
-    k.xmap = pl.xmap; k.gx = gx; k.gy = gy;
-    k.inv_hw = 1.0f / (float)(L.Ho * L.Wo); k.inv_wo = 1.0f / (float)L.Wo; k.inv_gx = 1.0f / (float)gx; k.inv_gy = 1.0f / (float)gy;
-    if (p.kh == 3) {
-        const int cpt = p.Cin >> 4, row_bytes = L.W * p.in_ld * 4, pix_bytes = p.in_ld * 4;
-        for (int c = 0; c < kTab; ++c) {
-            if (c >= p.nchunks) { q.tab[c] = 15u << 28; continue; }
-            const int tap = c / cpt, cc = c - tap * cpt, dy = tap / 3, dx = tap - dy * 3;
-            q.tab[c] = (unsigned)(dy * row_bytes + dx * pix_bytes + cc * 64) | ((unsigned)tap << 28);
-        }
-    }
+    Lvl L;
+    fill_desc_args(q.k, p, pl, L);
+    q.k.nb = ceil_div(steps, sb);
+    q.k.sb = p.sb;
+    build_chunk_table(q.tab, kTab, p, L, kFmt);
     const bool k3 = p.kh == 3;
-    const dim3 grid(gx, gy, 1);
+    const dim3 grid(pl.gx, pl.gy, 1);
 #define KD_GO(bm_, bn_, nw_, sb_) if (pl.bm == bm_ && pl.bn == bn_ && nw == nw_ && sb == sb_) \
         return (p.sb & 1) ? kd_go<bm_ / 16, bn_ / 16, nw_, sb_, true>(q, k3, grid, st) : kd_go<bm_ / 16, bn_ / 16, nw_, sb_, false>(q, k3, grid, st);
     ORE_KD_BUILDS(KD_GO)
@@ -414,9 +328,4 @@ int launch_kd(const ConvP& p, const ConvPlan& pl, hipStream_t st) {
 
 }  // namespace oreconv
 
-#ifdef ORE_TRACE
-extern "C" int ore_debug_set_trace_kd(unsigned long long* buf) {
-    ORE_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_trace_kd), &buf, sizeof(buf)));
-    return ORE_OK;
-}
-#endif
+CONV_TRACE_SETTER(ore_debug_set_trace_kd, g_trace_kd)

@@ -21,7 +21,7 @@
 //
 // Replaces F.conv2d + FrozenBatchNorm2d + ReLU / bias of d2z:modeling/backbone/vovnet.py:205-219,310-332, fpn.py:113-154,
 // ref:fewx/modeling/fsod/fsod_cen.py:470 (conv3), fsod_roi_heads.py:500-520 (composed DSA + fc1).
-#include "ore_conv_internal.h"
+#include "ore_conv_desc.h"
 
 namespace {
 using namespace oreconv;
@@ -42,19 +42,7 @@ __device__ unsigned long long* g_trace_kw = nullptr;
 #define KW_TRR(i) do { } while (0)
 #endif
 
-__device__ __forceinline__ void decode_row(const ConvP& p, int m, int& lvl, int& b, int& oy, int& ox) {
-    lvl = 0;
-#pragma unroll
-    for (int l = 1; l < 4; ++l)
-        if (l < p.nlev && m >= p.lv[l].orow0) lvl = l;
-    const Lvl& L = p.lv[lvl];
-    const int r = m - L.orow0, hw = L.Ho * L.Wo;
-    b = r / hw;
-    const int q = r - b * hw;
-    oy = q / L.Wo;
-    ox = q - oy * L.Wo;
-}
-
+// (differs from the epilogue_one of ore_conv.hip in the bf16 addend, p.sb & 4)
 __device__ __forceinline__ float epilogue_one(const ConvP& p, float acc, int m, int n) {
     float v = acc;
     int lvl = 0, b = 0, oy = 0, ox = 0;
@@ -106,15 +94,6 @@ __device__ __forceinline__ bool finish4(const ConvP& p, f32x4 a, int m, int n, b
     vout = v;
     return true;
 }
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N >= 0 && N <= 63, "vmcnt immediate");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// XOR swizzle of the four 16-byte quads of a 64-byte row inside a 16-row group: with q' = q ^ SW[(r >> 2) & 3] every ds_read_b128
-// lane group (rows {0-3, 12-15} of quad q with rows 4-11 of quad q+1, and its mirror) touches 16 distinct 4-bank groups.
-__device__ __forceinline__ int swz(int r16) { return (0x1320 >> (((r16 >> 2) & 3) * 4)) & 3; }   // {0, 2, 3, 1}
 
 // SB: bf16 STORAGE build -- the tensors are bf16 in HBM and in LDS, the host passes the input-side sizes in 4-byte units (pairs of
 // channels), so the whole staging path below is byte-identical to the fp32 build: a K chunk is 64 bytes = 32 channels, a ds_read_b128

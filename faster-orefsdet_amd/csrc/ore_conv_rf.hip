@@ -10,11 +10,10 @@
 //   * a wave's WHOLE K slice is requested up front -- MAXS steps x (1 + GB) `buffer_load_dwordx4`, each lane fetching exactly the
 //     4 consecutive k of the MFMA fragment it will multiply (pixel / weight row = lane & 15, k quad = lane >> 4) -- and lands in
 //     VGPRs; the K loop is then MFMAs behind counted waits, one memory latency for the whole slice instead of one per step;
-//   * no LDS on the way in, no swizzle, no ring pointers: out-of-image taps, rows beyond M / Cout and chunks beyond K are the buffer
-//     descriptor's out-of-range zeros (voffset forced past num_records), so the issue loop has no branches;
+//   * no LDS on the way in, no swizzle, no ring pointers; the loads go through the descriptor addressing of ore_conv_desc.h (this
+//     kernel was its first user), so the issue loop has no branches;
 //   * the weight requests depend on nothing but the block's coordinates: they are issued before the row decode, whose latency they
-//     cover; the decode itself uses float reciprocals instead of integer divisions; the epilogue operands (scale / shift, the FPN
-//     top-down addend) are requested in the prologue too;
+//     cover; the epilogue operands (scale / shift, the FPN top-down addend) are requested in the prologue too;
 //   * K is split over the NW = 4 / 8 / 16 waves of the block (wave w owns a CONTIGUOUS range of 16-channel chunks, so its walk over
 //     (tap, chunk) is one scalar add per step), partial tiles meet in LDS as in k_conv_kw; slices longer than MAXS steps run as
 //     several batches.
@@ -23,43 +22,15 @@
 //
 // Replaces F.conv2d + FrozenBatchNorm2d + ReLU / bias of d2z:modeling/backbone/vovnet.py:205-219,310-332 (stages 4-5), fpn.py:126-145
 // (laterals 4-5), ref:fewx/modeling/fsod/fsod_roi_heads.py:500-520 (composed DSA + fc1) at batch 1.
-#include "ore_conv_internal.h"
+#include "ore_conv_desc.h"
 
 namespace {
 using namespace oreconv;
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-#ifdef ORE_TRACE
-__device__ unsigned long long* g_trace_rf = nullptr;
-#define RF_TR(i) do { if (g_trace_rf && threadIdx.x == 0) g_trace_rf[(size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#define RF_TRR(i) do { if (g_trace_rf && threadIdx.x == 0) g_trace_rf[(size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 16 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define RF_TR(i) do { } while (0)
-#define RF_TRR(i) do { } while (0)
-#endif
-
+CONV_TRACE_SYMBOL(g_trace_rf)
 constexpr int kTab = kRfTab;                      // chunk table entries (3x3 layers)
+constexpr ChunkFmt kFmt = kChunkTapLow;
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ f32x4 bload(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
-}
-// n / d for 0 <= n < 2^22, d > 0, with inv = 1.0f / d: one multiply, one conversion and two corrections instead of ~40 instructions
-__device__ __forceinline__ int fdiv(int n, int d, float inv) {
-    int q = (int)((float)n * inv);
-    int r = n - q * d;
-    q += r >= d ? 1 : 0;
-    r -= r >= d ? d : 0;
-    q -= r < 0 ? 1 : 0;
-    return q;
-}
-
-// Kernel arguments: every scalar the kernel needs, compact and in ONE place, so that they arrive with a handful of wide scalar loads
-// issued together at the top (hipcc otherwise fetches the fields of a big by-value struct one `s_load` + `s_waitcnt lgkmcnt(0)` at a
-// time, next to their first use: fourteen serial round trips = most of the 2300-4600 clocks of prologue the traces show).
 struct RfK {
     const float* in; const float* w; const float* scale; const float* shift; const float* add; float* out; float* colsum;
     unsigned in_bytes, w_bytes, sc_bytes, add_bytes;      // num_records of the buffer descriptors
@@ -71,29 +42,13 @@ struct RfK {
 };
 struct RfP {
     RfK k;
-    // 3x3 layers: per 16-channel chunk c of the K axis, (byte offset of its (tap, channel chunk) from the window's first pixel) | tap
-    // -- the offset is a multiple of 64, the tap index 0..8 rides in the low bits; chunks beyond K carry tap 15 (never valid).  Built
-    // on the host per launch and passed BY VALUE (kernel argument segment -> scalar loads): the issue loop of a wave then has no
-    // tap arithmetic at all.
-    unsigned tab[kTab];
+    unsigned tab[kTab];      // 3x3: the chunk table, format kFmt
 };
-
-// which tile does this block compute (tile_of_block of ore_conv_internal.h, with host-made reciprocals instead of integer divisions)
-__device__ __forceinline__ void rf_tile(const RfK& k, int& bx, int& by) {
-    bx = blockIdx.x; by = blockIdx.y;
-    if (k.xmap == 0) return;
-    const int T = k.gx * k.gy;
-    const int lin = by * k.gx + bx, r = lin & 7, kk = lin >> 3;
-    const int qd = T >> 3, rem = T & 7;
-    const int t = r * qd + min(r, rem) + kk;
-    if (k.xmap == 1) { bx = fdiv(t, k.gy, k.inv_gy); by = t - bx * k.gy; }
-    else { by = fdiv(t, k.gx, k.inv_gx); bx = t - by * k.gx; }
-}
 
 template <int GB, int NW, int MAXS, int KS>
 __global__ __launch_bounds__(NW * 64) void k_conv_rf(RfP q) {
     extern __shared__ __attribute__((aligned(16))) float lds[];      // [NW][GB][64 lanes][4] partial tiles
-    RF_TR(0); RF_TRR(1);
+    CONV_TR(g_trace_rf, 0); CONV_TRR(g_trace_rf, 1);
     RfK p = q.k;
     // all scalar arguments are wanted HERE: one batch of scalar loads, one wait
     asm volatile("" :: "s"(p.in), "s"(p.w), "s"(p.scale), "s"(p.shift), "s"(p.add), "s"(p.out), "s"(p.colsum), "s"(p.in_bytes), "s"(p.w_bytes),
@@ -104,16 +59,11 @@ __global__ __launch_bounds__(NW * 64) void k_conv_rf(RfP q) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int bx, by;
-    rf_tile(p, bx, by);
+    tile_of_block_rcp(p, bx, by);
     const int m0 = bx * 16, n0 = by * (16 * GB);
     const int r16 = lane & 15, kq = lane >> 4;
-    const int row_bytes = p.W * p.in_ld * 4, pix_bytes = p.in_ld * 4;
-    // The pixel descriptor starts `bias` bytes BEFORE the tensor, so that the per-lane offset of the window's first pixel (which lies
-    // above / left of the image for border rows) is never negative; a valid tap's soffset brings the address back inside the tensor,
-    // an invalid tap never leaves the range check (the hardware checks voffset + instruction offset, soffset is added behind it).
-    const int bias = p.pad * (row_bytes + pix_bytes);
-    const __amdgpu_buffer_rsrc_t rw = make_rsrc(p.w, p.w_bytes);
-    const __amdgpu_buffer_rsrc_t ri = make_rsrc(reinterpret_cast<const char*>(p.in) - bias, p.in_bytes + (unsigned)bias);
+    const int bias = window_bias(p);
+    const __amdgpu_buffer_rsrc_t rw = make_rsrc(p.w, p.w_bytes), ri = make_pixel_rsrc(p, bias);
 
     // ---- weight side first: needs only the block's coordinates, and its requests cover the latency of everything below
     unsigned b_off[GB];
@@ -138,24 +88,12 @@ __global__ __launch_bounds__(NW * 64) void k_conv_rf(RfP q) {
     // ---- pixel side: ONE row per lane (r16), decoded with float reciprocals
     const int m = m0 + r16;
     const int hw = p.Ho * p.Wo;
-    int b = 0, oy = 0, ox = 0;
+    Pixel px = {0, 0, 0};
     unsigned tapmask = 0u;                                           // bit dy * KS + dx: that tap of this lane's window lies inside the image
     unsigned a_voff = kOOB;                                          // bias + byte offset of the window's first pixel, channel in_coff + kq * 4
     if (m < p.M) {
-        b = fdiv(m, hw, p.inv_hw);
-        const int rr = m - b * hw;
-        oy = fdiv(rr, p.Wo, p.inv_wo);
-        ox = rr - oy * p.Wo;
-        const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
-        unsigned rmask = 0u, cmask = 0u;
-#pragma unroll
-        for (int d = 0; d < KS; ++d) {
-            rmask |= (unsigned)(iy0 + d) < (unsigned)p.H ? 1u << d : 0u;
-            cmask |= (unsigned)(ix0 + d) < (unsigned)p.W ? 1u << d : 0u;
-        }
-#pragma unroll
-        for (int d = 0; d < KS; ++d) tapmask |= ((rmask >> d) & 1u) ? cmask << (d * KS) : 0u;
-        a_voff = (unsigned)(bias + (((p.irow0 + b * p.H * p.W) + iy0 * p.W + ix0) * p.in_ld + p.in_coff + kq * 4) * 4);
+        px = pixel_of_row(p, m, hw);
+        CONV_WINDOW_OF_PIXEL(KS, p, px, kq, bias, tapmask, a_voff);
     }
     // epilogue operands of the lanes that will finish a tile (waves 0 .. GB-1: tile j2 = wave, pixel r16, channel quad kq): requested
     // through range-checked descriptors (a channel beyond Cout reads 0), behind the main loads -- no branch, no wait of their own
@@ -164,13 +102,13 @@ __global__ __launch_bounds__(NW * 64) void k_conv_rf(RfP q) {
     const __amdgpu_buffer_rsrc_t rsc = make_rsrc(p.scale, p.scale ? p.sc_bytes : 0u), rsh = make_rsrc(p.shift, p.shift ? p.sc_bytes : 0u);
     const __amdgpu_buffer_rsrc_t rad = make_rsrc(p.add, p.add ? p.add_bytes : 0u);
     const unsigned e_voff = e_on ? (unsigned)(en * 4) : kOOB;
-    const unsigned e_aoff = e_on ? (unsigned)((((b * p.add_H + (oy >> 1)) * p.add_W + (ox >> 1)) * p.add_ld + p.add_coff + en) * 4) : kOOB;
+    const unsigned e_aoff = e_on ? (unsigned)(addend_index(p, px, en) * 4) : kOOB;
 
     f32x4 acc[2][GB];                                                // even / odd steps: two independent accumulation chains
 #pragma unroll
     for (int j = 0; j < GB; ++j) acc[0][j] = acc[1][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     f32x4 e_sc = {1.f, 1.f, 1.f, 1.f}, e_sh = {0.f, 0.f, 0.f, 0.f}, e_add = {0.f, 0.f, 0.f, 0.f};
-    RF_TR(2);
+    CONV_TR(g_trace_rf, 2);
     for (int bt = 0; bt < p.nb; ++bt) {
         // ---- request the batch.  Weights (the first batch's are in flight already): one scalar base per batch, the step is an
         // instruction offset (t * 64 bytes) -- no per-step instruction besides the load.  Pixels: 1x1 layers the same (+ a select that
@@ -189,8 +127,8 @@ __global__ __launch_bounds__(NW * 64) void k_conv_rf(RfP q) {
                 af[t] = bload(ri, (live ? a_voff : kOOB) + (unsigned)(t * 64), s_b);
             } else {
                 const unsigned e = q.tab[w_c + t];
-                const bool ok = (tapmask & (1u << (e & 15u))) != 0u;
-                af[t] = bload(ri, ok ? a_voff : kOOB, e & ~63u);
+                const bool ok = (tapmask & (1u << chunk_tap(kFmt, e))) != 0u;
+                af[t] = bload(ri, ok ? a_voff : kOOB, chunk_off(kFmt, e));
             }
         }
         w_c += MAXS;
@@ -200,7 +138,7 @@ __global__ __launch_bounds__(NW * 64) void k_conv_rf(RfP q) {
             if (p.add) e_add = bload(rad, e_aoff, 0u);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (bt == 0) RF_TR(3);
+        if (bt == 0) CONV_TR(g_trace_rf, 3);
         // ---- multiply as the fragments land (the compiler counts the waits: loads return in order)
 #pragma unroll
         for (int t = 0; t < MAXS; ++t) {
@@ -209,17 +147,17 @@ __global__ __launch_bounds__(NW * 64) void k_conv_rf(RfP q) {
 #pragma unroll
                 for (int j = 0; j < GB; ++j)
                     acc[t & 1][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(bf[t][j][tt], af[t][tt], acc[t & 1][j], 0, 0, 0);   // D^T: lane = pixel
-            if (bt == 0 && t == 0) RF_TR(4);
+            if (bt == 0 && t == 0) CONV_TR(g_trace_rf, 4);
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    RF_TR(5);
+    CONV_TR(g_trace_rf, 5);
 
     // ---- the NW partial tiles meet in LDS; waves 0 .. GB-1 finish one 16x16 tile each
 #pragma unroll
     for (int j = 0; j < GB; ++j) *reinterpret_cast<f32x4*>(lds + ((wave * GB) + j) * 256 + lane * 4) = acc[0][j] + acc[1][j];
     __syncthreads();
-    RF_TR(6);
+    CONV_TR(g_trace_rf, 6);
     if (wave < GB) {
         f32x4 a = *reinterpret_cast<const f32x4*>(lds + (0 * GB + wave) * 256 + lane * 4);
 #pragma unroll
@@ -257,10 +195,10 @@ __global__ __launch_bounds__(NW * 64) void k_conv_rf(RfP q) {
             }
         }
     }
-    RF_TR(8);
+    CONV_TR(g_trace_rf, 8);
 #ifdef ORE_TRACE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    RF_TR(9); RF_TRR(10);
+    CONV_TR(g_trace_rf, 9); CONV_TRR(g_trace_rf, 10);
 #endif
 }
 
@@ -280,31 +218,13 @@ namespace oreconv {
 int launch_rf(const ConvP& p, const ConvPlan& pl, hipStream_t st) {
     const int gb = pl.build[0], nw = pl.build[1], maxs = pl.build[2];
     const int steps = ceil_div(p.nchunks, nw);
-    const int gx = pl.gx, gy = pl.gy;
-    const Lvl& L = p.lv[0];
     RfP q;
-    RfK& k = q.k;
-    k.in = p.in; k.w = p.w; k.scale = p.scale; k.shift = p.shift; k.add = p.add; k.out = p.out; k.colsum = p.colsum;
-    k.in_bytes = (unsigned)(((long long)L.irow0 + (long long)p.B * L.H * L.W) * p.in_ld * 4);
-    k.w_bytes = (unsigned)((long long)p.Cout16 * p.K * 4);
-    k.sc_bytes = (unsigned)p.Cout * 4u;
-    k.add_bytes = p.add ? (unsigned)((long long)p.B * p.add_H * p.add_W * p.add_ld * 4) : 0u;
-    k.M = p.M; k.K = p.K; k.Cout = p.Cout; k.Cout16 = p.Cout16; k.nchunks = p.nchunks; k.nb = ceil_div(steps, maxs);
-    k.irow0 = L.irow0; k.H = L.H; k.W = L.W; k.Ho = L.Ho; k.Wo = L.Wo; k.in_ld = p.in_ld; k.in_coff = p.in_coff; k.stride = p.stride; k.pad = p.pad;
-    k.out_ld = p.out_ld; k.out_coff = p.out_coff; k.relu_cout = p.relu_cout;
-    k.add_H = p.add_H; k.add_W = p.add_W; k.add_ld = p.add_ld; k.add_coff = p.add_coff;
-    k.xmap = pl.xmap; k.gx = gx; k.gy = gy;
-    k.inv_hw = 1.0f / (float)(L.Ho * L.Wo); k.inv_wo = 1.0f / (float)L.Wo; k.inv_gx = 1.0f / (float)gx; k.inv_gy = 1.0f / (float)gy;
-    if (p.kh == 3) {                                                  // the chunk table of a 3x3 layer (see RfP)
-        const int cpt = p.Cin >> 4, row_bytes = L.W * p.in_ld * 4, pix_bytes = p.in_ld * 4;
-        for (int c = 0; c < kTab; ++c) {
-            if (c >= p.nchunks) { q.tab[c] = 15u; continue; }
-            const int tap = c / cpt, cc = c - tap * cpt, dy = tap / 3, dx = tap - dy * 3;
-            q.tab[c] = (unsigned)(dy * row_bytes + dx * pix_bytes + cc * 64) | (unsigned)tap;
-        }
-    }
+    Lvl L;
+    fill_desc_args(q.k, p, pl, L);
+    q.k.nb = ceil_div(steps, maxs);
+    build_chunk_table(q.tab, kTab, p, L, kFmt);
     const bool k3 = p.kh == 3;
-    const dim3 grid(gx, gy, 1);
+    const dim3 grid(pl.gx, pl.gy, 1);
 #define RF_GO(g, w, s) if (gb == g && nw == w && maxs == s) return rf_go<g, w, s>(q, k3, grid, st);
     ORE_RF_BUILDS(RF_GO)
 #undef RF_GO
@@ -313,9 +233,4 @@ int launch_rf(const ConvP& p, const ConvPlan& pl, hipStream_t st) {
 
 }  // namespace oreconv
 
-#ifdef ORE_TRACE
-extern "C" int ore_debug_set_trace_rf(unsigned long long* buf) {
-    ORE_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_trace_rf), &buf, sizeof(buf)));
-    return ORE_OK;
-}
-#endif
+CONV_TRACE_SETTER(ore_debug_set_trace_rf, g_trace_rf)

@@ -28,23 +28,6 @@ extern "C" int ore_debug_set_trace_roi(unsigned long long* buf) {
 
 namespace {
 
-__device__ __forceinline__ float ore_expf(float x) {
-    if (x > 88.0f) x = 88.0f;
-    if (x < -87.0f) x = -87.0f;
-    const float n = rintf(x * 1.44269504088896341f);
-    float r = fmaf(n, -0.693359375f, x);
-    r = fmaf(n, 2.12194440e-4f, r);
-    float p = 1.9875691500e-4f;
-    p = fmaf(p, r, 1.3981999507e-3f);
-    p = fmaf(p, r, 8.3334519073e-3f);
-    p = fmaf(p, r, 4.1665795894e-2f);
-    p = fmaf(p, r, 1.6666665459e-1f);
-    p = fmaf(p, r, 5.0000001201e-1f);
-    const float e = fmaf(p, r * r, r) + 1.0f;
-    const int ni = (int)n;
-    return e * __uint_as_float((unsigned)(ni + 127) << 23);
-}
-
 struct RoiP {
     const void* feat[4]; int ld[4], coff[4], H[4], W[4]; float scale[4];
     int n_levels, min_level, C, pooled;

@@ -1,0 +1,116 @@
+"""Detection demo: run the detector of a config on image files and save the annotated pictures; the command line of ref:demo.py.
+
+    python demo.py --input a.jpg b.jpg --output out_dir --opts MODEL.WEIGHTS w.pth
+
+Images are decoded with Pillow and drawn on the device.  Video (--video-input, --webcam) needs OpenCV to decode and to show frames;
+this package neither ships nor requires it, and the two flags say so when it is missing."""
+import argparse
+import glob
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+DEFAULT_CONFIG = os.path.join(HERE, "configs", "fsod", "finetune_vovnet.yaml")
+
+
+def get_parser():
+    parser = argparse.ArgumentParser(description="Draw the few-shot detector's boxes, class names and scores on images (on the GPU).")
+    parser.add_argument("--config-file", default=DEFAULT_CONFIG, metavar="FILE", help="the model's yaml config (default: %(default)s)")
+    parser.add_argument("--input", nargs="+", metavar="IMAGE", help="image files, or one quoted glob pattern")
+    parser.add_argument("--output", metavar="PATH", help="where the pictures go: a directory, or a file name when there is one input")
+    parser.add_argument("--confidence-threshold", type=float, default=0.9, metavar="T", help="detections scoring below T are not drawn (default: %(default)s)")
+    parser.add_argument("--video-input", metavar="VIDEO", help="annotate a video file instead (needs OpenCV)")
+    parser.add_argument("--webcam", action="store_true", help="annotate the first camera's frames instead (needs OpenCV)")
+    parser.add_argument("--opts", nargs=argparse.REMAINDER, default=[], metavar="KEY VALUE", help="config overrides, e.g. MODEL.WEIGHTS model.pth; must come last")
+    return parser
+
+
+def setup_cfg(args):
+    """The frozen config of the run.  The second stage's score threshold is the one knob this detector reads at test time."""
+    from fewx.config import get_cfg
+    cfg = get_cfg()
+    cfg.merge_from_file(args.config_file)
+    cfg.merge_from_list(list(args.opts))
+    cfg.MODEL.ROI_HEADS.SCORE_THRESH_TEST = float(args.confidence_threshold)
+    cfg.freeze()
+    return cfg
+
+
+def input_paths(patterns):
+    """The image paths of --input: several names are taken as they are, a single one may be a glob pattern."""
+    if len(patterns) > 1:
+        return list(patterns)
+    found = sorted(glob.glob(os.path.expanduser(patterns[0])))
+    if not found:
+        sys.exit(f"demo.py: no file matches {patterns[0]!r}")
+    return found
+
+
+def output_path(output, image_path, n_inputs):
+    if os.path.isdir(output):
+        return os.path.join(output, os.path.basename(image_path))
+    if n_inputs > 1:
+        sys.exit(f"demo.py: {n_inputs} inputs need a directory as --output, and {output!r} is not one")
+    return output
+
+
+def run_images(demo, args, log):
+    from detectron2.data.detection_utils import read_image
+    paths = input_paths(args.input)
+    for path in paths:
+        target = output_path(args.output, path, len(paths))
+        predictions, picture = demo.run_on_image(read_image(path, format="BGR"))
+        picture.save(target)
+        log.info("%s: %d detections -> %s", path, len(predictions["instances"]), target)
+
+
+def run_video(demo, args, cv2):
+    capture = cv2.VideoCapture(0 if args.webcam else args.video_input)
+    writer = None
+    try:
+        for frame in demo.run_on_video(capture):
+            if args.output:
+                if writer is None:
+                    rate = capture.get(cv2.CAP_PROP_FPS) or 30.0
+                    writer = cv2.VideoWriter(args.output, cv2.VideoWriter_fourcc(*"mp4v"), float(rate), (frame.shape[1], frame.shape[0]), True)
+                writer.write(frame)
+            else:
+                cv2.imshow("detections", frame)
+                if cv2.waitKey(1) == 27:                      # Esc ends the show
+                    break
+    finally:
+        capture.release()
+        if writer is not None:
+            writer.release()
+
+
+def main(argv=None):
+    args = get_parser().parse_args(argv)
+    video = args.webcam or bool(args.video_input)
+    cv2 = None
+    if video:
+        if args.input:
+            sys.exit("demo.py: --input and a video source exclude each other")
+        try:
+            import cv2
+        except ImportError:
+            flag = "--webcam" if args.webcam else "--video-input"
+            sys.exit(f"demo.py: {flag} needs OpenCV (the cv2 module) to decode and show video, and it is not installed. "
+                     "Annotate image files with --input, or hand your own frames to predictor.VisualizationDemo.run_on_video.")
+    elif not args.input:
+        sys.exit("demo.py: nothing to do; name images with --input (or a video with --video-input / --webcam)")
+    elif not args.output:
+        sys.exit("demo.py: --input needs --output: pictures are written to files, there is no window to show them in")
+
+    from detectron2.utils.logger import setup_logger
+    from predictor import VisualizationDemo
+    log = setup_logger()
+    demo = VisualizationDemo(setup_cfg(args))
+    if video:
+        run_video(demo, args, cv2)
+    else:
+        run_images(demo, args, log)
+
+
+if __name__ == "__main__":
+    main()

@@ -16,10 +16,8 @@ import torch
 
 def _pil_read_image(path, format="BGR"):
     """detectron2.data.detection_utils.read_image for RGB / BGR (d2z:data/detection_utils.py): HxWx3 uint8."""
-    from PIL import Image
-    with open(path, "rb") as f:
-        img = np.asarray(Image.open(f).convert("RGB"))
-    return np.ascontiguousarray(img[:, :, ::-1]) if format == "BGR" else img
+    from detectron2.data.detection_utils import read_image
+    return read_image(path, "BGR" if format == "BGR" else "RGB")
 
 
 class DatasetMapperWithSupport:

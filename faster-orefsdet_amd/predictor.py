@@ -1,0 +1,274 @@
+"""The demo's predictors (ref:predictor.py): VisualizationDemo draws a detector's boxes on images and video frames, AsyncPredictor keeps
+several frames in flight.  Drawing is the package's device overlay (orehip.overlay_draw, render contract "overlay v1"), not matplotlib;
+AsyncPredictor is one process with several engines on several HIP streams, not one process per GPU."""
+from collections import deque
+
+import numpy as np
+import torch
+
+from detectron2.data import MetadataCatalog
+from detectron2.engine.defaults import DefaultPredictor
+from detectron2.utils.video_visualizer import VideoVisualizer
+from detectron2.utils.visualizer import ColorMode, VisImage, Visualizer, default_overlay_params, thing_classes
+
+__all__ = ["AsyncPredictor", "VisualizationDemo"]
+
+
+class _Slot:
+    """One frame's worth of machinery: an engine, its stream, a pinned staging buffer, the event behind the frame's last kernel."""
+    __slots__ = ("engine", "stream", "stage", "event", "count")
+
+
+class _Pass:
+    """A frame between `put` and `get`."""
+    __slots__ = ("slot", "rec", "raw", "vis", "hw")
+
+
+class AsyncPredictor:
+    """A predictor that runs frames asynchronously: `put(image)` enqueues one BGR frame ([h, w, 3] uint8: numpy array, CPU tensor or
+    device tensor), `get()` returns the oldest frame's {"instances": Instances} -- results come back in `put` order.  `predictor(image)`
+    is put + get.  One process, no workers and no threads: `inflight` engines (model.make_engine()), each with its own HIP stream,
+    pinned staging buffer and result record.  `put` enqueues upload, device resize and the detection pass on the next slot's stream and
+    returns; when every slot is busy it first completes the oldest pass.  `get` performs the frame's one host wait.
+
+    put(image, draw=True) -- or draw={overlay_draw keyword arguments} -- also enqueues the detection overlay behind the pass, on the
+    same stream, reading the pass's record and its device-side count: the result then carries "vis_image", the annotated frame on the
+    device in the input's channel order (BGR), still with one host wait per frame.
+
+    1 <= inflight <= 4: a process opens 4 hardware queues by default, and this class does not ask for more.  num_gpus must be 1: one
+    process per device is a launcher's job.  The engines are keyed like model.engine(): a `put` that finds the weights or the support
+    set changed completes what is pending, then rebuilds them."""
+
+    MAX_INFLIGHT = 4
+
+    def __init__(self, cfg, num_gpus: int = 1, inflight: int = 4):
+        if num_gpus != 1:
+            raise ValueError(f"AsyncPredictor: num_gpus {num_gpus}: one process drives one device (start one process per GPU)")
+        if not isinstance(inflight, int) or not 1 <= inflight <= self.MAX_INFLIGHT:
+            raise ValueError(f"AsyncPredictor: inflight {inflight} outside 1 .. {self.MAX_INFLIGHT} (the hardware queues of one process)")
+        self.inflight = inflight
+        self.predictor = DefaultPredictor(cfg)            # the one-image predictor over the same model
+        self.cfg, self.model = self.predictor.cfg, self.predictor.model
+        self.metadata = getattr(self.predictor, "metadata", None)
+        self.input_format = self.predictor.input_format
+        self._slots, self._key = [], None
+        self._pending, self._done = deque(), deque()
+        self._next = 0
+
+    # ---- engines ------------------------------------------------------------------------------------------------
+    def _close_engines(self):
+        for s in self._slots:
+            s.engine.close()
+        self._slots, self._key = [], None
+
+    def _ensure_engines(self):
+        m = self.model
+        m.init_model()
+        key = m._engine_key_now()
+        if self._key == key and self._slots:
+            return
+        while self._pending:                                  # passes of the old engines finish on the old engines
+            self._done.append(self._complete(self._pending.popleft()))
+        self._close_engines()
+        dev = m.device
+        with torch.cuda.device(dev):
+            for _ in range(self.inflight):
+                s = _Slot()
+                s.engine = m.make_engine(classes=key[3])
+                if not getattr(s.engine, "has_roi", False):
+                    s.engine.close()
+                    self._close_engines()
+                    raise ValueError("AsyncPredictor needs the second stage inside the engine (a support set with rcnn_8 features)")
+                s.stream = torch.cuda.Stream(device=dev)
+                s.stage, s.event = None, torch.cuda.Event()
+                s.count = s.engine.buffer("final_count").view(torch.int32).reshape(-1)[:1]
+                self._slots.append(s)
+        self._key, self._next = key, 0
+
+    # ---- put / get ----------------------------------------------------------------------------------------------
+    DRAW_KEYS = ("score_thresh", "line_width", "text_scale", "edge_alpha", "label_alpha", "palette", "color_by", "names")
+
+    def _draw_args(self, draw, h, w):
+        """The overlay's keyword arguments of one frame, checked here, before anything of the frame is enqueued: what can be
+        refused on the host is refused while the slot's engine is still idle."""
+        import orehip
+        kw = dict(default_overlay_params(h, w), names=thing_classes(self.metadata), color_by="instance",
+                  palette=np.ascontiguousarray(orehip.OVERLAY_PALETTE[:, ::-1]))           # the frame is BGR
+        if isinstance(draw, dict):
+            unknown = sorted(set(draw) - set(self.DRAW_KEYS))
+            if unknown:
+                raise ValueError(f"AsyncPredictor.put: draw takes {', '.join(self.DRAW_KEYS)}; not {', '.join(map(str, unknown))}")
+            kw.update(draw)
+        elif draw is not True:
+            raise ValueError("AsyncPredictor.put: draw is True or a dict of overlay_draw keyword arguments")
+        if not (1 <= int(kw["line_width"]) <= 16 and 0 <= int(kw["text_scale"]) <= 8 and 0 <= int(kw.get("edge_alpha", 0)) <= 255
+                and 0 <= int(kw.get("label_alpha", 0)) <= 255):
+            raise ValueError("AsyncPredictor.put: line_width 1 .. 16, text_scale 0 .. 8, alphas 0 .. 255")
+        kw["palette"] = orehip._overlay_palette(kw["palette"])
+        orehip._overlay_color_by(kw["color_by"])
+        return kw
+
+    @torch.no_grad()
+    def put(self, image, draw=None):
+        import orehip
+        if isinstance(image, np.ndarray):
+            image = torch.from_numpy(np.ascontiguousarray(image))
+        if not torch.is_tensor(image) or image.dim() != 3 or image.shape[2] != 3 or image.dtype != torch.uint8:
+            raise ValueError("AsyncPredictor.put takes an [h, w, 3] uint8 BGR image")
+        h, w = int(image.shape[0]), int(image.shape[1])
+        try:
+            draw_kw = self._draw_args(draw, h, w) if draw else None
+        except orehip.OreError as err:
+            raise ValueError(f"AsyncPredictor.put: {err}") from err
+        self._ensure_engines()
+        if len(self._pending) == len(self._slots):
+            self._done.append(self._complete(self._pending.popleft()))
+        slot = self._slots[self._next]                        # completion is first in, first out: the next slot in turn is free
+        m, e = self.model, slot.engine
+        p = _Pass()
+        p.slot, p.hw, p.vis = slot, (h, w), None
+        if image.is_cuda:                                     # the frame was produced on the caller's stream: the slot's stream follows it
+            slot.stream.wait_stream(torch.cuda.current_stream(image.device))
+        with torch.cuda.device(m.device), torch.cuda.stream(slot.stream):
+            if image.is_cuda:
+                raw = image.to(m.device).contiguous()
+                ours = raw.data_ptr() != image.data_ptr()
+                if not ours:
+                    image.record_stream(slot.stream)
+            else:
+                n = h * w * 3
+                if slot.stage is None or slot.stage.numel() < n:
+                    slot.stage = torch.empty(max(n, 1 << 20), dtype=torch.uint8, pin_memory=True)
+                stage = slot.stage[:n].view(h, w, 3)
+                stage.copy_(image)                            # the slot's previous upload finished with its pass
+                raw, ours = torch.empty(h, w, 3, dtype=torch.uint8, device=m.device), True
+                raw.copy_(stage, non_blocking=True)
+            nh, nw = orehip.resize_shortest_edge_shape(h, w, m._test_size[0], m._test_size[1])
+            img = orehip.resize_bilinear_u8(raw, nh, nw, swap_rb=self.input_format == "RGB")
+            p.rec = e.detect_classes_begin(img, h, w) if getattr(e, "class_ids", None) else e.detect_begin(img, h, w)
+            p.raw = raw
+            if draw_kw is not None:
+                R = e._rec_rows
+                boxes, scores, classes = orehip.record_views(p.rec, R, R)
+                try:                                          # in place on the slot's own upload; a caller's device frame is left as it was
+                    p.vis = orehip.overlay_draw(raw, boxes, scores, classes, slot.count, out=raw if ours else None, **draw_kw)
+                except BaseException:
+                    e.detect_end(p.rec)                       # the pass has begun: end it, so that the engine is free for the next put
+                    raise
+            slot.event.record(slot.stream)
+        self._pending.append(p)
+        self._next = (self._next + 1) % len(self._slots)      # only now: a put that raised leaves its slot the next in turn
+
+    def _complete(self, p):
+        """The one host wait of a frame -- the event behind its last kernel -- then the record is cut at the count."""
+        from detectron2.structures import Boxes, Instances
+        slot = p.slot
+        p.slot.event.synchronize()
+        with torch.cuda.device(self.model.device), torch.cuda.stream(slot.stream):
+            boxes, scores, classes = slot.engine.detect_end(p.rec)      # the count word is there: no second wait
+        cur = torch.cuda.current_stream(self.model.device)
+        p.rec.record_stream(cur)                              # allocated on the slot's stream, used from here on on the caller's
+        res = Instances(p.hw)
+        res.pred_boxes = Boxes(boxes)
+        res.scores = scores
+        res.pred_classes = classes
+        out = {"instances": res}
+        if p.vis is not None:
+            p.vis.record_stream(cur)
+            out["vis_image"] = p.vis
+        return out
+
+    def get(self):
+        if self._done:
+            return self._done.popleft()
+        if not self._pending:
+            raise IndexError("AsyncPredictor.get: nothing was put")
+        return self._complete(self._pending.popleft())
+
+    def __len__(self):
+        return len(self._pending) + len(self._done)
+
+    def __call__(self, image):
+        self.put(image)
+        return self.get()
+
+    def shutdown(self):
+        while self._pending:
+            self._complete(self._pending.popleft())
+        self._done.clear()
+        self._close_engines()
+
+    @property
+    def default_buffer_size(self):
+        return self.inflight
+
+
+class VisualizationDemo:
+    """VisualizationDemo(cfg, instance_mode=ColorMode.IMAGE, parallel=False) (ref:predictor.py): run_on_image(bgr) -> (predictions,
+    VisImage); run_on_video(frames) -> annotated BGR frames.  parallel=True predicts through an AsyncPredictor, which also draws."""
+
+    def __init__(self, cfg, instance_mode=ColorMode.IMAGE, parallel=False):
+        if instance_mode not in (ColorMode.IMAGE, ColorMode.SEGMENTATION):
+            raise NotImplementedError(f"VisualizationDemo: {instance_mode} needs instance masks; boxes only")
+        self.instance_mode, self.parallel = instance_mode, bool(parallel)
+        self.predictor = AsyncPredictor(cfg) if self.parallel else DefaultPredictor(cfg)
+        # the class names drawn into the labels: those of the first test dataset, as the predictor itself resolves them
+        self.metadata = getattr(self.predictor, "metadata", None)
+        if self.metadata is None:
+            self.metadata = MetadataCatalog.get("demo")
+
+    def _upload(self, image):
+        """The BGR frame on the model's device, once: the detector and the overlay both read it there."""
+        import orehip
+        if isinstance(image, np.ndarray):
+            image = torch.from_numpy(np.ascontiguousarray(image))
+        return orehip.to_device(image, self.predictor.model.device).contiguous()
+
+    def run_on_image(self, image):
+        """image: [h, w, 3] uint8 in BGR order.  Returns the model's predictions and the drawn VisImage."""
+        color_by = "class" if self.instance_mode == ColorMode.SEGMENTATION else "instance"
+        if self.parallel:
+            self.predictor.put(image, draw={"color_by": color_by})
+            out = self.predictor.get()
+            return {"instances": out["instances"]}, VisImage(out["vis_image"], "BGR")
+        frame = self._upload(image)
+        predictions = self.predictor(frame)
+        vis = Visualizer(frame, self.metadata, instance_mode=self.instance_mode, channel_order="BGR")
+        return predictions, vis.draw_instance_predictions(predictions["instances"])
+
+    @staticmethod
+    def _frames(source):
+        """A generator over the frames of `source`: an iterable as it is; a capture-like object (isOpened() / read() returning
+        (ok, frame), the shape of cv2.VideoCapture) is polled until it closes or a read fails."""
+        if not (callable(getattr(source, "isOpened", None)) and callable(getattr(source, "read", None))):
+            yield from source
+            return
+        more = source.isOpened()
+        while more:
+            more, frame = source.read()
+            if more:
+                yield frame
+                more = source.isOpened()
+
+    def run_on_video(self, video):
+        """video: an iterable of BGR frames, or an object with isOpened() / read().  Yields the annotated BGR frames ([h, w, 3] uint8
+        numpy), in order; parallel=True keeps AsyncPredictor.default_buffer_size frames in flight."""
+        frames = self._frames(video)
+        if self.parallel:
+            draw = {"color_by": "class"}
+            pending = 0
+            for frame in frames:
+                if pending == self.predictor.default_buffer_size:
+                    yield self.predictor.get()["vis_image"].cpu().numpy()
+                    pending -= 1
+                self.predictor.put(frame, draw=draw)
+                pending += 1
+            while pending:
+                yield self.predictor.get()["vis_image"].cpu().numpy()
+                pending -= 1
+        else:
+            video_visualizer = VideoVisualizer(self.metadata, self.instance_mode, channel_order="BGR")
+            for frame in frames:
+                dev = self._upload(frame)
+                predictions = self.predictor(dev)
+                yield video_visualizer.draw_instance_predictions(dev, predictions["instances"]).img.cpu().numpy()

@@ -769,6 +769,42 @@ int ore_tta_merge_fwd(const float* pool_boxes, const float* pool_scores, const i
                       int32_t out_h, int32_t out_w, float score_thresh, float nms_thresh, int32_t topk, void* out_record,
                       int32_t rec_rows, int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ detection overlay --------- */
+/* Detections drawn onto an interleaved [h][w][3] uint8 frame on the device (detectron2's Visualizer.draw_instance_predictions for
+ * boxes: d2z:utils/visualizer.py; the demo's VisualizationDemo / AsyncPredictor), enqueued on `stream`, no host synchronisation.  The
+ * rows are read where a detection pass left them: boxes [n][4] fp32 xyxy at the frame's size, scores [n], classes [n] int64 (NULL: all
+ * 0), n = min(*n_dev if n_dev else n_host, max_rows) -- a pending pass's record and its device count serve as they are.
+ * dst_hwc == src_hwc draws in place; otherwise the frame is copied and drawn in the same pass (the two must not overlap).
+ * Render contract "overlay v1" -- all pixel arithmetic integer, the result bit-exact and independent of scheduling:
+ *   blend(p, c, a) = (p * (255 - a) + c * a + 127) / 255 per channel, integer division, a in 0 .. 255.
+ *   Row i is drawn iff its four coordinates and its score are finite, score >= score_thresh (fp32) and the integer rectangle
+ *     X0 = max((int)floorf(x0), 0), Y0 = max((int)floorf(y0), 0), X1 = min((int)ceilf(x1), w) - 1, Y1 = min((int)ceilf(y1), h) - 1
+ *     is non-empty (X1 >= X0 and Y1 >= Y0).
+ *   Draw order: area_i = (x1 - x0) * (y1 - y0) in fp32 on the raw coordinates, each operation rounded on its own (a NaN product, inf * 0,
+ *     counts as 0), descending, ties by i ascending: large boxes first, small ones on top.
+ *   Colour c_i = palette[(color_by ? class_i : i) mod n_palette] (non-negative mod); palette [n_palette][3] uint8 in the frame's channel
+ *     order, 1 <= n_palette <= 256.
+ *   Outline: the rectangle's pixels with x - X0 < L, X1 - x < L, y - Y0 < L or Y1 - y < L (L = line_width, 1 .. 16) become
+ *     blend(p, c_i, edge_alpha).
+ *   Label (text_scale S >= 1; S = 0 draws none): text = name + " " + pct + "%", or pct + "%" when the name is empty; name =
+ *     names[class_i], table [n_names][32] ASCII NUL-padded, empty when the id is out of range or names_dev is NULL; pct =
+ *     clamp((int)rintf(score * 100.0f), 0, 100), the product in fp32, half to even; at most 40 characters.  Glyph cells 6S x 11S, pad S:
+ *     the label rectangle is len * 6S + 2S wide and 13S high at lx = clamp(X0, 0, max(w - width, 0)), ly = clamp(Y0, 0, max(h -
+ *     height, 0)), pixels outside the frame dropped.  Its pixels become blend(p, 0, label_alpha); glyph pixel (u, v) of character ch
+ *     (cell k at lx + S + k * 6S, ly + S) is set iff atlas[ch - 32][v / S][u / S] (characters outside 32 .. 126: blank) and is then
+ *     replaced by the text colour t = c + ((255 - c) * 7) / 10 per channel.
+ *   Per pixel the instances apply in draw order; per instance outline, then label background, then glyph.
+ *   atlas_dev [95][11][6] bytes (0 / 1) for ASCII 32 .. 126 (needed when S >= 1).
+ * Limits (ORE_EINVAL): sides 1 .. ORE_OVERLAY_MAX_SIDE, max_rows <= ore_det_record_rows(), L in 1 .. 16, S in 0 .. 8, alphas 0 .. 255;
+ * frames 4-byte aligned.  workspace: ore_overlay_workspace_bytes(max_rows) (0 for max_rows out of range), private to the stream. */
+#define ORE_OVERLAY_MAX_SIDE 8192
+size_t ore_overlay_workspace_bytes(int32_t max_rows);
+int ore_overlay_draw_fwd(const uint8_t* src_hwc, uint8_t* dst_hwc, int32_t h, int32_t w, const float* boxes, const float* scores,
+                         const int64_t* classes, const int32_t* n_dev, int32_t n_host, int32_t max_rows, float score_thresh,
+                         int32_t line_width, int32_t text_scale, int32_t edge_alpha, int32_t label_alpha, const uint8_t* palette_dev,
+                         int32_t n_palette, int32_t color_by, const uint8_t* names_dev, int32_t n_names, const uint8_t* atlas_dev,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 """The demo's predictors (ref:predictor.py): VisualizationDemo draws a detector's boxes on images and video frames, AsyncPredictor keeps
 several frames in flight.  Drawing is the package's device overlay (orehip.overlay_draw, render contract "overlay v1"), not matplotlib;
-AsyncPredictor is one process with several engines on several HIP streams, not one process per GPU."""
+AsyncPredictor is one process with several engines on several HIP streams, not one process per GPU.  TiledPredictor is DefaultPredictor's
+contract over fewx.modeling.TiledInference, for frames larger than one detector pass."""
 from collections import deque
 
 import numpy as np
@@ -11,7 +12,29 @@ from detectron2.engine.defaults import DefaultPredictor
 from detectron2.utils.video_visualizer import VideoVisualizer
 from detectron2.utils.visualizer import ColorMode, VisImage, Visualizer, default_overlay_params, thing_classes
 
-__all__ = ["AsyncPredictor", "VisualizationDemo"]
+__all__ = ["AsyncPredictor", "TiledPredictor", "VisualizationDemo"]
+
+
+class TiledPredictor:
+    """DefaultPredictor's contract with sliced inference behind it:
+
+        pred = TiledPredictor(cfg, tile=(640, 640), overlap=128)
+        outputs = pred(bgr_frame)          # {"instances": Instances} at the frame's own size
+
+    builds the model as DefaultPredictor does (cfg.MODEL.WEIGHTS, the metadata of cfg.DATASETS.TEST[0]) and wraps it in
+    fewx.modeling.TiledInference(cfg, model, **tiling).  The frame is BGR [h, w, 3] uint8 (numpy array, CPU or device tensor);
+    cfg.INPUT.FORMAT == "RGB" exchanges the channels on the device."""
+
+    def __init__(self, cfg, **tiling):
+        from fewx.modeling import TiledInference
+        self.predictor = DefaultPredictor(cfg)
+        self.cfg, self.model = self.predictor.cfg, self.predictor.model
+        self.metadata = getattr(self.predictor, "metadata", None)
+        self.input_format = self.predictor.input_format
+        self.tiled = TiledInference(self.cfg, self.model, **tiling)
+
+    def __call__(self, original_image):
+        return self.tiled([{"image_raw": original_image, "swap_rb": self.input_format == "RGB"}])[0]
 
 
 class _Slot:

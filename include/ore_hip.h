@@ -805,6 +805,35 @@ int ore_overlay_draw_fwd(const uint8_t* src_hwc, uint8_t* dst_hwc, int32_t h, in
                          int32_t n_palette, int32_t color_by, const uint8_t* names_dev, int32_t n_names, const uint8_t* atlas_dev,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ tiled inference ----------- */
+/* The device side of TiledInference (fewx/modeling/tiled_inference.py): a frame larger than one detector pass is cut into overlapping
+ * tiles at native resolution, every tile (and, optionally, the resized full frame) is one source of detection rows, and the rows of all
+ * sources are merged by ore_tta_merge_fwd.  Both calls are enqueued on `stream`, no host synchronisation.
+ * ore_tile_gather_u8_fwd: src_hwc [h][w][3] uint8 interleaved -> dst [ny * nx][3][th][tw] uint8 planar, the image layout of
+ *   ore_engine_eval_fwd / ore_engine_eval_batch_fwd with img_is_u8 = 1, in one launch.  Tile iy * nx + ix starts at y0 = min(iy *
+ *   stride_y, h - th), x0 = min(ix * stride_x, w - tw) and holds exactly frame[y0 : y0 + th, x0 : x0 + tw] transposed to planar; swap_rb
+ *   exchanges channels 0 and 2.  src and its rows may start at any byte; nothing outside the frame is read and nothing outside dst[0,
+ *   ny * nx * 3 * th * tw) is written.  ORE_EINVAL: a side outside 1 .. 8192, th > h, tw > w, a stride outside 1 .. 8192, a grid that
+ *   does not reach the far edge ((ny - 1) * stride_y < h - th, likewise x), ny * nx > 128, dst overlapping src.
+ * ore_tile_collect_fwd: one source's detection rows -- boxes [n][4] xyxy in the source's own coordinates, scores [n], classes [n] int64
+ *   (NULL: all 0), n = min(*n_dev if n_dev else n_host, max_rows) -- into the pool of ore_tta_merge_fwd (boxes [pool_cap][4], scores,
+ *   classes int64, running count *pool_n).
+ *   Seam rule, fp32, on the source-local coordinates: `edges` bit 1 = left, 2 = top, 4 = right, 8 = bottom says the source continues
+ *   into the frame on that side; a row is rejected iff (edges & 1 and x0 < margin) or (edges & 2 and y0 < margin) or (edges & 4 and
+ *   x1 > fl(src_w - margin)) or (edges & 8 and y1 > fl(src_h - margin)).  A comparison with NaN is false: such a row passes here and
+ *   the merge drops it.
+ *   Kept rows become x' = fl(fl(x * sx) + ox), y' = fl(fl(y * sy) + oy), every operation rounded on its own (a tile: sx = sy = 1, (ox,
+ *   oy) its origin; the full-frame pass: ox = oy = 0, edges = 0, the ratios computed in double and rounded to fp32 by the caller), and
+ *   are appended in row order (a stable compaction) at *pool_n, which the call advances; source == 0 restarts the pool at 0; rows that
+ *   would pass pool_cap are cut.  src_counts[source] = the rows appended, src_dropped[source] = the rows the seam rule rejected.
+ *   ORE_EINVAL: source sides outside 1 .. 8192, edges outside 0 .. 15, margin < 0 or NaN.  No float atomics: bit-reproducible. */
+int ore_tile_gather_u8_fwd(const uint8_t* src_hwc, int32_t h, int32_t w, int32_t th, int32_t tw, int32_t stride_y, int32_t stride_x,
+                           int32_t ny, int32_t nx, int32_t swap_rb, uint8_t* dst, void* stream);
+int ore_tile_collect_fwd(const float* boxes, const float* scores, const int64_t* classes, const int32_t* n_dev, int32_t n_host,
+                         int32_t max_rows, float sx, float sy, float ox, float oy, int32_t src_h, int32_t src_w, int32_t edges,
+                         float margin, float* pool_boxes, float* pool_scores, int64_t* pool_classes, int32_t* pool_n, int32_t pool_cap,
+                         int32_t* src_counts, int32_t* src_dropped, int32_t source, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

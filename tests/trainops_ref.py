@@ -643,8 +643,8 @@ NOT_COVERED = {
     "pack_conv_weights_multi": "weight layouts, bitwise: test_hip_dgrad.py::test_dgrad_pack_layout",
     "winograd_covers": "a host predicate of the conv plan: tests/test_conv_plan_host.py",
     "winograd_weight": "the Winograd weight transform: pinned with the launches that use it in tests/test_hip_dgrad.py",
-    "roi_align": "ROIAlign: its own golden and property tests (tests/test_hip_train.py, tests/test_hip_properties.py)",
-    "roi_align_batched": "ROIAlign: its own golden and property tests",
+    "roi_align": "ROIAlign forward: held to float64 in tests/test_hip_inferops.py (tests/inferops_ref.py roi_align_ref)",
+    "roi_align_batched": "ROIAlign forward, batched: held to float64 in tests/test_hip_inferops.py::test_roi_align_batched",
     "roi_align_bwd": "ROIAlign backward: its own golden and property tests",
     "roi_losses": "loss kernels of ore_train.hip: golden and property tests of their own",
     "centernet_loss_sums": "loss kernels of ore_train.hip: golden and property tests of their own",

@@ -3,12 +3,17 @@ matching and its accumulation on the device (orehip.coco_eval, csrc/ore_coco_eva
 is read with the json module, the 12 summary numbers are computed from the precision / recall arrays here.
 
 The detections stay on the device from `model()` to the result: `process()` keeps the output tensors and adds no synchronisation;
-`evaluate()` gathers them to rank 0 (`comm.gather`), groups them by (category, image) on the device and runs the evaluation there."""
+`evaluate()` gathers them to rank 0 (`comm.gather`), groups them by (category, image) on the device and runs the evaluation there.
+
+An output that carries "proposals" is also scored with proposal recall, results["box_proposals"] = AR@100 .. ARl@1000
+(ref:fewx/evaluation/coco_evaluation.py:126-128, 207-244, 453-561), on the device as well (orehip.proposal_recall,
+csrc/ore_proposal_recall.hip)."""
 import copy
 import itertools
 import json
 import logging
 import os
+import pickle
 from collections import OrderedDict
 
 import numpy as np
@@ -26,6 +31,20 @@ AREA_RNG = [[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2,
 AREA_LBL = ["all", "small", "medium", "large"]
 MAX_DETS = [1, 10, 100]
 METRICS = ["AP", "AP50", "AP75", "APs", "APm", "APl"]
+# proposal recall (the reference's _eval_box_proposals): limits x areas, keys in its order
+PROPOSAL_LIMITS = [100, 1000]
+PROPOSAL_AREAS = {"all": "", "small": "s", "medium": "m", "large": "l"}
+
+
+def proposal_iou_thrs():
+    """The reference's default thresholds: torch.arange(0.5, 0.95 + 1e-5, 0.05, dtype=float32)."""
+    return torch.arange(0.5, 0.95 + 1e-5, 0.05, dtype=torch.float32)
+
+
+def proposal_recalls(counts, num_pos):
+    """The reference's last two fp32 steps from the integer counts of overlaps >= threshold: recalls = count / num_pos, ar = mean."""
+    recalls = torch.as_tensor(counts, dtype=torch.int64).reshape(-1).float() / float(num_pos)       # num_pos 0: NaN, as there
+    return recalls, recalls.mean()
 
 
 def coco_gt_from_dataset_dicts(dataset_dicts, metadata):
@@ -84,7 +103,14 @@ class CocoGT:
         self.ids = np.array([int(a["id"]) for a in rows], dtype=np.int64)
         cnt = np.bincount(pair[order], minlength=len(self.cat_ids) * I) if len(rows) else np.zeros(len(self.cat_ids) * I, np.int64)
         self.off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32)
+        # the per-image view (proposal recall): every annotation of an image in json order, whatever its category
+        rows = [a for im in self.img_ids for a in by_img.get(im, [])]
+        self.img_boxes = np.array([[float(v) for v in a["bbox"]] for a in rows], dtype=np.float64).reshape(-1, 4)
+        self.img_area = np.array([float(a["area"]) for a in rows], dtype=np.float64)
+        self.img_crowd = np.array([int(a.get("iscrowd", 0)) for a in rows], dtype=np.int32)
+        self.img_off = np.concatenate([[0], np.cumsum([len(by_img.get(im, [])) for im in self.img_ids])]).astype(np.int32)
         self._dev = {}
+        self._dev_img = {}
 
     def device(self, device):
         key = str(device)
@@ -92,6 +118,14 @@ class CocoGT:
             t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
             self._dev[key] = {"boxes": t(self.boxes), "area": t(self.area), "crowd": t(self.crowd), "id": t(self.ids), "off": t(self.off)}
         return self._dev[key]
+
+    def device_images(self, device):
+        """The per-image view on the device: "boxes" XYWH fp64, "area" fp64, "crowd" int32, "off" [I + 1] int32."""
+        key = str(device)
+        if key not in self._dev_img:
+            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+            self._dev_img[key] = {"boxes": t(self.img_boxes), "area": t(self.img_area), "crowd": t(self.img_crowd), "off": t(self.img_off)}
+        return self._dev_img[key]
 
 
 def summarize(precision, recall, iou_thrs=IOU_THRS, max_dets=MAX_DETS):
@@ -183,19 +217,25 @@ class COCOEvaluator(DatasetEvaluator):
             id_map = self._metadata.get("thing_dataset_id_to_contiguous_id")
             self._gt = CocoGT(gt_json, {v: k for k, v in id_map.items()} if id_map else {i: c["id"] for i, c in enumerate(gt_json["categories"])})
         self._workspace = None
+        self._proposal_workspace = None
         self.precision = self.recall = self.scores = None
+        self.proposal_stats = None
         self.reset()
 
     def reset(self):
         self._predictions = []
+        self._proposals = []
 
     def process(self, inputs, outputs):
-        """Keeps (image_id, boxes XYXY, scores, classes) of every output as they are -- device tensors, no copy, no sync."""
+        """Keeps (image_id, boxes XYXY, scores, classes) of every output that has "instances" and (image_id, proposal boxes XYXY,
+        objectness logits) of every output that has "proposals", as they are -- device tensors, no copy, no sync."""
         for inp, out in zip(inputs, outputs):
-            if "instances" not in out:
-                continue
-            inst = out["instances"]
-            self._predictions.append((inp["image_id"], inst.pred_boxes.tensor, inst.scores, inst.pred_classes))
+            if "instances" in out:
+                inst = out["instances"]
+                self._predictions.append((inp["image_id"], inst.pred_boxes.tensor, inst.scores, inst.pred_classes))
+            if "proposals" in out:
+                prop = out["proposals"]
+                self._proposals.append((inp["image_id"], prop.proposal_boxes.tensor, prop.objectness_logits))
 
     def _gather_predictions(self):
         """All ranks' predictions on the main process, rank after rank (comm.gather to rank 0); [] on the other ranks."""
@@ -206,6 +246,15 @@ class COCOEvaluator(DatasetEvaluator):
         preds = comm.gather(mine, dst=0)
         preds = list(itertools.chain(*preds))
         return preds if comm.is_main_process() else []
+
+    def _gather_proposals(self):
+        """As _gather_predictions, for the proposals."""
+        if not self._distributed or comm.get_world_size() == 1:
+            return list(self._proposals)
+        mine = [(i, b.detach().cpu(), s.detach().cpu()) for i, b, s in self._proposals]
+        props = comm.gather(mine, dst=0)
+        props = list(itertools.chain(*props))
+        return props if comm.is_main_process() else []
 
     def _coco_results(self, preds):
         """instances_to_coco_json of every prediction, in order, with dataset category ids: the results json rows."""
@@ -228,21 +277,26 @@ class COCOEvaluator(DatasetEvaluator):
 
     def evaluate(self):
         preds = self._gather_predictions()
+        props = self._gather_proposals()
         if self._distributed and not comm.is_main_process():
             return {}
-        if len(preds) == 0:
+        if len(preds) == 0 and len(props) == 0:
             self._logger.warning("[COCOEvaluator] Did not receive valid predictions.")
             return {}
-        unknown = sorted({p[0] for p in preds if p[0] not in self._gt.img_index})
+        unknown = sorted({p[0] for p in preds + props if p[0] not in self._gt.img_index})
         if unknown:
             raise ValueError(f"Results do not correspond to current coco set: image ids {unknown[:5]} are not in '{self._dataset_name}'")
+        self._results = OrderedDict()
+        if props:
+            self._results["box_proposals"] = self._eval_box_proposals(props)
+        if len(preds) == 0:
+            return copy.deepcopy(self._results)
         if self._output_dir:
             os.makedirs(self._output_dir, exist_ok=True)
             path = os.path.join(self._output_dir, "coco_instances_results.json")
             self._logger.info("Saving results to {}".format(path))
             with open(path, "w") as f:
                 json.dump(self._coco_results(preds), f)
-        self._results = OrderedDict()
         n_det = sum(int(p[2].numel()) for p in preds)
         if n_det == 0:
             self._logger.warning("No predictions from the model!")
@@ -250,6 +304,64 @@ class COCOEvaluator(DatasetEvaluator):
             return copy.deepcopy(self._results)
         self._results["bbox"] = self._eval_device(preds)
         return copy.deepcopy(self._results)
+
+    def _device_of(self, tensors):
+        dev = next((t.device for t in tensors if t.is_cuda), None)
+        if dev is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError("COCOEvaluator evaluates on the GPU (orehip); no GPU is available")
+            dev = torch.device("cuda", torch.cuda.current_device())
+        return dev
+
+    def _proposal_recall(self, props):
+        """The device call: every (limit, area) chain of every entry at once; the workspace is kept between evaluations.  Returns the
+        CPU copies of "num_pos" [L * A], "counts" [L * A, T] and "status"."""
+        import orehip
+        gt = self._gt
+        dev = self._device_of([p[1] for p in props])
+        counts = [int(p[2].numel()) for p in props]
+        img_idx = [gt.img_index[p[0]] for p in props]
+        boxes = torch.cat([p[1].reshape(-1, 4).to(dev, torch.float32) for p in props])
+        logits = torch.cat([p[2].reshape(-1).to(dev, torch.float32) for p in props])
+        S, cells = orehip.proposal_recall_sizes(counts, img_idx, gt.img_off, PROPOSAL_LIMITS)
+        wsb = orehip.lib().ore_proposal_recall_workspace_bytes(len(counts), int(logits.numel()), S, cells, len(PROPOSAL_AREAS), len(PROPOSAL_LIMITS))
+        ws = self._proposal_workspace
+        if ws is None or ws.device != dev or ws.numel() < wsb:
+            ws = self._proposal_workspace = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        out = orehip.proposal_recall(boxes, logits, counts, img_idx, gt.device_images(dev), gt.img_off, AREA_RNG, PROPOSAL_LIMITS,
+                                     proposal_iou_thrs().numpy(), workspace=ws)
+        return {k: out[k].cpu() for k in ("num_pos", "counts", "status")}
+
+    def _eval_box_proposals(self, props):
+        """The reference's _eval_box_proposals: box_proposals.pkl (with an output_dir), then AR at limits 100 / 1000 over the area
+        ranges all / small / medium / large, each float(ar) * 100, in the reference's key order."""
+        if self._output_dir:
+            os.makedirs(self._output_dir, exist_ok=True)
+            ids, boxes, logits = [], [], []
+            for img_id, b, s in props:
+                ids.append(img_id)
+                boxes.append(b.detach().cpu().numpy().reshape(-1, 4))
+                logits.append(s.detach().cpu().numpy().reshape(-1))
+            data = {"boxes": boxes, "objectness_logits": logits, "ids": ids, "bbox_mode": 0}      # BoxMode.XYXY_ABS
+            with open(os.path.join(self._output_dir, "box_proposals.pkl"), "wb") as f:
+                pickle.dump(data, f)
+        self._logger.info("Evaluating bbox proposals ...")
+        out = self._proposal_recall(props)
+        if int(out["status"][0]) != 0:
+            raise RuntimeError(f"proposal recall: the device call skipped entries (status {int(out['status'][0])})")
+        res, stats = {}, {}
+        A = len(PROPOSAL_AREAS)
+        for l, limit in enumerate(PROPOSAL_LIMITS):
+            for a, suffix in enumerate(PROPOSAL_AREAS.values()):
+                c = l * A + a
+                num_pos = int(out["num_pos"][c])
+                recalls, ar = proposal_recalls(out["counts"][c], num_pos)
+                key = "AR{}@{:d}".format(suffix, limit)
+                res[key] = float(ar.item() * 100)
+                stats[key] = {"ar": ar, "recalls": recalls, "num_pos": num_pos}
+        self.proposal_stats = stats
+        self._logger.info("Proposal metrics: \n" + " | ".join(f"{k} {v:.3f}" for k, v in res.items()))
+        return res
 
     def _eval_device(self, preds):
         import orehip

@@ -167,6 +167,10 @@ class CenterNet2Detector(nn.Module):
         # detected, pred_classes all 0); "all" = every class of support_dict; a list of class ids = those classes in that order.  One
         # pass then detects every selected class (pred_classes = class ids).  Not a config key: the config tree is the reference's.
         self.support_classes = None
+        # True: the result dict of model([request]) / inference() also carries "proposals", the first-stage proposals of that pass
+        # (post-NMS top-k) at the requested output size, as detectron2's ProposalNetwork returns them -- what COCOEvaluator scores with
+        # proposal recall ("box_proposals").  "instances" is unchanged.  Not with support_classes (proposals are per class there).
+        self.output_proposals = False
         self._engine = None
         self._engine_key = None
         self.max_hw = (int(cfg.INPUT.MAX_SIZE_TEST), int(cfg.INPUT.MAX_SIZE_TEST))
@@ -431,6 +435,45 @@ class CenterNet2Detector(nn.Module):
         boxes, scores, _ = e.proposals()
         return [make_proposals((img.shape[-2], img.shape[-1]), boxes.clone(), scores.clone())]
 
+    def _proposals_of_last_pass(self, e, inp, img_hw):
+        """The first-stage proposals engine `e` holds from its last pass, cloned, through detector_postprocess to the request's output
+        size (scale, clip, drop empty): Instances with proposal_boxes / objectness_logits.  One more host wait: the proposal count."""
+        from detectron2.structures import Boxes, Instances
+        boxes, scores, _ = e.proposals()
+        p = Instances((int(img_hw[0]), int(img_hw[1])))
+        p.proposal_boxes = Boxes(boxes.clone())
+        p.objectness_logits = scores.clone()
+        return detector_postprocess(p, inp.get("height", img_hw[0]), inp.get("width", img_hw[1]))
+
+    @property
+    def output_proposals(self):
+        return "inference" in self.__dict__
+
+    @output_proposals.setter
+    def output_proposals(self, on):
+        # the switch replaces this object's `inference`; off, the class's method -- and its fast path -- is what runs, untouched
+        if on:
+            self.__dict__["inference"] = self._inference_with_proposals
+        else:
+            self.__dict__.pop("inference", None)
+
+    @torch.no_grad()
+    def _inference_with_proposals(self, batched_inputs, detected_instances=None, do_postprocess=True):
+        """`inference` with output_proposals on: the checked path, then the proposals of the same engine pass beside "instances"
+        (with do_postprocess only: without it the result is the bare Instances list, as in `inference`)."""
+        assert not self.training
+        self.init_model()
+        assert len(batched_inputs) == 1, "only 1 query image in test (ref fsod_cen.py:438-439)"
+        inp = batched_inputs[0]
+        if self.support_classes is not None:
+            raise ValueError("output_proposals does not combine with support_classes: an N-way pass has one proposal set per class")
+        if "image_raw" in inp:
+            inp = self._resolve_raw(inp)
+        out = self._inference_checked(inp, inp["image"], do_postprocess)
+        if do_postprocess:
+            out[0]["proposals"] = self._proposals_of_last_pass(self._engine, inp, inp["image"].shape[-2:])
+        return out
+
     @torch.no_grad()
     def inference(self, batched_inputs, detected_instances=None, do_postprocess=True):
         assert not self.training
@@ -546,11 +589,12 @@ class CenterNet2Detector(nn.Module):
         the reference passes one at a time).  Requests of equal image size and dtype are folded, up to `max_fold` per engine pass
         (Engine.eval_forward_batch: dense stages batched, detection tail and second stage per image); results come back in request
         order and equal the one-at-a-time results (tests/test_hip_parity.py).  With support_classes set (N-way inference) the requests
-        are answered one image at a time, each by the one-pass N-way call of `inference`: a pass holds one query image and its classes."""
+        are answered one image at a time, each by the one-pass N-way call of `inference`: a pass holds one query image and its classes.
+        With output_proposals on they are answered one image at a time as well."""
         from detectron2.structures import Boxes, Instances
         assert not self.training
         self.init_model()
-        if self.support_classes is not None:
+        if self.support_classes is not None or self.output_proposals:
             return [self.inference([r], do_postprocess=do_postprocess)[0] for r in requests]
         requests = [self._resolve_raw(r) if "image_raw" in r else r for r in requests]
         key = (self._state_key(), str(self.device), self.conv_operands, max_fold)

@@ -671,6 +671,84 @@ def coco_eval(det_boxes: torch.Tensor, det_scores: torch.Tensor, det_image: torc
     return out
 
 
+class ProposalRecallDesc(C.Structure):
+    _fields_ = [("n_entries", C.c_int32), ("n_images", C.c_int32),
+                ("prop_boxes", C.c_void_p), ("prop_logits", C.c_void_p), ("n_props", C.c_int32),
+                ("entry_off", C.c_void_p), ("entry_image", C.c_void_p),
+                ("gt_boxes", C.c_void_p), ("gt_area", C.c_void_p), ("gt_crowd", C.c_void_p), ("gt_off", C.c_void_p), ("n_gts", C.c_int32),
+                ("area_rngs_host", C.c_void_p), ("n_areas", C.c_int32), ("limits_host", C.c_void_p), ("n_limits", C.c_int32),
+                ("iou_thrs_host", C.c_void_p), ("n_iou_thrs", C.c_int32),
+                ("n_slots", C.c_int32), ("n_iou_cells", C.c_int64),
+                ("num_pos", C.c_void_p), ("gt_overlaps", C.c_void_p), ("counts", C.c_void_p), ("status", C.c_void_p),
+                ("entry_overlaps", C.c_void_p), ("entry_slot_off", C.c_void_p), ("entry_valid", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+def proposal_recall_sizes(entry_counts, entry_image, gt_off_host, limits) -> Tuple[int, int]:
+    """(n_slots, n_iou_cells) of one ore_proposal_recall call, from what the host knows: the proposal count and image index of every
+    entry and the per-image GT offsets (include/ore_hip.h)."""
+    cnt = np.asarray(entry_counts, dtype=np.int64).reshape(-1)
+    img = np.asarray(entry_image, dtype=np.int64).reshape(-1)
+    per = np.diff(np.asarray(gt_off_host, dtype=np.int64))
+    g = per[img] if len(img) else np.zeros(0, np.int64)
+    cells = np.minimum(cnt, int(max(limits))) * g
+    return int(g.sum()), int(cells[cells > lib().ore_proposal_recall_lds_cells()].sum())
+
+
+def proposal_recall(prop_boxes: torch.Tensor, prop_logits: torch.Tensor, entry_counts, entry_image, gt: Dict[str, torch.Tensor], gt_off_host,
+                    area_rngs, limits, iou_thrs, per_image: bool = False, workspace: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """The reference's proposal recall (_evaluate_box_proposals) on the device for every (limit, area range) pair: ore_proposal_recall.
+    prop_boxes [N, 4] XYXY fp32 and prop_logits [N] fp32: the proposals of all prediction entries concatenated; entry_counts /
+    entry_image: host sequences, the proposal count of every entry and the index of its image among the id-sorted images.  gt: the
+    per-image view (CocoGT.device_images): device "boxes" [G, 4] XYWH fp64, "area" fp64, "crowd" int32, "off" [I + 1] int32;
+    gt_off_host: the same offsets on the host.  area_rngs [A][2], limits [L], iou_thrs [T] fp32 are host sequences; chain c = l * A + a.
+    Returns device tensors: "num_pos" [L * A] int64; "gt_overlaps" [L * A, S] fp32, row c ascending, its first num_pos[c] values valid;
+    "counts" [L * A, T] int64 (overlaps >= threshold); "status" [1] int32 (0: every entry was evaluated); with per_image=True also
+    "entry_overlaps" [L * A, S] (entry e's recorded vector of chain c at [c, entry_slot_off[e] : + entry_valid[e, c]]),
+    "entry_slot_off" [E + 1] int32, "entry_valid" [E, L * A] int32.  Enqueued on the current stream, no sync."""
+    dev = prop_boxes.device
+    cnt = np.ascontiguousarray(entry_counts, dtype=np.int64).reshape(-1)
+    img = np.ascontiguousarray(entry_image, dtype=np.int32).reshape(-1)
+    off_h = np.ascontiguousarray(gt_off_host, dtype=np.int64).reshape(-1)
+    E, I, N, G = len(cnt), len(off_h) - 1, int(prop_logits.numel()), int(gt["area"].numel())
+    if len(img) != E or int(cnt.sum()) != N or (E and (int(img.min()) < 0 or int(img.max()) >= I)) or int(gt["off"].numel()) != I + 1:
+        raise OreError(f"proposal_recall: {E} entries with {int(cnt.sum())} proposals, {N} rows, {len(img)} image indices, {I} images")
+    area = np.ascontiguousarray(area_rngs, dtype=np.float64).reshape(-1, 2)
+    lim = np.ascontiguousarray(limits, dtype=np.int32)
+    thr = np.ascontiguousarray(iou_thrs, dtype=np.float32)
+    A, L, T = len(area), len(lim), len(thr)
+    S, cells = proposal_recall_sizes(cnt, img, off_h, lim)
+    wsb = lib().ore_proposal_recall_workspace_bytes(E, N, S, cells, A, L)
+    if wsb == 0:
+        raise OreError(f"proposal_recall: bad sizes (entries {E}, proposals {N}, slots {S}, areas {A}, limits {L})")
+    if workspace is None or workspace.numel() < wsb:
+        workspace = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    entry_off = torch.from_numpy(np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32)).to(dev)
+    entry_img = torch.from_numpy(img).to(dev)
+    prop_boxes, prop_logits = prop_boxes.float().contiguous(), prop_logits.float().contiguous()
+    out = {"num_pos": torch.empty(L * A, dtype=torch.int64, device=dev), "gt_overlaps": torch.empty(L * A, S, dtype=torch.float32, device=dev),
+           "counts": torch.empty(L * A, T, dtype=torch.int64, device=dev), "status": torch.empty(1, dtype=torch.int32, device=dev)}
+    if per_image:
+        out.update({"entry_overlaps": torch.empty(L * A, S, dtype=torch.float32, device=dev),
+                    "entry_slot_off": torch.empty(E + 1, dtype=torch.int32, device=dev),
+                    "entry_valid": torch.empty(max(E, 1), L * A, dtype=torch.int32, device=dev)})
+    p = lambda t: _ptr(t) if t.numel() else None
+    d = ProposalRecallDesc(n_entries=E, n_images=I, prop_boxes=p(prop_boxes), prop_logits=p(prop_logits), n_props=N,
+                           entry_off=_ptr(entry_off), entry_image=p(entry_img),
+                           gt_boxes=p(gt["boxes"]), gt_area=p(gt["area"]), gt_crowd=p(gt["crowd"]), gt_off=_ptr(gt["off"]), n_gts=G,
+                           area_rngs_host=area.ctypes.data, n_areas=A, limits_host=lim.ctypes.data, n_limits=L,
+                           iou_thrs_host=thr.ctypes.data, n_iou_thrs=T, n_slots=S, n_iou_cells=cells,
+                           num_pos=_ptr(out["num_pos"]), gt_overlaps=p(out["gt_overlaps"]), counts=_ptr(out["counts"]), status=_ptr(out["status"]),
+                           entry_overlaps=p(out["entry_overlaps"]) if per_image else None,
+                           entry_slot_off=_ptr(out["entry_slot_off"]) if per_image else None,
+                           entry_valid=out["entry_valid"].data_ptr() if per_image else None,
+                           workspace=_ptr(workspace), workspace_bytes=wsb)
+    _chk(lib().ore_proposal_recall(C.byref(d), _stream()), "ore_proposal_recall")
+    if per_image:
+        out["entry_valid"] = out["entry_valid"][:E]
+    return out
+
+
 def nms(boxes: torch.Tensor, scores: torch.Tensor, thr: float) -> torch.Tensor:
     """torchvision.ops.nms semantics (stable order); returns int64 keep indices (this call syncs to read the count)."""
     n = scores.numel()

@@ -717,6 +717,43 @@ size_t ore_coco_eval_workspace_bytes(int32_t n_cats, int32_t n_images, int32_t n
                                      int32_t n_areas, int32_t max_det);
 int ore_coco_eval(const ore_coco_eval_desc* desc, const ore_coco_eval_images* per_image /* NULL: not wanted */, void* stream);
 
+/* ------------------------------------------------------------------ proposal recall ----------- */
+/* Proposal AR (AR@100 .. ARl@1000 of "box_proposals") on the device: the reference's _evaluate_box_proposals
+ * (ref:fewx/evaluation/coco_evaluation.py:453-561) for every (limit, area range) pair in one call, bit-exact.
+ * Proposals of all prediction entries concatenated: prop_boxes [n_props][4] XYXY fp32, prop_logits [n_props] fp32; entry e owns rows
+ * entry_off[e] .. entry_off[e + 1] (int32 [n_entries + 1]) and belongs to image entry_image[e] (index into the images sorted by id).
+ * Ground truth per image, json order, every category: gt_off [n_images + 1] int32, gt_boxes [n_gts][4] XYWH fp64, gt_area fp64,
+ * gt_crowd int32.  Host parameter arrays: area_rngs [A][2] doubles (rounded to fp32 here), limits [L] (1 .. 2048), iou_thrs [T <= 16]
+ * fp32; A * L <= 8.  Chain c = l * A + a.
+ * Per entry: proposals by logit descending, ties in input order; the image's non-crowd GTs as fp32 XYXY; IoU in fp32 as detectron2's
+ * pairwise_iou; per chain the greedy extraction over the first limit proposals and the GTs whose fp32 area lies in [lo, hi]: largest
+ * remaining IoU, ties to the lowest GT then the lowest proposal, min(P', G) times, the rest of the G-long vector 0.
+ * Capacities the caller states (they bound what is written; an entry that does not fit is skipped and *status becomes non-zero):
+ * n_slots >= the sum over the entries of their image's GT count (crowd included); n_iou_cells >= the sum over the entries of
+ * min(P, max limit) * that GT count where this product exceeds ore_proposal_recall_lds_cells().
+ * Outputs: num_pos [L * A] int64; gt_overlaps [L * A][n_slots] fp32, row c ascending, its first num_pos[c] values valid (the
+ * rest all-ones bit patterns); counts [L * A][T] int64: overlaps >= iou_thrs[t]; status [1] int32: 0, or non-zero for an entry with bad
+ * offsets / image index or one past the stated capacities.  Optional (all three or none): entry_overlaps [L * A][n_slots] fp32, the
+ * recorded vector of entry e and chain c at [c][entry_slot_off[e] ..] with entry_valid[e][c] values; entry_slot_off [n_entries + 1]
+ * int32; entry_valid [n_entries][L * A] int32.  Deterministic (integer atomics only count), no host synchronisation. */
+typedef struct ore_proposal_recall_desc {
+    int32_t n_entries, n_images;
+    const float* prop_boxes; const float* prop_logits; int32_t n_props;
+    const int32_t* entry_off; const int32_t* entry_image;
+    const double* gt_boxes; const double* gt_area; const int32_t* gt_crowd; const int32_t* gt_off; int32_t n_gts;
+    const double* area_rngs_host; int32_t n_areas;
+    const int32_t* limits_host; int32_t n_limits;
+    const float* iou_thrs_host; int32_t n_iou_thrs;
+    int32_t n_slots; int64_t n_iou_cells;
+    int64_t* num_pos; float* gt_overlaps; int64_t* counts; int32_t* status;
+    float* entry_overlaps; int32_t* entry_slot_off; int32_t* entry_valid;
+    void* workspace; size_t workspace_bytes;
+} ore_proposal_recall_desc;
+int32_t ore_proposal_recall_lds_cells(void);
+size_t ore_proposal_recall_workspace_bytes(int32_t n_entries, int32_t n_props, int32_t n_slots, int64_t n_iou_cells, int32_t n_areas,
+                                           int32_t n_limits);
+int ore_proposal_recall(const ore_proposal_recall_desc* desc, void* stream);
+
 /* ------------------------------------------------------------------ image resize -------------- */
 /* Pillow's Image.resize(size, BILINEAR) for 8-bit images, byte for byte (ImagingResample: antialiased separable triangle filter,
  * 22-bit fixed-point weights, horizontal pass to a uint8 intermediate, then the vertical pass); replaces the CPU resize of

@@ -95,6 +95,9 @@ __device__ __forceinline__ float ore_expf(float x) {
     return e * __uint_as_float((unsigned)(ni + 127) << 23);
 }
 
+// the sigmoid the proposal decode thresholds with (ore_detect.hip) and the heat maps show (ore_heatmap.hip; ore_sigmoid_host on the host)
+__device__ __forceinline__ float ore_sigmoid(float x) { return 1.0f / (1.0f + ore_expf(-x)); }
+
 namespace oreroi {
 // ore_roi_predict_post_fwd with the fc1 rows still in K-split partial sums (csrc/ore_roi.hip; h_parts = 0: as the C-ABI entry)
 int roi_predict_post(const float* h, int32_t C, int32_t h_parts, const float* h_bias, const float* cls_w, const float* cls_b,

@@ -33,8 +33,6 @@ __device__ int g_det_ablate = 0;      // tools/det_ablate.py: parts of k_nms_sca
 
 namespace {
 
-__device__ __forceinline__ float ore_sigmoid(float x) { return 1.0f / (1.0f + ore_expf(-x)); }
-
 struct DetP {
     int n_levels;
     const float* head[8]; int head_ld;

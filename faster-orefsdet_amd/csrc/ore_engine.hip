@@ -110,6 +110,7 @@ struct ore_engine {
     struct GraphKey { int u8, H, W, B, K; hipGraphExec_t exec; };
     std::vector<GraphKey> graphs;
     Geo last{};
+    long long pass_serial = 0;        // passes begun (every assignment of `last`): ore_engine_last_geometry
     double last_flops = 0.0;
     // optional per-launch HIP-event timing of the conv kernels (eager mode only; bench.py roofline leg)
     bool profiling = false;
@@ -852,7 +853,7 @@ extern "C" int ore_engine_backbone_fwd(ore_engine* e, const void* img, int32_t i
     if (rc) return rc;
     ORE_CHECK_ARG(img, "null image");
     const Geo g = make_geo(B, H, W);
-    e->last = g;
+    e->last = g; ++e->pass_serial;
     PrecisionScope ps(e->sb() ? ORE_CONV_FP32 : e->conv_precision);
     return run_backbone(e, img, is_u8, g, (hipStream_t)stream, &e->last_flops);
 }
@@ -937,7 +938,7 @@ extern "C" int ore_engine_eval_batch_fwd(ore_engine* e, const void* img, int32_t
     ORE_CHECK_ARG(img, "null image");
     hipStream_t st = (hipStream_t)stream;
     const Geo g = make_geo(B, H, W);
-    e->last = g;
+    e->last = g; ++e->pass_serial;
     PrecisionScope ps(e->sb() ? ORE_CONV_FP32 : e->conv_precision);
     const size_t bytes = (size_t)B * 3 * H * W * (is_u8 ? 1 : 4);
     ORE_CHECK_ARG(bytes <= e->img_bytes, "image batch exceeds the engine's input buffer");
@@ -975,7 +976,7 @@ static int eval_classes(ore_engine* e, const void* img, int32_t is_u8, int32_t H
     if (rc) return rc;
     ORE_CHECK_ARG(img, "null image");
     const Geo g1 = make_geo(1, H, W), gK = make_geo(K, H, W);
-    e->last = gK;                                        // buffers read back as a K-image batch: block k = class slot k
+    e->last = gK; ++e->pass_serial;                                        // buffers read back as a K-image batch: block k = class slot k
     PrecisionScope ps(e->conv_precision);
     const size_t bytes = (size_t)3 * H * W * (is_u8 ? 1 : 4);
     ORE_CHECK_ARG(bytes <= e->img_bytes, "image exceeds the engine's input buffer");
@@ -1207,6 +1208,16 @@ extern "C" int ore_engine_buffer(ore_engine* e, const char* name, void** ptr, in
     }
     ore_set_error("ore_engine_buffer: unknown buffer '%s'", name);
     return ORE_ENOENT;
+}
+
+extern "C" int ore_engine_last_geometry(ore_engine* e, int32_t out[16]) {
+    ORE_CHECK_ARG(e && e->finalized && out, "ore_engine_last_geometry: bad args");
+    const Geo& g = e->last;
+    out[0] = g.B; out[1] = g.H; out[2] = g.W;
+    for (int l = 0; l < 3; ++l) { out[3 + 3 * l] = g.h[l + 3]; out[4 + 3 * l] = g.w[l + 3]; out[5 + 3 * l] = e->cfg.strides[l]; }
+    out[12] = (int32_t)(e->pass_serial & 0x7fffffffLL); out[13] = (int32_t)(e->pass_serial >> 31);
+    out[14] = out[15] = 0;
+    return ORE_OK;
 }
 
 extern "C" int32_t ore_engine_buffer_is_bf16(ore_engine* e, const char* name) {

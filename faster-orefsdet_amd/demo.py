@@ -2,7 +2,8 @@
 
     python demo.py --input a.jpg b.jpg --output out_dir --opts MODEL.WEIGHTS w.pth
 
-Images are decoded with Pillow and drawn on the device.  Video (--video-input, --webcam) needs OpenCV to decode and to show frames;
+--heatmap objectness | attention | <buffer>[:<channel>] (p4, pos3:17, ...) lays that heat map of the detection pass under the boxes
+(--heatmap-alpha, --heatmap-colormap jet | gray).  Images are decoded with Pillow and drawn on the device.  Video (--video-input, --webcam) needs OpenCV to decode and to show frames;
 this package neither ships nor requires it, and the two flags say so when it is missing."""
 import argparse
 import glob
@@ -19,6 +20,10 @@ def get_parser():
     parser.add_argument("--input", nargs="+", metavar="IMAGE", help="image files, or one quoted glob pattern")
     parser.add_argument("--output", metavar="PATH", help="where the pictures go: a directory, or a file name when there is one input")
     parser.add_argument("--confidence-threshold", type=float, default=0.9, metavar="T", help="detections scoring below T are not drawn (default: %(default)s)")
+    parser.add_argument("--heatmap", metavar="KIND", help="lay a heat map of the pass under the boxes: objectness, attention, or a level buffer "
+                        "with an optional channel such as p4 or pos3:17")
+    parser.add_argument("--heatmap-alpha", type=int, default=128, metavar="A", help="the heat map's opacity, 0 .. 255 (default: %(default)s)")
+    parser.add_argument("--heatmap-colormap", default="jet", choices=("jet", "gray"), help="the heat map's colour table (default: %(default)s)")
     parser.add_argument("--video-input", metavar="VIDEO", help="annotate a video file instead (needs OpenCV)")
     parser.add_argument("--webcam", action="store_true", help="annotate the first camera's frames instead (needs OpenCV)")
     parser.add_argument("--opts", nargs=argparse.REMAINDER, default=[], metavar="KEY VALUE", help="config overrides, e.g. MODEL.WEIGHTS model.pth; must come last")
@@ -103,9 +108,14 @@ def main(argv=None):
         sys.exit("demo.py: --input needs --output: pictures are written to files, there is no window to show them in")
 
     from detectron2.utils.logger import setup_logger
-    from predictor import VisualizationDemo
+    from predictor import VisualizationDemo, heatmap_args
     log = setup_logger()
-    demo = VisualizationDemo(setup_cfg(args))
+    heatmap = {"kind": args.heatmap, "alpha": args.heatmap_alpha, "lut": args.heatmap_colormap} if args.heatmap else None
+    try:
+        heatmap = heatmap_args(heatmap, "--heatmap")          # the flags alone, before anything is built
+    except ValueError as err:
+        sys.exit(f"demo.py: {err}")
+    demo = VisualizationDemo(setup_cfg(args), heatmap=heatmap)
     if video:
         run_video(demo, args, cv2)
     else:

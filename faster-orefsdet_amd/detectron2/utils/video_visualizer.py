@@ -1,5 +1,5 @@
 """d2z:utils/video_visualizer.py for box detections, by the render contract of detectron2.utils.visualizer."""
-from .visualizer import ColorMode, _BOXES_ONLY, draw_boxes, thing_classes
+from .visualizer import ColorMode, _BOXES_ONLY, draw_boxes, draw_heat, thing_classes
 
 __all__ = ["VideoVisualizer"]
 
@@ -19,6 +19,11 @@ class VideoVisualizer:
 
     def draw_instance_predictions(self, frame, predictions):
         return draw_boxes(frame, predictions, channel_order=self.channel_order, names=thing_classes(self.metadata), color_by="class")
+
+    def draw_heatmap(self, frame, source, **style):
+        """A heat map of a detection pass over the frame (detectron2.utils.visualizer.draw_heat) -> VisImage; hand its .img to
+        draw_instance_predictions to put the boxes on top."""
+        return draw_heat(frame, source, channel_order=self.channel_order, **style)
 
     def draw_sem_seg(self, *args, **kwargs):
         raise NotImplementedError("draw_sem_seg: " + _BOXES_ONLY)

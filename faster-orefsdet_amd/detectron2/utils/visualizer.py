@@ -1,6 +1,7 @@
 """d2z:utils/visualizer.py for box detections: ColorMode, VisImage and a Visualizer whose draw_instance_predictions renders boxes,
 class names and scores by the package's own render contract ("overlay v1", include/ore_hip.h) instead of matplotlib: on the device
 for device Instances (orehip.overlay_draw), on the host for host Instances (orehip.overlay_host) -- the same bytes either way.
+draw_heatmap lays a heat map of a detection pass over the frame ("heatmap v1": orehip.heatmap_draw / heatmap_host).
 Masks, keypoints, panoptic and semantic drawing are not built: those methods raise."""
 from enum import Enum, unique
 from math import isqrt
@@ -8,7 +9,7 @@ from math import isqrt
 import numpy as np
 import torch
 
-__all__ = ["ColorMode", "VisImage", "Visualizer", "default_overlay_params"]
+__all__ = ["ColorMode", "VisImage", "Visualizer", "default_overlay_params", "draw_heat"]
 
 _BOXES_ONLY = "this package draws boxes only (draw_instance_predictions); masks, keypoints, panoptic and semantic drawing are not built"
 
@@ -75,6 +76,32 @@ def draw_boxes(frame, predictions, *, channel_order, names, color_by, score_thre
     return VisImage(out, channel_order)
 
 
+def draw_heat(frame, source, *, channel_order, in_hw=None, **style):
+    """One frame + a heat source -> VisImage.  source: an orehip.HeatSource or HeatLevels (device: the frame goes to its device and
+    the kernel draws), or a sequence of (uint8 map, stride) with in_hw -- device maps draw on the device, host maps through
+    heatmap_host: the same bytes either way.  style: lut, alpha, alpha_mode of orehip.heatmap_draw.  The frame itself is left as it was."""
+    import orehip
+    unknown = sorted(set(style) - {"lut", "alpha", "alpha_mode"})
+    if unknown:
+        raise ValueError(f"draw_heatmap takes lut, alpha, alpha_mode (and in_hw with bare maps); not {', '.join(unknown)}")
+    if isinstance(source, orehip.HeatSource):
+        dev = source.device
+    elif isinstance(source, orehip.HeatLevels):
+        dev = source.maps[0].device
+    else:
+        source = list(source)
+        first = source[0][0] if source and isinstance(source[0], (tuple, list)) and len(source[0]) == 2 else None
+        dev = first.device if torch.is_tensor(first) and first.is_cuda else None
+    if dev is not None:
+        if not torch.is_tensor(frame):
+            frame = torch.from_numpy(np.ascontiguousarray(frame))
+        out = orehip.heatmap_draw(orehip.to_device(frame, dev).contiguous(), source, in_hw, channel_order=channel_order, **style)
+    else:
+        host = frame.cpu().numpy() if torch.is_tensor(frame) else np.ascontiguousarray(frame)
+        out = orehip.heatmap_host(host, source, in_hw, channel_order=channel_order, **style)
+    return VisImage(out, channel_order)
+
+
 class Visualizer:
     """Visualizer(img_rgb, metadata=None, scale=1.0, instance_mode=ColorMode.IMAGE): img_rgb is [h, w, 3] in 0 .. 255, a numpy array
     or a uint8 tensor (host or device).  The overlay draws at the frame's size, so scale must be 1.0.  channel_order="BGR" (an
@@ -100,6 +127,14 @@ class Visualizer:
         SEGMENTATION by class.  Returns the drawn VisImage."""
         self.output = draw_boxes(self.img, predictions, channel_order=self.channel_order, names=thing_classes(self.metadata),
                                  color_by="class" if self._instance_mode == ColorMode.SEGMENTATION else "instance")
+        return self.output
+
+    def draw_heatmap(self, source, **style):
+        """A heat map of a detection pass over the image (draw_heat: an orehip.HeatSource / HeatLevels, or (map, stride) pairs with
+        in_hw=; lut, alpha, alpha_mode).  The result becomes the image later draws start from, so boxes drawn afterwards lie on top
+        of the heat map.  Returns the drawn VisImage."""
+        self.output = draw_heat(self.img, source, channel_order=self.channel_order, **style)
+        self.img = self.output.img
         return self.output
 
     def get_output(self):

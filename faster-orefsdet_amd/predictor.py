@@ -1,7 +1,8 @@
 """The demo's predictors (ref:predictor.py): VisualizationDemo draws a detector's boxes on images and video frames, AsyncPredictor keeps
 several frames in flight.  Drawing is the package's device overlay (orehip.overlay_draw, render contract "overlay v1"), not matplotlib;
 AsyncPredictor is one process with several engines on several HIP streams, not one process per GPU.  TiledPredictor is DefaultPredictor's
-contract over fewx.modeling.TiledInference, for frames larger than one detector pass."""
+contract over fewx.modeling.TiledInference, for frames larger than one detector pass.  Both predictors can lay a heat map of the pass
+under the boxes (heatmap=...: orehip.heatmap_draw, render contract "heatmap v1"): objectness, attention or a feature channel."""
 from collections import deque
 
 import numpy as np
@@ -12,7 +13,56 @@ from detectron2.engine.defaults import DefaultPredictor
 from detectron2.utils.video_visualizer import VideoVisualizer
 from detectron2.utils.visualizer import ColorMode, VisImage, Visualizer, default_overlay_params, thing_classes
 
-__all__ = ["AsyncPredictor", "TiledPredictor", "VisualizationDemo"]
+__all__ = ["AsyncPredictor", "TiledPredictor", "VisualizationDemo", "heatmap_args"]
+
+HEATMAP_KEYS = ("kind", "slot", "lut", "alpha", "alpha_mode")
+
+
+def heatmap_args(heatmap, who="heatmap"):
+    """A heatmap= argument -- a kind ("objectness", "attention", "<buffer>[:<channel>]") or a dict with "kind" and any of slot, lut,
+    alpha, alpha_mode -- as the checked keyword set {kind, slot, lut, alpha, alpha_mode}; None stays None.  Everything that can be
+    refused without an engine is refused here (ValueError): the kind's form, the table, alpha, the slot's type."""
+    import orehip
+    if heatmap is None:
+        return None
+    kw = {"slot": 0, "lut": "jet", "alpha": 128, "alpha_mode": "constant"}
+    if isinstance(heatmap, str):
+        kw["kind"] = heatmap
+    elif isinstance(heatmap, dict):
+        unknown = sorted(set(heatmap) - set(HEATMAP_KEYS), key=str)
+        if unknown or "kind" not in heatmap:
+            raise ValueError(f"{who}: a dict takes {', '.join(HEATMAP_KEYS)} (kind is needed); not {', '.join(map(str, unknown)) or 'one without kind'}")
+        kw.update(heatmap)
+    else:
+        raise ValueError(f"{who}: None, a kind or a dict of {', '.join(HEATMAP_KEYS)}")
+    try:
+        orehip.heat_kind(kw["kind"])
+        orehip._heatmap_style(kw["alpha"], kw["alpha_mode"])
+        kw["lut"] = kw["lut"] if isinstance(kw["lut"], str) and kw["lut"] in orehip.HEATMAP_LUTS else orehip.heatmap_lut(kw["lut"])
+    except orehip.OreError as err:
+        raise ValueError(f"{who}: {err}") from err
+    if isinstance(kw["slot"], bool) or not isinstance(kw["slot"], (int, np.integer)) or kw["slot"] < 0:
+        raise ValueError(f"{who}: slot {kw['slot']!r} is a non-negative integer")
+    return kw
+
+
+def _heatmap_fits(kw, engine, who):
+    """What of a checked heatmap= needs the engine: the channel exists, the slot is a class slot of the pass.  Host only."""
+    import orehip
+    what = orehip.heat_kind(kw["kind"])
+    ch = engine.buffer_dims(what["buffers"][0])[2]
+    if what["channel"] != "mean" and what["channel"] >= ch:
+        raise ValueError(f"{who}: {kw['kind']!r}: the buffer has {ch} channels")
+    slots = len(getattr(engine, "class_ids", None) or ()) or 1
+    if kw["slot"] >= slots:
+        raise ValueError(f"{who}: slot {kw['slot']}: the pass has {slots} class slot(s)")
+
+
+def _draw_heatmap(frame, engine, kw, out=None):
+    """The heat map of the engine's last pass over a BGR device frame, on the current stream."""
+    import orehip
+    return orehip.heatmap_draw(frame, engine.heat_source(kw["kind"], kw["slot"]), out=out, lut=kw["lut"], alpha=kw["alpha"],
+                               alpha_mode=kw["alpha_mode"], channel_order="BGR")
 
 
 class TiledPredictor:
@@ -56,7 +106,9 @@ class AsyncPredictor:
 
     put(image, draw=True) -- or draw={overlay_draw keyword arguments} -- also enqueues the detection overlay behind the pass, on the
     same stream, reading the pass's record and its device-side count: the result then carries "vis_image", the annotated frame on the
-    device in the input's channel order (BGR), still with one host wait per frame.
+    device in the input's channel order (BGR), still with one host wait per frame.  put(image, heatmap=kind) -- or a dict, see
+    heatmap_args -- enqueues a heat map of the pass behind it, before the overlay: "vis_image" then shows the heat map with the boxes
+    (if drawn) on top.
 
     1 <= inflight <= 4: a process opens 4 hardware queues by default, and this class does not ask for more.  num_gpus must be 1: one
     process per device is a launcher's job.  The engines are keyed like model.engine(): a `put` that finds the weights or the support
@@ -132,7 +184,7 @@ class AsyncPredictor:
         return kw
 
     @torch.no_grad()
-    def put(self, image, draw=None):
+    def put(self, image, draw=None, heatmap=None):
         import orehip
         if isinstance(image, np.ndarray):
             image = torch.from_numpy(np.ascontiguousarray(image))
@@ -143,7 +195,10 @@ class AsyncPredictor:
             draw_kw = self._draw_args(draw, h, w) if draw else None
         except orehip.OreError as err:
             raise ValueError(f"AsyncPredictor.put: {err}") from err
+        heat_kw = heatmap_args(heatmap, "AsyncPredictor.put: heatmap")
         self._ensure_engines()
+        if heat_kw is not None:
+            _heatmap_fits(heat_kw, self._slots[self._next].engine, "AsyncPredictor.put: heatmap")
         if len(self._pending) == len(self._slots):
             self._done.append(self._complete(self._pending.popleft()))
         slot = self._slots[self._next]                        # completion is first in, first out: the next slot in turn is free
@@ -170,14 +225,18 @@ class AsyncPredictor:
             img = orehip.resize_bilinear_u8(raw, nh, nw, swap_rb=self.input_format == "RGB")
             p.rec = e.detect_classes_begin(img, h, w) if getattr(e, "class_ids", None) else e.detect_begin(img, h, w)
             p.raw = raw
-            if draw_kw is not None:
-                R = e._rec_rows
-                boxes, scores, classes = orehip.record_views(p.rec, R, R)
-                try:                                          # in place on the slot's own upload; a caller's device frame is left as it was
-                    p.vis = orehip.overlay_draw(raw, boxes, scores, classes, slot.count, out=raw if ours else None, **draw_kw)
-                except BaseException:
-                    e.detect_end(p.rec)                       # the pass has begun: end it, so that the engine is free for the next put
-                    raise
+            try:                                              # in place on the slot's own upload; a caller's device frame is left as it was
+                if heat_kw is not None:
+                    p.vis = _draw_heatmap(raw, e, heat_kw, out=raw if ours else None)
+                    ours = True                               # the picture so far is this frame's own: the boxes go onto it in place
+                if draw_kw is not None:
+                    R = e._rec_rows
+                    boxes, scores, classes = orehip.record_views(p.rec, R, R)
+                    base = raw if p.vis is None else p.vis
+                    p.vis = orehip.overlay_draw(base, boxes, scores, classes, slot.count, out=base if ours else None, **draw_kw)
+            except BaseException:
+                e.detect_end(p.rec)                           # the pass has begun: end it, so that the engine is free for the next put
+                raise
             slot.event.record(slot.stream)
         self._pending.append(p)
         self._next = (self._next + 1) % len(self._slots)      # only now: a put that raised leaves its slot the next in turn
@@ -228,9 +287,12 @@ class AsyncPredictor:
 
 class VisualizationDemo:
     """VisualizationDemo(cfg, instance_mode=ColorMode.IMAGE, parallel=False) (ref:predictor.py): run_on_image(bgr) -> (predictions,
-    VisImage); run_on_video(frames) -> annotated BGR frames.  parallel=True predicts through an AsyncPredictor, which also draws."""
+    VisImage); run_on_video(frames) -> annotated BGR frames.  parallel=True predicts through an AsyncPredictor, which also draws.
+    heatmap=kind -- "objectness", "attention", "<buffer>[:<channel>]", or a dict (heatmap_args) -- lays that heat map of the detection
+    pass under the boxes; None (the default) draws the boxes alone."""
 
-    def __init__(self, cfg, instance_mode=ColorMode.IMAGE, parallel=False):
+    def __init__(self, cfg, instance_mode=ColorMode.IMAGE, parallel=False, heatmap=None):
+        self.heatmap = heatmap_args(heatmap, "VisualizationDemo: heatmap")
         if instance_mode not in (ColorMode.IMAGE, ColorMode.SEGMENTATION):
             raise NotImplementedError(f"VisualizationDemo: {instance_mode} needs instance masks; boxes only")
         self.instance_mode, self.parallel = instance_mode, bool(parallel)
@@ -251,13 +313,30 @@ class VisualizationDemo:
         """image: [h, w, 3] uint8 in BGR order.  Returns the model's predictions and the drawn VisImage."""
         color_by = "class" if self.instance_mode == ColorMode.SEGMENTATION else "instance"
         if self.parallel:
-            self.predictor.put(image, draw={"color_by": color_by})
+            self.predictor.put(image, draw={"color_by": color_by}, heatmap=self.heatmap)
             out = self.predictor.get()
             return {"instances": out["instances"]}, VisImage(out["vis_image"], "BGR")
         frame = self._upload(image)
         predictions = self.predictor(frame)
+        frame = self._heat(frame)
         vis = Visualizer(frame, self.metadata, instance_mode=self.instance_mode, channel_order="BGR")
         return predictions, vis.draw_instance_predictions(predictions["instances"])
+
+    def _heat(self, frame):
+        """The frame with the heat map of the pass the predictor has just run (a new tensor), or the frame itself without one."""
+        if self.heatmap is None:
+            return frame
+        import orehip
+        who = "VisualizationDemo: heatmap"
+        engine_of = getattr(self.predictor.model, "engine", None)
+        if not callable(engine_of):
+            raise ValueError(f"{who}: this model has no engine whose pass could be drawn")
+        engine = engine_of()                                  # the engine of the current weights and support set: the one the call ran on
+        _heatmap_fits(self.heatmap, engine, who)
+        try:
+            return _draw_heatmap(frame, engine, self.heatmap)
+        except orehip.OreError as err:                        # e.g. the engine has not run a pass
+            raise ValueError(f"{who}: {err}") from err
 
     @staticmethod
     def _frames(source):
@@ -284,7 +363,7 @@ class VisualizationDemo:
                 if pending == self.predictor.default_buffer_size:
                     yield self.predictor.get()["vis_image"].cpu().numpy()
                     pending -= 1
-                self.predictor.put(frame, draw=draw)
+                self.predictor.put(frame, draw=draw, heatmap=self.heatmap)
                 pending += 1
             while pending:
                 yield self.predictor.get()["vis_image"].cpu().numpy()
@@ -294,4 +373,4 @@ class VisualizationDemo:
             for frame in frames:
                 dev = self._upload(frame)
                 predictions = self.predictor(dev)
-                yield video_visualizer.draw_instance_predictions(dev, predictions["instances"]).img.cpu().numpy()
+                yield video_visualizer.draw_instance_predictions(self._heat(dev), predictions["instances"]).img.cpu().numpy()

@@ -842,6 +842,65 @@ int ore_overlay_draw_fwd(const uint8_t* src_hwc, uint8_t* dst_hwc, int32_t h, in
                          int32_t n_palette, int32_t color_by, const uint8_t* names_dev, int32_t n_names, const uint8_t* atlas_dev,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ heat maps ----------------- */
+/* Heat maps of a detection pass drawn over an interleaved [h][w][3] uint8 frame on the device (ref:demo_visualizer.py Have_a_Look /
+ * visualize_grid_attention_v2; ref:fewx/modeling/fsod/debug.py debug_test): where the class-agnostic objectness fired, where the
+ * query-support correlation responded, what a feature channel looks like.  The sources are the level buffers a pass leaves in the engine
+ * (ore_engine_buffer: rows, ch, ld, coff).  Everything is enqueued on `stream`: no host synchronisation, no allocation, at most three
+ * launches (two with norm "unit").
+ * Render contract "heatmap v1" -- bit-exact and independent of scheduling:
+ *   Inputs: the frame; 1 .. 3 level maps, level l being h_l x w_l scalars at stride s_l; the model-input size (in_h, in_w) the maps were
+ *     computed at (the unpadded size); a table lut [256][3] uint8 in the frame's channel order; alpha 0 .. 255 and alpha_mode.
+ *   A, scalar per location (ore_heatmap_levels_fwd; fp32, or bf16 widened exactly): channel = c takes that channel; channel =
+ *     ORE_HEATMAP_MEAN builds four fp32 partial sums over the channels c % 4 == j, each in ascending channel order, combines them as
+ *     (s0 + s1) + (s2 + s3) and divides by (float)ch (ch a multiple of 4; every operation rounded on its own, the division correctly
+ *     rounded).  transform ORE_HEATMAP_SIGMOID then applies 1 / (1 + ore_expf(-v)), the function the proposal decode thresholds with
+ *     (ore_sigmoid_host is the same sequence of operations on the host).
+ *   B, quantisation: norm ORE_HEATMAP_UNIT: q = (int)(fminf(fmaxf(v, 0), 1) * 255.0f) -- truncation, NaN gives 0.  norm
+ *     ORE_HEATMAP_MAX: m = the maximum over all levels of fmaxf(v, 0) (found as an integer maximum over the bits of non-negative
+ *     floats: no float atomics), q = (int)(fminf(fmaxf(v / m, 0), 1) * 255.0f), and m == 0 gives q = 0 everywhere.
+ *   C, per frame pixel (x, y), all integer, for every level: U = floor(((2 x + 1) * in_w * 256) / (2 * w * s_l)) - 128 clamped to [0,
+ *     (w_l - 1) * 256]; x0 = U >> 8, fx = U & 255, x1 = min(x0 + 1, w_l - 1); V, y0, y1, fy likewise from y, in_h, h, h_l;
+ *     top = q[y0][x0] * (256 - fx) + q[y0][x1] * fx, bot the same on row y1, val_l = (top * (256 - fy) + bot * fy + 32768) >> 16;
+ *     v = max over the levels of val_l.  (Cell (i, j) sits at input pixel (j * s + s / 2, i * s + s / 2).)
+ *   D, blend: col = lut[v]; A = alpha (ORE_HEATMAP_ALPHA_CONSTANT) or (alpha * v + 127) / 255 (ORE_HEATMAP_ALPHA_VALUE: cold regions
+ *     stay as they are); out_c = (img_c * (255 - A) + col_c * A + 127) / 255, integer division.  dst_hwc == src_hwc draws in place,
+ *     otherwise the two must not overlap; bytes outside the frame are never written.
+ * ore_heatmap_levels_fwd: stages A + B of n_levels level buffers into the workspace.  src_l = row 0 of level l's buffer ([batch * h_l *
+ *   w_l] rows of ld_l elements, the `ch` channels at element coff_l); level_hw = host [n_levels][2] (h_l, w_l), level_ld / level_coff =
+ *   host [n_levels]; slot = the image of the batch that is read.  The uint8 map of level l is then at workspace +
+ *   ore_heatmap_level_offset(n_levels, level_hw, l), h_l * w_l bytes, rows contiguous.  The workspace
+ *   (ore_heatmap_workspace_bytes(n_levels, level_hw); 0 for dimensions out of range) is private to the stream.
+ * ore_heatmap_draw_fwd: stages C + D from 1 .. 3 such maps (device pointers; level_stride = host [n_levels]).
+ * Limits (ORE_EINVAL): frame sides 1 .. ORE_OVERLAY_MAX_SIDE, frames 4-byte aligned; map sides 1 .. ORE_HEATMAP_MAX_MAP_SIDE; in_h, in_w
+ * 1 .. ORE_HEATMAP_MAX_INPUT_SIDE; strides 1 .. ORE_HEATMAP_MAX_STRIDE; the mean needs ch, ld and coff multiples of 4. */
+#define ORE_HEATMAP_MAX_LEVELS 3
+#define ORE_HEATMAP_MAX_MAP_SIDE 4096
+#define ORE_HEATMAP_MAX_INPUT_SIDE 8192
+#define ORE_HEATMAP_MAX_STRIDE 128
+#define ORE_HEATMAP_MEAN (-1)
+#define ORE_HEATMAP_IDENTITY 0
+#define ORE_HEATMAP_SIGMOID 1
+#define ORE_HEATMAP_UNIT 0
+#define ORE_HEATMAP_MAX 1
+#define ORE_HEATMAP_ALPHA_CONSTANT 0
+#define ORE_HEATMAP_ALPHA_VALUE 1
+size_t ore_heatmap_workspace_bytes(int32_t n_levels, const int32_t* level_hw);
+size_t ore_heatmap_level_offset(int32_t n_levels, const int32_t* level_hw, int32_t level);
+int ore_heatmap_levels_fwd(int32_t n_levels, const void* src0, const void* src1, const void* src2, const int32_t* level_hw,
+                           const int32_t* level_ld, const int32_t* level_coff, int32_t ch, int32_t is_bf16, int32_t batch, int32_t slot,
+                           int32_t channel, int32_t transform, int32_t norm, void* workspace, size_t workspace_bytes, void* stream);
+int ore_heatmap_draw_fwd(const uint8_t* src_hwc, uint8_t* dst_hwc, int32_t h, int32_t w, int32_t n_levels, const uint8_t* map0,
+                         const uint8_t* map1, const uint8_t* map2, const int32_t* level_hw, const int32_t* level_stride, int32_t in_h,
+                         int32_t in_w, const uint8_t* lut_dev, int32_t alpha, int32_t alpha_mode, void* stream);
+/* y[i] = 1 / (1 + ore_expf(-x[i])) on the host: ore_sigmoid of the kernels, operation by operation (fmaf fused, nothing else). */
+int ore_sigmoid_host(const float* x, float* y, int64_t n);
+/* The geometry of the engine's last pass, for readers of its level buffers: out[0 .. 2] = B, H, W (the batch -- the class slots of an
+ * N-way pass -- and the unpadded input size); out[3 + 3 l ..] = h_l, w_l, stride_l for l = 0 .. 2 (p3 .. p5); out[12], out[13] = the
+ * pass serial's low 31 bits and the bits above: a count of the passes the engine has begun, so that a reader can tell that the buffers
+ * it took views of have been written again.  out[14], out[15] = 0. */
+int ore_engine_last_geometry(ore_engine* e, int32_t out[16]);
+
 /* ------------------------------------------------------------------ tiled inference ----------- */
 /* The device side of TiledInference (fewx/modeling/tiled_inference.py): a frame larger than one detector pass is cut into overlapping
  * tiles at native resolution, every tile (and, optionally, the resized full frame) is one source of detection rows, and the rows of all

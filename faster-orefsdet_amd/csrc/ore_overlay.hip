@@ -11,6 +11,8 @@
 //                      touches does no pixel traffic.
 // All pixel arithmetic is integer; no atomics, no dependence on block order: the picture is bit-exact and the same run to run.
 // Compiled with -ffp-contract=off: the area and the percentage are single fp32 operations, each rounded on its own.
+// "overlay v1, track colouring" (ore_overlay_draw_ids_fwd, color_by 2): only k_overlay_prepare learns it -- a row with a negative id is
+// not drawn, the colour comes from the id and "#<id> " goes in front of the text; k_overlay_draw is the same kernel.
 #include "ore_common.h"
 
 namespace {
@@ -41,7 +43,7 @@ __host__ __device__ inline Layout overlay_layout(int max_rows) {
 }
 
 struct PrepArgs {
-    const float* boxes; const float* scores; const int64_t* classes; const int32_t* n_dev; int32_t n_host, max_rows;
+    const float* boxes; const float* scores; const int64_t* classes; const int64_t* ids; const int32_t* n_dev; int32_t n_host, max_rows;
     int32_t h, w; float score_thresh; int32_t L, S;
     const uint8_t* palette; int32_t n_palette, color_by; const uint8_t* names; int32_t n_names;
     int32_t* count; Inst* inst; uint8_t* text;
@@ -61,7 +63,9 @@ __global__ __launch_bounds__(OV_PREP_T) void k_overlay_prepare(const PrepArgs a)
     f32x4 b = {0.f, 0.f, 0.f, 0.f};
     float sc = 0.f, area = 0.f;
     int X0 = 0, Y0 = 0, X1 = -1, Y1 = -1, ok = 0;
-    if (i < n) {
+    const bool by_track = a.color_by == 2;
+    const long long id = (by_track && i < n) ? (long long)a.ids[i] : 0ll;
+    if (i < n && id >= 0) {
         b = *reinterpret_cast<const f32x4*>(a.boxes + (size_t)i * 4);
         sc = a.scores[i];
         if (finite32(b.x) && finite32(b.y) && finite32(b.z) && finite32(b.w) && finite32(sc) && sc >= a.score_thresh) {
@@ -87,7 +91,7 @@ __global__ __launch_bounds__(OV_PREP_T) void k_overlay_prepare(const PrepArgs a)
             rank += (v.w > area || (v.w == area && j + 3 < i)) ? 1 : 0;
         }
         const long long cls = a.classes ? (long long)a.classes[i] : 0ll;
-        long long ci = (a.color_by ? cls : (long long)i) % a.n_palette;
+        long long ci = (by_track ? id : a.color_by ? cls : (long long)i) % a.n_palette;
         if (ci < 0) ci += a.n_palette;
         const uint8_t* pc = a.palette + ci * 3;
         uint32_t col = 0, tcol = 0;
@@ -102,18 +106,26 @@ __global__ __launch_bounds__(OV_PREP_T) void k_overlay_prepare(const PrepArgs a)
         if (a.S >= 1) {
             uint8_t* t = a.text + (size_t)rank * OV_TEXT;
             int len = 0;
+            auto put = [&](uint8_t ch) { if (len < OV_TEXT) t[len++] = ch; };    // the cut at 40 characters: nothing is written past it
+            if (by_track) {                                   // "#" + decimal(id) + " ": up to 21 characters
+                put('#');
+                unsigned long long div = 1ull;
+                while ((unsigned long long)id / div >= 10ull) div *= 10ull;
+                for (; div > 0ull; div /= 10ull) put((uint8_t)('0' + ((unsigned long long)id / div) % 10ull));
+                put(' ');
+            }
+            const int len0 = len;
             if (a.names && cls >= 0 && cls < a.n_names) {
                 const uint8_t* nm = a.names + (size_t)cls * OV_NAME;
-                while (len < OV_NAME && nm[len] != 0) { t[len] = nm[len]; ++len; }
+                for (int k = 0; k < OV_NAME && nm[k] != 0; ++k) put(nm[k]);
             }
-            if (len > 0) t[len++] = ' ';
+            if (len > len0) put(' ');
             const float p100 = sc * 100.0f;
             const int pct = (int)fminf(fmaxf(rintf(p100), 0.0f), 100.0f);
-            if (pct >= 100) t[len++] = '1';
-            if (pct >= 10) t[len++] = (uint8_t)('0' + (pct / 10) % 10);
-            t[len++] = (uint8_t)('0' + pct % 10);
-            t[len++] = '%';
-            if (len > OV_TEXT) len = OV_TEXT;                 // 32 + 1 + 3 + 1 = 37: never cuts
+            if (pct >= 100) put('1');
+            if (pct >= 10) put((uint8_t)('0' + (pct / 10) % 10));
+            put((uint8_t)('0' + pct % 10));
+            put('%');                                         // without an id 32 + 1 + 3 + 1 = 37: never cuts
             q.len = len;
             q.lw = len * 6 * a.S + 2 * a.S;
             q.lh = 13 * a.S;
@@ -262,37 +274,38 @@ extern "C" size_t ore_overlay_workspace_bytes(int32_t max_rows) {
     return max_rows >= 0 && max_rows <= OV_MAX_ROWS ? overlay_layout(max_rows).total : 0;
 }
 
-extern "C" int ore_overlay_draw_fwd(const uint8_t* src_hwc, uint8_t* dst_hwc, int32_t h, int32_t w, const float* boxes, const float* scores,
-                                    const int64_t* classes, const int32_t* n_dev, int32_t n_host, int32_t max_rows, float score_thresh,
-                                    int32_t line_width, int32_t text_scale, int32_t edge_alpha, int32_t label_alpha,
-                                    const uint8_t* palette_dev, int32_t n_palette, int32_t color_by, const uint8_t* names_dev,
-                                    int32_t n_names, const uint8_t* atlas_dev, void* workspace, size_t workspace_bytes, void* stream) {
-    ORE_CHECK_ARG(src_hwc && dst_hwc && palette_dev && workspace, "ore_overlay_draw_fwd: null pointer");
-    ORE_CHECK_ARG(h >= 1 && h <= ORE_OVERLAY_MAX_SIDE && w >= 1 && w <= ORE_OVERLAY_MAX_SIDE, "ore_overlay_draw_fwd: frame %dx%d, sides 1 .. %d", h, w,
+// both entries: color_by 0 .. 2 and ids as k_overlay_prepare takes them, checked by the caller; `who` names the entry in messages
+static int overlay_draw(const char* who, const uint8_t* src_hwc, uint8_t* dst_hwc, int32_t h, int32_t w, const float* boxes, const float* scores,
+                        const int64_t* classes, const int64_t* ids, const int32_t* n_dev, int32_t n_host, int32_t max_rows, float score_thresh,
+                        int32_t line_width, int32_t text_scale, int32_t edge_alpha, int32_t label_alpha,
+                        const uint8_t* palette_dev, int32_t n_palette, int32_t color_by, const uint8_t* names_dev,
+                        int32_t n_names, const uint8_t* atlas_dev, void* workspace, size_t workspace_bytes, void* stream) {
+    ORE_CHECK_ARG(src_hwc && dst_hwc && palette_dev && workspace, "%s: null pointer", who);
+    ORE_CHECK_ARG(h >= 1 && h <= ORE_OVERLAY_MAX_SIDE && w >= 1 && w <= ORE_OVERLAY_MAX_SIDE, "%s: frame %dx%d, sides 1 .. %d", who, h, w,
                   ORE_OVERLAY_MAX_SIDE);
-    ORE_CHECK_ARG(max_rows >= 0 && max_rows <= OV_MAX_ROWS && (n_dev || n_host >= 0), "ore_overlay_draw_fwd: max_rows %d (0 .. %d), n_host %d", max_rows,
+    ORE_CHECK_ARG(max_rows >= 0 && max_rows <= OV_MAX_ROWS && (n_dev || n_host >= 0), "%s: max_rows %d (0 .. %d), n_host %d", who, max_rows,
                   OV_MAX_ROWS, n_host);
-    ORE_CHECK_ARG(max_rows == 0 || (boxes && scores), "ore_overlay_draw_fwd: null rows");
-    ORE_CHECK_ARG(line_width >= 1 && line_width <= 16 && text_scale >= 0 && text_scale <= 8, "ore_overlay_draw_fwd: line_width %d (1 .. 16), text_scale %d (0 .. 8)",
+    ORE_CHECK_ARG(max_rows == 0 || (boxes && scores), "%s: null rows", who);
+    ORE_CHECK_ARG(line_width >= 1 && line_width <= 16 && text_scale >= 0 && text_scale <= 8, "%s: line_width %d (1 .. 16), text_scale %d (0 .. 8)", who,
                   line_width, text_scale);
-    ORE_CHECK_ARG(edge_alpha >= 0 && edge_alpha <= 255 && label_alpha >= 0 && label_alpha <= 255, "ore_overlay_draw_fwd: edge_alpha %d, label_alpha %d (0 .. 255)",
+    ORE_CHECK_ARG(edge_alpha >= 0 && edge_alpha <= 255 && label_alpha >= 0 && label_alpha <= 255, "%s: edge_alpha %d, label_alpha %d (0 .. 255)", who,
                   edge_alpha, label_alpha);
-    ORE_CHECK_ARG(n_palette >= 1 && n_palette <= 256 && n_names >= 0, "ore_overlay_draw_fwd: n_palette %d (1 .. 256), n_names %d (>= 0)", n_palette, n_names);
-    ORE_CHECK_ARG(text_scale == 0 || atlas_dev, "ore_overlay_draw_fwd: labels need the glyph atlas");
-    ORE_CHECK_ARG(score_thresh == score_thresh, "ore_overlay_draw_fwd: score_thresh is NaN");
+    ORE_CHECK_ARG(n_palette >= 1 && n_palette <= 256 && n_names >= 0, "%s: n_palette %d (1 .. 256), n_names %d (>= 0)", who, n_palette, n_names);
+    ORE_CHECK_ARG(text_scale == 0 || atlas_dev, "%s: labels need the glyph atlas", who);
+    ORE_CHECK_ARG(score_thresh == score_thresh, "%s: score_thresh is NaN", who);
     const size_t bytes = (size_t)h * w * 3;
     const uintptr_t ps = (uintptr_t)src_hwc, pd = (uintptr_t)dst_hwc;
-    ORE_CHECK_ARG(ps % 4 == 0 && pd % 4 == 0, "ore_overlay_draw_fwd: the frames must be 4-byte aligned");
-    ORE_CHECK_ARG(ps == pd || (ps < pd ? pd - ps : ps - pd) >= bytes, "ore_overlay_draw_fwd: src and dst overlap (equal = in place, else disjoint)");
+    ORE_CHECK_ARG(ps % 4 == 0 && pd % 4 == 0, "%s: the frames must be 4-byte aligned", who);
+    ORE_CHECK_ARG(ps == pd || (ps < pd ? pd - ps : ps - pd) >= bytes, "%s: src and dst overlap (equal = in place, else disjoint)", who);
     const Layout lay = overlay_layout(max_rows);
     if (workspace_bytes < lay.total) {
-        ore_set_error("ore_overlay_draw_fwd: workspace %zu < %zu", workspace_bytes, lay.total);
+        ore_set_error("%s: workspace %zu < %zu", who, workspace_bytes, lay.total);
         return ORE_ENOMEM;
     }
     char* ws = static_cast<char*>(workspace);
     hipStream_t st = (hipStream_t)stream;
-    PrepArgs p{boxes, scores, classes, n_dev, n_host, max_rows, h, w, score_thresh, line_width, text_scale,
-               palette_dev, n_palette, color_by ? 1 : 0, names_dev, names_dev ? n_names : 0,
+    PrepArgs p{boxes, scores, classes, ids, n_dev, n_host, max_rows, h, w, score_thresh, line_width, text_scale,
+               palette_dev, n_palette, color_by, names_dev, names_dev ? n_names : 0,
                (int32_t*)(ws + lay.count), (Inst*)(ws + lay.inst), (uint8_t*)(ws + lay.text)};
     k_overlay_prepare<<<1, OV_PREP_T, 0, st>>>(p);
     int rc;
@@ -303,4 +316,26 @@ extern "C" int ore_overlay_draw_fwd(const uint8_t* src_hwc, uint8_t* dst_hwc, in
     k_overlay_draw<<<(unsigned)((npix + OV_T * OV_PX - 1) / (OV_T * OV_PX)), OV_T, 0, st>>>(
         d, src_hwc, dst_hwc, (const int32_t*)(ws + lay.count), (const Inst*)(ws + lay.inst), (const uint8_t*)(ws + lay.text), atlas_dev);
     return ore_launch_status("k_overlay_draw");
+}
+
+extern "C" int ore_overlay_draw_fwd(const uint8_t* src_hwc, uint8_t* dst_hwc, int32_t h, int32_t w, const float* boxes, const float* scores,
+                                    const int64_t* classes, const int32_t* n_dev, int32_t n_host, int32_t max_rows, float score_thresh,
+                                    int32_t line_width, int32_t text_scale, int32_t edge_alpha, int32_t label_alpha,
+                                    const uint8_t* palette_dev, int32_t n_palette, int32_t color_by, const uint8_t* names_dev,
+                                    int32_t n_names, const uint8_t* atlas_dev, void* workspace, size_t workspace_bytes, void* stream) {
+    return overlay_draw("ore_overlay_draw_fwd", src_hwc, dst_hwc, h, w, boxes, scores, classes, nullptr, n_dev, n_host, max_rows, score_thresh,
+                        line_width, text_scale, edge_alpha, label_alpha, palette_dev, n_palette, color_by ? 1 : 0, names_dev, n_names,
+                        atlas_dev, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ore_overlay_draw_ids_fwd(const uint8_t* src_hwc, uint8_t* dst_hwc, int32_t h, int32_t w, const float* boxes, const float* scores,
+                                        const int64_t* classes, const int64_t* ids, const int32_t* n_dev, int32_t n_host, int32_t max_rows,
+                                        float score_thresh, int32_t line_width, int32_t text_scale, int32_t edge_alpha, int32_t label_alpha,
+                                        const uint8_t* palette_dev, int32_t n_palette, int32_t color_by, const uint8_t* names_dev,
+                                        int32_t n_names, const uint8_t* atlas_dev, void* workspace, size_t workspace_bytes, void* stream) {
+    ORE_CHECK_ARG(color_by >= 0 && color_by <= 2, "ore_overlay_draw_ids_fwd: color_by %d (0 instance, 1 class, 2 track)", color_by);
+    ORE_CHECK_ARG(color_by != 2 || max_rows == 0 || ids, "ore_overlay_draw_ids_fwd: color_by 2 (track) needs ids");
+    return overlay_draw("ore_overlay_draw_ids_fwd", src_hwc, dst_hwc, h, w, boxes, scores, classes, color_by == 2 ? ids : nullptr, n_dev, n_host,
+                        max_rows, score_thresh, line_width, text_scale, edge_alpha, label_alpha, palette_dev, n_palette, color_by, names_dev,
+                        n_names, atlas_dev, workspace, workspace_bytes, stream);
 }

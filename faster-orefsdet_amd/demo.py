@@ -3,7 +3,9 @@
     python demo.py --input a.jpg b.jpg --output out_dir --opts MODEL.WEIGHTS w.pth
 
 --heatmap objectness | attention | <buffer>[:<channel>] (p4, pos3:17, ...) lays that heat map of the detection pass under the boxes
-(--heatmap-alpha, --heatmap-colormap jet | gray).  Images are decoded with Pillow and drawn on the device.  Video (--video-input, --webcam) needs OpenCV to decode and to show frames;
+(--heatmap-alpha, --heatmap-colormap jet | gray).  --track follows the detections from frame to frame (ids that persist, boxes coloured and
+labelled by them) over a video, or over several --input images taken as a sequence in the given order, and prints the number of tracks
+started.  Images are decoded with Pillow and drawn on the device.  Video (--video-input, --webcam) needs OpenCV to decode and to show frames;
 this package neither ships nor requires it, and the two flags say so when it is missing."""
 import argparse
 import glob
@@ -24,6 +26,8 @@ def get_parser():
                         "with an optional channel such as p4 or pos3:17")
     parser.add_argument("--heatmap-alpha", type=int, default=128, metavar="A", help="the heat map's opacity, 0 .. 255 (default: %(default)s)")
     parser.add_argument("--heatmap-colormap", default="jet", choices=("jet", "gray"), help="the heat map's colour table (default: %(default)s)")
+    parser.add_argument("--track", action="store_true", help="follow the detections across the frames: ids that persist, colours and labels by id; "
+                        "needs --video-input, --webcam or several --input frames (a sequence in the given order); prints the tracks started")
     parser.add_argument("--video-input", metavar="VIDEO", help="annotate a video file instead (needs OpenCV)")
     parser.add_argument("--webcam", action="store_true", help="annotate the first camera's frames instead (needs OpenCV)")
     parser.add_argument("--opts", nargs=argparse.REMAINDER, default=[], metavar="KEY VALUE", help="config overrides, e.g. MODEL.WEIGHTS model.pth; must come last")
@@ -69,6 +73,19 @@ def run_images(demo, args, log):
         log.info("%s: %d detections -> %s", path, len(predictions["instances"]), target)
 
 
+def run_sequence(demo, args, log):
+    """--track over image files: the inputs are the frames of one sequence, in the order given."""
+    from PIL import Image
+    from detectron2.data.detection_utils import read_image
+    paths = input_paths(args.input)
+    if len(paths) < 2:
+        sys.exit("demo.py: --track needs a sequence: --video-input, --webcam or at least two --input frames")
+    targets = [output_path(args.output, path, len(paths)) for path in paths]
+    for path, target, frame in zip(paths, targets, demo.run_on_video(read_image(path, format="BGR") for path in paths)):
+        Image.fromarray(frame[:, :, ::-1].copy()).save(target)
+        log.info("%s -> %s", path, target)
+
+
 def run_video(demo, args, cv2):
     capture = cv2.VideoCapture(0 if args.webcam else args.video_input)
     writer = None
@@ -104,6 +121,8 @@ def main(argv=None):
                      "Annotate image files with --input, or hand your own frames to predictor.VisualizationDemo.run_on_video.")
     elif not args.input:
         sys.exit("demo.py: nothing to do; name images with --input (or a video with --video-input / --webcam)")
+    elif args.track and len(args.input) < 2 and not any(ch in args.input[0] for ch in "*?["):
+        sys.exit("demo.py: --track needs a sequence: --video-input, --webcam or at least two --input frames")
     elif not args.output:
         sys.exit("demo.py: --input needs --output: pictures are written to files, there is no window to show them in")
 
@@ -115,11 +134,15 @@ def main(argv=None):
         heatmap = heatmap_args(heatmap, "--heatmap")          # the flags alone, before anything is built
     except ValueError as err:
         sys.exit(f"demo.py: {err}")
-    demo = VisualizationDemo(setup_cfg(args), heatmap=heatmap)
+    demo = VisualizationDemo(setup_cfg(args), heatmap=heatmap, track=args.track)
     if video:
         run_video(demo, args, cv2)
+    elif args.track:
+        run_sequence(demo, args, log)
     else:
         run_images(demo, args, log)
+    if args.track:
+        print(f"tracks started: {demo.track_stats()['started']}")
 
 
 if __name__ == "__main__":

@@ -51,9 +51,9 @@ class VisImage:
         Image.fromarray(self.get_image()).save(filepath)
 
 
-def draw_boxes(frame, predictions, *, channel_order, names, color_by, score_thresh=0.0):
+def draw_boxes(frame, predictions, *, channel_order, names, color_by, score_thresh=0.0, ids=None):
     """One frame + Instances -> VisImage.  Device Instances: the frame goes to their device and the kernel draws; host Instances:
-    overlay_host.  The frame itself is left as it was."""
+    overlay_host.  The frame itself is left as it was.  ids: the rows' track ids (an orehip.BoxTracker update's) for color_by="track"."""
     import orehip
     if not predictions.has("pred_boxes") or not predictions.has("scores"):
         raise ValueError("the overlay draws pred_boxes with their scores (pred_classes optional)")
@@ -64,6 +64,8 @@ def draw_boxes(frame, predictions, *, channel_order, names, color_by, score_thre
     h, w = int(frame.shape[0]), int(frame.shape[1])
     palette = orehip.OVERLAY_PALETTE if channel_order == "RGB" else np.ascontiguousarray(orehip.OVERLAY_PALETTE[:, ::-1])
     kw = dict(default_overlay_params(h, w), score_thresh=score_thresh, palette=palette, color_by=color_by, names=names)
+    if ids is not None:
+        kw["ids"] = ids.long().contiguous() if torch.is_tensor(ids) else np.asarray(ids, dtype=np.int64)
     if boxes.is_cuda:
         if not torch.is_tensor(frame):
             frame = torch.from_numpy(np.ascontiguousarray(frame))

@@ -2,7 +2,9 @@
 several frames in flight.  Drawing is the package's device overlay (orehip.overlay_draw, render contract "overlay v1"), not matplotlib;
 AsyncPredictor is one process with several engines on several HIP streams, not one process per GPU.  TiledPredictor is DefaultPredictor's
 contract over fewx.modeling.TiledInference, for frames larger than one detector pass.  Both predictors can lay a heat map of the pass
-under the boxes (heatmap=...: orehip.heatmap_draw, render contract "heatmap v1"): objectness, attention or a feature channel."""
+under the boxes (heatmap=...: orehip.heatmap_draw, render contract "heatmap v1"): objectness, attention or a feature channel.
+Both can follow the detections across the frames of a video (track=...: orehip.BoxTracker, association contract "track v1"): ids that
+persist, and boxes coloured and labelled by them."""
 from collections import deque
 
 import numpy as np
@@ -94,7 +96,7 @@ class _Slot:
 
 class _Pass:
     """A frame between `put` and `get`."""
-    __slots__ = ("slot", "rec", "raw", "vis", "hw")
+    __slots__ = ("slot", "rec", "raw", "vis", "hw", "ids")
 
 
 class AsyncPredictor:
@@ -108,7 +110,10 @@ class AsyncPredictor:
     same stream, reading the pass's record and its device-side count: the result then carries "vis_image", the annotated frame on the
     device in the input's channel order (BGR), still with one host wait per frame.  put(image, heatmap=kind) -- or a dict, see
     heatmap_args -- enqueues a heat map of the pass behind it, before the overlay: "vis_image" then shows the heat map with the boxes
-    (if drawn) on top.
+    (if drawn) on top.  put(image, track=tracker) -- an orehip.BoxTracker on the model's device, the caller's -- enqueues the tracker's
+    update behind the pass, on the same stream, on the pending record and the device-side count: the result's Instances then carries
+    track_ids, and a drawn frame is coloured and labelled by them (color_by "track") unless draw says otherwise.  The tracker orders
+    its updates across the slots' streams on the device, so the frames are associated in `put` order with the passes still overlapping.
 
     1 <= inflight <= 4: a process opens 4 hardware queues by default, and this class does not ask for more.  num_gpus must be 1: one
     process per device is a launcher's job.  The engines are keyed like model.engine(): a `put` that finds the weights or the support
@@ -163,11 +168,11 @@ class AsyncPredictor:
     # ---- put / get ----------------------------------------------------------------------------------------------
     DRAW_KEYS = ("score_thresh", "line_width", "text_scale", "edge_alpha", "label_alpha", "palette", "color_by", "names")
 
-    def _draw_args(self, draw, h, w):
+    def _draw_args(self, draw, h, w, tracked=False):
         """The overlay's keyword arguments of one frame, checked here, before anything of the frame is enqueued: what can be
         refused on the host is refused while the slot's engine is still idle."""
         import orehip
-        kw = dict(default_overlay_params(h, w), names=thing_classes(self.metadata), color_by="instance",
+        kw = dict(default_overlay_params(h, w), names=thing_classes(self.metadata), color_by="track" if tracked else "instance",
                   palette=np.ascontiguousarray(orehip.OVERLAY_PALETTE[:, ::-1]))           # the frame is BGR
         if isinstance(draw, dict):
             unknown = sorted(set(draw) - set(self.DRAW_KEYS))
@@ -180,23 +185,26 @@ class AsyncPredictor:
                 and 0 <= int(kw.get("label_alpha", 0)) <= 255):
             raise ValueError("AsyncPredictor.put: line_width 1 .. 16, text_scale 0 .. 8, alphas 0 .. 255")
         kw["palette"] = orehip._overlay_palette(kw["palette"])
-        orehip._overlay_color_by(kw["color_by"])
+        if orehip._overlay_color_by(kw["color_by"], has_ids=False) == 2 and not tracked:
+            raise ValueError('AsyncPredictor.put: color_by "track" needs track=')
         return kw
 
     @torch.no_grad()
-    def put(self, image, draw=None, heatmap=None):
+    def put(self, image, draw=None, heatmap=None, track=None):
         import orehip
         if isinstance(image, np.ndarray):
             image = torch.from_numpy(np.ascontiguousarray(image))
         if not torch.is_tensor(image) or image.dim() != 3 or image.shape[2] != 3 or image.dtype != torch.uint8:
             raise ValueError("AsyncPredictor.put takes an [h, w, 3] uint8 BGR image")
         h, w = int(image.shape[0]), int(image.shape[1])
+        if track is not None and not (isinstance(track, orehip.BoxTracker) and track.device == torch.device(self.model.device)):
+            raise ValueError("AsyncPredictor.put: track is an orehip.BoxTracker on the model's device")
         try:
-            draw_kw = self._draw_args(draw, h, w) if draw else None
+            draw_kw = self._draw_args(draw, h, w, track is not None) if draw else None
         except orehip.OreError as err:
             raise ValueError(f"AsyncPredictor.put: {err}") from err
         heat_kw = heatmap_args(heatmap, "AsyncPredictor.put: heatmap")
-        self._ensure_engines()
+        self._ensure_engines()                                # rebuilds engines if need be; a tracker is the caller's and stays as it is
         if heat_kw is not None:
             _heatmap_fits(heat_kw, self._slots[self._next].engine, "AsyncPredictor.put: heatmap")
         if len(self._pending) == len(self._slots):
@@ -204,7 +212,7 @@ class AsyncPredictor:
         slot = self._slots[self._next]                        # completion is first in, first out: the next slot in turn is free
         m, e = self.model, slot.engine
         p = _Pass()
-        p.slot, p.hw, p.vis = slot, (h, w), None
+        p.slot, p.hw, p.vis, p.ids = slot, (h, w), None, None
         if image.is_cuda:                                     # the frame was produced on the caller's stream: the slot's stream follows it
             slot.stream.wait_stream(torch.cuda.current_stream(image.device))
         with torch.cuda.device(m.device), torch.cuda.stream(slot.stream):
@@ -229,11 +237,14 @@ class AsyncPredictor:
                 if heat_kw is not None:
                     p.vis = _draw_heatmap(raw, e, heat_kw, out=raw if ours else None)
                     ours = True                               # the picture so far is this frame's own: the boxes go onto it in place
-                if draw_kw is not None:
+                if track is not None or draw_kw is not None:
                     R = e._rec_rows
                     boxes, scores, classes = orehip.record_views(p.rec, R, R)
+                if track is not None:                         # the one launch behind the pass: every check that can refuse is behind us
+                    p.ids = track.update(boxes, scores, classes, slot.count)
+                if draw_kw is not None:
                     base = raw if p.vis is None else p.vis
-                    p.vis = orehip.overlay_draw(base, boxes, scores, classes, slot.count, out=base if ours else None, **draw_kw)
+                    p.vis = orehip.overlay_draw(base, boxes, scores, classes, slot.count, out=base if ours else None, ids=p.ids, **draw_kw)
             except BaseException:
                 e.detect_end(p.rec)                           # the pass has begun: end it, so that the engine is free for the next put
                 raise
@@ -254,6 +265,9 @@ class AsyncPredictor:
         res.pred_boxes = Boxes(boxes)
         res.scores = scores
         res.pred_classes = classes
+        if p.ids is not None:
+            p.ids.record_stream(cur)
+            res.track_ids = p.ids[:len(scores)]
         out = {"instances": res}
         if p.vis is not None:
             p.vis.record_stream(cur)
@@ -270,8 +284,8 @@ class AsyncPredictor:
     def __len__(self):
         return len(self._pending) + len(self._done)
 
-    def __call__(self, image):
-        self.put(image)
+    def __call__(self, image, track=None):
+        self.put(image, track=track)
         return self.get()
 
     def shutdown(self):
@@ -289,10 +303,13 @@ class VisualizationDemo:
     """VisualizationDemo(cfg, instance_mode=ColorMode.IMAGE, parallel=False) (ref:predictor.py): run_on_image(bgr) -> (predictions,
     VisImage); run_on_video(frames) -> annotated BGR frames.  parallel=True predicts through an AsyncPredictor, which also draws.
     heatmap=kind -- "objectness", "attention", "<buffer>[:<channel>]", or a dict (heatmap_args) -- lays that heat map of the detection
-    pass under the boxes; None (the default) draws the boxes alone."""
+    pass under the boxes; None (the default) draws the boxes alone.  track=True follows the detections across the frames of
+    run_on_video (an orehip.BoxTracker, reset at the start of every call): ids that persist, boxes coloured and labelled by them;
+    track_stats() then counts the tracks started.  run_on_image ignores it."""
 
-    def __init__(self, cfg, instance_mode=ColorMode.IMAGE, parallel=False, heatmap=None):
+    def __init__(self, cfg, instance_mode=ColorMode.IMAGE, parallel=False, heatmap=None, track=False):
         self.heatmap = heatmap_args(heatmap, "VisualizationDemo: heatmap")
+        self.track, self.tracker = bool(track), None
         if instance_mode not in (ColorMode.IMAGE, ColorMode.SEGMENTATION):
             raise NotImplementedError(f"VisualizationDemo: {instance_mode} needs instance masks; boxes only")
         self.instance_mode, self.parallel = instance_mode, bool(parallel)
@@ -338,6 +355,21 @@ class VisualizationDemo:
         except orehip.OreError as err:                        # e.g. the engine has not run a pass
             raise ValueError(f"{who}: {err}") from err
 
+    def _tracker(self):
+        """The demo's tracker on the model's device, built on first use and empty at the start of every video."""
+        import orehip
+        if self.tracker is None:
+            self.tracker = orehip.BoxTracker(self.predictor.model.device)
+        else:
+            self.tracker.reset()
+        return self.tracker
+
+    def track_stats(self):
+        """BoxTracker.stats() of the last run_on_video: tracks, started (the particle count), frames, dropped.  One host sync."""
+        if self.tracker is None:
+            return {"tracks": 0, "started": 0, "frames": 0, "dropped": 0}
+        return self.tracker.stats()
+
     @staticmethod
     def _frames(source):
         """A generator over the frames of `source`: an iterable as it is; a capture-like object (isOpened() / read() returning
@@ -356,20 +388,23 @@ class VisualizationDemo:
         """video: an iterable of BGR frames, or an object with isOpened() / read().  Yields the annotated BGR frames ([h, w, 3] uint8
         numpy), in order; parallel=True keeps AsyncPredictor.default_buffer_size frames in flight."""
         frames = self._frames(video)
+        tracker = None
+        if self.track:
+            tracker = self._tracker()
         if self.parallel:
-            draw = {"color_by": "class"}
+            draw = {"color_by": "track" if tracker is not None else "class"}
             pending = 0
             for frame in frames:
                 if pending == self.predictor.default_buffer_size:
                     yield self.predictor.get()["vis_image"].cpu().numpy()
                     pending -= 1
-                self.predictor.put(frame, draw=draw, heatmap=self.heatmap)
+                self.predictor.put(frame, draw=draw, heatmap=self.heatmap, track=tracker)
                 pending += 1
             while pending:
                 yield self.predictor.get()["vis_image"].cpu().numpy()
                 pending -= 1
         else:
-            video_visualizer = VideoVisualizer(self.metadata, self.instance_mode, channel_order="BGR")
+            video_visualizer = VideoVisualizer(self.metadata, self.instance_mode, channel_order="BGR", track=tracker if tracker is not None else False)
             for frame in frames:
                 dev = self._upload(frame)
                 predictions = self.predictor(dev)

@@ -841,6 +841,54 @@ int ore_overlay_draw_fwd(const uint8_t* src_hwc, uint8_t* dst_hwc, int32_t h, in
                          int32_t line_width, int32_t text_scale, int32_t edge_alpha, int32_t label_alpha, const uint8_t* palette_dev,
                          int32_t n_palette, int32_t color_by, const uint8_t* names_dev, int32_t n_names, const uint8_t* atlas_dev,
                          void* workspace, size_t workspace_bytes, void* stream);
+/* "overlay v1, track colouring": ore_overlay_draw_fwd with one more row array, ids [max_rows] int64 (the ids_out of
+ * ore_track_update_fwd), and one more colour source, color_by == 2 ("track").  With color_by == 2 a row is drawn iff it is drawn by
+ * overlay v1 and ids[i] >= 0; its colour is c_i = palette[ids[i] mod n_palette]; its label text is "#" + decimal(ids[i]) + " " in front
+ * of the text overlay v1 defines, cut at the same 40 characters, and the label rectangle follows from the new text's length.  Draw
+ * order, outline, label geometry and blends are overlay v1's.  color_by 0 and 1 ignore ids (NULL allowed) and give the bytes of
+ * ore_overlay_draw_fwd; color_by == 2 with ids == NULL, or a color_by outside 0 .. 2, is ORE_EINVAL. */
+int ore_overlay_draw_ids_fwd(const uint8_t* src_hwc, uint8_t* dst_hwc, int32_t h, int32_t w, const float* boxes, const float* scores,
+                             const int64_t* classes, const int64_t* ids, const int32_t* n_dev, int32_t n_host, int32_t max_rows,
+                             float score_thresh, int32_t line_width, int32_t text_scale, int32_t edge_alpha, int32_t label_alpha,
+                             const uint8_t* palette_dev, int32_t n_palette, int32_t color_by, const uint8_t* names_dev, int32_t n_names,
+                             const uint8_t* atlas_dev, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ detection tracking -------- */
+/* Detections followed from frame to frame on the device: every row of a frame gets the id of the track it continues, or a new one.
+ * The update is enqueued on `stream` -- one launch, no host synchronisation, no allocation -- and reads the rows where a detection pass
+ * left them, with ore_overlay_draw_fwd's conventions: boxes [rows][4] fp32 xyxy, scores [rows], classes [rows] int64 (NULL: all 0),
+ * n = min(*n_dev if n_dev else n_host, max_rows) (a negative count is 0).  ids_out [max_rows] int64 serves ore_overlay_draw_ids_fwd as
+ * it is.  The contract has the shape of detectron2's VideoVisualizer._assign_colors (IoU association among equal labels, a time to live
+ * for a track the detector missed) but is one-to-one and fully ordered, which that heuristic is not: no equality with it is claimed.
+ * Association contract "track v1" -- bit-exact, a function of the inputs alone:
+ *   State: an ordered list of m <= capacity tracks (box[4] fp32 xyxy, class int64, id int64, ttl int32), and next_id (int64, starts at
+ *     0), frames, dropped (int64).  capacity 1 .. ORE_TRACK_MAX_TRACKS.
+ *   Live rows: row i < n is live iff its four coordinates and its score are finite and score >= score_thresh (fp32).  Every other row
+ *     of 0 .. max_rows - 1 gets ids_out[i] = -1 and takes no part.
+ *   IoU(t, d), fp32, every operation rounded on its own: area = (x1 - x0) * (y1 - y0); iw = min(x1t, x1d) - max(x0t, x0d), ih likewise;
+ *     inter = (iw > 0 && ih > 0) ? iw * ih : 0; iou = inter > 0 ? inter / ((area_t + area_d) - inter) : 0.
+ *   Candidates: (track t, live row d) with iou > iou_thresh (strict; a NaN compares false) and, unless class_aware == 0, equal classes.
+ *   Matching: the candidates ordered by (iou descending, track slot ascending, row ascending) are taken greedily: a pair is accepted
+ *     iff neither its track nor its row has been taken.  A matched row takes its track's id.
+ *   New ids: the unmatched live rows get next_id, next_id + 1, ... in row order; next_id advances by their number.
+ *   The new list: first the live rows in row order (the row's box and class, its id, ttl = the call's ttl), then the unmatched old
+ *     tracks in their order with ttl - 1, those with a new ttl > 0 only.  A list longer than capacity is cut at capacity -- the tail,
+ *     the longest-unmatched survivors, is lost -- and dropped grows by the number cut (capacity >= max_rows never loses a live row).
+ *     frames += 1.
+ * The state is one caller-owned device buffer of ore_track_state_bytes(capacity) bytes (0 for a capacity out of range), 16-byte
+ * aligned: a 32-byte header { int32 m, capacity; int64 next_id, frames, dropped }, then boxes [capacity][4] fp32, classes [capacity]
+ * int64, ids [capacity] int64, ttl [capacity] int32, rounded up to 16 bytes.  Slots m .. capacity - 1 hold zeros.  ore_track_reset
+ * writes the empty state; only it and ore_track_update_fwd write the buffer, and `capacity` is the same in every call on one buffer.
+ * ore_track_workspace_bytes is what `workspace` must hold (0: the update works in LDS and registers; NULL is then allowed).
+ * Limits (ORE_EINVAL before any launch): capacity 1 .. ORE_TRACK_MAX_TRACKS, max_rows 0 .. ore_det_record_rows(), ttl 1 .. 1 << 20,
+ * iou_thresh finite and >= 0, score_thresh not NaN; state, ids_out and the row arrays pairwise disjoint; boxes 16-byte aligned. */
+#define ORE_TRACK_MAX_TRACKS 1024
+size_t ore_track_state_bytes(int32_t capacity);
+int ore_track_reset(void* state, int32_t capacity, void* stream);
+size_t ore_track_workspace_bytes(int32_t capacity, int32_t max_rows);
+int ore_track_update_fwd(void* state, int32_t capacity, const float* boxes, const float* scores, const int64_t* classes,
+                         const int32_t* n_dev, int32_t n_host, int32_t max_rows, float score_thresh, float iou_thresh, int32_t ttl,
+                         int32_t class_aware, int64_t* ids_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ heat maps ----------------- */
 /* Heat maps of a detection pass drawn over an interleaved [h][w][3] uint8 frame on the device (ref:demo_visualizer.py Have_a_Look /

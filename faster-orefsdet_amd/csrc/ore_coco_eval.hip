@@ -13,17 +13,16 @@
 //   k_unit_match    one wave per unit: fp64 IoU matrix (LDS, or global past the LDS size), then one lane per (area, threshold) chain
 //                   running the greedy match over the unit's detections; writes a 2-bit code per (unit, area, threshold, rank) and the
 //                   per-area count of non-ignored GTs; also the unit's sort keys
-//   k_sort_*        bitonic sort of the kept detections by (category, score descending, image, rank) -- a unique key
+//   k_bitonic_*     bitonic sort of the kept detections by (category, score descending, image, rank) -- a unique key
 //   k_elem_flags    per sorted detection: TP / FP bit masks over the (area, threshold) chains, rank, score
 //   k_accumulate    one block per (threshold, category, area, maxDet): integer prefix sums of TP / FP, recall and precision, the
 //                   right-to-left precision envelope and searchsorted(side='left') at the recall thresholds, through recall buckets
-#include "ore_common.h"
+#include "ore_block.h"
 
 namespace {
 
 constexpr int kMaxT = 16, kMaxR = 128, kMaxA = 8, kMaxM = 4;
 constexpr int kMatched = 1, kIgnored = 2;       // per-chain detection code
-constexpr int kSortL = 2048;                    // elements per LDS bitonic block (1024 threads)
 constexpr int kIouLds = 6144;                   // IoU matrix in LDS up to this many fp64 entries
 constexpr int kGtmLds = 8192;                   // GT-matched flags in LDS up to this many bytes (chains x GTs)
 constexpr int kAccThreads = 256, kAccPer = 16;  // accumulate: threads per block, consecutive elements per thread and tile
@@ -41,7 +40,9 @@ struct Key {
     uint64_t hi, lo;   // hi: category << 32 | descending score bits; lo: image << 32 | rank
 };
 
-__device__ __forceinline__ bool key_gt(const Key& a, const Key& b) { return a.hi > b.hi || (a.hi == b.hi && a.lo > b.lo); }
+struct key_gt {
+    __device__ __forceinline__ bool operator()(const Key& a, const Key& b) const { return a.hi > b.hi || (a.hi == b.hi && a.lo > b.lo); }
+};
 
 __device__ __forceinline__ uint32_t score_desc_bits(float s) {
     if (s == 0.0f) s = 0.0f;                    // -0 and +0 compare equal in the reference's sort
@@ -57,40 +58,33 @@ struct Ws {
 
 inline int64_t units_cap(int64_t KI, int64_t N, int64_t G) { return KI < N + G ? KI : N + G; }
 
-inline int64_t sort_size(int64_t N) {
-    int64_t p = kSortL;
-    while (p < N) p <<= 1;
-    return p;
-}
-
 inline Ws ws_layout(int32_t K, int32_t I, int32_t N, int32_t G, int32_t AT, int32_t maxD) {
     Ws w{};
     w.KI = (int64_t)K * I;
     w.U = units_cap(w.KI, N, G);
-    w.P = sort_size(N);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) & ~(size_t)255; return r; };
-    w.hdr = take(256);
-    w.d_cnt = take(w.KI * 4);
-    w.d_fill = take(w.KI * 4);
-    w.d_off = take(w.KI * 4);
-    w.unit_of_pair = take(w.KI * 4);
-    w.ekoff = take((size_t)(K + 1) * 4);
-    w.ukoff = take((size_t)(K + 1) * 4);
-    w.unit_pair = take(w.U * 4);
-    w.unit_eoff = take(w.U * 4);
-    w.unit_det = take(w.U * maxD * 4);
-    w.bucket = take((size_t)N * 4);
-    w.codes = take(w.U * AT * maxD);
-    w.npig = take(w.U * kMaxA * 4);
-    w.gtm = take((size_t)G * AT);
-    w.iou = take((size_t)G * maxD * 8);
-    w.keys = take(w.P * sizeof(Key));
-    w.e_rank = take(w.P * 4);
-    w.e_score = take(w.P * 4);
-    w.e_tp = take(w.P * 8);
-    w.e_fp = take(w.P * 8);
-    w.total = o;
+    w.P = bitonic_size(N);
+    WsCursor c;
+    w.hdr = c.take(256);
+    w.d_cnt = c.take(w.KI * 4);
+    w.d_fill = c.take(w.KI * 4);
+    w.d_off = c.take(w.KI * 4);
+    w.unit_of_pair = c.take(w.KI * 4);
+    w.ekoff = c.take((size_t)(K + 1) * 4);
+    w.ukoff = c.take((size_t)(K + 1) * 4);
+    w.unit_pair = c.take(w.U * 4);
+    w.unit_eoff = c.take(w.U * 4);
+    w.unit_det = c.take(w.U * maxD * 4);
+    w.bucket = c.take((size_t)N * 4);
+    w.codes = c.take(w.U * AT * maxD);
+    w.npig = c.take(w.U * kMaxA * 4);
+    w.gtm = c.take((size_t)G * AT);
+    w.iou = c.take((size_t)G * maxD * 8);
+    w.keys = c.take(w.P * sizeof(Key));
+    w.e_rank = c.take(w.P * 4);
+    w.e_score = c.take(w.P * 4);
+    w.e_tp = c.take(w.P * 8);
+    w.e_fp = c.take(w.P * 8);
+    w.total = c.o;
     return w;
 }
 
@@ -102,28 +96,6 @@ __global__ void k_det_count(const int32_t* det_image, const int32_t* det_cat, in
     const int k = det_cat[j], i = det_image[j];
     if (k < 0 || k >= K || i < 0 || i >= I) return;             // not an evaluated category / image: dropped
     atomicAdd(&d_cnt[(int64_t)k * I + i], 1);
-}
-
-// inclusive scan of v over a block of NT threads; returns it and the block total
-template <int NT>
-__device__ __forceinline__ int64_t block_scan(int64_t v, int64_t* sh, int64_t& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int64_t n = __shfl_up(v, o, 64);
-        if (lane >= o) v += n;
-    }
-    if (lane == 63) sh[w] = v;
-    __syncthreads();
-    int64_t pre = 0, tot = 0;
-#pragma unroll
-    for (int q = 0; q < NT / 64; ++q) {
-        pre += q < w ? sh[q] : 0;
-        tot += sh[q];
-    }
-    __syncthreads();
-    total = tot;
-    return v + pre;
 }
 
 __global__ __launch_bounds__(1024) void k_pairs_scan(const int32_t* d_cnt, const int32_t* gt_off, int32_t K, int32_t I, int32_t maxD,
@@ -143,7 +115,7 @@ __global__ __launch_bounds__(1024) void k_pairs_scan(const int32_t* d_cnt, const
         // three exclusive scans in one word: units per tile <= 1024 (11 bits), detections < 2^21 (the host bounds N)
         int64_t tot;
         const int64_t packed = (int64_t)has | ((int64_t)dc << 11) | ((int64_t)kept << 32);
-        const int64_t inc = block_scan<1024>(packed, sh, tot) - packed;
+        const int64_t inc = block_incl_scan<16>(packed, sh, tot) - packed;
         const int64_t eu = cu + (inc & 0x7ff), ed = cd + ((inc >> 11) & 0x1fffff), ee = ce + (inc >> 32);
         if (p < KI) {
             d_off[p] = (int32_t)ed;
@@ -313,41 +285,6 @@ __global__ void k_keys_fill(Key* keys, const int32_t* hdr, int64_t P) {
     if (e < P && e >= hdr[1]) keys[e] = Key{~0ull, ~0ull};
 }
 
-// bitonic steps k in [k_lo, k_hi] (powers of two), j from min(k, kSortL) / 2 down to 1, on one LDS block of kSortL elements
-__global__ __launch_bounds__(1024) void k_sort_local(Key* keys, int64_t k_lo, int64_t k_hi) {
-    __shared__ Key s[kSortL];
-    const int64_t base = (int64_t)blockIdx.x * kSortL;
-    for (int q = threadIdx.x; q < kSortL; q += 1024) s[q] = keys[base + q];
-    __syncthreads();
-    for (int64_t k = k_lo; k <= k_hi; k <<= 1) {
-        for (int j = (int)((k < kSortL ? k : kSortL) >> 1); j > 0; j >>= 1) {
-            const int t = threadIdx.x;
-            const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));    // lower index of the t-th pair at distance j
-            const int l = i + j;
-            const bool asc = ((base + i) & k) == 0;
-            const Key x = s[i], y = s[l];
-            if (asc ? key_gt(x, y) : key_gt(y, x)) {
-                s[i] = y;
-                s[l] = x;
-            }
-            __syncthreads();
-        }
-    }
-    for (int q = threadIdx.x; q < kSortL; q += 1024) keys[base + q] = s[q];
-}
-
-__global__ void k_sort_global(Key* keys, int64_t P, int64_t k, int64_t j) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= P / 2) return;
-    const int64_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i + j;
-    const bool asc = (i & k) == 0;
-    const Key x = keys[i], y = keys[l];
-    if (asc ? key_gt(x, y) : key_gt(y, x)) {
-        keys[i] = y;
-        keys[l] = x;
-    }
-}
-
 // ------------------------------------------------------------------ accumulate
 
 __global__ void k_elem_flags(const Key* keys, const int32_t* hdr, int32_t I, int32_t AT, int32_t maxD, const int32_t* unit_of_pair,
@@ -445,7 +382,7 @@ __global__ __launch_bounds__(kAccThreads) void k_accumulate(Params P, int32_t K,
             v[q] = c;
         }
         int64_t tot;
-        const int64_t pre = carry + block_scan<kAccThreads>(run, sh, tot) - run;
+        const int64_t pre = carry + block_incl_scan<kAccThreads / 64>(run, sh, tot) - run;
         int64_t acc = pre;
 #pragma unroll
         for (int q = 0; q < kAccPer; ++q) {
@@ -569,12 +506,7 @@ extern "C" int ore_coco_eval(const ore_coco_eval_desc* d, const ore_coco_eval_im
                            per_image ? per_image->dt_ignore : nullptr, per_image ? per_image->gt_npig : nullptr);
     }
     hipLaunchKernelGGL(k_keys_fill, dim3((unsigned)ceil_div((int)w.P, 256)), dim3(256), 0, s, keys, hdr, w.P);
-    hipLaunchKernelGGL(k_sort_local, dim3((unsigned)(w.P / kSortL)), dim3(1024), 0, s, keys, (int64_t)2, (int64_t)kSortL);
-    for (int64_t k = 2 * kSortL; k <= w.P; k <<= 1) {
-        for (int64_t j = k >> 1; j >= kSortL; j >>= 1)
-            hipLaunchKernelGGL(k_sort_global, dim3((unsigned)ceil_div((int)(w.P / 2), 256)), dim3(256), 0, s, keys, w.P, k, j);
-        hipLaunchKernelGGL(k_sort_local, dim3((unsigned)(w.P / kSortL)), dim3(1024), 0, s, keys, k, k);
-    }
+    bitonic_sort_rows<Key, key_gt>(keys, w.P, 1, s);
     hipLaunchKernelGGL(k_elem_flags, dim3((unsigned)ceil_div((int)w.P, 256)), dim3(256), 0, s, keys, hdr, I, AT, maxD, unit_of_pair,
                        unit_det, d->det_scores, codes, e_rank, e_score, e_tp, e_fp);
     hipLaunchKernelGGL(k_accumulate, dim3((unsigned)(P.T * K * P.A * P.M)), dim3(kAccThreads), 0, s, P, K, ekoff, ukoff, npig, e_rank,

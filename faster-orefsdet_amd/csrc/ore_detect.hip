@@ -17,7 +17,7 @@
 //   k_nms_scan      one block walks the 64-row blocks in order: in-block greedy resolution on the
 //                   diagonal word (wave-uniform), then all waves OR the kept rows into the removed
 //                   set; stops early once post_topk survivors (plus score ties) are known.
-#include "ore_common.h"
+#include "ore_block.h"
 
 #ifdef ORE_TRACE
 // make -C csrc trace: s_memtime stamps of block 0 / thread 0 of k_level_select (slots 0..15) and of the consumer wave of k_nms_scan_t
@@ -771,8 +771,6 @@ __global__ void k_fill_upper_zero(unsigned long long* mask, size_t nwords) {
     if (i < nwords) mask[i] = 0ull;
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct DetLayout {
     size_t lvl_cnt, lvl_boxes, lvl_scores, lvl_loc, s_boxes, s_scores, s_order, mask, total;
     int words;
@@ -780,17 +778,17 @@ struct DetLayout {
 DetLayout det_layout(int L, int P) {
     DetLayout o{};
     const size_t cap = (size_t)L * P;
-    size_t a = 0;
-    o.lvl_cnt = a; a = align256(a + sizeof(int) * 16);
-    o.lvl_boxes = a; a = align256(a + cap * 16);
-    o.lvl_scores = a; a = align256(a + cap * 4);
-    o.lvl_loc = a; a = align256(a + cap * 8);
-    o.s_boxes = a; a = align256(a + cap * 16);
-    o.s_scores = a; a = align256(a + cap * 4);
-    o.s_order = a; a = align256(a + cap * 4);
+    WsCursor c;
+    o.lvl_cnt = c.take(sizeof(int) * 16);
+    o.lvl_boxes = c.take(cap * 16);
+    o.lvl_scores = c.take(cap * 4);
+    o.lvl_loc = c.take(cap * 8);
+    o.s_boxes = c.take(cap * 16);
+    o.s_scores = c.take(cap * 4);
+    o.s_order = c.take(cap * 4);
     o.words = (int)((cap + 63) / 64);
-    o.mask = a; a = align256(a + (size_t)o.words * 64 * (size_t)o.words * 8);   // rows rounded up to whole 64-row blocks (transposed tiles)
-    o.total = a;
+    o.mask = c.take((size_t)o.words * 64 * (size_t)o.words * 8);   // rows rounded up to whole 64-row blocks (transposed tiles)
+    o.total = c.o;
     return o;
 }
 
@@ -998,16 +996,16 @@ struct NmsLayout { size_t s_boxes, s_scores, s_order, n, mask, out_b, out_s, tot
 NmsLayout nms_layout(int n) {
     NmsLayout o{};
     const size_t cap = n > 0 ? n : 1;
-    size_t a = 0;
-    o.s_boxes = a; a = align256(a + cap * 16);
-    o.s_scores = a; a = align256(a + cap * 4);
-    o.s_order = a; a = align256(a + cap * 4);
-    o.n = a; a = align256(a + 16);
+    WsCursor c;
+    o.s_boxes = c.take(cap * 16);
+    o.s_scores = c.take(cap * 4);
+    o.s_order = c.take(cap * 4);
+    o.n = c.take(16);
     o.words = (int)((cap + 63) / 64);
-    o.mask = a; a = align256(a + (size_t)o.words * 64 * (size_t)o.words * 8);   // rows rounded up to whole 64-row blocks (transposed tiles)
-    o.out_b = a; a = align256(a + cap * 16);
-    o.out_s = a; a = align256(a + cap * 4);
-    o.total = a;
+    o.mask = c.take((size_t)o.words * 64 * (size_t)o.words * 8);   // rows rounded up to whole 64-row blocks (transposed tiles)
+    o.out_b = c.take(cap * 16);
+    o.out_s = c.take(cap * 4);
+    o.total = c.o;
     return o;
 }
 }  // namespace

@@ -14,7 +14,7 @@
 // All pixel arithmetic is integer.  Compiled with -ffp-contract=off: ore_sigmoid and its host twin are the same single operations.
 #include <math.h>
 #include <string.h>
-#include "ore_common.h"
+#include "ore_block.h"
 
 namespace {
 
@@ -132,7 +132,6 @@ __device__ __forceinline__ void axis_step(const Axis& a, uint32_t& q, uint32_t& 
 }
 __device__ __forceinline__ int axis_pos(const Axis& a, uint32_t q) { return min(max((int)q - 128, 0), a.hi); }
 
-__device__ __forceinline__ uint32_t blend8(uint32_t p, uint32_t c, uint32_t al) { return (p * (255u - al) + c * al + 127u) / 255u; }
 
 __global__ __launch_bounds__(HM_T) void k_heatmap_render(const RenderArgs a, const uint8_t* src, uint8_t* dst, const uint8_t* __restrict__ lut) {
     __shared__ uint32_t s_lut[256];                // entry k: channel c in byte c

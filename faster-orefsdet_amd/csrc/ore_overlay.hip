@@ -13,7 +13,7 @@
 // Compiled with -ffp-contract=off: the area and the percentage are single fp32 operations, each rounded on its own.
 // "overlay v1, track colouring" (ore_overlay_draw_ids_fwd, color_by 2): only k_overlay_prepare learns it -- a row with a negative id is
 // not drawn, the colour comes from the id and "#<id> " goes in front of the text; k_overlay_draw is the same kernel.
-#include "ore_common.h"
+#include "ore_block.h"
 
 namespace {
 
@@ -49,7 +49,6 @@ struct PrepArgs {
     int32_t* count; Inst* inst; uint8_t* text;
 };
 
-__device__ __forceinline__ bool finite32(float v) { return (__builtin_bit_cast(uint32_t, v) & 0x7f800000u) != 0x7f800000u; }
 // (int)v for v clamped to [0, hi] first: the contract's max / min on the integer, without a float -> int conversion out of range
 __device__ __forceinline__ int clamp_to_int(float v, int hi) { return (int)fminf(fmaxf(v, 0.0f), (float)hi); }
 
@@ -144,7 +143,6 @@ struct DrawArgs {
     uint32_t magic_cell, magic_s;                  // ceil(2^20 / 6S), ceil(2^20 / S): g / d == (g * magic) >> 20 for g < 2048, d <= 48
 };
 
-__device__ __forceinline__ uint32_t blend8(uint32_t p, uint32_t c, uint32_t al) { return (p * (255u - al) + c * al + 127u) / 255u; }
 __device__ __forceinline__ uint32_t blend24(uint32_t px, uint32_t col, uint32_t al) {
     return blend8(px & 255u, col & 255u, al) | (blend8((px >> 8) & 255u, (col >> 8) & 255u, al) << 8) |
            (blend8((px >> 16) & 255u, (col >> 16) & 255u, al) << 16);

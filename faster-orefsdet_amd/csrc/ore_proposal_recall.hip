@@ -12,9 +12,9 @@
 //                  row) for each; a step is one wave reduction on (value, lowest GT), the winner's column and row are retired (rows: a
 //                  bit mask spread over the lanes, 32 rows each) and only the columns whose arg-max row was retired are scanned again.
 //                  The recorded vector goes into the chain's key row at the entry's slots; unused slots keep the all-ones pattern.
-//   k_sort_*       bitonic sort of every chain's key row (non-negative fp32 bit patterns order as unsigned integers; all-ones last)
+//   k_bitonic_*    bitonic sort of every chain's key row (non-negative fp32 bit patterns order as unsigned integers; all-ones last)
 //   k_counts       per (chain, threshold): num_pos minus the lower bound of the threshold in the sorted row
-#include "ore_common.h"
+#include "ore_block.h"
 
 namespace {
 
@@ -22,7 +22,6 @@ constexpr int kMaxA = 8, kMaxL = 4, kMaxChains = 8, kMaxT = 16;
 constexpr int kMaxRows = 2048;                  // largest limit: the retired-row mask is 32 rows per lane
 constexpr int kIouLds = 11264;                  // IoU matrix in LDS up to this many fp32 cells (rows x the image's GT count)
 constexpr int kColLds = 256;                    // column state in LDS up to this many non-crowd GTs
-constexpr int kSortL = 2048;                    // keys per LDS bitonic block (1024 threads)
 constexpr int kThreads = 64 * kMaxChains;
 constexpr int kGtStride = 6;                    // x0, y0, x1, y1, box area, fp32(json area)
 
@@ -37,27 +36,20 @@ struct Ws {
     int64_t P;
 };
 
-inline int64_t sort_size(int64_t n) {
-    int64_t p = kSortL;
-    while (p < n) p <<= 1;
-    return p;
-}
-
 inline Ws ws_layout(int32_t E, int32_t N, int32_t S, int64_t cells, int32_t AL) {
     Ws w{};
-    w.P = sort_size(S);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) & ~(size_t)255; return r; };
-    w.slot_off = take((size_t)(E + 1) * 4);
-    w.iou_off = take((size_t)(E + 1) * 8);
-    w.order = take((size_t)N * 4);
-    w.gtb = take((size_t)S * kGtStride * 4);
-    w.cmax = take((size_t)S * AL * 4);
-    w.carg = take((size_t)S * AL * 4);
-    w.valid = take((size_t)E * AL * 4);
-    w.iou = take((size_t)cells * 4);
-    w.keys = take((size_t)w.P * AL * 4);
-    w.total = o;
+    w.P = bitonic_size(S);
+    WsCursor c;
+    w.slot_off = c.take((size_t)(E + 1) * 4);
+    w.iou_off = c.take((size_t)(E + 1) * 8);
+    w.order = c.take((size_t)N * 4);
+    w.gtb = c.take((size_t)S * kGtStride * 4);
+    w.cmax = c.take((size_t)S * AL * 4);
+    w.carg = c.take((size_t)S * AL * 4);
+    w.valid = c.take((size_t)E * AL * 4);
+    w.iou = c.take((size_t)cells * 4);
+    w.keys = c.take((size_t)w.P * AL * 4);
+    w.total = c.o;
     return w;
 }
 
@@ -78,27 +70,6 @@ __device__ __forceinline__ Entry read_entry(int e, const int32_t* entry_off, con
 
 __device__ __forceinline__ int64_t matrix_cells(const Entry& en, int maxR) { return (int64_t)(en.P < maxR ? en.P : maxR) * en.G; }
 
-// inclusive scan of v over a block of 1024 threads; returns it and the block total
-__device__ __forceinline__ int64_t block_scan(int64_t v, int64_t* sh, int64_t& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int64_t n = __shfl_up(v, o, 64);
-        if (lane >= o) v += n;
-    }
-    if (lane == 63) sh[w] = v;
-    __syncthreads();
-    int64_t pre = 0, tot = 0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        pre += q < w ? sh[q] : 0;
-        tot += sh[q];
-    }
-    __syncthreads();
-    total = tot;
-    return v + pre;
-}
-
 __global__ __launch_bounds__(1024) void k_entry_scan(const int32_t* entry_off, const int32_t* entry_image, const int32_t* gt_off, int32_t E,
                                                      int32_t N, int32_t I, int32_t Gt, int32_t maxR, int32_t* slot_off, int64_t* iou_off,
                                                      int32_t* status) {
@@ -115,7 +86,7 @@ __global__ __launch_bounds__(1024) void k_entry_scan(const int32_t* entry_off, c
             cells = c > kIouLds ? c : 0;
         }
         int64_t ts, tc;
-        const int64_t is = block_scan(slots, sh, ts), ic = block_scan(cells, sh, tc);
+        const int64_t is = block_incl_scan<16>(slots, sh, ts), ic = block_incl_scan<16>(cells, sh, tc);
         if (e < E) {
             const int64_t so = cs + is - slots;
             slot_off[e] = (int32_t)(so < 0x7fffffff ? so : 0x7fffffff);
@@ -309,42 +280,9 @@ __global__ __launch_bounds__(kThreads) void k_entry(Params P, const float* prop_
     for (int j = K + lane; j < nvalid; j += 64) out[j] = 0;     // +0.0f: GTs past the last proposal
 }
 
-// bitonic steps k in [k_lo, k_hi] (powers of two), j from min(k, kSortL) / 2 down to 1, on one LDS block of kSortL keys of row blockIdx.y
-__global__ __launch_bounds__(1024) void k_sort_local(uint32_t* keys, int64_t P, int64_t k_lo, int64_t k_hi) {
-    __shared__ uint32_t s[kSortL];
-    uint32_t* row = keys + (int64_t)blockIdx.y * P;
-    const int64_t base = (int64_t)blockIdx.x * kSortL;
-    for (int q = threadIdx.x; q < kSortL; q += 1024) s[q] = row[base + q];
-    __syncthreads();
-    for (int64_t k = k_lo; k <= k_hi; k <<= 1) {
-        for (int j = (int)((k < kSortL ? k : kSortL) >> 1); j > 0; j >>= 1) {
-            const int t = threadIdx.x;
-            const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));    // lower index of the t-th pair at distance j
-            const int m = i + j;
-            const bool asc = ((base + i) & k) == 0;
-            const uint32_t x = s[i], y = s[m];
-            if (asc ? x > y : y > x) {
-                s[i] = y;
-                s[m] = x;
-            }
-            __syncthreads();
-        }
-    }
-    for (int q = threadIdx.x; q < kSortL; q += 1024) row[base + q] = s[q];
-}
-
-__global__ void k_sort_global(uint32_t* keys, int64_t P, int64_t k, int64_t j) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= P / 2) return;
-    uint32_t* row = keys + (int64_t)blockIdx.y * P;
-    const int64_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), m = i + j;
-    const bool asc = (i & k) == 0;
-    const uint32_t x = row[i], y = row[m];
-    if (asc ? x > y : y > x) {
-        row[i] = y;
-        row[m] = x;
-    }
-}
+struct u32_gt {
+    __device__ __forceinline__ bool operator()(uint32_t a, uint32_t b) const { return a > b; }
+};
 
 __global__ void k_counts(Params P, const uint32_t* keys, int64_t Psort, int32_t n_slots, const unsigned long long* num_pos,
                          int64_t* counts) {
@@ -438,14 +376,7 @@ extern "C" int ore_proposal_recall(const ore_proposal_recall_desc* d, void* stre
         if (S > 0)
             ORE_HIP(hipMemcpy2DAsync(d->entry_overlaps, (size_t)S * 4, keys, (size_t)w.P * 4, (size_t)S * 4, AL, hipMemcpyDeviceToDevice, s));
     }
-    if (S > 1) {
-        const dim3 gl((unsigned)(w.P / kSortL), (unsigned)AL), gg((unsigned)ceil_div((int)(w.P / 2), 256), (unsigned)AL);
-        hipLaunchKernelGGL(k_sort_local, gl, dim3(1024), 0, s, keys, w.P, (int64_t)2, (int64_t)kSortL);
-        for (int64_t k = 2 * kSortL; k <= w.P; k <<= 1) {
-            for (int64_t j = k >> 1; j >= kSortL; j >>= 1) hipLaunchKernelGGL(k_sort_global, gg, dim3(256), 0, s, keys, w.P, k, j);
-            hipLaunchKernelGGL(k_sort_local, gl, dim3(1024), 0, s, keys, w.P, k, k);
-        }
-    }
+    if (S > 1) bitonic_sort_rows<uint32_t, u32_gt>(keys, w.P, AL, s);
     if (S > 0) ORE_HIP(hipMemcpy2DAsync(d->gt_overlaps, (size_t)S * 4, keys, (size_t)w.P * 4, (size_t)S * 4, AL, hipMemcpyDeviceToDevice, s));
     hipLaunchKernelGGL(k_counts, dim3((unsigned)AL), dim3(64), 0, s, P, keys, w.P, S, num_pos, d->counts);
     return ore_launch_status("ore_proposal_recall");

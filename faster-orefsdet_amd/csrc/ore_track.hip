@@ -15,7 +15,7 @@
 //             track its place behind the rows; the new list, the header and ids_out are written from registers and LDS.  Every read of
 //             the state precedes a barrier that precedes every write of it.
 // Compiled with -ffp-contract=off: the IoU is single fp32 operations, each rounded on its own (the expression of ore_proposal_recall).
-#include "ore_common.h"
+#include "ore_block.h"
 
 namespace {
 
@@ -46,7 +46,6 @@ struct UpdArgs {
     float score_thresh, iou_thresh; int32_t ttl, class_aware; int64_t* ids_out;
 };
 
-__device__ __forceinline__ bool finite32(float v) { return (__builtin_bit_cast(uint32_t, v) & 0x7f800000u) != 0x7f800000u; }
 
 __global__ __launch_bounds__(TR_MAX_T) void k_track_reset(void* state, int capacity) {
     const State s = track_state(state, capacity);

@@ -9,7 +9,7 @@
 //                     greedy NMS (the IoU arithmetic of ore_nms_fwd, csrc/ore_detect.hip nms_mask_body), first topk survivors
 // Latency-bound work on <= 8192 rows: few, plain kernels.  Compiled with -ffp-contract=off: every fp32 operation below is rounded on
 // its own, as numpy rounds them.
-#include "ore_common.h"
+#include "ore_block.h"
 
 namespace {
 
@@ -62,8 +62,6 @@ __global__ __launch_bounds__(256) void k_tta_collect(const CollectArgs a) {
         a.var_counts[a.v] = n;
     }
 }
-
-__device__ __forceinline__ bool finite32(float v) { return (__builtin_bit_cast(uint32_t, v) & 0x7f800000u) != 0x7f800000u; }
 
 // rows with a non-finite value dropped, Boxes.clip to (out_h, out_w), score > score_thresh.  key = the score of a row that stays, -1 of
 // one that leaves (scores that stay are > score_thresh >= 0): one sort then puts the stayers first
@@ -197,17 +195,16 @@ struct MergeLayout { size_t c_boxes, key, s_boxes, s_scores, s_cls, n_valid, mas
 MergeLayout merge_layout(int cap) {
     MergeLayout o{};
     const size_t c = cap > 0 ? cap : 1;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t a = 0;
-    o.c_boxes = a; a = al(a + c * 16);
-    o.key = a; a = al(a + c * 4);
-    o.s_boxes = a; a = al(a + c * 16);
-    o.s_scores = a; a = al(a + c * 4);
-    o.s_cls = a; a = al(a + c * 4);
-    o.n_valid = a; a = al(a + 16);
+    WsCursor w;
+    o.c_boxes = w.take(c * 16);
+    o.key = w.take(c * 4);
+    o.s_boxes = w.take(c * 16);
+    o.s_scores = w.take(c * 4);
+    o.s_cls = w.take(c * 4);
+    o.n_valid = w.take(16);
     o.words = (int)((c + 63) / 64);
-    o.mask = a; a = al(a + c * (size_t)o.words * 8);
-    o.total = a;
+    o.mask = w.take(c * (size_t)o.words * 8);
+    o.total = w.o;
     return o;
 }
 

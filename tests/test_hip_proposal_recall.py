@@ -123,10 +123,18 @@ def test_random_sets_cover_the_paths():
     assert any(a["category_id"] == 9 for gt, _ in sets for a in gt["annotations"]) and any(a["iscrowd"] for gt, _ in sets for a in gt["annotations"])
 
 
-@pytest.mark.parametrize("big", [(3000, 40), (300, 1100)], ids=["3000_gts_40_proposals", "300_gts_1100_proposals"])
-def test_past_the_lds_sizes_and_both_limits_bitwise(ore, big):
-    """The IoU matrix and the column state of that image live in the workspace; 1100 proposals are cut by both limits."""
+@pytest.mark.parametrize("big,n_entries", [((3000, 40), None), ((300, 1100), None), ((300, 1100), 1025)],
+                         ids=["3000_gts_40_proposals", "300_gts_1100_proposals", "1025_entries"])
+def test_past_the_lds_sizes_and_both_limits_bitwise(ore, big, n_entries):
+    """The IoU matrix and the column state of that image live in the workspace; 1100 proposals are cut by both limits.  With 1025
+    entries k_entry_scan walks two 1024-entry tiles, and the last entry -- the big image once more -- takes its slot and matrix
+    offsets from the first tile's totals."""
     gt, entries = _dataset(4321, big=big)
+    if n_entries:
+        first = max(entries, key=lambda e: len(e[2]))
+        small = min((e for e in entries if len(e[2]) > 0), key=lambda e: len(e[2]))
+        entries = entries + [small] * (n_entries - 1 - len(entries)) + [first]
+        assert len(entries) == n_entries and sum(a["image_id"] == first[0] for a in gt["annotations"]) == big[0]
     assert max(len(e[2]) for e in entries) >= big[1] and big[0] * min(big[1], 1000) > ore.lib().ore_proposal_recall_lds_cells()
     ref = _check(gt, entries, _run(ore, gt, entries))
     assert ref["AR@1000"]["num_pos"] >= 0.8 * big[0] and (ref["AR@1000"]["gt_overlaps"] > 0).any()

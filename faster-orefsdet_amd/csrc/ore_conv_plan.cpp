@@ -136,7 +136,12 @@ ConvPlan plan_wino(const ConvP& c) {
     // below these row counts a launch is latency-bound, not multiply-bound (tools/wino_time.py: 128 -> 128 at 1600 rows 13.4 -> 10.3 us,
     // 96 -> 96 at 1600-1900 rows and everything at 400 rows a tie)
     if (K.wino_mode != 2 && !c.wino_lstride && c.M < ((c.Cin == 64 || c.Cin == 128) ? 1500 : 3000)) return none();
+    // the kernels read each image through a buffer descriptor of its own: its bytes are the descriptor's num_records and must stay
+    // below kOOB, the offset that marks a column outside the image
+    for (int l = 0; l < c.nlev; ++l)
+        if ((long long)c.lv[l].H * c.lv[l].W * c.in_ld * 4 >= (long long)kOOB) return none();
     const int nb = patch_tiles(c, 4);                       // batches of 4 x 16 outputs
+    if (nb >= (1 << 22)) return none();                     // k_conv3x3_wino_nu decodes a batch number by fdiv
     if (c.Cin == 80 || c.Cin == 96 || c.Cin == 112) {       // k_conv3x3_wino_nu: NCGB groups of 16 output channels per block
         const int ncgb = c.Cin == 80 ? 3 : 2;
         const int gy = ceil_div(c.Cout16 / 16, ncgb);

@@ -18,8 +18,12 @@
 //           64..127 (their partial sums meet the others' in the output transform).  Either way a wave multiplies 4 positions x 32
 //           output channels x 64 input channels and keeps exactly those transformed WEIGHTS IN REGISTERS (128 VGPRs) for the whole
 //           launch -- no weight traffic after the prologue.
-//   P1      input transform: thread = (tile, xi, 4 channels); 8 global loads (two rows of the 4x4 patch, out-of-image -> zero page),
-//           X = d[ra] +- d[rb], then the four nu combinations -> V[pos][tile][CIN] in LDS (rows XOR-swizzled by tile: no padding).
+//   P1      input transform: thread = (tile, 4 channels) for two xi (CIN = 64: three rows of the 4x4 patch) or all four (CIN = 128:
+//           the whole patch); every pixel is loaded once, through a buffer descriptor of its (level, image) -- a tap outside the
+//           image is the descriptor's out-of-range zero (wino_image / wino_patch below), there is no zero page and no pointer
+//           select --, all loads go out together; X = d[ra] +- d[rb], then the four nu combinations -> V[pos][tile][CIN] in LDS
+//           (rows XOR-swizzled by tile: no padding).  The batch walk is contiguous: (level, image, row, column of batches) are
+//           carried from batch to batch, nothing is divided inside the loop.
 //   P2      per 16 input channels and position ONE ds_read_b128 (tile fragment) feeds 8 MFMAs (2 channel groups x 4 k);
 //           64 x 2 MFMAs per wave and batch.  The nu half of the output transform happens in registers (Z_j = sum_nu A^T[j][nu] M),
 //           Z[xi][kh][j][tile][co] goes to LDS.
@@ -35,7 +39,7 @@
 //
 // Replaces F.conv2d(3x3, pad 1) + FrozenBatchNorm2d + ReLU of d2z:modeling/backbone/vovnet.py:205-219,408-412 (stem_2, OSA2 layers),
 // fpn.py:139-145 (fpn_output3) and conv3x3 + bias of ref:CenterNet2/centernet/modeling/dense_heads/centernet_head.py:141-150 (tower).
-#include "ore_conv_internal.h"
+#include "ore_conv_desc.h"
 #include <algorithm>
 
 namespace {
@@ -44,6 +48,7 @@ using namespace oreconv;
 struct WinoP {
     const float* in; int in_ld, in_coff;
     int B, nlev; Lvl lv[4]; int bat0[5]; int nbx[4], nby[4];      // batches of level l: [bat0[l], bat0[l+1]), nbx x nby per image
+    float inv_per[4], inv_nbx[4];                                 // 1 / (nbx * nby), 1 / nbx: the strided walk of k_conv3x3_wino_nu decodes by fdiv
     const float* U; int Cout, Cout16;
     size_t u_lstride; int blk0[5];                                // per-level weights (u_lstride != 0): level l's U is u_lstride floats
                                                                   // further and blocks [blk0[l], blk0[l+1]) of a block row work on level l only
@@ -52,7 +57,43 @@ struct WinoP {
     int nbat;
 };
 
-__device__ __attribute__((aligned(16))) float g_zero_wino[4] = {0.f, 0.f, 0.f, 0.f};
+// The input of one (level, image) as a buffer descriptor, and the 4-column x NR-row patch of a P1 thread read through it.
+//   descriptor   base = the image's first pixel (64-bit scalar arithmetic), num_records = H * W * in_ld * 4 < 2^31 (plan_wino): the
+//                image before it, the image behind it and another pyramid level are all outside it.
+//   column term  cv[c] = ix * pixel bytes + the thread's channel offset, or kOOB for a column outside [0, W): one compare and select
+//                per patch column, shared by all rows.
+//   row term     rv[r] = min((unsigned)iy, H) * row bytes: row -1 (as unsigned: huge) and every row >= H become row H, whose offset is
+//                num_records -- out of range with any valid column -- and no row term is negative or exceeds num_records.
+// So a lane's offset rv + cv is < num_records exactly for a pixel of the image, lies in [num_records, num_records + row bytes) for a
+// row outside it, and in [2^31, 2^31 + num_records] for a column outside it WHATEVER the row: nothing wraps round 2^32, nothing comes
+// back into the image, and the hardware returns zeros for all of them.
+struct WinoImg { __amdgpu_buffer_rsrc_t rs; unsigned pix_bytes, row_bytes; int H, W; };
+__device__ __forceinline__ WinoImg wino_image(const WinoP& p, int irow0, int H, int W, int b) {
+    WinoImg im;
+    im.pix_bytes = (unsigned)p.in_ld * 4u; im.row_bytes = (unsigned)W * im.pix_bytes; im.H = H; im.W = W;
+    im.rs = make_rsrc(p.in + ((long long)irow0 + (long long)b * (H * W)) * p.in_ld, (unsigned)H * im.row_bytes);
+    return im;
+}
+template <int NR>
+__device__ __forceinline__ void wino_patch(const WinoImg& im, int iy0, int ix0, unsigned chan_bytes, f32x4 (&d)[NR][4]) {
+    unsigned cv[4], rv[NR];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) cv[c] = (unsigned)(ix0 + c) < (unsigned)im.W ? (unsigned)(ix0 + c) * im.pix_bytes + chan_bytes : kOOB;
+#pragma unroll
+    for (int r = 0; r < NR; ++r) rv[r] = min((unsigned)(iy0 + r), (unsigned)im.H) * im.row_bytes;
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) d[r][c] = bload4(im.rs, rv[r] + cv[c]);
+    __builtin_amdgcn_sched_barrier(0);              // every load goes out ahead of the first transform instruction: one round trip
+}
+// one xi item of the input transform: the row combination X[0..3] of the patch columns -> the four nu combinations, rows of V
+__device__ __forceinline__ void wino_v_store(float* vr, int stride16, const f32x4 (&X)[4]) {
+    *reinterpret_cast<f32x4*>(vr) = X[0] - X[2];
+    *reinterpret_cast<f32x4*>(vr + stride16) = X[1] + X[2];
+    *reinterpret_cast<f32x4*>(vr + 2 * stride16) = X[2] - X[1];
+    *reinterpret_cast<f32x4*>(vr + 3 * stride16) = X[1] - X[3];
+}
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt, i.e. it would make every phase wait for the
 // global stores of the output transform and for the LDS-DMA that is meant to fly under the next phase (measured: 0.8 us per batch).
@@ -164,54 +205,66 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino(WinoP p) {
         }
 
     // ---- P1 items of this thread: (tile t1, row combination xi1, quad q1), the same tile / quad for all its items
-    constexpr int IT = 16 * 4 * QV / 512;           // 2 (CIN 64) or 4 (CIN 128)
     const int q1 = tid % QV, t1 = (tid / QV) & 15;
-    const int xi1_0 = CIN == 64 ? (tid >> 8) : 0;   // CIN 64: items xi = (tid >> 8) + 2 it; CIN 128: xi = it
+    // CIN 64: items xi = h1, h1 + 2 with h1 = the wave group (uniform): patch rows h1 .. h1 + 2; CIN 128: all four xi, all four rows
+    constexpr int NR = CIN == 64 ? 3 : 4;
+    const int h1 = CIN == 64 ? __builtin_amdgcn_readfirstlane(tid >> 8) : 0;
     const int ty1 = t1 >> 3, tx1 = t1 & 7;
+    const unsigned chan1 = (unsigned)(p.in_coff + q1 * 4) * 4u;
     // ---- P3 item: (tile t3, column j3, quad cq3)
     const int cq3 = tid % QZ, j3 = (tid / QZ) & 1, t3 = tid / (2 * QZ);
     const bool p3_on = t3 < 16;
     const int ty3 = (t3 & 15) >> 3, tx3 = t3 & 7;
-    const float* zero = g_zero_wino;
+
+    // ---- the block's first batch, decoded once; the walk is contiguous, so (level, image, byi, bxi) are carried from batch to batch
+    // and the level's fields stay in registers for all its batches
+    int lvl = 0;
+#pragma unroll
+    for (int l = 1; l < 4; ++l)
+        if (l < p.nlev && bat_first >= p.bat0[l]) lvl = l;
+    int H = p.lv[lvl].H, W = p.lv[lvl].W, irow0 = p.lv[lvl].irow0, orow0 = p.lv[lvl].orow0, nbx = p.nbx[lvl], nby = p.nby[lvl];
+    int b, byi, bxi;
+    {
+        const int r0 = bat_first - p.bat0[lvl], per = nbx * nby;
+        b = r0 / per;
+        const int r1 = r0 - b * per;
+        byi = r1 / nbx; bxi = r1 - byi * nbx;
+    }
 
     for (int bat = bat_first; bat < bat_end; bat += bat_step) {
-        int lvl = 0;
-#pragma unroll
-        for (int l = 1; l < 4; ++l)
-            if (l < p.nlev && bat >= p.bat0[l]) lvl = l;
-        const Lvl L = p.lv[lvl];
-        const int r0 = bat - p.bat0[lvl], per = p.nbx[lvl] * p.nby[lvl];
-        const int b = r0 / per, r1 = r0 - b * per;
-        const int byi = r1 / p.nbx[lvl], bxi = r1 - byi * p.nbx[lvl];
-        const int H = L.H, W = L.W;
-        // ---------------- P1: input transform -> V
+        // ---------------- P1: input transform -> V (all loads of the patch issued together, each pixel once)
         {
-            const int iy0 = (byi * 2 + ty1) * 2 - 1, ix0 = (bxi * 8 + tx1) * 2 - 1;
-            const float* base = p.in + (ptrdiff_t)(L.irow0 + b * H * W) * p.in_ld + p.in_coff + q1 * 4;
+            const WinoImg im = wino_image(p, irow0, H, W, b);
+            f32x4 d[NR][4];
+            wino_patch<NR>(im, (byi * 2 + ty1) * 2 - 1 + h1, (bxi * 8 + tx1) * 2 - 1, chan1, d);
+            float* vrow = V + t1 * CIN + ((q1 ^ t1) << 2);
+            f32x4 X[4];
+            if constexpr (CIN == 64) {
+                // d holds the patch rows h1, h1 + 1, h1 + 2.  h1 = 0: xi 0 = row 0 - row 2, xi 2 = row 2 - row 1;
+                // h1 = 1: xi 1 = row 1 + row 2, xi 3 = row 1 - row 3
+                if (h1 == 0) {
 #pragma unroll
-            for (int it = 0; it < IT; ++it) {
-                const int x1 = CIN == 64 ? xi1_0 + 2 * it : it;
-                const int ra = (0x1210 >> (x1 * 4)) & 3, rb = (0x3122 >> (x1 * 4)) & 3;      // {0,1,2,1}, {2,2,1,3}
-                const float sgn = x1 == 1 ? 1.0f : -1.0f;
-                f32x4 da[4], db[4];
+                    for (int c = 0; c < 4; ++c) X[c] = d[0][c] - d[2][c];
+                    wino_v_store(vrow, 16 * CIN, X);
 #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const int ix = ix0 + c, iya = iy0 + ra, iyb = iy0 + rb;
-                    const bool okx = (unsigned)ix < (unsigned)W;
-                    const bool oka = okx && (unsigned)iya < (unsigned)H, okb = okx && (unsigned)iyb < (unsigned)H;
-                    const float* pa = oka ? base + (ptrdiff_t)(iya * W + ix) * p.in_ld : zero;
-                    const float* pb = okb ? base + (ptrdiff_t)(iyb * W + ix) * p.in_ld : zero;
-                    da[c] = *reinterpret_cast<const f32x4*>(pa);
-                    db[c] = *reinterpret_cast<const f32x4*>(pb);
+                    for (int c = 0; c < 4; ++c) X[c] = d[2][c] - d[1][c];
+                    wino_v_store(vrow + (2 * 4) * 16 * CIN, 16 * CIN, X);
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) X[c] = d[0][c] + d[1][c];
+                    wino_v_store(vrow + (1 * 4) * 16 * CIN, 16 * CIN, X);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) X[c] = d[0][c] - d[2][c];
+                    wino_v_store(vrow + (3 * 4) * 16 * CIN, 16 * CIN, X);
                 }
-                f32x4 X[4];
+            } else {
 #pragma unroll
-                for (int c = 0; c < 4; ++c) X[c] = da[c] + sgn * db[c];
-                float* vrow = V + ((x1 * 4) * 16 + t1) * CIN + ((q1 ^ t1) << 2);
-                *reinterpret_cast<f32x4*>(vrow) = X[0] - X[2];
-                *reinterpret_cast<f32x4*>(vrow + 16 * CIN) = X[1] + X[2];
-                *reinterpret_cast<f32x4*>(vrow + 32 * CIN) = X[2] - X[1];
-                *reinterpret_cast<f32x4*>(vrow + 48 * CIN) = X[1] - X[3];
+                for (int x1 = 0; x1 < 4; ++x1) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        X[c] = x1 == 0 ? d[0][c] - d[2][c] : x1 == 1 ? d[1][c] + d[2][c] : x1 == 2 ? d[2][c] - d[1][c] : d[1][c] - d[3][c];
+                    wino_v_store(vrow + (x1 * 4) * 16 * CIN, 16 * CIN, X);
+                }
             }
         }
         lds_barrier();
@@ -267,13 +320,24 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino(WinoP p) {
                 if (n + r < p.relu_cout) { v0[r] = fmaxf(v0[r], 0.f); v1[r] = fmaxf(v1[r], 0.f); }
             const int oy = (byi * 2 + ty3) * 2, ox = (bxi * 8 + tx3) * 2 + j3;
             if (ox < W && oy < H) {
-                float* o = p.out + (size_t)(L.orow0 + b * H * W + oy * W + ox) * p.out_ld + p.out_coff + n;
+                float* o = p.out + (size_t)(orow0 + b * H * W + oy * W + ox) * p.out_ld + p.out_coff + n;
                 *reinterpret_cast<f32x4*>(o) = v0;
                 if (oy + 1 < H) *reinterpret_cast<f32x4*>(o + (size_t)W * p.out_ld) = v1;
             }
         }
         // no barrier here: the next P1 writes V (all reads of V happened before the second barrier), the next P2 writes Z only
         // behind the next P1's barrier, which every wave reaches after its P3
+        // ---- the next batch: one to the right, else the next row of batches, else the next image, else the next level
+        if (++bxi == nbx) {
+            bxi = 0;
+            if (++byi == nby) {
+                byi = 0;
+                if (++b == p.B && bat + bat_step < bat_end) {
+                    b = 0; ++lvl;
+                    H = p.lv[lvl].H; W = p.lv[lvl].W; irow0 = p.lv[lvl].irow0; orow0 = p.lv[lvl].orow0; nbx = p.nbx[lvl]; nby = p.nby[lvl];
+                }
+            }
+        }
     }
 }
 
@@ -287,7 +351,8 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino(WinoP p) {
 //           the last block column multiply zero weights (a block owns its CU for the whole launch, skipping them would free nothing).
 //   LDS     rows padded by 4 floats instead of XOR-swizzled (the strides 84 / 100 / 116 and 52 / 36 floats are odd multiples of 16
 //           bytes: the 16 tiles x 4 quads of a fragment read fall on all banks evenly).
-//   P1      thread = (tile, 4 channels) for all four xi: the 4 x 4 patch in 16 loads issued together (one round trip), 16 LDS stores.
+//   P1      thread = (tile, 4 channels) for all four xi: the 4 x 4 patch in 16 descriptor loads issued together (one round trip),
+//           16 LDS stores.  The walk over batches is strided, so each batch number is decoded, by fdiv with host-made reciprocals.
 template <int CIN, int NCGB>
 __global__ __launch_bounds__(512, 2) void k_conv3x3_wino_nu(WinoP p) {
     constexpr int NC = CIN / 16, COUTB = NCGB * 16;
@@ -320,31 +385,27 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino_nu(WinoP p) {
     const int n3 = blockIdx.y * COUTB + cq3 * 4;
     const bool p3_on = t3 < 16 && n3 < p.Cout;
     const int ty3 = (t3 & 15) >> 3, tx3 = t3 & 7;
-    const float* zero = g_zero_wino;
+    const unsigned chan1 = (unsigned)(p.in_coff + q1 * 4) * 4u;
 
+    // the walk is strided (batch bat of block bat mod gridDim.x), so every batch is decoded: level, then image / row / column of
+    // batches by fdiv with the host's reciprocals; the level's fields are reloaded only when the level changes
+    int lvl = 0, H = p.lv[0].H, W = p.lv[0].W, irow0 = p.lv[0].irow0, orow0 = p.lv[0].orow0, nbx = p.nbx[0], per = p.nbx[0] * p.nby[0];
+    int lvl_b0 = 0, lvl_b1 = p.bat0[1];
+    float inv_per = p.inv_per[0], inv_nbx = p.inv_nbx[0];
     for (int bat = blockIdx.x; bat < p.nbat; bat += gridDim.x) {
-        int lvl = 0;
-#pragma unroll
-        for (int l = 1; l < 4; ++l)
-            if (l < p.nlev && bat >= p.bat0[l]) lvl = l;
-        const Lvl L = p.lv[lvl];
-        const int r0 = bat - p.bat0[lvl], per = p.nbx[lvl] * p.nby[lvl];
-        const int b = r0 / per, r1 = r0 - b * per;
-        const int byi = r1 / p.nbx[lvl], bxi = r1 - byi * p.nbx[lvl];
-        const int H = L.H, W = L.W;
-        // ---------------- P1: input transform -> V
+        if (bat >= lvl_b1) {
+            do { ++lvl; } while (bat >= p.bat0[lvl + 1]);
+            H = p.lv[lvl].H; W = p.lv[lvl].W; irow0 = p.lv[lvl].irow0; orow0 = p.lv[lvl].orow0; nbx = p.nbx[lvl]; per = nbx * p.nby[lvl];
+            lvl_b0 = p.bat0[lvl]; lvl_b1 = p.bat0[lvl + 1]; inv_per = p.inv_per[lvl]; inv_nbx = p.inv_nbx[lvl];
+        }
+        const int r0 = bat - lvl_b0;
+        const int b = fdiv(r0, per, inv_per), r1 = r0 - b * per;
+        const int byi = fdiv(r1, nbx, inv_nbx), bxi = r1 - byi * nbx;
+        // ---------------- P1: input transform -> V (the 4 x 4 patch in 16 loads issued together)
         if (p1_on) {
-            const int iy0 = (byi * 2 + ty1) * 2 - 1, ix0 = (bxi * 8 + tx1) * 2 - 1;
-            const float* base = p.in + (ptrdiff_t)(L.irow0 + b * H * W) * p.in_ld + p.in_coff + q1 * 4;
+            const WinoImg im = wino_image(p, irow0, H, W, b);
             f32x4 d[4][4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const int iy = iy0 + r, ix = ix0 + c;
-                    const bool ok = (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
-                    d[r][c] = *reinterpret_cast<const f32x4*>(ok ? base + (ptrdiff_t)(iy * W + ix) * p.in_ld : zero);
-                }
+            wino_patch<4>(im, (byi * 2 + ty1) * 2 - 1, (bxi * 8 + tx1) * 2 - 1, chan1, d);
             float* vrow = V + t1 * VS + q1 * 4;
 #pragma unroll
             for (int x1 = 0; x1 < 4; ++x1) {
@@ -352,11 +413,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino_nu(WinoP p) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c)
                     X[c] = x1 == 0 ? d[0][c] - d[2][c] : x1 == 1 ? d[1][c] + d[2][c] : x1 == 2 ? d[2][c] - d[1][c] : d[1][c] - d[3][c];
-                float* vr = vrow + (x1 * 4) * 16 * VS;
-                *reinterpret_cast<f32x4*>(vr) = X[0] - X[2];
-                *reinterpret_cast<f32x4*>(vr + 16 * VS) = X[1] + X[2];
-                *reinterpret_cast<f32x4*>(vr + 32 * VS) = X[2] - X[1];
-                *reinterpret_cast<f32x4*>(vr + 48 * VS) = X[1] - X[3];
+                wino_v_store(vrow + (x1 * 4) * 16 * VS, 16 * VS, X);
             }
         }
         lds_barrier();
@@ -410,7 +467,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino_nu(WinoP p) {
                 if (n3 + r < p.relu_cout) { v0[r] = fmaxf(v0[r], 0.f); v1[r] = fmaxf(v1[r], 0.f); }
             const int oy = (byi * 2 + ty3) * 2, ox = (bxi * 8 + tx3) * 2 + j3;
             if (ox < W && oy < H) {
-                float* o = p.out + (size_t)(L.orow0 + b * H * W + oy * W + ox) * p.out_ld + p.out_coff + n3;
+                float* o = p.out + (size_t)(orow0 + b * H * W + oy * W + ox) * p.out_ld + p.out_coff + n3;
                 *reinterpret_cast<f32x4*>(o) = v0;
                 if (oy + 1 < H) *reinterpret_cast<f32x4*>(o + (size_t)W * p.out_ld) = v1;
             }
@@ -458,6 +515,7 @@ int launch_wino(const ConvP& c, const ConvPlan& pl, hipStream_t st) {
     for (int l = 0; l < c.nlev; ++l) {
         p.lv[l] = c.lv[l];
         p.nbx[l] = ceil_div(c.lv[l].W, 16); p.nby[l] = ceil_div(c.lv[l].H, 4);
+        p.inv_per[l] = 1.0f / (float)(p.nbx[l] * p.nby[l]); p.inv_nbx[l] = 1.0f / (float)p.nbx[l];
         p.bat0[l] = nb;
         nb += c.B * p.nbx[l] * p.nby[l];
     }

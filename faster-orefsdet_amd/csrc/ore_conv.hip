@@ -15,14 +15,15 @@
 // agent-scope release + ticket counter elects the last arriver, which acquires and sums the slabs in slice order
 // (bitwise deterministic) and runs the fused epilogue.  The counters reset themselves.
 //
-// Fused epilogue: y = acc*scale[n] + shift[n] (+ nearest-2x top-down add) (+ ReLU on n < relu_cout), optional
-// per-tile column sums of y (the eSE average pool) so no extra pass over the activation is needed.
+// Fused epilogue (the contract every forward conv kernel shares: ore_conv_epilogue.h): y = acc*scale[n] + shift[n] (+ nearest-2x
+// top-down add) (+ ReLU on n < relu_cout), optional per-tile column sums of y (the eSE average pool) so no extra pass over the
+// activation is needed.
 // Rows may span several pyramid levels (level-major), so p3/p4/p5 run as ONE launch with per-level epilogue params.
 //
 // Replaces F.conv2d + FrozenBatchNorm2d + ReLU / bias / Scale of the reference (see include/ore_hip.h).
 #include <string.h>
 #include "ore_common.h"
-#include "ore_conv_internal.h"
+#include "ore_conv_epilogue.h"
 
 namespace {
 using namespace oreconv;
@@ -30,18 +31,6 @@ using namespace oreconv;
 // 16 bytes of zeros: the source of every out-of-image / out-of-range staging load, so that the loads themselves are
 // unconditional (no branch around a load => the compiler keeps them in flight behind counted vmcnt waits).
 __device__ __attribute__((aligned(16))) float g_zero16[4] = {0.f, 0.f, 0.f, 0.f};
-
-// (fp32 addend only; the epilogue_one of ore_conv_kw.hip also takes a bf16 one, p.sb & 4)
-__device__ __forceinline__ float epilogue_one(const ConvP& p, float acc, int m, int n) {
-    float v = acc;
-    int lvl = 0, b = 0, oy = 0, ox = 0;
-    if (p.ep_stride || p.add) decode_row(p, m, lvl, b, oy, ox);
-    if (p.scale) v = v * p.scale[lvl * p.ep_stride + n];
-    if (p.shift) v = v + p.shift[lvl * p.ep_stride + n];
-    if (p.add) v += p.add[(size_t)((b * p.add_H + (oy >> 1)) * p.add_W + (ox >> 1)) * p.add_ld + p.add_coff + n];
-    if (n < p.relu_cout) v = fmaxf(v, 0.0f);
-    return v;
-}
 
 #ifdef ORE_TRACE
 // Phase-timeline build (make trace -> lib/libore_hip_trace.so; tools/conv_phase_trace.py): thread 0 of every block stamps s_memtime
@@ -221,28 +210,20 @@ __global__ __launch_bounds__(256) void k_conv_igemm(ConvP p) {
         sh_sc[tid] = (okn && p.scale) ? p.scale[n] : 1.0f;
         sh_sh[tid] = (okn && p.shift) ? p.shift[n] : 0.0f;
     }
-    const bool vec_ok = (p.out_ld & 3) == 0 && (p.out_coff & 3) == 0 && ((uintptr_t)p.out & 15) == 0;
+    const bool vec_ok = CONV_OUT_VEC_OK(p, false);
     // finish one accumulator vector: 4 channels of one pixel
     auto finish = [&](f32x4 a, int m, int n, f32x4& vout) -> bool {
         if (m >= p.M || n >= p.Cout) return false;
         f32x4 v;
         if (ep_pre && !p.add) {
             v = a * *reinterpret_cast<const f32x4*>(sh_sc + (n - n0)) + *reinterpret_cast<const f32x4*>(sh_sh + (n - n0));
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (n + r < p.relu_cout) v[r] = fmaxf(v[r], 0.0f);
+            CONV_RELU4(v, n, p.relu_cout)
         } else {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = n + r < p.Cout ? epilogue_one(p, a[r], m, n + r) : 0.0f;
+            for (int r = 0; r < 4; ++r) v[r] = n + r < p.Cout ? epilogue_one<false>(p, a[r], m, n + r) : 0.0f;
         }
         float* o = p.out + (size_t)m * p.out_ld + p.out_coff + n;
-        if (vec_ok && n + 3 < p.Cout) {
-            *reinterpret_cast<f32x4*>(o) = v;
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (n + r < p.Cout) o[r] = v[r];
-        }
+        CONV_STORE4_F32(o, v, vec_ok, n, p.Cout)
         vout = v;
         return true;
     };
@@ -326,9 +307,8 @@ __global__ __launch_bounds__(256) void k_conv_igemm(ConvP p) {
                 const int tl = q >> 6, ln = q & 63;                     // tile index ((wmn*TM + i)*TN + j), source lane
                 const int j2 = tl % TN, i2 = (tl / TN) % TM, w2 = tl / (TM * TN);
                 const int wm2 = w2 / WGN, wn2 = w2 % WGN;
-                f32x4 a = *reinterpret_cast<const f32x4*>(lds + (0 * NT + tl) * 256 + ln * 4);
-#pragma unroll
-                for (int g = 1; g < WGK; ++g) a += *reinterpret_cast<const f32x4*>(lds + (g * NT + tl) * 256 + ln * 4);
+                f32x4 a;
+                CONV_SUM_WAVE_TILES(a, WGK, lds, NT, tl, ln)
                 const int m = m0 + wm2 * WM + i2 * 16 + (ln & 15);
                 const int n = n0 + wn2 * WN + j2 * 16 + (ln >> 4) * 4;
                 f32x4 vo;
@@ -421,11 +401,7 @@ __global__ __launch_bounds__(256) void k_conv_igemm(ConvP p) {
     if (p.colsum) {
         // column sums of this tile: the 16 pixel lanes of a channel group -> xor 1, 2, 4, 8; then across the WGM waves
 #pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int d = 1; d < 16; d <<= 1)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) csum[j][r] += __shfl_xor(csum[j][r], d);
+        for (int j = 0; j < TN; ++j) CONV_COLSUM16(csum[j])
         const bool owner = (lane & 15) == 0;                         // holds channels j*16 + cg4 .. +3
         if (WGM > 1) {
             __syncthreads();
@@ -544,7 +520,7 @@ __global__ __launch_bounds__(256) void k_conv3x3_patch(PatchP p) {
     const int wrow = wave * TM;
     f32x4 pre_sc4[TN], pre_sh4[TN];                            // epilogue operands fetched under the main loop's loads
 #pragma unroll
-    for (int j = 0; j < TN; ++j)
+    for (int j = 0; j < TN; ++j)                               // CONV_SCALE_SHIFT4 (ore_conv_epilogue.h), open-coded: its n + r changes this kernel's code
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int n = n0 + j * 16 + g4 + r;
@@ -606,17 +582,9 @@ __global__ __launch_bounds__(256) void k_conv3x3_patch(PatchP p) {
             const int gy = ty0 + wrow + i, gx = tx0 + li;
             if (gy < L.H && gx < L.W) {
                 f32x4 v = acc[i][j] * pre_sc4[j] + pre_sh4[j];
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (n + r < p.relu_cout) v[r] = fmaxf(v[r], 0.f);
+                CONV_RELU4(v, n, p.relu_cout)
                 float* o = p.out + (size_t)(obase + gy * L.W + gx) * p.out_ld + p.out_coff + n;
-                if (n + 3 < p.Cout) {
-                    *reinterpret_cast<f32x4*>(o) = v;
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (n + r < p.Cout) o[r] = v[r];
-                }
+                CONV_STORE4_F32(o, v, true, n, p.Cout)
             }
         }
     }
@@ -693,7 +661,7 @@ __global__ __launch_bounds__(512) void k_conv3x3_patch_db(PatchP p) {
     const int li = lane & 15, g4 = (lane >> 4) * 4;
     f32x4 pre_sc4[TN], pre_sh4[TN];
 #pragma unroll
-    for (int j = 0; j < TN; ++j)
+    for (int j = 0; j < TN; ++j)                               // CONV_SCALE_SHIFT4 (ore_conv_epilogue.h), open-coded: its n + r changes this kernel's code
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int n = n0 + j * 16 + g4 + r;
@@ -744,17 +712,9 @@ __global__ __launch_bounds__(512) void k_conv3x3_patch_db(PatchP p) {
         const int gy = ty0 + wave, gx = tx0 + li;
         if (gy < L.H && gx < L.W) {
             f32x4 v = acc[j] * pre_sc4[j] + pre_sh4[j];
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (n + r < p.relu_cout) v[r] = fmaxf(v[r], 0.f);
+            CONV_RELU4(v, n, p.relu_cout)
             float* o = p.out + (size_t)(obase + gy * L.W + gx) * p.out_ld + p.out_coff + n;
-            if (n + 3 < p.Cout) {
-                *reinterpret_cast<f32x4*>(o) = v;
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (n + r < p.Cout) o[r] = v[r];
-            }
+            CONV_STORE4_F32(o, v, true, n, p.Cout)
         }
     }
 }
@@ -913,11 +873,7 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv3x3_ws(PatchP
         const int n = n0 + g4;
         if (kh == 0 && n < p.Cout) {
             f32x4 sc4, sh4;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                sc4[r] = (p.scale && n + r < p.Cout) ? p.scale[cur_g.lvl * p.ep_stride + n + r] : 1.0f;
-                sh4[r] = (p.shift && n + r < p.Cout) ? p.shift[cur_g.lvl * p.ep_stride + n + r] : 0.0f;
-            }
+            CONV_SCALE_SHIFT4(p, cur_g.lvl, n, sc4, sh4)
 #pragma unroll
             for (int sg = 0; sg < TH; ++sg) {
                 f32x4 a = acc[sg];
@@ -925,20 +881,12 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void k_conv3x3_ws(PatchP
                 const int gy = cur_g.ty0 + sg, gx = cur_g.tx0 + li;
                 if (gy < cur_g.Ho && gx < cur_g.Wo) {
                     f32x4 v = a * sc4 + sh4;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (n + r < p.relu_cout) v[r] = fmaxf(v[r], 0.f);
+                    CONV_RELU4(v, n, p.relu_cout)
                     if constexpr (SB) {                          // bf16 output tensor (Cout % 64 == 0 on this path: whole vectors)
                         st4(reinterpret_cast<ore_bf16_t*>(p.out) + (size_t)(cur_g.obase + gy * cur_g.Wo + gx) * p.out_ld + p.out_coff + n, v);
                     } else {
-                    float* o = p.out + (size_t)(cur_g.obase + gy * cur_g.Wo + gx) * p.out_ld + p.out_coff + n;
-                    if (n + 3 < p.Cout) {
-                        *reinterpret_cast<f32x4*>(o) = v;
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            if (n + r < p.Cout) o[r] = v[r];
-                    }
+                        float* o = p.out + (size_t)(cur_g.obase + gy * cur_g.Wo + gx) * p.out_ld + p.out_coff + n;
+                        CONV_STORE4_F32(o, v, true, n, p.Cout)
                     }
                 }
             }

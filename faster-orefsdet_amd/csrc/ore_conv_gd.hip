@@ -24,6 +24,7 @@
 // d2z:modeling/backbone/fpn.py:130-150 (lateral 3); ref:fewx/modeling/fsod/fsod_cen.py conv3 after the correlation;
 // d2z:modeling/roi_heads/box_head.py fc1 (conv_gd_splitk).
 #include "ore_conv_desc.h"
+#include "ore_conv_epilogue.h"
 
 namespace {
 using namespace oreconv;
@@ -220,10 +221,10 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_conv_gd(GdP q) {
     wait_vmcnt<0>();                                   // the zero-fill tail DMAs
     __syncthreads();
 
-    // ---- epilogue: every wave finishes its own TA x TB tiles from registers
+    // ---- epilogue (ore_conv_epilogue.h): every wave finishes its own TA x TB tiles from registers
     const __amdgpu_buffer_rsrc_t rsc = make_rsrc(p.scale, p.scale ? p.sc_bytes : 0u), rsh = make_rsrc(p.shift, p.shift ? p.sc_bytes : 0u);
     const __amdgpu_buffer_rsrc_t rad = make_rsrc(p.add, p.add ? p.add_bytes : 0u);
-    const bool vec_ok = (p.out_ld & 3) == 0 && (p.out_coff & 3) == 0 && ((uintptr_t)p.out & 15) == 0;
+    const bool vec_ok = CONV_OUT_VEC_OK(p, false);
     float* cs = lds;                                   // [WGM][GB][16] column sums of the waves' row bands
     const int kq = lane >> 4;
 #pragma unroll
@@ -245,27 +246,14 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_conv_gd(GdP q) {
 #endif
                 v = acc[i][j] * e_sc + e_sh;
                 if (p.add) v += bload4(rad, (unsigned)(addend_index(p, pixel_of_row(p, m, hw), en) * 4));
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if (en + r < p.relu_cout) v[r] = fmaxf(v[r], 0.0f);
-                    if (en + r >= p.Cout) v[r] = 0.0f;
-                }
+                CONV_RELU_ZERO4(v, en, p.relu_cout, p.Cout)
                 float* o = p.out + (size_t)blockIdx.z * p.out_zstride + (size_t)m * p.out_ld + p.out_coff + en;
-                if (vec_ok && en + 3 < p.Cout) {
-                    *reinterpret_cast<f32x4*>(o) = v;
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (en + r < p.Cout) o[r] = v[r];
-                }
+                CONV_STORE4_F32(o, v, vec_ok, en, p.Cout)
             }
             csum += v;
         }
         if (p.colsum) {                                // the 16 pixel lanes of a channel quad, then the waves' row bands in order
-#pragma unroll
-            for (int d = 1; d < 16; d <<= 1)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) csum[r] += __shfl_xor(csum[r], d);
+            CONV_COLSUM16(csum)
             if ((lane & 15) == 0) *reinterpret_cast<f32x4*>(cs + (wm * GB + wn * TB + j) * 16 + kq * 4) = csum;
         }
     }

@@ -11,12 +11,13 @@
 //     lands in LDS as zeros): ~6 instructions per piece and step;
 //   * a wave owns a CONTIGUOUS range of the K axis and works in batches of SB steps on a double-buffered private LDS region: the DMAs of
 //     batch b+1 are in flight while batch b is multiplied; waits are counted (`s_waitcnt vmcnt`), there is no barrier in the K loop.
-// K is split over the NW waves of a block, partial tiles meet in LDS, epilogue = k_conv_kw's (scale / shift, FPN top-down add, ReLU,
-// per-tile column sums, channel-slice output).  Single level, fp32 storage, no input affine.
+// K is split over the NW waves of a block, partial tiles meet in LDS, epilogue = ore_conv_epilogue.h's (scale / shift, FPN top-down add,
+// ReLU, per-tile column sums, channel-slice output).  Single level, fp32 storage, no input affine.
 //
 // Replaces F.conv2d + FrozenBatchNorm2d + ReLU / bias of d2z:modeling/backbone/vovnet.py:205-219,310-332 (stages 3-5), fpn.py:126-145
 // (laterals), ref:fewx/modeling/fsod/fsod_cen.py:470 (conv3) at batch 1.
 #include "ore_conv_desc.h"
+#include "ore_conv_epilogue.h"
 
 namespace {
 using namespace oreconv;
@@ -202,7 +203,7 @@ __global__ __launch_bounds__(NW * 64) void k_conv_kd(KdP q) {
     float* cs = lds + RED_F;
     const __amdgpu_buffer_rsrc_t rsc = make_rsrc(p.scale, p.scale ? p.sc_bytes : 0u), rsh = make_rsrc(p.shift, p.shift ? p.sc_bytes : 0u);
     const __amdgpu_buffer_rsrc_t rad = make_rsrc(p.add, p.add ? p.add_bytes : 0u);
-    const bool vec_ok = (p.out_ld & 3) == 0 && (p.out_coff & 3) == 0 && ((uintptr_t)p.out & ((p.sb & 2) ? 7 : 15)) == 0;
+    const bool vec_ok = CONV_OUT_VEC_OK(p, p.sb & 2);
 #pragma unroll
     for (int q0 = 0; q0 < NT * 64; q0 += T) {
         const int it = q0 + tid;                                  // a wave's 64 items are one 16x16 tile: lane = accumulator lane
@@ -224,47 +225,22 @@ __global__ __launch_bounds__(NW * 64) void k_conv_kd(KdP q) {
                     e_add = bload4(rad, on ? ai * 4u : kOOB);
                 }
             }
-            f32x4 a = *reinterpret_cast<const f32x4*>(lds + (0 * NT + tl) * 256 + ln * 4);
-#pragma unroll
-            for (int g = 1; g < NW; ++g) a += *reinterpret_cast<const f32x4*>(lds + (g * NT + tl) * 256 + ln * 4);
+            f32x4 a;
+            CONV_SUM_WAVE_TILES(a, NW, lds, NT, tl, ln)
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if (on) {
                 v = a * e_sc + e_sh + e_add;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if (en + r < p.relu_cout) v[r] = fmaxf(v[r], 0.0f);
-                    if (en + r >= p.Cout) v[r] = 0.0f;
-                }
-                if (p.sb & 2) {                                   // bf16 output tensor: rounded once, here; the eSE pool sums the ROUNDED values
-                    const s16x4 h = to_bf16x4(v);
-                    unsigned short* o = reinterpret_cast<unsigned short*>(p.out) + (size_t)m * p.out_ld + p.out_coff + en;
-                    if (vec_ok && en + 3 < p.Cout) {
-                        *reinterpret_cast<s16x4*>(o) = h;
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            if (en + r < p.Cout) o[r] = (unsigned short)h[r];
-                    }
-                    v = from_bf16x4(h);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (en + r >= p.Cout) v[r] = 0.0f;
+                CONV_RELU_ZERO4(v, en, p.relu_cout, p.Cout)
+                if (p.sb & 2) {                                   // bf16 output tensor
+                    CONV_STORE4_BF16(reinterpret_cast<unsigned short*>(p.out) + (size_t)m * p.out_ld + p.out_coff + en, v, vec_ok, en, p.Cout)
+                    CONV_ZERO_PAST4(v, en, p.Cout)
                 } else {
                     float* o = p.out + (size_t)m * p.out_ld + p.out_coff + en;
-                    if (vec_ok && en + 3 < p.Cout) {
-                        *reinterpret_cast<f32x4*>(o) = v;
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            if (en + r < p.Cout) o[r] = v[r];
-                    }
+                    CONV_STORE4_F32(o, v, vec_ok, en, p.Cout)
                 }
             }
             if (p.colsum) {                                       // column sums of the tile: the 16 pixel lanes of a channel quad
-#pragma unroll
-                for (int d = 1; d < 16; d <<= 1)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] += __shfl_xor(v[r], d);
+                CONV_COLSUM16(v)
                 if ((ln & 15) == 0) *reinterpret_cast<f32x4*>(cs + tl * 16 + (ln >> 4) * 4) = v;
             }
         }

@@ -13,8 +13,9 @@
 //   * per step and wave: (BM/16 + BN/16) DMA instructions, as many ds_read_b128, 4 x (BM/16) x (BN/16) MFMAs, ~10 VALU of addressing.
 // The four partial tiles are summed through LDS in wave order; cross-block split-K (grid.z) uses the same slab + agent-scope
 // release/acquire ticket as k_conv_igemm (last arriver sums the slabs in slice order: bitwise deterministic).
-// Epilogue = k_conv_igemm's: y = acc*scale[n] + shift[n] (+ nearest-2x top-down add) (+ ReLU on n < relu_cout), per-tile column sums
-// (eSE average pool), channel-slice output.  BF build: both operands rounded to bf16 as the fragments leave LDS (ORE_CONV_BF16).
+// Epilogue = the shared contract of ore_conv_epilogue.h: y = acc*scale[n] + shift[n] (+ nearest-2x top-down add) (+ ReLU on
+// n < relu_cout), per-tile column sums (eSE average pool), channel-slice output.  BF build: both operands rounded to bf16 as the
+// fragments leave LDS (ORE_CONV_BF16).
 // Not planned here (the planner leaves such layers to k_conv_igemm): any input-side affine (in_mul / in_add / in_relu:
 // the eSE gate of the FPN laterals reaches this kernel pre-multiplied into the weights instead, ore_ese_gate_scaled_weight_fwd; the
 // GroupNorm fold of the head's last conv stays on k_conv_igemm), Cin % 16 != 0.
@@ -22,6 +23,7 @@
 // Replaces F.conv2d + FrozenBatchNorm2d + ReLU / bias of d2z:modeling/backbone/vovnet.py:205-219,310-332, fpn.py:113-154,
 // ref:fewx/modeling/fsod/fsod_cen.py:470 (conv3), fsod_roi_heads.py:500-520 (composed DSA + fc1).
 #include "ore_conv_desc.h"
+#include "ore_conv_epilogue.h"
 
 namespace {
 using namespace oreconv;
@@ -42,55 +44,24 @@ __device__ unsigned long long* g_trace_kw = nullptr;
 #define KW_TRR(i) do { } while (0)
 #endif
 
-// (differs from the epilogue_one of ore_conv.hip in the bf16 addend, p.sb & 4)
-__device__ __forceinline__ float epilogue_one(const ConvP& p, float acc, int m, int n) {
-    float v = acc;
-    int lvl = 0, b = 0, oy = 0, ox = 0;
-    if (p.ep_stride || p.add) decode_row(p, m, lvl, b, oy, ox);
-    if (p.scale) v = v * p.scale[lvl * p.ep_stride + n];
-    if (p.shift) v = v + p.shift[lvl * p.ep_stride + n];
-    if (p.add) {
-        const size_t ai = (size_t)((b * p.add_H + (oy >> 1)) * p.add_W + (ox >> 1)) * p.add_ld + p.add_coff + n;
-        v += (p.sb & 4) ? bf16_bits_to_f32(reinterpret_cast<const unsigned short*>(p.add)[ai]) : p.add[ai];
-    }
-    if (n < p.relu_cout) v = fmaxf(v, 0.0f);
-    return v;
-}
-
-// finish one accumulator vector (4 consecutive channels of one pixel): epilogue + store
+// finish one accumulator vector (4 consecutive channels of one pixel): epilogue + store (ore_conv_epilogue.h, steps 1-6)
 __device__ __forceinline__ bool finish4(const ConvP& p, f32x4 a, int m, int n, bool vec_ok, f32x4& vout) {
     if (m >= p.M || n >= p.Cout) return false;
     f32x4 v;
     if (p.ep_stride == 0 && !p.add && n + 3 < p.Cout && p.scale && p.shift) {       // the common form: two 16-byte operand loads
         v = a * *reinterpret_cast<const f32x4*>(p.scale + n) + *reinterpret_cast<const f32x4*>(p.shift + n);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (n + r < p.relu_cout) v[r] = fmaxf(v[r], 0.0f);
+        CONV_RELU4(v, n, p.relu_cout)
     } else {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = n + r < p.Cout ? epilogue_one(p, a[r], m, n + r) : 0.0f;
+        for (int r = 0; r < 4; ++r) v[r] = n + r < p.Cout ? epilogue_one<true>(p, a[r], m, n + r) : 0.0f;
     }
-    if (p.sb & 2) {                                       // bf16 output tensor: round once, here; what is summed for the eSE pool is the
-        const s16x4 h = to_bf16x4(v);                     // ROUNDED value (the stored tensor is the layer's output in this mode)
-        unsigned short* o = reinterpret_cast<unsigned short*>(p.out) + (size_t)m * p.out_ld + p.out_coff + n;
-        if (vec_ok && n + 3 < p.Cout) {
-            *reinterpret_cast<s16x4*>(o) = h;
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (n + r < p.Cout) o[r] = (unsigned short)h[r];
-        }
-        vout = from_bf16x4(h);
+    if (p.sb & 2) {                                       // bf16 output tensor
+        CONV_STORE4_BF16(reinterpret_cast<unsigned short*>(p.out) + (size_t)m * p.out_ld + p.out_coff + n, v, vec_ok, n, p.Cout)
+        vout = v;
         return true;
     }
     float* o = p.out + (size_t)m * p.out_ld + p.out_coff + n;
-    if (vec_ok && n + 3 < p.Cout) {
-        *reinterpret_cast<f32x4*>(o) = v;
-    } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (n + r < p.Cout) o[r] = v[r];
-    }
+    CONV_STORE4_F32(o, v, vec_ok, n, p.Cout)
     vout = v;
     return true;
 }
@@ -321,7 +292,7 @@ __global__ __launch_bounds__(NW * 64) void k_conv_kw(ConvP p, const float* __res
             *reinterpret_cast<f32x4*>(lds + ((wave * NT) + i * GB + j) * 256 + lane * 4) = acc[i][j];
     __syncthreads();
     KW_TR(7);
-    const bool vec_ok = (p.out_ld & 3) == 0 && (p.out_coff & 3) == 0 && ((uintptr_t)p.out & ((p.sb & 2) ? 7 : 15)) == 0;
+    const bool vec_ok = CONV_OUT_VEC_OK(p, p.sb & 2);
     const int ntile = by * gridDim.x + bx;
     if (p.splitk <= 1) {
         float* cs = lds + RED_F;
@@ -331,16 +302,12 @@ __global__ __launch_bounds__(NW * 64) void k_conv_kw(ConvP p, const float* __res
             if (q < NT * 64) {
                 const int tl = q >> 6, ln = q & 63;
                 const int j2 = tl % GB, i2 = tl / GB;
-                f32x4 a = *reinterpret_cast<const f32x4*>(lds + (0 * NT + tl) * 256 + ln * 4);
-#pragma unroll
-                for (int g = 1; g < NW; ++g) a += *reinterpret_cast<const f32x4*>(lds + (g * NT + tl) * 256 + ln * 4);
+                f32x4 a;
+                CONV_SUM_WAVE_TILES(a, NW, lds, NT, tl, ln)
                 f32x4 vo = {0.f, 0.f, 0.f, 0.f};
                 if (!finish4(p, a, m0 + i2 * 16 + (ln & 15), n0 + j2 * 16 + (ln >> 4) * 4, vec_ok, vo)) vo = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (p.colsum) {                                   // column sums of the tile: the 16 pixel lanes of a channel quad
-#pragma unroll
-                    for (int d = 1; d < 16; d <<= 1)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) vo[r] += __shfl_xor(vo[r], d);
+                    CONV_COLSUM16(vo)
                     if ((ln & 15) == 0) *reinterpret_cast<f32x4*>(cs + tl * 16 + (ln >> 4) * 4) = vo;
                 }
             }
@@ -426,11 +393,7 @@ __global__ __launch_bounds__(NW * 64) void k_conv_kw(ConvP p, const float* __res
         }
     if (p.colsum) {
 #pragma unroll
-        for (int j = 0; j < GB; ++j)
-#pragma unroll
-            for (int d = 1; d < 16; d <<= 1)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) csum[j][r] += __shfl_xor(csum[j][r], d);
+        for (int j = 0; j < GB; ++j) CONV_COLSUM16(csum[j])
         if ((lane & 15) == 0)
 #pragma unroll
             for (int j = 0; j < GB; ++j)
@@ -608,7 +571,7 @@ __global__ __launch_bounds__(256) void k_conv_gs(ConvP p, const float* __restric
     wait_vmcnt<0>();
 
     // ---- epilogue straight from the accumulators: this lane = pixel row (lane & 15), channels (lane >> 4) * 4 .. + 3 of each tile
-    const bool vec_ok = (p.out_ld & 3) == 0 && (p.out_coff & 3) == 0 && ((uintptr_t)p.out & ((p.sb & 2) ? 7 : 15)) == 0;
+    const bool vec_ok = CONV_OUT_VEC_OK(p, p.sb & 2);
     const int cg4 = (lane >> 4) * 4;
     f32x4 csum[TN];
 #pragma unroll
@@ -623,11 +586,7 @@ __global__ __launch_bounds__(256) void k_conv_gs(ConvP p, const float* __restric
     if (p.colsum) {
         float* cs = lds + NS * STAGE_F + DUMMY_F;
 #pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int d = 1; d < 16; d <<= 1)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) csum[j][r] += __shfl_xor(csum[j][r], d);
+        for (int j = 0; j < TN; ++j) CONV_COLSUM16(csum[j])
         __syncthreads();
         if ((lane & 15) == 0)
 #pragma unroll

@@ -17,12 +17,13 @@
 //   * K is split over the NW = 4 / 8 / 16 waves of the block (wave w owns a CONTIGUOUS range of 16-channel chunks, so its walk over
 //     (tap, chunk) is one scalar add per step), partial tiles meet in LDS as in k_conv_kw; slices longer than MAXS steps run as
 //     several batches.
-// Epilogue semantics = k_conv_kw's: y = acc * scale[n] + shift[n] (+ nearest-2x top-down add) (+ ReLU on n < relu_cout), per-tile
-// column sums of the final values (the eSE average pool), channel-slice output.  Single level, fp32 storage, no input affine.
+// Epilogue semantics = ore_conv_epilogue.h's: y = acc * scale[n] + shift[n] (+ nearest-2x top-down add) (+ ReLU on n < relu_cout),
+// per-tile column sums of the final values (the eSE average pool), channel-slice output.  Single level, fp32 storage, no input affine.
 //
 // Replaces F.conv2d + FrozenBatchNorm2d + ReLU / bias of d2z:modeling/backbone/vovnet.py:205-219,310-332 (stages 4-5), fpn.py:126-145
 // (laterals 4-5), ref:fewx/modeling/fsod/fsod_roi_heads.py:500-520 (composed DSA + fc1) at batch 1.
 #include "ore_conv_desc.h"
+#include "ore_conv_epilogue.h"
 
 namespace {
 using namespace oreconv;
@@ -159,33 +160,19 @@ __global__ __launch_bounds__(NW * 64) void k_conv_rf(RfP q) {
     __syncthreads();
     CONV_TR(g_trace_rf, 6);
     if (wave < GB) {
-        f32x4 a = *reinterpret_cast<const f32x4*>(lds + (0 * GB + wave) * 256 + lane * 4);
-#pragma unroll
-        for (int g = 1; g < NW; ++g) a += *reinterpret_cast<const f32x4*>(lds + (g * GB + wave) * 256 + lane * 4);
+        f32x4 a;
+        CONV_SUM_WAVE_TILES(a, NW, lds, GB, wave, lane)
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (e_on) {
             if (!p.scale) e_sc = f32x4{1.f, 1.f, 1.f, 1.f};
             v = a * e_sc + e_sh + e_add;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (en + r < p.relu_cout) v[r] = fmaxf(v[r], 0.0f);
-                if (en + r >= p.Cout) v[r] = 0.0f;
-            }
+            CONV_RELU_ZERO4(v, en, p.relu_cout, p.Cout)
             float* o = p.out + (size_t)m * p.out_ld + p.out_coff + en;
-            const bool vec_ok = (p.out_ld & 3) == 0 && (p.out_coff & 3) == 0 && ((uintptr_t)p.out & 15) == 0;
-            if (vec_ok && en + 3 < p.Cout) {
-                *reinterpret_cast<f32x4*>(o) = v;
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (en + r < p.Cout) o[r] = v[r];
-            }
+            const bool vec_ok = CONV_OUT_VEC_OK(p, false);
+            CONV_STORE4_F32(o, v, vec_ok, en, p.Cout)
         }
         if (p.colsum) {                                              // column sums of the tile: the 16 pixel lanes of a channel quad
-#pragma unroll
-            for (int d = 1; d < 16; d <<= 1)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] += __shfl_xor(v[r], d);
+            CONV_COLSUM16(v)
             if (r16 == 0) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {

@@ -40,6 +40,7 @@
 // Replaces F.conv2d(3x3, pad 1) + FrozenBatchNorm2d + ReLU of d2z:modeling/backbone/vovnet.py:205-219,408-412 (stem_2, OSA2 layers),
 // fpn.py:139-145 (fpn_output3) and conv3x3 + bias of ref:CenterNet2/centernet/modeling/dense_heads/centernet_head.py:141-150 (tower).
 #include "ore_conv_desc.h"
+#include "ore_conv_epilogue.h"
 #include <algorithm>
 
 namespace {
@@ -311,13 +312,10 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino(WinoP p) {
             }
             const f32x4 y0 = (z[0] + z[1]) + z[2], y1 = (z[1] - z[2]) - z[3];
             const int n = blockIdx.y * COUTB + cq3 * 4;
-            f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
-            if (p.scale) sc = *reinterpret_cast<const f32x4*>(p.scale + lvl * p.ep_stride + n);
-            if (p.shift) sh = *reinterpret_cast<const f32x4*>(p.shift + lvl * p.ep_stride + n);
+            f32x4 sc, sh;                                            // (ore_conv_epilogue.h, steps 1 and 3; Cout % 4 == 0: whole quads)
+            scale_shift4_vec(p, lvl, n, sc, sh);
             f32x4 v0 = y0 * sc + sh, v1 = y1 * sc + sh;
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (n + r < p.relu_cout) { v0[r] = fmaxf(v0[r], 0.f); v1[r] = fmaxf(v1[r], 0.f); }
+            CONV_RELU4_X2(v0, v1, n, p.relu_cout)
             const int oy = (byi * 2 + ty3) * 2, ox = (bxi * 8 + tx3) * 2 + j3;
             if (ox < W && oy < H) {
                 float* o = p.out + (size_t)(orow0 + b * H * W + oy * W + ox) * p.out_ld + p.out_coff + n;
@@ -458,13 +456,10 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_wino_nu(WinoP p) {
                 z[x] = *reinterpret_cast<const f32x4*>(zr) + *reinterpret_cast<const f32x4*>(zr + 2 * 16 * ZS);
             }
             const f32x4 y0 = (z[0] + z[1]) + z[2], y1 = (z[1] - z[2]) - z[3];
-            f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
-            if (p.scale) sc = *reinterpret_cast<const f32x4*>(p.scale + lvl * p.ep_stride + n3);
-            if (p.shift) sh = *reinterpret_cast<const f32x4*>(p.shift + lvl * p.ep_stride + n3);
+            f32x4 sc, sh;
+            scale_shift4_vec(p, lvl, n3, sc, sh);
             f32x4 v0 = y0 * sc + sh, v1 = y1 * sc + sh;
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (n3 + r < p.relu_cout) { v0[r] = fmaxf(v0[r], 0.f); v1[r] = fmaxf(v1[r], 0.f); }
+            CONV_RELU4_X2(v0, v1, n3, p.relu_cout)
             const int oy = (byi * 2 + ty3) * 2, ox = (bxi * 8 + tx3) * 2 + j3;
             if (ox < W && oy < H) {
                 float* o = p.out + (size_t)(orow0 + b * H * W + oy * W + ox) * p.out_ld + p.out_coff + n3;

@@ -10,7 +10,9 @@ a change of the flags of an object is reported too.  Prints one line per file --
 difference.  Cross-compiles; needs no GPU.
 
 One known false alarm: hipcc does not always emit the two __device__ variables of the -DORE_TRACE build of ore_conv_kw.hip (g_zero_kw,
-g_trace_kw) in the same order, even for two compilations of one tree.  A diff that only swaps those two data symbols is that; run again.
+g_trace_kw) in the same order, even for two compilations of one tree.  A diff that only swaps those two data symbols is that; run again.  The swap has
+also been seen to persist over repeated runs of one pair of trees (it appeared with a whitespace-only edit of a header): then compare the two
+files with --keep -- the lines in front of the data symbols must be identical and the sorted files equal.
 """
 import argparse
 import difflib

@@ -205,7 +205,9 @@ __global__ __launch_bounds__(256) void k_sgd_step(float* __restrict__ p, const f
     const float lr = chunk_lr[c] * (lr_scale_dev ? *lr_scale_dev : lr_scale);
     const float wd = chunk_wd[c];
     float gi = g[i] * grad_scale;
-    if (clip > 0.0f) gi = fminf(fmaxf(gi, -clip), clip);
+    // plain comparisons, not fminf / fmaxf: a NaN gradient stays a NaN (torch.clamp), so a diverged step shows in buf and p instead of
+    // turning into a step of -clip; every other value, -0 and +-Inf included, gives the bits fminf(fmaxf(gi, -clip), clip) gave
+    if (clip > 0.0f) gi = gi > clip ? clip : (gi < -clip ? -clip : gi);
     const float pi = p[i];
     gi = gi + wd * pi;
     const float b = momentum * buf[i] + gi;

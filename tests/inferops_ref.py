@@ -591,9 +591,9 @@ NOT_COVERED = {
     "k_roi_finalize": "bit-exact against the C twin",
     "k_roi_tail": "bit-exact against the C twin",
     "k_roi_merge_classes": "bit-exact against the C twin (tests/test_hip_nway.py)",
-    "k_roi_align_bwd": "training: tests/test_hip_train.py, tests/test_hip_properties.py",
-    "k_roi_align_bwd_col": "training: tests/test_hip_train.py, tests/test_hip_properties.py",
-    "k_roi_align_bwd_tile": "training: tests/test_hip_train.py, tests/test_hip_properties.py",
+    "k_roi_align_bwd": "training: held to float64 in tests/test_hip_trainloss.py (tests/trainloss_ref.py roi_align_bwd_ref)",
+    "k_roi_align_bwd_col": "training: held to float64 in tests/test_hip_trainloss.py (tests/trainloss_ref.py roi_align_bwd_ref)",
+    "k_roi_align_bwd_tile": "training: held to float64 in tests/test_hip_trainloss.py (tests/trainloss_ref.py roi_align_bwd_ref)",
     "k_roi_bwd_finalize": "training: tests/test_hip_train.py, tests/test_hip_properties.py",
 }
 

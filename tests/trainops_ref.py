@@ -645,10 +645,10 @@ NOT_COVERED = {
     "winograd_weight": "the Winograd weight transform: pinned with the launches that use it in tests/test_hip_dgrad.py",
     "roi_align": "ROIAlign forward: held to float64 in tests/test_hip_inferops.py (tests/inferops_ref.py roi_align_ref)",
     "roi_align_batched": "ROIAlign forward, batched: held to float64 in tests/test_hip_inferops.py::test_roi_align_batched",
-    "roi_align_bwd": "ROIAlign backward: its own golden and property tests",
-    "roi_losses": "loss kernels of ore_train.hip: golden and property tests of their own",
-    "centernet_loss_sums": "loss kernels of ore_train.hip: golden and property tests of their own",
-    "centernet_loss_grad": "loss kernels of ore_train.hip: golden and property tests of their own",
+    "roi_align_bwd": "ROIAlign backward, all three launch forms: held to float64 in tests/test_hip_trainloss.py (tests/trainloss_ref.py roi_align_bwd_ref)",
+    "roi_losses": "loss kernels of ore_train.hip: held to float64 in tests/test_hip_trainloss.py (tests/trainloss_ref.py)",
+    "centernet_loss_sums": "loss kernels of ore_train.hip: held to float64 in tests/test_hip_trainloss.py (tests/trainloss_ref.py)",
+    "centernet_loss_grad": "loss kernels of ore_train.hip: held to float64 in tests/test_hip_trainloss.py (tests/trainloss_ref.py)",
 }
 
 

@@ -5,6 +5,14 @@ d2z:engine/defaults.py:60-79 create_ddp_model; d2z:solver/lr_scheduler.py:132-16
     losses.backward()  [DDP: bucketed gradient all-reduce, averaged, overlapped with backward]
     clip_grad_value_(p, 1.0) per parameter;  torch.optim.SGD(momentum .9, wd 1e-4, box_predictor lr x2).step()
     WarmupMultiStepLR(steps 10000/11000, gamma .1, linear warm-up 500 iters from factor 2.5e-4)
+The reference's other solver settings (ref:fewx/solver/build.py:19-59, :136) are built as well:
+    SOLVER.CLIP_GRADIENTS.CLIP_TYPE "norm"   clip_grad_norm_(p, CLIP_VALUE, NORM_TYPE) once PER PARAMETER, NORM_TYPE 2.0, 1.0 or inf
+    SOLVER.NESTEROV                          torch.optim.SGD(nesterov=True)
+    CLIP_TYPE "full_model"                   one clip_grad_norm_ over all parameters: detectron2's later clip type of that name, an
+                                             extension over the reference (whose enum has only "value" and "norm")
+The norm is that of the exchanged, averaged gradient (grad_scale * g, as under DDP).  It is a deterministic segmented reduction on the
+step's stream (ore_grad_norm_fwd: two or three launches, no host read), followed by the update (ore_sgd_step_clipnorm_fwd); value
+clipping without Nesterov stays the one launch of ore_sgd_step_fwd.
 
 MI355X design: every parameter that receives a gradient lives in ONE flat fp32 bucket (parameters, gradients and momentum are
 three parallel buffers cut into 256-float chunks; a parameter is padded to whole chunks).  `p.data` / `p.grad` are views, so
@@ -90,6 +98,11 @@ class FlatBucket:
         self.momentum = torch.zeros(off, dtype=torch.float32, device=dev)
         self.chunk_lr = torch.tensor(lr_c, dtype=torch.float32, device=dev)      # the group's base rate (before the schedule factor)
         self.chunk_wd = torch.tensor(wd_c, dtype=torch.float32, device=dev)
+        # the segments of the norm clip: the parameter of every chunk, and every parameter's element count and first chunk
+        idx_c = [i for i, n in enumerate(self.numels) for _ in range((n + CHUNK - 1) // CHUNK)]
+        self.chunk_param = torch.tensor(idx_c, dtype=torch.int32, device=dev)
+        self.param_numel = torch.tensor(self.numels, dtype=torch.int64, device=dev)
+        self.param_chunk0 = torch.tensor([o // CHUNK for o in self.offsets], dtype=torch.int64, device=dev)
         self.tensors: List[torch.nn.Parameter] = []
         for (name, p, _, _), o, n in zip(entries, self.offsets, self.numels):
             with torch.no_grad():
@@ -279,21 +292,45 @@ class FlatDataParallel(torch.nn.Module):
 
 
 class FlatSGD:
-    """torch.optim.SGD + clip_grad_value_ as one HIP launch over the flat bucket.  Keeps the parts of the torch.optim interface
-    the reference's trainer and checkpointer touch: param_groups (lr is read by the LR logger and written by the scheduler),
-    zero_grad(), step(), state_dict()/load_state_dict()."""
+    """torch.optim.SGD + the reference's gradient clipper as HIP launches over the flat bucket.  Keeps the parts of the torch.optim
+    interface the reference's trainer and checkpointer touch: param_groups (lr is read by the LR logger and written by the scheduler),
+    zero_grad(), step(), state_dict()/load_state_dict().
+
+    clip_type "value" (clip_grad_value_, one launch with the update), "norm" (clip_grad_norm_ per parameter) or "full_model" (one
+    clip_grad_norm_ over all parameters); norm_type 2.0, 1.0 or inf; nesterov as torch.optim.SGD's.  After a step in a norm mode
+    `grad_norm_dev` holds that step's per-parameter norms ("norm" [P], bucket order), coefficients ("coef" [P]) and, in full-model
+    mode, the norm over all parameters ("total" [1]) as device tensors: reading them is the caller's synchronisation, not the step's."""
+
+    CLIP_TYPES = ("value", "norm", "full_model")
+    NORM_TYPES = (2.0, 1.0, float("inf"))
 
     def __init__(self, bucket: FlatBucket, base_lr: float, momentum: float, clip_value: float, nesterov: bool = False,
-                 apply_fn: Optional[Callable] = None):
-        if nesterov:
-            raise NotImplementedError("SOLVER.NESTEROV is false in every reference config")
+                 apply_fn: Optional[Callable] = None, clip_type: str = "value", norm_type: float = 2.0):
+        if clip_type not in self.CLIP_TYPES:
+            raise ValueError("Unknown SOLVER.CLIP_GRADIENTS.CLIP_TYPE: {!r} (one of {})".format(clip_type, ", ".join(self.CLIP_TYPES)))
+        if clip_type != "value" and float(norm_type) not in self.NORM_TYPES:
+            raise NotImplementedError("SOLVER.CLIP_GRADIENTS.NORM_TYPE {}: only 2.0, 1.0 and inf are built; any other exponent goes "
+                                      "through powf, whose accuracy has been measured at the exponents 1, 2 and 4 only "
+                                      "(tests/trainloss_ref.py), so no bound could be stated for it".format(norm_type))
+        if nesterov and float(momentum) <= 0:
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")        # torch.optim.SGD's words
         self.bucket = bucket
         self.base_lr = float(base_lr)
         self.momentum = float(momentum)
         self.clip_value = float(clip_value)
+        self.nesterov = bool(nesterov)
+        # clipping switched off (clip_value <= 0) is the value form with its clamp off, whatever the type
+        self.clip_type = clip_type if self.clip_value > 0 else "value"
+        self.norm_type = float(norm_type)
         self.lr_factor = 1.0                       # schedule factor; param_groups[i]["lr"] = group base x factor
         self.lr_dev: Optional[torch.Tensor] = None # the same factor on the device (a captured step reads it there: GraphedTrainStep)
         self._apply = apply_fn
+        self.grad_norm_dev: Optional[Dict[str, torch.Tensor]] = None
+        self._norm_ws = None
+        if self.clip_type != "value" and bucket.params.is_cuda:       # workspaces are sized here: step() allocates nothing
+            import orehip
+            self._norm_ws = orehip.grad_norm_workspace(bucket.numels, bucket.params.device)
+            self.grad_norm_dev = {k: self._norm_ws[k] for k in ("norm", "coef", "total")}
         self.param_groups = []
         for p, g, wd in zip(bucket.tensors, bucket.base_lrs, bucket.weight_decays):
             self.param_groups.append({"params": [p], "lr": g, "initial_lr": g, "weight_decay": wd, "momentum": momentum})
@@ -315,13 +352,26 @@ class FlatSGD:
         if fin is not None:
             fin()
         scale = getattr(b, "grad_scale", 1.0)
+        plain = self.clip_type == "value" and not self.nesterov
         if self._apply is not None:                # tests on CPU inject the oracle's update here; the product path is the HIP kernel
-            self._apply(b, self.lr_factor, self.momentum, self.clip_value, scale)
+            if plain:
+                self._apply(b, self.lr_factor, self.momentum, self.clip_value, scale)
+            else:
+                self._apply(b, self.lr_factor, self.momentum, self.clip_value, scale, clip_type=self.clip_type,
+                            norm_type=self.norm_type, nesterov=self.nesterov)
             return
         import orehip
-        from orehip import autograd as A
-        orehip.sgd_step(b.params, b.grads, b.momentum, b.chunk_lr, b.chunk_wd, lr_scale=self.lr_factor, momentum=self.momentum,
-                        clip_value=self.clip_value, grad_scale=scale, lr_scale_dev=self.lr_dev)
+        if plain:
+            orehip.sgd_step(b.params, b.grads, b.momentum, b.chunk_lr, b.chunk_wd, lr_scale=self.lr_factor, momentum=self.momentum,
+                            clip_value=self.clip_value, grad_scale=scale, lr_scale_dev=self.lr_dev)
+        else:
+            coef = None
+            if self.clip_type != "value":
+                _, coef, _ = orehip.grad_norms(b.grads, b.param_numel, b.param_chunk0, self._norm_ws, self.norm_type,
+                                               self.clip_type == "full_model", self.clip_value, scale)
+            orehip.sgd_step_norm(b.params, b.grads, b.momentum, b.chunk_lr, b.chunk_wd, b.chunk_param, b.param_numel, b.param_chunk0,
+                                 coef, lr_scale=self.lr_factor, momentum=self.momentum, clip_value=self.clip_value, grad_scale=scale,
+                                 nesterov=self.nesterov, lr_scale_dev=self.lr_dev)
         # The kernel rewrote the parameters through raw pointers: tell torch (every cache in the package -- engines, hipGraphs,
         # packed / composed weights -- keys on the parameters' version counters) and drop the packed copies.
         self.after_step()
@@ -367,9 +417,8 @@ def build_optimizer(cfg, model) -> FlatSGD:
     inner = model.module if isinstance(model, FlatDataParallel) else model
     bucket = get_bucket(inner, cfg)
     clip = cfg.SOLVER.CLIP_GRADIENTS
-    if clip.ENABLED and clip.CLIP_TYPE != "value":
-        raise NotImplementedError("only CLIP_TYPE=value is built (the reference configs use value clipping)")
-    return FlatSGD(bucket, cfg.SOLVER.BASE_LR, cfg.SOLVER.MOMENTUM, clip.CLIP_VALUE if clip.ENABLED else 0.0, cfg.SOLVER.NESTEROV)
+    return FlatSGD(bucket, cfg.SOLVER.BASE_LR, cfg.SOLVER.MOMENTUM, clip.CLIP_VALUE if clip.ENABLED else 0.0, cfg.SOLVER.NESTEROV,
+                   clip_type=clip.CLIP_TYPE if clip.ENABLED else "value", norm_type=clip.NORM_TYPE)
 
 
 def warmup_factor_at_iter(method: str, it: int, warmup_iters: int, warmup_factor: float) -> float:

@@ -2092,6 +2092,69 @@ def sgd_step(params: torch.Tensor, grads: torch.Tensor, momentum_buf: torch.Tens
                                 lr_scale, momentum, clip_value, grad_scale, _stream()), "ore_sgd_step_fwd")
 
 
+GRAD_NORM_KINDS = {2.0: 2, 1.0: 1, float("inf"): 0}          # NORM_TYPE -> ore_grad_norm_fwd's norm_kind
+
+
+def grad_norm_geometry() -> Tuple[int, int]:
+    """(chunks of 256 floats one partial sum covers, partials one pass of the per-parameter reduction takes) of ore_grad_norm_fwd."""
+    g, w = C.c_int32(), C.c_int32()
+    _chk(lib().ore_grad_norm_geometry(C.byref(g), C.byref(w)), "ore_grad_norm_geometry")
+    return g.value, w.value
+
+
+def grad_norm_workspace(numels, device) -> Dict[str, torch.Tensor]:
+    """Everything ore_grad_norm_fwd needs besides the bucket's own tables, sized once (ore_grad_norm_plan): the device tables part0 /
+    part_param, the workspaces partial / acc and the outputs norm / coef / total (NaN until a launch writes them)."""
+    P = len(numels)
+    ne = (C.c_int64 * P)(*[int(n) for n in numels])
+    nc, npart = C.c_int64(), C.c_int64()
+    _chk(lib().ore_grad_norm_plan(ne, P, None, None, 0, C.byref(nc), C.byref(npart)), "ore_grad_norm_plan")
+    part0, part_param = (C.c_int32 * (P + 1))(), (C.c_int32 * npart.value)()
+    _chk(lib().ore_grad_norm_plan(ne, P, part0, part_param, npart.value, C.byref(nc), C.byref(npart)), "ore_grad_norm_plan")
+    nan = lambda n: torch.full((n,), float("nan"), dtype=torch.float32, device=device)   # noqa: E731
+    return {"n_params": P, "n_chunks": nc.value, "n_parts": npart.value,
+            "part0": torch.tensor(list(part0), dtype=torch.int32, device=device),
+            "part_param": torch.tensor(list(part_param), dtype=torch.int32, device=device),
+            "partial": nan(npart.value), "acc": nan(P), "norm": nan(P), "coef": nan(P), "total": nan(1)}
+
+
+def grad_norms(grads: torch.Tensor, param_numel: torch.Tensor, param_chunk0: torch.Tensor, ws: Dict[str, torch.Tensor],
+               norm_type: float = 2.0, full_model: bool = False, clip_value: float = 1.0,
+               grad_scale: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The p-norms of grad_scale * gradient over a flat bucket and the clip coefficients min(clip_value / (norm + 1e-6), 1) (see
+    ore_grad_norm_fwd) -> ws's device tensors (norm [P], coef [P], total [1]); total is written in full-model mode only.  param_numel /
+    param_chunk0: the bucket's int64 tables; ws: grad_norm_workspace(numels).  No host read, no allocation: capturable."""
+    if float(norm_type) not in GRAD_NORM_KINDS:
+        raise NotImplementedError(f"NORM_TYPE {norm_type}: only 2, 1 and inf are built")
+    P = ws["n_params"]
+    assert grads.is_cuda and grads.dtype == torch.float32 and grads.is_contiguous() and grads.numel() == ws["n_chunks"] * 256
+    assert param_numel.dtype == torch.int64 and param_chunk0.dtype == torch.int64 and param_numel.numel() == P == param_chunk0.numel()
+    _chk(lib().ore_grad_norm_fwd(_ptr(grads), P, _ptr(param_numel), _ptr(param_chunk0), _ptr(ws["part_param"]), _ptr(ws["part0"]),
+                                 ws["n_parts"], GRAD_NORM_KINDS[float(norm_type)], int(bool(full_model)), clip_value, grad_scale,
+                                 _ptr(ws["partial"]), _ptr(ws["acc"]), _ptr(ws["norm"]), _ptr(ws["coef"]), _ptr(ws["total"]), _stream()),
+         "ore_grad_norm_fwd")
+    return ws["norm"], ws["coef"], ws["total"]
+
+
+def sgd_step_norm(params: torch.Tensor, grads: torch.Tensor, momentum_buf: torch.Tensor, chunk_lr: torch.Tensor, chunk_wd: torch.Tensor,
+                  chunk_param: torch.Tensor, param_numel: torch.Tensor, param_chunk0: torch.Tensor, coef: Optional[torch.Tensor],
+                  lr_scale: float = 1.0, momentum: float = 0.9, clip_value: float = 1.0, grad_scale: float = 1.0,
+                  nesterov: bool = False, lr_scale_dev: Optional[torch.Tensor] = None) -> None:
+    """In-place SGD over a flat bucket with the gradient multiplied by coef[parameter] (grad_norms), or value-clamped when coef is
+    None; Nesterov momentum on request (see ore_sgd_step_clipnorm_fwd)."""
+    n = params.numel()
+    assert n % 256 == 0 and grads.numel() == n and momentum_buf.numel() == n and chunk_lr.numel() == n // 256 == chunk_wd.numel()
+    assert chunk_param.numel() == n // 256 and chunk_param.dtype == torch.int32
+    assert param_numel.dtype == torch.int64 and param_chunk0.dtype == torch.int64 and param_numel.numel() == param_chunk0.numel()
+    assert coef is None or (coef.dtype == torch.float32 and coef.numel() == param_numel.numel())
+    for t in (params, grads, momentum_buf, chunk_lr, chunk_wd):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+    _chk(lib().ore_sgd_step_clipnorm_fwd(_ptr(params), _ptr(grads), _ptr(momentum_buf), n // 256, _ptr(chunk_lr), _ptr(chunk_wd),
+                                         _ptr(chunk_param), _ptr(param_numel), _ptr(param_chunk0), _ptr(coef), _ptr(lr_scale_dev),
+                                         lr_scale, momentum, clip_value, grad_scale, int(bool(nesterov)), _stream()),
+         "ore_sgd_step_clipnorm_fwd")
+
+
 def pack_conv_weight_dev(w_oihw: torch.Tensor, dgrad: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Device-side repack of OIHW master weights (runs every optimizer step): forward layout [Cout16][tap][Cin], or the
     data-gradient layout [Cin16][flipped tap][Cout16]."""

@@ -392,6 +392,32 @@ int ore_roi_losses_fwd(const float* scores, const float* deltas, const float* bo
 int ore_sgd_step_fwd(float* params, const float* grads, float* momentum_buf, int64_t n_chunks, const float* chunk_lr,
                      const float* chunk_wd, const float* lr_scale_dev, float lr_scale, float momentum, float clip_value,
                      float grad_scale, void* stream);
+/* Norm clip + SGD with or without Nesterov momentum over the same bucket (csrc/ore_optim.hip; ref:fewx/solver/build.py:19-59, :136):
+ *   g^ = grad_scale*grad; norm = ||g^ over S||_p; coef = min(clip / (norm + 1e-6), 1) (a NaN stays one); g = g^*coef; g += wd*p;
+ *   buf = momentum*buf + g; p -= lr*(nesterov ? g + momentum*buf : buf)
+ * = torch.nn.utils.clip_grad_norm_(S, clip, p) + torch.optim.SGD(nesterov).step.  S is one parameter (the reference's per-parameter
+ * clipper), or with full_model every parameter of the bucket (detectron2's later "full_model" clip type; not in the reference).
+ * ore_grad_norm_geometry: the chunks one partial sum covers and the partials one pass of the per-parameter reduction takes.
+ * ore_grad_norm_plan (host only): from numel[n_params], *n_chunks (sum of ceil(numel / 256)) and *n_parts; part0 [n_params + 1]
+ * (first partial of every parameter, then n_parts) and part_param [part_cap >= n_parts] (the parameter of every partial) where
+ * non-NULL.  Call it with NULL tables to size them.
+ * ore_grad_norm_fwd: two launches (three with full_model), fixed summation order, no floating-point atomics, no host read.  Device
+ * arrays: numel, chunk0 [n_params] int64 (elements; first chunk), part_param, part0 as planned (int32); workspaces partial [n_parts]
+ * and acc [n_params]; outputs norm [n_params], coef [n_params] and, with full_model, total [1] (the norm over all parameters; coef
+ * then holds the one coefficient n_params times).  norm_kind 2, 1, or 0 for the maximum norm.  Elements beyond numel (the padding of
+ * a parameter's last chunk) are in no norm.
+ * ore_sgd_step_clipnorm_fwd: the update; chunk_param [n_chunks] int32 names the parameter of a chunk.  coef NULL: the value clamp of
+ * ore_sgd_step_fwd instead of the multiplication (value clipping with Nesterov).  Padding elements are not written. */
+int ore_grad_norm_geometry(int32_t* chunks_per_partial, int32_t* partials_per_pass);
+int ore_grad_norm_plan(const int64_t* numel, int32_t n_params, int32_t* part0, int32_t* part_param, int64_t part_cap,
+                       int64_t* n_chunks, int64_t* n_parts);
+int ore_grad_norm_fwd(const float* grads, int32_t n_params, const int64_t* numel, const int64_t* chunk0, const int32_t* part_param,
+                      const int32_t* part0, int64_t n_parts, int32_t norm_kind, int32_t full_model, float clip_value,
+                      float grad_scale, float* partial, float* acc, float* norm, float* coef, float* total, void* stream);
+int ore_sgd_step_clipnorm_fwd(float* params, const float* grads, float* momentum_buf, int64_t n_chunks, const float* chunk_lr,
+                              const float* chunk_wd, const int32_t* chunk_param, const int64_t* numel, const int64_t* chunk0,
+                              const float* coef, const float* lr_scale_dev, float lr_scale, float momentum, float clip_value,
+                              float grad_scale, int32_t nesterov, void* stream);
 
 /* ------------------------------------------------------------------ backward of trainable layers */
 /* What torch.autograd does for F.conv2d / F.linear / ReLU / FrozenBN inside `losses.backward()` (d2z:engine/train_loop.py:279;

@@ -36,6 +36,10 @@ def main():
     ap.add_argument("--graph-step", action="store_true", help="the WHOLE iteration (forward, losses, backward, clip + SGD) as one replayed hipGraph "
                     "(fewx.solver.GraphedTrainStep; single process)")
     ap.add_argument("--roi-bwd", default=None, choices=("tiled", "fixed", "atomic"), help="A/B aid: the ROIAlign backward form (default: the library's)")
+    ap.add_argument("--clip-type", default=None, choices=("value", "norm", "full_model"), help="SOLVER.CLIP_GRADIENTS.CLIP_TYPE (default: the "
+                    "config's, value): norm = clip_grad_norm_ per parameter, full_model = one norm over all parameters")
+    ap.add_argument("--norm-type", type=float, default=None, help="SOLVER.CLIP_GRADIENTS.NORM_TYPE: 2, 1 or inf (default: the config's, 2)")
+    ap.add_argument("--nesterov", action="store_true", help="SOLVER.NESTEROV (default: the config's, off)")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -52,6 +56,12 @@ def main():
     cfg = get_cfg()
     cfg.merge_from_file(os.path.join(ROOT, "faster-orefsdet_amd", "configs", "fsod", "finetune_vovnet.yaml"))
     cfg.merge_from_list(["MODEL.DEVICE", "cuda", "INPUT.FS.SUPPORT_SHOT", a.shots])
+    if a.clip_type is not None:
+        cfg.SOLVER.CLIP_GRADIENTS.CLIP_TYPE = a.clip_type
+    if a.norm_type is not None:
+        cfg.SOLVER.CLIP_GRADIENTS.NORM_TYPE = a.norm_type
+    if a.nesterov:
+        cfg.SOLVER.NESTEROV = True
     cfg.freeze()
     torch.manual_seed(0)
     m = build_model(cfg)
@@ -122,6 +132,8 @@ def main():
                           "config": {"workload": "finetune_vovnet.yaml train step, %d x (1 query %dx%d + %d support 240x240) per GPU" % (a.batch, a.size, a.size, a.shots),
                                      "batch_per_gpu": a.batch,
                                      "bucket_bytes": 4 * opt.bucket.size},
+                          "optimizer": {"clip_type": opt.clip_type, "norm_type": opt.norm_type, "nesterov": opt.nesterov,
+                                        "clip_value": opt.clip_value, "parameters": len(opt.bucket.numels)},
                           "train_graph": bool(a.graph), "train_graph_error": m.__dict__.get("_ore_train_graph_error"),
                           "whole_step_graph": None if stepper is None else {"replays": stepper.replays, "eager_steps": stepper.eager_steps, "error": stepper.error},
                           "losses": {k: float(v.detach()) for k, v in losses.items()}}))

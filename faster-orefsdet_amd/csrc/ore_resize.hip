@@ -15,25 +15,12 @@
 
 namespace {
 
-constexpr int TW = 64, TH = 16, NT = 256;
+constexpr int TW = ORE_RESIZE_TW, TH = ORE_RESIZE_TH, NT = 256;
 // threads of a one-launch block: a tile of a 3x reduction stages ~60 source rows, and with 1080x1920 -> 320x569 only 180 tiles exist for
 // 256 CUs, so the block's own width is what hides its latencies (measured 14.3 / 9.7 / 8.1 us at 256 / 512 / 1024; profiles/EXPERIMENTS.md)
 constexpr int NTF = 1024;
-constexpr int ORE_RESIZE_LDS_BYTES = 64 * 1024;          // dynamic LDS a launch may ask for without opting in to more
 
-__device__ __forceinline__ uint32_t clip8(int32_t acc) {
-    const int32_t v = acc >> ORE_RESIZE_PREC;
-    return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
-
-// the four bytes src[p .. p + 4) as a word; bytes outside [0, total) read as 0 without being touched
-__device__ __forceinline__ uint32_t guarded_word(const uint8_t* src, int64_t p, int64_t total) {
-    uint32_t wd = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-        if (p + b >= 0 && p + b < total) wd |= (uint32_t)src[p + b] << (b * 8);
-    return wd;
-}
+__device__ __forceinline__ uint32_t clip8(int32_t acc) { return ore_resize_clip8(acc); }
 
 struct FusedArgs {
     const uint8_t* src; int32_t h, w;
@@ -79,16 +66,10 @@ __global__ __launch_bounds__(NTF) void k_resize_fused(const FusedArgs a) {
     for (int i = tid; i < nrows * S16; i += NTF) {
         const int rr = i / S16, v = i - rr * S16;
         const int64_t row_lo = ((int64_t)(r0 + rr) * a.w + cx0) * 3;
-        const int64_t p = ((row_lo + al) & ~(int64_t)15) - al + (int64_t)v * 16;
+        const int64_t p = ore_resize_granule_at(row_lo, al, v);
         if (p >= row_lo + (int64_t)ncols * 3) continue;
-        uint4 val;
-        if (p >= 0 && p + 16 <= total) {
-            val = *reinterpret_cast<const uint4*>(a.src + p);
-        } else {                                                  // the granule straddles an end of the image: byte by byte, inside only
-            val = make_uint4(guarded_word(a.src, p, total), guarded_word(a.src, p + 4, total), guarded_word(a.src, p + 8, total),
-                             guarded_word(a.src, p + 12, total));
-        }
-        *reinterpret_cast<uint4*>(s_src + rr * a.S + v * 16) = val;
+        // a granule that straddles an end of the image is read byte by byte, inside only
+        *reinterpret_cast<uint4*>(s_src + rr * a.S + v * 16) = ore_resize_granule_load(a.src, p, 0, total);
     }
     __syncthreads();
 
@@ -100,22 +81,9 @@ __global__ __launch_bounds__(NTF) void k_resize_fused(const FusedArgs a) {
         const int rr = i >> 6, x = i & (TW - 1);
         if (x >= tw) continue;
         const int64_t row_lo = ((int64_t)(r0 + rr) * a.w + cx0) * 3;
-        const int at = rr * a.S + (int)((row_lo + al) & 15) + (s_xb[2 * x] - cx0) * 3, sh = at & 3;
-        const uint32_t* q = reinterpret_cast<const uint32_t*>(s_src + (at - sh));
-        const int groups = (s_xb[2 * x + 1] + 3) >> 2;
-        const int32_t* k = s_kx + x * ksx4;
-        int32_t acc0 = 1 << (ORE_RESIZE_PREC - 1), acc1 = acc0, acc2 = acc0;
-        uint32_t lo = q[0];
-        for (int g = 0; g < groups; ++g) {
-            const uint32_t w1 = q[3 * g + 1], w2 = q[3 * g + 2], w3 = q[3 * g + 3];
-            const uint32_t d0 = __builtin_amdgcn_alignbyte(w1, lo, sh), d1 = __builtin_amdgcn_alignbyte(w2, w1, sh),
-                           d2 = __builtin_amdgcn_alignbyte(w3, w2, sh);
-            lo = w3;
-            const int4 kk = *reinterpret_cast<const int4*>(k + 4 * g);
-            acc0 += (int32_t)(d0 & 255) * kk.x + (int32_t)(d0 >> 24) * kk.y + (int32_t)((d1 >> 16) & 255) * kk.z + (int32_t)((d2 >> 8) & 255) * kk.w;
-            acc1 += (int32_t)((d0 >> 8) & 255) * kk.x + (int32_t)(d1 & 255) * kk.y + (int32_t)(d1 >> 24) * kk.z + (int32_t)((d2 >> 16) & 255) * kk.w;
-            acc2 += (int32_t)((d0 >> 16) & 255) * kk.x + (int32_t)((d1 >> 8) & 255) * kk.y + (int32_t)(d2 & 255) * kk.z + (int32_t)(d2 >> 24) * kk.w;
-        }
+        const int at = rr * a.S + (int)((row_lo + al) & 15) + (s_xb[2 * x] - cx0) * 3;
+        int32_t acc0, acc1, acc2;
+        ore_resize_htaps_lds(s_src, at, (s_xb[2 * x + 1] + 3) >> 2, s_kx + x * ksx4, acc0, acc1, acc2);
         s_inter[(p0 * a.R + rr) * TW + x] = (uint8_t)clip8(acc0);
         s_inter[(1 * a.R + rr) * TW + x] = (uint8_t)clip8(acc1);
         s_inter[(p2 * a.R + rr) * TW + x] = (uint8_t)clip8(acc2);
@@ -129,15 +97,8 @@ __global__ __launch_bounds__(NTF) void k_resize_fused(const FusedArgs a) {
         const int ymin = s_yb[2 * y] - r0, cnt = s_yb[2 * y + 1];
         const int32_t* k = s_ky + y * a.ksy;
         const uint8_t* col = s_inter + ((size_t)c * a.R + ymin) * TW + x4;
-        int32_t a0 = 1 << (ORE_RESIZE_PREC - 1), a1 = a0, a2 = a0, a3 = a0;
-        for (int t = 0; t < cnt; ++t) {
-            const uint32_t wd = *reinterpret_cast<const uint32_t*>(col + t * TW);
-            const int32_t kk = k[t];
-            a0 += (int32_t)(wd & 255) * kk;
-            a1 += (int32_t)((wd >> 8) & 255) * kk;
-            a2 += (int32_t)((wd >> 16) & 255) * kk;
-            a3 += (int32_t)(wd >> 24) * kk;
-        }
+        int32_t a0, a1, a2, a3;
+        ore_resize_vtaps_lds(col, TW, cnt, k, a0, a1, a2, a3);
         uint8_t* o = a.dst + ((size_t)c * a.nh + (y0 + y)) * a.nw + x0 + x4;
         const int n = tw - x4;
         const uint32_t b0 = clip8(a0), b1 = clip8(a1), b2 = clip8(a2), b3 = clip8(a3);
@@ -160,13 +121,8 @@ __global__ __launch_bounds__(NT) void k_resize_h(const uint8_t* __restrict__ src
     const int xmin = xb[2 * x], cnt = xb[2 * x + 1];
     const uint8_t* p = src + ((size_t)r * w + xmin) * 3;
     const int32_t* k = kx + (size_t)x * ksx;
-    int32_t acc0 = 1 << (ORE_RESIZE_PREC - 1), acc1 = acc0, acc2 = acc0;
-    for (int t = 0; t < cnt; ++t) {
-        const int32_t kk = k[t];
-        acc0 += (int32_t)p[3 * t] * kk;
-        acc1 += (int32_t)p[3 * t + 1] * kk;
-        acc2 += (int32_t)p[3 * t + 2] * kk;
-    }
+    int32_t acc0, acc1, acc2;
+    ore_resize_taps_mem(p, 3, cnt, k, acc0, acc1, acc2);
     uint8_t* o = mid + ((size_t)r * nw + x) * 3;
     o[0] = (uint8_t)clip8(acc0);
     o[1] = (uint8_t)clip8(acc1);
@@ -180,44 +136,17 @@ __global__ __launch_bounds__(NT) void k_resize_v(const uint8_t* __restrict__ mid
     const int ymin = yb[2 * y], cnt = yb[2 * y + 1];
     const uint8_t* p = mid + ((size_t)ymin * nw + x) * 3;
     const int32_t* k = ky + (size_t)y * ksy;
-    int32_t acc0 = 1 << (ORE_RESIZE_PREC - 1), acc1 = acc0, acc2 = acc0;
-    for (int t = 0; t < cnt; ++t) {
-        const int32_t kk = k[t];
-        const uint8_t* q = p + (size_t)t * nw * 3;
-        acc0 += (int32_t)q[0] * kk;
-        acc1 += (int32_t)q[1] * kk;
-        acc2 += (int32_t)q[2] * kk;
-    }
+    int32_t acc0, acc1, acc2;
+    ore_resize_taps_mem(p, (size_t)nw * 3, cnt, k, acc0, acc1, acc2);
     const size_t plane = (size_t)nh * nw, at = (size_t)y * nw + x;
     dst[(swap_rb ? 2 : 0) * plane + at] = (uint8_t)clip8(acc0);
     dst[plane + at] = (uint8_t)clip8(acc1);
     dst[(swap_rb ? 0 : 2) * plane + at] = (uint8_t)clip8(acc2);
 }
 
-// widest source span (last window's end - first window's start) of any run of `tile` outputs
-int32_t max_tile_span(int32_t in, int32_t out, int32_t tile) {
-    const ore_resize_axis ax = ore_resize_axis_of(in, out);
-    int32_t worst = 0;
-    for (int32_t t0 = 0; t0 < out; t0 += tile) {
-        const int32_t t1 = (t0 + tile < out ? t0 + tile : out) - 1;
-        int32_t lo, n0, lo1, n1;
-        ore_resize_window(ax, in, t0, &lo, &n0);
-        ore_resize_window(ax, in, t1, &lo1, &n1);
-        if (lo1 + n1 - lo > worst) worst = lo1 + n1 - lo;
-    }
-    return worst;
-}
+using FusedLds = ore_resize_fused_lds;
 
-struct FusedLds { int32_t R, S; size_t bytes; };
-
-FusedLds fused_lds(int32_t h, int32_t w, int32_t nh, int32_t nw) {
-    const int32_t ksx = ore_resize_axis_of(w, nw).ksize, ksy = ore_resize_axis_of(h, nh).ksize;
-    FusedLds l;
-    l.R = max_tile_span(h, nh, TH);
-    l.S = ((max_tile_span(w, nw, TW) * 3 + 15 + 15) & ~15);       // a row starts up to 15 bytes into its first granule
-    l.bytes = (size_t)(TW * ((ksx + 3) & ~3) + ((TH * ksy + 3) & ~3) + TW * 2 + TH * 2) * 4 + (size_t)3 * l.R * TW + (size_t)l.R * l.S + 32;
-    return l;
-}
+FusedLds fused_lds(int32_t h, int32_t w, int32_t nh, int32_t nw) { return ore_resize_fused_lds_of(h, w, nh, nw, TH, TW); }
 
 bool sizes_ok(int32_t h, int32_t w, int32_t nh, int32_t nw) {
     return h >= 1 && w >= 1 && nh >= 1 && nw >= 1 && h <= ORE_RESIZE_MAX_SIDE && w <= ORE_RESIZE_MAX_SIDE && nh <= ORE_RESIZE_MAX_SIDE &&

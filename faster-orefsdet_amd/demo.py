@@ -6,7 +6,10 @@
 (--heatmap-alpha, --heatmap-colormap jet | gray).  --track follows the detections from frame to frame (ids that persist, boxes coloured and
 labelled by them) over a video, or over several --input images taken as a sequence in the given order, and prints the number of tracks
 started.  Images are decoded with Pillow and drawn on the device.  Video (--video-input, --webcam) needs OpenCV to decode and to show frames;
-this package neither ships nor requires it, and the two flags say so when it is missing."""
+this package neither ships nor requires it, and the two flags say so when it is missing.
+--support-json ANN.json --support-root DIR [--shots N] enrols every category of a COCO json from its annotated images (under DIR) before
+the first frame: support crops and prototypes are computed on the device, in place of a support_feature.pkl.  With more than one
+category every one of them is detected (N-way)."""
 import argparse
 import glob
 import os
@@ -28,6 +31,10 @@ def get_parser():
     parser.add_argument("--heatmap-colormap", default="jet", choices=("jet", "gray"), help="the heat map's colour table (default: %(default)s)")
     parser.add_argument("--track", action="store_true", help="follow the detections across the frames: ids that persist, colours and labels by id; "
                         "needs --video-input, --webcam or several --input frames (a sequence in the given order); prints the tracks started")
+    parser.add_argument("--support-json", metavar="ANN.json", help="enrol every category of this COCO annotation file as a support class before "
+                        "the first frame (instead of support_feature.pkl); needs --support-root")
+    parser.add_argument("--support-root", metavar="DIR", help="the directory of the images --support-json names")
+    parser.add_argument("--shots", type=int, default=None, metavar="N", help="with --support-json: the first N annotations of each category (default: all)")
     parser.add_argument("--video-input", metavar="VIDEO", help="annotate a video file instead (needs OpenCV)")
     parser.add_argument("--webcam", action="store_true", help="annotate the first camera's frames instead (needs OpenCV)")
     parser.add_argument("--opts", nargs=argparse.REMAINDER, default=[], metavar="KEY VALUE", help="config overrides, e.g. MODEL.WEIGHTS model.pth; must come last")
@@ -43,6 +50,18 @@ def setup_cfg(args):
     cfg.MODEL.ROI_HEADS.SCORE_THRESH_TEST = float(args.confidence_threshold)
     cfg.freeze()
     return cfg
+
+
+def enrol_support(model, args, log):
+    """--support-json: every category of the annotation file becomes a support class of the model."""
+    from fewx.data.datasets.register_coco import load_coco_json
+    from fewx.data.support import enrol_from_records
+    shots = enrol_from_records(model, load_coco_json(args.support_json, args.support_root, extra_annotation_keys=["id"]), shot=args.shots)
+    if not shots:
+        sys.exit(f"demo.py: {args.support_json} holds no annotation to enrol")
+    if len(shots) > 1:
+        model.support_classes = "all"
+    log.info("enrolled %s from %s", ", ".join(f"class {c}: {n} shots" for c, n in shots.items()), args.support_json)
 
 
 def input_paths(patterns):
@@ -125,6 +144,10 @@ def main(argv=None):
         sys.exit("demo.py: --track needs a sequence: --video-input, --webcam or at least two --input frames")
     elif not args.output:
         sys.exit("demo.py: --input needs --output: pictures are written to files, there is no window to show them in")
+    if bool(args.support_json) != bool(args.support_root) or (args.shots is not None and not args.support_json):
+        sys.exit("demo.py: --support-json and --support-root go together (and --shots with them)")
+    if args.shots is not None and args.shots < 1:
+        sys.exit("demo.py: --shots must be at least 1")
 
     from detectron2.utils.logger import setup_logger
     from predictor import VisualizationDemo, heatmap_args
@@ -135,6 +158,8 @@ def main(argv=None):
     except ValueError as err:
         sys.exit(f"demo.py: {err}")
     demo = VisualizationDemo(setup_cfg(args), heatmap=heatmap, track=args.track)
+    if args.support_json:
+        enrol_support(demo.predictor.model, args, log)
     if video:
         run_video(demo, args, cv2)
     elif args.track:

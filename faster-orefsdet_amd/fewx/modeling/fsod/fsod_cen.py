@@ -160,6 +160,7 @@ class CenterNet2Detector(nn.Module):
             score_thresh=cfg.MODEL.CENTERNET.INFERENCE_TH, pre_topk=cfg.MODEL.CENTERNET.PRE_NMS_TOPK_TEST,
             nms_thresh=cfg.MODEL.CENTERNET.NMS_TH_TEST, post_topk=cfg.MODEL.CENTERNET.POST_NMS_TOPK_TEST)
         self.support_dict = None
+        self._enrolled_shots = {}          # class id -> the crops and support boxes enrol() installed it from (enrol(replace=False))
         # "fp32" (the reference's precision) or "bf16": operand precision of the MFMA convs of the EVAL engines this detector
         # builds (orehip.set_conv_precision / include/ore_hip.h ORE_CONV_BF16 -- BASELINE configs[4]); set it before the first forward
         self.conv_operands = "fp32"
@@ -185,6 +186,9 @@ class CenterNet2Detector(nn.Module):
         """{'p3': {cls: [1,C,32,32]}, 'p4': ..., 'p5': ..., 'rcnn_8': ..., 'rcnn_4': ...} (the support_feature.pkl layout)."""
         self.support_dict = {k: {c: f.to(self.device) for c, f in v.items()} for k, v in support_dict.items()}
         self._engine_key = None
+        # shots kept by enrol() go with the prototypes they gave: a class that was replaced or dropped here loses them
+        p3 = self.support_dict.get("p3", {})
+        self._enrolled_shots = {c: e for c, e in self._enrolled_shots.items() if p3.get(c) is e["ref"]}
 
     def init_model(self, support_file="./support_dir/support_feature.pkl", support_df=None, read_image=None,
                    support_df_path="./datasets/coco/10_shot_support_df.pkl", image_root="./datasets/coco"):
@@ -270,6 +274,46 @@ class CenterNet2Detector(nn.Module):
                 cur.setdefault(k, {}).update(v)
             self.set_support_dict(cur)
         return out
+
+    # ---- enrolment from annotated frames -----------------------------------------------------------------------
+    @torch.no_grad()
+    def enrol(self, frames, boxes, cls_id, frame_index=None, replace=True):
+        """Installs support class `cls_id` from annotated frames: orehip.support_crops (frames: one [h, w, 3] uint8 image in the model's
+        channel order or a list of them, boxes [K, 4] XYXY absolute, frame_index [K]: "support crop v1", include/ore_hip.h) ->
+        compute_support_dict(crops, support boxes, cls_id, merge=True).  replace=False adds the K shots to the ones this class was
+        enrolled with, and the class then holds exactly what one call with all its shots gives: rcnn_8 / rcnn_4 one row per shot in
+        enrolment order, p3..p5 the mean over all shots.  The feature kernels a pass takes depend on its batch size, so rows computed
+        two at a time and five at a time differ in the last bit; the shots' crops and boxes (uint8, on the device) are therefore what
+        is kept per enrolled class (until set_support_dict replaces or drops it), and the features are computed over all of them in
+        one pass: an addition costs a pass over all the class's shots.  A class installed any other way has
+        no kept shots, and adding to it is a ValueError.  The cached engines are dropped as by set_support_dict, so
+        support_classes = "all" sees the class at the next forward.
+        Returns the crops and support boxes of this call's K shots: ([K, 3, 240, 240] uint8 on the device, [K, 4] float32 on the host)."""
+        import orehip
+        crops, sboxes = orehip.support_crops(frames, boxes, frame_index, device=self.device)
+        all_crops, all_boxes = crops, sboxes
+        if not replace and self.support_dict is not None and cls_id in self.support_dict.get("p3", {}):
+            old = self._enrolled_shots.get(cls_id)
+            if old is None:
+                raise ValueError(f"support class {cls_id!r} was not installed by enrol(): its shots are not known, so none can be added "
+                                 "to it (enrol it with replace=True)")
+            all_crops, all_boxes = torch.cat([old["crops"], crops]), torch.cat([old["boxes"], sboxes])
+        self.compute_support_dict(all_crops, all_boxes, cls_id=cls_id, merge=True)
+        self._enrolled_shots[cls_id] = {"crops": all_crops, "boxes": all_boxes, "ref": self.support_dict["p3"][cls_id]}
+        return crops, sboxes
+
+    def forget(self, cls_id):
+        """Removes support class `cls_id` from every level of support_dict (KeyError for an unknown id) and drops the cached engines as
+        set_support_dict does; with the last class gone, support_dict is None again."""
+        if self.support_dict is None or not any(cls_id in v for v in self.support_dict.values()):
+            raise KeyError(cls_id)
+        cur = {k: {c: f for c, f in v.items() if c != cls_id} for k, v in self.support_dict.items()}
+        if not cur.get("p3"):
+            self.support_dict = None
+            self._engine_key = None
+            self._enrolled_shots = {}
+        else:
+            self.set_support_dict(cur)
 
     def save_support_file(self, support_file="./support_dir/support_feature.pkl"):
         """Writes self.support_dict in the reference's pickle layout (CPU tensors keyed by level then class id)."""

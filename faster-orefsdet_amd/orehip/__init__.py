@@ -991,6 +991,134 @@ def resize_bilinear_u8(img_hwc_u8: torch.Tensor, nh: int, nw: int, swap_rb: bool
 
 
 # ---------------------------------------------------------------------------------------------------
+# support crops: annotated frames -> the S x S crops and support boxes of a support set (csrc/ore_support.hip, csrc/ore_support_plan.cpp)
+# ---------------------------------------------------------------------------------------------------
+SUPPORT_JOB_INTS = 32                                    # ORE_SUPPORT_JOB_INTS; the record's words are ORE_SJ_* (include/ore_hip.h)
+SUPPORT_FILL = (104, 116, 124)                           # round(cfg.MODEL.PIXEL_MEAN): padding normalises to about 0
+_SJ_H, _SJ_RECT, _SJ_DST, _SJ_XB, _SJ_YB, _SJ_KX, _SJ_KY, _SJ_KSX, _SJ_KSY, _SJ_FORM, _SJ_D, _SJ_X0, _SJ_BOX = 2, 4, 8, 12, 13, 14, 15, 16, 17, 18, 24, 25, 27
+_SUPPORT_BUF: Dict[tuple, dict] = {}                     # (device, stream) -> pinned job buffers with their uploads' events, the device copy, the workspace
+
+
+def _support_box(box) -> np.ndarray:
+    b = np.ascontiguousarray(np.asarray(box, dtype=np.float32).reshape(4))
+    return b
+
+
+def _support_refused(h, w, box, size, context, index=None) -> ValueError:
+    which = "box" if index is None else f"box {index}"
+    return ValueError(f"support crop: {which} {[float(v) for v in box]} lies outside its {h}x{w} frame, or a size is out of range "
+                      f"(frame sides 1 .. 8192, 2 * context {context} < size {size} <= 8192)")
+
+
+def support_crop_form(h: int, w: int, box, size: int = 240, context: int = 16) -> int:
+    """The form the crop of this box takes (ore_support_crop_form): RESIZE_FORM_LDS (served by the one launch that covers every such
+    job of a call) or RESIZE_FORM_WORKSPACE (a horizontal and a vertical launch through a workspace slice)."""
+    b = _support_box(box)
+    form = int(lib().ore_support_crop_form(int(h), int(w), b.ctypes.data, int(size), int(context)))
+    if form == 0:
+        raise _support_refused(h, w, b, size, context)
+    return form
+
+
+def support_crop_plan(h: int, w: int, box, size: int = 240, context: int = 16) -> dict:
+    """The plan of one support crop (ore_support_crop_plan, host only; the contract is "support crop v1" of include/ore_hip.h):
+    {"D", "origin" (x0, y0), "src" (rx0, ry0, rx1, ry1), "dst" (dx0, dy0, dx1, dy1), "box" float32 [4] inside the crop, "form",
+    "workspace_bytes", and the job's resample tables "x_bounds" [nw, 2], "x_coeffs" [nw, ksx], "y_bounds" [nh, 2], "y_coeffs" [nh, ksy]}."""
+    L = lib()
+    h, w, size, context = int(h), int(w), int(size), int(context)
+    b = _support_box(box)
+    n = int(L.ore_support_crop_job_ints(h, w, b.ctypes.data, size, context))
+    if n == 0:
+        raise _support_refused(h, w, b, size, context)
+    buf = np.zeros(SUPPORT_JOB_INTS + n, dtype=np.int32)
+    _chk(L.ore_support_crop_plan(h, w, b.ctypes.data, size, context, None, SUPPORT_JOB_INTS, 0, buf.ctypes.data, buf.ctypes.data),
+         "ore_support_crop_plan")
+    r = buf[:SUPPORT_JOB_INTS]
+    src, dst = tuple(int(v) for v in r[_SJ_RECT:_SJ_RECT + 4]), tuple(int(v) for v in r[_SJ_DST:_SJ_DST + 4])
+    nw, nh, ksx, ksy = dst[2] - dst[0], dst[3] - dst[1], int(r[_SJ_KSX]), int(r[_SJ_KSY])
+    return {"D": int(r[_SJ_D]), "origin": (int(r[_SJ_X0]), int(r[_SJ_X0 + 1])), "src": src, "dst": dst,
+            "box": r[_SJ_BOX:_SJ_BOX + 4].view(np.float32).copy(), "form": int(r[_SJ_FORM]),
+            "workspace_bytes": int(L.ore_support_crop_workspace_bytes(h, w, b.ctypes.data, size, context)),
+            "x_bounds": buf[r[_SJ_XB]:r[_SJ_XB] + nw * 2].reshape(nw, 2).copy(), "x_coeffs": buf[r[_SJ_KX]:r[_SJ_KX] + nw * ksx].reshape(nw, ksx).copy(),
+            "y_bounds": buf[r[_SJ_YB]:r[_SJ_YB] + nh * 2].reshape(nh, 2).copy(), "y_coeffs": buf[r[_SJ_KY]:r[_SJ_KY] + nh * ksy].reshape(nh, ksy).copy()}
+
+
+def support_crops(frames, boxes, frame_index=None, size: int = 240, context: int = 16, fill=SUPPORT_FILL,
+                  out: Optional[torch.Tensor] = None, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Support crops of K boxes ("support crop v1", include/ore_hip.h).  frames: one [h, w, 3] uint8 tensor / array or a list of them
+    (sizes may differ; a host frame is uploaded once through pinned memory), boxes [K, 4] XYXY absolute, frame_index [K] (default: all
+    0).  Returns (crops [K, 3, size, size] uint8 on the device, planar, the frames' channel order; support boxes [K, 4] float32 on the
+    host).  All K jobs are planned on the host into one pinned buffer, uploaded with one copy, and run by at most three launches on
+    the current stream; the host does not wait for the device: a pinned buffer is written again only once the upload that read it
+    is seen complete (an event query), and while none is free another one is added.  The buffers are cached per (device, stream)
+    and do not touch the resize tables' cache.  A box outside its frame: ValueError naming its index."""
+    L = lib()
+    size, context = int(size), int(context)
+    if torch.is_tensor(frames) or isinstance(frames, np.ndarray):
+        frames = [frames]
+    frames = [torch.from_numpy(np.ascontiguousarray(f)) if isinstance(f, np.ndarray) else f for f in frames]
+    if device is None:
+        device = next((f.device for f in frames if f.is_cuda), None) or torch.device("cuda", torch.cuda.current_device())
+    dev = torch.device(device)
+    bx = np.ascontiguousarray(torch.as_tensor(boxes).detach().cpu().numpy() if torch.is_tensor(boxes) else np.asarray(boxes), dtype=np.float32).reshape(-1, 4)
+    K = len(bx)
+    fi = np.zeros(K, dtype=np.int64) if frame_index is None else np.asarray(torch.as_tensor(frame_index).cpu().numpy(), dtype=np.int64).reshape(-1)
+    if K < 1 or len(fi) != K or (fi < 0).any() or (fi >= len(frames)).any():
+        raise ValueError(f"support_crops: {K} boxes, {len(fi)} frame indices into {len(frames)} frames")
+    fill = tuple(int(v) for v in fill)
+    if len(fill) != 3 or min(fill) < 0 or max(fill) > 255:
+        raise ValueError(f"support_crops: fill must be three bytes, not {fill}")
+    for f in frames:
+        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3:
+            raise ValueError(f"support_crops takes [h, w, 3] uint8 frames, not {tuple(f.shape)} {f.dtype}")
+    with torch.cuda.device(dev):
+        used = sorted(set(int(i) for i in fi))
+        on_dev = {i: (frames[i] if frames[i].is_cuda else frames[i].contiguous().pin_memory().to(dev, non_blocking=True)).contiguous() for i in used}
+        # sizes first: table words and workspace slice of every job
+        n_tab, n_ws = [], []
+        for k in range(K):
+            h, w = int(frames[fi[k]].shape[0]), int(frames[fi[k]].shape[1])
+            n = int(L.ore_support_crop_job_ints(h, w, bx[k].ctypes.data, size, context))
+            if n == 0:
+                raise _support_refused(h, w, bx[k], size, context, k)
+            n_tab.append(n)
+            n_ws.append(int(L.ore_support_crop_workspace_bytes(h, w, bx[k].ctypes.data, size, context)))
+        total, ws_bytes = K * SUPPORT_JOB_INTS + sum(n_tab), sum(n_ws)
+        cur = _stream()
+        st = _SUPPORT_BUF.setdefault((str(dev), cur), {"pinned": [], "dev": None, "ws": None})
+        # a pinned buffer whose last upload has completed (queried, not waited for); a backlog on the stream adds a buffer instead
+        slot = next((p for p in st["pinned"] if p["host"].numel() >= total and (p["event"] is None or p["event"].query())), None)
+        if slot is None:
+            st["pinned"] = [p for p in st["pinned"] if p["host"].numel() >= total or not (p["event"] is None or p["event"].query())]     # outgrown and idle: dropped
+            slot = {"host": torch.empty(total, dtype=torch.int32, pin_memory=True), "event": None}
+            st["pinned"].append(slot)
+        if st["dev"] is None or st["dev"].numel() < total:
+            st["dev"] = torch.empty(total, dtype=torch.int32, device=dev)
+        if ws_bytes and (st["ws"] is None or st["ws"].numel() < ws_bytes):
+            st["ws"] = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        st["last"] = slot                                                      # the latest call's plan (tools/bench_support.py replays it)
+        host, base = slot["host"], slot["host"].data_ptr()
+        t_off, w_off = K * SUPPORT_JOB_INTS, 0
+        for k in range(K):
+            f = on_dev[int(fi[k])]
+            _chk(L.ore_support_crop_plan(int(f.shape[0]), int(f.shape[1]), bx[k].ctypes.data, size, context, f.data_ptr(), t_off, w_off,
+                                         base + 4 * k * SUPPORT_JOB_INTS, base), "ore_support_crop_plan")
+            t_off += n_tab[k]
+            w_off += n_ws[k]
+        st["dev"][:total].copy_(host[:total], non_blocking=True)               # the call's one upload
+        slot["event"] = torch.cuda.Event()
+        slot["event"].record(torch.cuda.current_stream(dev))
+        if out is None:
+            out = torch.empty(K, 3, size, size, dtype=torch.uint8, device=dev)
+        assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (K, 3, size, size) and out.is_contiguous()
+        _chk(L.ore_support_crop_u8_fwd(_ptr(st["dev"]), base, total, K, size, fill[0] | fill[1] << 8 | fill[2] << 16, _ptr(out),
+                                       _ptr(st["ws"]) if ws_bytes else None, ws_bytes, cur), "ore_support_crop_u8_fwd")
+        rec = host[:K * SUPPORT_JOB_INTS].view(K, SUPPORT_JOB_INTS)
+        sboxes = rec[:, _SJ_BOX:_SJ_BOX + 4].contiguous().view(torch.float32).clone()
+    return out, sboxes
+
+
+# ---------------------------------------------------------------------------------------------------
 # test-time augmentation tail (csrc/ore_tta.hip): flipped variants, per-variant collection, the merge
 # ---------------------------------------------------------------------------------------------------
 TTA_MAX_CANDIDATES = 8192                                # rows one ore_tta_merge_fwd takes (include/ore_hip.h)

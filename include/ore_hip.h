@@ -805,6 +805,68 @@ size_t ore_resize_workspace_bytes(int32_t h, int32_t w, int32_t nh, int32_t nw);
 int ore_resize_bilinear_u8_fwd(const uint8_t* src_hwc, int32_t h, int32_t w, uint8_t* dst_chw, int32_t nh, int32_t nw, int32_t swap_rb,
                                const int32_t* tables_dev, int32_t form, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ support crops -------------- */
+/* "Support crop v1": the S x S support crop of one annotated box of a frame, and the box inside the crop -- what compute_support_dict
+ * and generate_support take.  A contract of this package, shaped like FewX's crop_support (a square window around the object with
+ * `context` pixels of context at the crop's scale); no equality with FewX is claimed.  The resampler is the one above (Pillow's
+ * BILINEAR), so Pillow is the oracle.  With frame [h][w][3] uint8, box (x1, y1, x2, y2) XYXY absolute fp32, c = context,
+ * T = S - 2c, all integer arithmetic with floor division:
+ *   integer box        bx0 = max(0, floor x1), by0 = max(0, floor y1), bx1 = min(w, ceil x2), by1 = min(h, ceil y2); bw = bx1 - bx0,
+ *                      bh = by1 - by0; bw < 1 or bh < 1 (the box lies outside the frame) is refused
+ *   window             L = max(bw, bh), m = (c * L + T - 1) / T, D = L + 2m, origin x0 = bx0 - (D - bw) / 2, y0 = by0 - (D - bh) / 2
+ *   source rectangle   window clipped to the frame: rx0 = max(x0, 0), rx1 = min(x0 + D, w), ry0, ry1 likewise
+ *   destination rect   dx0 = ((rx0 - x0) * S + D / 2) / D, dx1 = ((rx1 - x0) * S + D / 2) / D, dy0, dy1 likewise
+ *   pixels             crop[:, dy0:dy1, dx0:dx1] = Image.fromarray(frame[ry0:ry1, rx0:rx1]).resize((dx1 - dx0, dy1 - dy0), BILINEAR),
+ *                      every other pixel = fill (per channel); planar [3][S][S] in the frame's channel order
+ *   support box        fp32, in this order, no contraction: sx = float(dx1 - dx0) / float(rx1 - rx0), x' = float(dx0) + (x - float(rx0)) * sx
+ *                      (y likewise), then clipped to [0, S]
+ * A call's K jobs live in one buffer of int32 words that the caller owns: K records of ORE_SUPPORT_JOB_INTS words, then every job's
+ * resample tables (x bounds [nw][2] | y bounds [nh][2] | x coefficients [nw][ksx] | y coefficients [nh][ksy], nw = dx1 - dx0,
+ * nh = dy1 - dy0, each axis exactly what ore_resize_plan(source side, destination side) writes).  Record words (ORE_SJ_*): the
+ * frame's device address (low, high word) and size, the source and destination rectangles, the offsets (in words from the buffer's
+ * start) and tap counts of the four tables, the job's form and LDS sizing, the byte offset of its workspace slice (low, high), D and the
+ * window origin, and the support box as four float bit patterns.
+ * ore_support_crop_job_ints: words of one job's tables (0: the job is refused -- box outside the frame, or sizes out of range: frame
+ *   sides 1 .. 8192, 2 * context < S <= 8192).  A buffer holds K * ORE_SUPPORT_JOB_INTS + the sum of these.
+ * ore_support_crop_form: ORE_RESIZE_FORM_LDS where the job's 16 x 64 output tiles fit the one-launch LDS budget of the resize (64 KiB
+ *   of staged source, intermediate and tables), else ORE_RESIZE_FORM_WORKSPACE (0: refused).  ore_support_crop_workspace_bytes: the
+ *   job's slice of the workspace, (ry1 - ry0) * nw * 3 bytes rounded up to 16, 0 for a job of the LDS form.
+ * ore_support_crop_plan (host only, no GPU needed): writes the record to record_host[ORE_SUPPORT_JOB_INTS] and the tables to
+ *   buffer_host + table_off; frame_dev is stored, not read.
+ * ore_support_crop_u8_fwd: dst [K][3][S][S] uint8 from K jobs (frames of any sizes).  One launch serves every tile of every job of the
+ *   LDS form; jobs of the workspace form take a horizontal launch into their workspace slices and a vertical one: at most three
+ *   launches whatever K.  Every byte of dst is written exactly once, fill included; nothing else is written.  fill_rgb = channel 0 |
+ *   channel 1 << 8 | channel 2 << 16.  jobs_host is the buffer as planned (read on the host to check every record against the buffer,
+ *   the workspace and the canvas before anything is launched), jobs_dev its copy on the device, complete in stream order. */
+#define ORE_SUPPORT_JOB_INTS 32
+#define ORE_SJ_FRAME_LO 0
+#define ORE_SJ_FRAME_HI 1
+#define ORE_SJ_H 2
+#define ORE_SJ_W 3
+#define ORE_SJ_RX0 4      /* source rectangle rx0, ry0, rx1, ry1 */
+#define ORE_SJ_DX0 8      /* destination rectangle dx0, dy0, dx1, dy1 */
+#define ORE_SJ_XB 12      /* table offsets: x bounds, y bounds, x coefficients, y coefficients */
+#define ORE_SJ_YB 13
+#define ORE_SJ_KX 14
+#define ORE_SJ_KY 15
+#define ORE_SJ_KSX 16
+#define ORE_SJ_KSY 17
+#define ORE_SJ_FORM 18
+#define ORE_SJ_LDS_R 19
+#define ORE_SJ_LDS_S 20
+#define ORE_SJ_WS_LO 21
+#define ORE_SJ_WS_HI 22
+#define ORE_SJ_D 24
+#define ORE_SJ_X0 25      /* window origin x0, y0 */
+#define ORE_SJ_BOX 27     /* support box, four float bit patterns */
+size_t ore_support_crop_job_ints(int32_t h, int32_t w, const float* box_xyxy, int32_t S, int32_t context);
+int32_t ore_support_crop_form(int32_t h, int32_t w, const float* box_xyxy, int32_t S, int32_t context);
+size_t ore_support_crop_workspace_bytes(int32_t h, int32_t w, const float* box_xyxy, int32_t S, int32_t context);
+int ore_support_crop_plan(int32_t h, int32_t w, const float* box_xyxy, int32_t S, int32_t context, const uint8_t* frame_dev,
+                          int64_t table_off, int64_t workspace_off, int32_t* record_host, int32_t* buffer_host);
+int ore_support_crop_u8_fwd(const int32_t* jobs_dev, const int32_t* jobs_host, size_t buffer_ints, int32_t K, int32_t S, int32_t fill_rgb,
+                            uint8_t* dst, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ test-time augmentation ---- */
 /* The device side of GeneralizedRCNNWithTTA (d2z:modeling/test_time_augmentation.py): everything between and behind the engine passes
  * of one image's variants, enqueued on `stream`, no host synchronisation.

@@ -1,14 +1,16 @@
-// Backward kernels of the trainable layers ("..._bwd counterparts for trainable layers", 8b).
-//   k_pack_weight      OIHW master weights -> the forward igemm layout, or the flipped/transposed layout that turns the forward
-//                      kernel into the data-gradient conv (dX = conv(dZ, W^T flipped)); runs on device once per optimizer step
-//   k_wgrad            weight gradient dW[co][ky][kx][ci] = sum_rows dZ[row][co] * X[row shifted by tap][ci] on fp32 MFMA,
-//                      rows split over blocks, partial slabs reduced in a fixed order by k_wgrad_reduce (deterministic)
-//   k_relu_affine_bwd  dZ = dY * (Y > 0) * scale[c]          (conv + FrozenBN + ReLU epilogue backward)
-//   k_colsum_*         bias gradient = column sums of dZ, two deterministic stages
-// What they replace: torch.autograd of F.conv2d / F.linear / F.relu / FrozenBatchNorm2d
+// Backward kernels of the trainable layers ("..._bwd counterparts for trainable layers", 8b), the convolutions'
+// gradients apart (weight gradient: ore_conv_wgrad.hip; data gradient: the forward conv kernels on the flipped weights).
+//   k_pack_weight(_multi)   OIHW master weights -> the forward igemm layout, or the flipped/transposed layout that turns the forward
+//                           kernel into the data-gradient conv (dX = conv(dZ, W^T flipped)); runs on device once per optimizer step
+//   k_relu_affine_bwd       dZ = dY * (Y > 0) * scale[c]          (conv + FrozenBN + ReLU epilogue backward)
+//   k_colsum_chunks/_final  bias gradient = column sums of dZ, two deterministic stages
+//   k_corr_fwd_train, k_corr_bwd_a/_b   the correlation block of the head, forward (training form) and backward
+//   k_gn_apply, k_gn_apply_levels_h, k_gn_bwd_prod/_dx, k_colsum_seg/_seg_fin, k_scale_add   GroupNorm (+ ReLU) forward / backward
+//   k_maxpool_bwd, k_sumpool2, k_apool_fwd/_fwd_big/_bwd, k_group_sum/_bcast   pooling and group means, forward / backward
+//   k_granule_transpose, k_combine2(_bwd)   the layout change and the gated sum of the attention branch
+// What they replace: torch.autograd of F.relu / FrozenBatchNorm2d / GroupNorm / the poolings
 //   (d2z:layers/wrappers.py:48-91, d2z:layers/batch_norm.py:44-66) inside d2z:engine/train_loop.py:279 `losses.backward()`.
 #include "ore_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -59,546 +61,6 @@ __global__ __launch_bounds__(256) void k_pack_weight_multi(const ore_pack_job* _
         const int tap = (int)((i / Co16) % taps);
         const int ci = (int)(i / ((long long)Co16 * taps));
         jb.dst[i] = (co < Co && ci < Ci) ? jb.src[((size_t)co * Ci + ci) * taps + (taps - 1 - tap)] : 0.0f;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-struct WgradP {
-    const float* x; int x_ld, x_coff;
-    const float* dz; int dz_ld, dz_coff;
-    int B, H, W, Cin, Cout, kh, kw, pad;
-    int M, chunk;            // rows, rows per split (multiple of 16)
-    float* slab;             // [S][Cout][taps][Cin]
-    float* dw; float beta;   // S == 1: write OIHW directly (no slab, no reduce launch)
-    int bf16;                // ore_conv_set_precision(ORE_CONV_BF16): both operands rounded to bf16 (nearest even) as they are staged
-    float* db; float beta_b; // optional bias gradient = column sums of dZ, accumulated by the blocks that stage dZ anyway (blockIdx.y == 0):
-                             // slab z holds them behind its weight part (slab_stride = weight floats + Cout), S == 1 writes db directly
-    long long slab_stride;
-};
-
-// column sums of the dZ rows a block staged: every thread kept the running sum of its own (row lr, columns lc..lc+3) loads; the 16 rows
-// meet in LDS (one barrier, only when a bias gradient was asked for) and go to the slab's bias part, or straight to db when S == 1
-__device__ __forceinline__ void wgrad_bias_out(const WgradP& p, float (*sA)[80], f32x4 bsum, int co0, float* slab) {
-    const int tid = threadIdx.x, lr = tid >> 4, lc = (tid & 15) * 4;
-    __syncthreads();                                             // the K loop's last reads of sA are done
-    *reinterpret_cast<f32x4*>(&sA[lr][lc]) = bsum;
-    __syncthreads();
-    if (tid < 16 && co0 + lc < p.Cout) {
-        f32x4 s = *reinterpret_cast<const f32x4*>(&sA[0][lc]);
-#pragma unroll
-        for (int r = 1; r < 16; ++r) s += *reinterpret_cast<const f32x4*>(&sA[r][lc]);
-        if (p.dw) {
-            float* o = p.db + co0 + lc;
-            if (p.beta_b != 0.0f) s += p.beta_b * *reinterpret_cast<const f32x4*>(o);
-            *reinterpret_cast<f32x4*>(o) = s;
-        } else {
-            *reinterpret_cast<f32x4*>(slab + (size_t)p.Cout * p.kh * p.kw * p.Cin + co0 + lc) = s;
-        }
-    }
-}
-
-// bf16-operand mode of the weight gradient: dZ and X are rounded to bf16 on their way into LDS and multiplied on the fp32 MFMA --
-// a product of two bf16 values is exact in fp32 and the accumulation is fp32 either way, so the result is that of a bf16 MFMA up to
-// the summation order (the precision class of configs[4]; no speed-up here, the forward / data-gradient convs use the bf16 MFMA).
-__device__ __forceinline__ float bf16_rne(float v) {
-    unsigned u = __float_as_uint(v);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return __uint_as_float(u & 0xFFFF0000u);
-}
-__device__ __forceinline__ f32x4 bf16_rne4(f32x4 v) { return f32x4{bf16_rne(v.x), bf16_rne(v.y), bf16_rne(v.z), bf16_rne(v.w)}; }
-
-constexpr int WG_T = 64;     // block tile: 64 output channels x 64 input channels of one tap
-constexpr int WG_K = 16;     // rows per step
-constexpr int WG_LD = 80;
-static_assert(WG_LD == 80, "wgrad_bias_out reuses a staging buffer with this row stride");
-#ifndef ORE_WG_BLOCKS
-#define ORE_WG_BLOCKS 1536
-#endif
-// blocks aimed at per weight-gradient launch (rows are split until the grid has this many); env ORE_WG_BLOCKS overrides the build-time
-// target for A/B runs (1024 ... 3072 measured: no difference beyond noise, EXPERIMENTS.md)
-static int wg_blocks() {
-    static int v = 0;
-    if (!v) { const char* e = getenv("ORE_WG_BLOCKS"); v = e ? atoi(e) : 0; if (v < 64) v = ORE_WG_BLOCKS; }
-    return v;
-}
-#define WG_BLOCKS wg_blocks()
-
-// Which wave of the block owns which 32 x 32 quarter of the 64 x 64 tile rotates with the block index: layers whose widths are not
-// multiples of 64 (96, 112, 16 ...) leave some quarters without real channels, the waves owning them issue no matrix instructions, and
-// the rotation spreads those idle waves over the four SIMDs of a CU (co-resident blocks then fill the freed issue slots) instead of
-// parking them all on the same two.
-__device__ __forceinline__ int wg_wave() { return __builtin_amdgcn_readfirstlane((int)((threadIdx.x >> 6) + blockIdx.x + blockIdx.y + blockIdx.z) & 3); }
-// live 16-wide tiles (0, 1 or 2) of the 32 channels starting at c0
-__device__ __forceinline__ int wg_live(int C, int c0) { return C - c0 > 16 ? 2 : C - c0 > 0 ? 1 : 0; }
-struct WgI0 { static constexpr int value = 0; }; struct WgI1 { static constexpr int value = 1; }; struct WgI2 { static constexpr int value = 2; };
-#define WG_DISPATCH(f, nm, nn)                                                                                   \
-    do {                                                                                                         \
-        const int nm_ = (nm), nn_ = (nn);                                                                        \
-        if (nm_ == 0 || nn_ == 0) f(WgI0{}, WgI0{});                                                             \
-        else if (nm_ == 2 && nn_ == 2) f(WgI2{}, WgI2{});                                                        \
-        else if (nm_ == 2) f(WgI2{}, WgI1{});                                                                    \
-        else if (nn_ == 2) f(WgI1{}, WgI2{});                                                                    \
-        else f(WgI1{}, WgI1{});                                                                                  \
-    } while (0)
-
-__global__ __launch_bounds__(256) void k_wgrad(WgradP p) {
-    __shared__ float sA[2][WG_K][WG_LD];   // dZ rows x co
-    __shared__ float sB[2][WG_K][WG_LD];   // X  rows x ci
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = wg_wave();
-    const int wm = wave >> 1, wn = wave & 1;
-    const int n_ci_tiles = (p.Cin + WG_T - 1) / WG_T;
-    const int co0 = blockIdx.x * WG_T;
-    const int ci0 = (blockIdx.y % n_ci_tiles) * WG_T;
-    const int tap = blockIdx.y / n_ci_tiles;
-    const int dy = tap / p.kw - p.pad, dx = tap % p.kw - p.pad;
-    const int m_begin = blockIdx.z * p.chunk, m_end = min(p.M, m_begin + p.chunk);
-
-    const int lr = tid >> 4, lc = (tid & 15) * 4;     // this thread stages row lr, columns lc..lc+3 of both tiles
-    f32x4 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // operands through buffer descriptors sized to this block's rows (see k_wgrad3): rows / column groups outside read as zeros in
-    // hardware; the tap's validity (row of the image, column of the image) only exists for kernels larger than 1x1 and is carried from
-    // step to step instead of divided out
-    const int x_first = max(0, m_begin + dy * p.W + dx);
-    const int x_last = min(p.M, m_end + dy * p.W + dx + WG_K);                     // exclusive
-    const __amdgpu_buffer_rsrc_t rz = make_rsrc(p.dz + (size_t)m_begin * p.dz_ld, (unsigned)(m_end - m_begin) * (unsigned)p.dz_ld * 4u);
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x + (size_t)x_first * p.x_ld, (unsigned)max(x_last - x_first, 0) * (unsigned)p.x_ld * 4u);
-    constexpr unsigned OOB = 0x80000000u;
-    unsigned vz = co0 + lc < p.Cout ? (unsigned)(lr * p.dz_ld + p.dz_coff + co0 + lc) * 4u : OOB;
-    unsigned vx = ci0 + lc < p.Cin ? (unsigned)((m_begin + lr + dy * p.W + dx - x_first) * p.x_ld + p.x_coff + ci0 + lc) * 4u : OOB;
-    const unsigned step_z = (unsigned)(WG_K * p.dz_ld) * 4u, step_x = (unsigned)(WG_K * p.x_ld) * 4u;
-    const bool multi = p.kh * p.kw > 1;
-    int xq = 0, yq = 0;
-    if (multi) { xq = (m_begin + lr) % p.W; yq = ((m_begin + lr) / p.W) % p.H; }
-    auto load = [&](f32x4& va, f32x4& vb) {
-        va = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rz, (int)vz, 0, 0));
-        bool ok = true;
-        if (multi) {
-            const int ys = yq + dy, xs = xq + dx;
-            ok = ys >= 0 && ys < p.H && xs >= 0 && xs < p.W;
-            xq += WG_K;
-            while (xq >= p.W) { xq -= p.W; if (++yq == p.H) yq = 0; }
-        }
-        vb = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, ok ? (int)vx : (int)OOB, 0, 0));
-        vz += step_z; vx += step_x;
-    };
-    f32x4 va, vb;
-    load(va, vb);
-    const bool do_b = p.db != nullptr && blockIdx.y == 0;
-    f32x4 bsum = {0.f, 0.f, 0.f, 0.f};
-    int buf = 0;
-    // TM x TN = the 16 x 16 tiles of this wave's 32 x 32 part that hold real channels (wg_live): a wave whose part lies beyond Cout or
-    // Cin still stages and meets the barriers, but issues no matrix instructions
-    auto kloop = [&](auto TMc, auto TNc) {
-        constexpr int TM = decltype(TMc)::value, TN = decltype(TNc)::value;
-        for (int m0 = m_begin; m0 < m_end; m0 += WG_K) {
-            if (do_b) bsum += va;                                    // (fp32 dZ: the bias gradient is not an MFMA operand)
-            if (p.bf16) { va = bf16_rne4(va); vb = bf16_rne4(vb); }
-            *reinterpret_cast<f32x4*>(&sA[buf][lr][lc]) = va;
-            *reinterpret_cast<f32x4*>(&sB[buf][lr][lc]) = vb;
-            __syncthreads();
-            if (m0 + WG_K < m_end) load(va, vb);                     // next step's global loads fly under this step's MFMAs
-            if constexpr (TM > 0 && TN > 0) {
-#pragma unroll
-                for (int kk = 0; kk < WG_K / 4; ++kk) {
-                    const int k = kk * 4 + (lane >> 4);
-                    float a[TM], b[TN];
-#pragma unroll
-                    for (int t = 0; t < TM; ++t) a[t] = sA[buf][k][wm * 32 + t * 16 + (lane & 15)];
-#pragma unroll
-                    for (int t = 0; t < TN; ++t) b[t] = sB[buf][k][wn * 32 + t * 16 + (lane & 15)];
-#pragma unroll
-                    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                        for (int tn = 0; tn < TN; ++tn) acc[tm][tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[tm], b[tn], acc[tm][tn], 0, 0, 0);
-                }
-            }
-            buf ^= 1;                                                // the other buffer was last read two barriers ago
-        }
-    };
-    WG_DISPATCH(kloop, wg_live(p.Cout, co0 + wm * 32), wg_live(p.Cin, ci0 + wn * 32));
-    // D: column = lane & 15 (ci), row = (lane >> 4) * 4 + reg (co)
-    const int taps = p.kh * p.kw;
-    float* slab = p.slab + (size_t)blockIdx.z * p.slab_stride;
-    if (do_b) wgrad_bias_out(p, sA[0], bsum, co0, slab);
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < 2; ++tn) {
-            const int ci = ci0 + wn * 32 + tn * 16 + (lane & 15);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int co = co0 + wm * 32 + tm * 16 + (lane >> 4) * 4 + r;
-                if (co < p.Cout && ci < p.Cin) {
-                    if (p.dw) {
-                        float* o = p.dw + ((size_t)co * p.Cin + ci) * taps + tap;
-                        *o = p.beta != 0.0f ? p.beta * *o + acc[tm][tn][r] : acc[tm][tn][r];
-                    } else {
-                        slab[((size_t)co * taps + tap) * p.Cin + ci] = acc[tm][tn][r];
-                    }
-                }
-            }
-        }
-}
-
-// 3x3 variant: ONE block owns the three dx taps of one kernel row dy.  In flattened pixel order the x rows of the taps (dy, -1..+1)
-// of 16 consecutive output rows are 18 consecutive rows, so a step stages dZ[16][64] and X[18][64] once and issues 48 MFMAs on them
-// (k_wgrad: 16 MFMAs per staged pair) -- 2.8x fewer L2 bytes per FLOP, the limiter of k_wgrad at large M.  Taps that leave the image
-// are masked on the dZ operand (per output row and dx).
-__global__ __launch_bounds__(256) void k_wgrad3(WgradP p) {
-    __shared__ float sA[2][WG_K][WG_LD];       // dZ rows x co
-    __shared__ float sB[2][WG_K + 2][WG_LD];   // X rows (m0 + dy*W - 1 ...) x ci
-    __shared__ float sMf[2][WG_K][2];          // 1 / 0: tap (dy, -1) / (dy, +1) of this output row reads inside the image row (a row whose
-                                               // (dy) neighbour row leaves the image is staged as zeros: no mask for the centre tap)
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = wg_wave();
-    const int wm = wave >> 1, wn = wave & 1;
-    const int n_ci_tiles = (p.Cin + WG_T - 1) / WG_T;
-    const int co0 = blockIdx.x * WG_T;
-    const int ci0 = (blockIdx.y % n_ci_tiles) * WG_T;
-    const int dyi = blockIdx.y / n_ci_tiles;                 // kernel row 0..2
-    const int dy = dyi - 1;
-    const int m_begin = blockIdx.z * p.chunk, m_end = min(p.M, m_begin + p.chunk);
-    const int lr = tid >> 4, lc = (tid & 15) * 4;
-    f32x4 acc[3][2][2];
-#pragma unroll
-    for (int d = 0; d < 3; ++d)
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) acc[d][a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // Both operands come through buffer descriptors sized to what THIS block may read: dZ rows [m_begin, m_end), X rows from the first
-    // row a tap can reach (m_begin + dy W - 1, not below 0) to the last (not beyond M).  A row outside -- before the tensor, behind the
-    // chunk, behind the tensor -- and a column group beyond Cout / Cin (offset forced out of range) read as zeros in hardware: no
-    // branches, no zero-initialised registers, and the per-step address work is one add per load.  (Byte ranges stay below 2^31: checked
-    // on the host.)  The loop's vector instructions share the issue port with the MFMAs -- the round-4 form of this loop spent 3.3 of
-    // them per MFMA and kept the matrix pipe 61 % busy.
-    const int x_first = max(0, m_begin + dy * p.W - 1);
-    const int x_last = min(p.M, m_end + dy * p.W + WG_K + 2);                      // exclusive
-    const __amdgpu_buffer_rsrc_t rz = make_rsrc(p.dz + (size_t)m_begin * p.dz_ld, (unsigned)(m_end - m_begin) * (unsigned)p.dz_ld * 4u);
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x + (size_t)x_first * p.x_ld, (unsigned)max(x_last - x_first, 0) * (unsigned)p.x_ld * 4u);
-    constexpr unsigned OOB = 0x80000000u;
-    unsigned vz = co0 + lc < p.Cout ? (unsigned)(lr * p.dz_ld + p.dz_coff + co0 + lc) * 4u : OOB;
-    const bool ci_ok = ci0 + lc < p.Cin;
-    unsigned vx = ci_ok ? (unsigned)((m_begin + lr + dy * p.W - 1 - x_first) * p.x_ld + p.x_coff + ci0 + lc) * 4u : OOB;
-    unsigned vx2 = ci_ok && lr < 2 ? vx + (unsigned)(WG_K * p.x_ld) * 4u : OOB;
-    const unsigned step_z = (unsigned)(WG_K * p.dz_ld) * 4u, step_x = (unsigned)(WG_K * p.x_ld) * 4u;
-    // (x, y) of this thread's row inside its image, carried from step to step (a step advances the row by WG_K) instead of two integer
-    // divisions per thread and step
-    int xq = (m_begin + lr) % p.W, yq = ((m_begin + lr) / p.W) % p.H;
-    auto load = [&](f32x4& va, f32x4& vb, f32x4& vb2, int& msk) {
-        va = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rz, (int)vz, 0, 0));
-        vb = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)vx, 0, 0));       // staged rows 0..15
-        vb2 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)vx2, 0, 0));     // staged rows 16, 17 (lr < 2)
-        vz += step_z; vx += step_x; vx2 += step_x;
-        const int ys = yq + dy;
-        msk = (ys >= 0 && ys < p.H) ? ((xq > 0 ? 1 : 0) | 2 | (xq + 1 < p.W ? 4 : 0)) : 0;       // (rows behind m_end read dZ = 0: any mask)
-        xq += WG_K;
-        while (xq >= p.W) { xq -= p.W; if (++yq == p.H) yq = 0; }
-    };
-    f32x4 va, vb, vb2;
-    int msk;
-    load(va, vb, vb2, msk);
-    const bool do_b = p.db != nullptr && blockIdx.y == 0;
-    f32x4 bsum = {0.f, 0.f, 0.f, 0.f};
-    int buf = 0;
-    auto kloop = [&](auto TMc, auto TNc) {                       // (see k_wgrad: only the 16 x 16 tiles with real channels are multiplied)
-        constexpr int TM = decltype(TMc)::value, TN = decltype(TNc)::value;
-        for (int m0 = m_begin; m0 < m_end; m0 += WG_K) {
-            if (do_b) bsum += va;
-            if (p.bf16) { va = bf16_rne4(va); vb = bf16_rne4(vb); vb2 = bf16_rne4(vb2); }
-            *reinterpret_cast<f32x4*>(&sA[buf][lr][lc]) = (msk & 2) ? va : f32x4{0.f, 0.f, 0.f, 0.f};
-            *reinterpret_cast<f32x4*>(&sB[buf][lr][lc]) = vb;
-            if (lr < 2) *reinterpret_cast<f32x4*>(&sB[buf][WG_K + lr][lc]) = vb2;
-            if ((tid & 15) == 0) { sMf[buf][lr][0] = (msk & 1) ? 1.f : 0.f; sMf[buf][lr][1] = (msk & 4) ? 1.f : 0.f; }
-            __syncthreads();
-            if (m0 + WG_K < m_end) load(va, vb, vb2, msk);
-            if constexpr (TM > 0 && TN > 0) {
-#pragma unroll
-                for (int kk = 0; kk < WG_K / 4; ++kk) {
-                    const int k = kk * 4 + (lane >> 4);
-                    const float mL = sMf[buf][k][0], mR = sMf[buf][k][1];
-                    float a[TM];
-#pragma unroll
-                    for (int t = 0; t < TM; ++t) a[t] = sA[buf][k][wm * 32 + t * 16 + (lane & 15)];
-#pragma unroll
-                    for (int d = 0; d < 3; ++d) {
-                        float b[TN];
-#pragma unroll
-                        for (int t = 0; t < TN; ++t) b[t] = sB[buf][k + d][wn * 32 + t * 16 + (lane & 15)];
-#pragma unroll
-                        for (int tm = 0; tm < TM; ++tm) {
-                            // (a product with 0 / 1 instead of a select: dZ is finite where it matters -- an inf / NaN gradient row is
-                            // poisoned anyway through the centre tap)
-                            const float am = d == 0 ? a[tm] * mL : d == 2 ? a[tm] * mR : a[tm];
-#pragma unroll
-                            for (int tn = 0; tn < TN; ++tn)
-                                acc[d][tm][tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(am, b[tn], acc[d][tm][tn], 0, 0, 0);
-                        }
-                    }
-                }
-            }
-            buf ^= 1;
-        }
-    };
-    WG_DISPATCH(kloop, wg_live(p.Cout, co0 + wm * 32), wg_live(p.Cin, ci0 + wn * 32));
-    float* slab = p.slab + (size_t)blockIdx.z * p.slab_stride;
-    if (do_b) wgrad_bias_out(p, sA[0], bsum, co0, slab);
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const int tap = dyi * 3 + d;
-#pragma unroll
-        for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn) {
-                const int ci = ci0 + wn * 32 + tn * 16 + (lane & 15);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int co = co0 + wm * 32 + tm * 16 + (lane >> 4) * 4 + r;
-                    if (co < p.Cout && ci < p.Cin) {
-                        if (p.dw) {
-                            float* o = p.dw + ((size_t)co * p.Cin + ci) * 9 + tap;
-                            *o = p.beta != 0.0f ? p.beta * *o + acc[d][tm][tn][r] : acc[d][tm][tn][r];
-                        } else {
-                            slab[((size_t)co * 9 + tap) * p.Cin + ci] = acc[d][tm][tn][r];
-                        }
-                    }
-                }
-            }
-    }
-}
-
-// ---- bf16 MFMA weight gradient (ORE_CONV_BF16, BASELINE configs[4]; round 4) ---------------------------------------------------------
-// The same tile, row split and slab reduction as k_wgrad / k_wgrad3, but the two operands travel through LDS as bf16 (rounded once,
-// nearest even, as the fp32 rows are staged: half the LDS bytes) and meet on v_mfma_f32_16x16x32_bf16: ONE matrix instruction per 16 x 16
-// tile and 32 rows where the fp32 kernels issue eight.  The contraction runs over ROWS, i.e. down the columns of the row-major staged
-// tiles: `ds_read_b64_tr_b16` hands every lane 4 consecutive rows of its column (two reads = the 8 k of the instruction) -- the tiles are
-// written as they arrive (16 contiguous bytes per thread), no transposed stores, no bank conflicts on the way in.
-//   K3 = true: 3x3 / pad 1, one block owns the three dx taps of kernel row dy: X rows m0 + dy W - 1 .. m0 + dy W + 32 are staged once
-//     (34 rows), tap dx reads them shifted by dx; taps that leave the image are masked on the dZ side, which is staged in three copies
-//     (dZ * valid(row, dx)) so that the MFMA operand needs no per-element select;
-//   K3 = false: one tap per block (1x1 layers, Linear-over-rows, other kernel sizes).
-// fp32 accumulation, fp32 bias column sums of the UNROUNDED dZ; results differ from the fp32-MFMA build of the same mode only by the
-// summation order (bf16 x bf16 products are exact in fp32) -- tests/test_hip_bf16.py::test_conv_backward_bf16_vs_oracle holds both
-// to 1e-4 of the oracle's bf16 restatement.
-typedef short s16x4v __attribute__((ext_vector_type(4)));
-typedef short s16x8v __attribute__((ext_vector_type(8)));
-constexpr int WB_K = 32;      // rows per step
-constexpr int WB_LD = 72;     // bf16 per staged row: 64 + 8 (144 bytes: 16-byte aligned rows)
-
-__device__ __forceinline__ s16x8v pack_bf16x8(f32x4 a, f32x4 b) {
-    const s16x4 lo = to_bf16x4(a), hi = to_bf16x4(b);
-    return s16x8v{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-// the 16 x 16 x 32 operand of one MFMA tile: 8 consecutive rows (k) of column (lane & 15), rows 8 (lane >> 4) .. + 7 of a staged tile
-__device__ __forceinline__ bf16x8_t wb_frag(const short* tile_row0_col0) {
-    const int lane = threadIdx.x & 63, g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
-    const short* a = tile_row0_col0 + (8 * g + q) * WB_LD + 4 * pp;
-    const s16x4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4v*)a);
-    const s16x4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4v*)(a + 4 * WB_LD));
-    const s16x8v v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8_t, v);
-}
-
-template <bool K3>
-__global__ __launch_bounds__(256) void k_wgrad_bf(WgradP p) {
-    constexpr int ND = K3 ? 3 : 1;                        // dZ copies (one per dx tap)
-    constexpr int XR = K3 ? WB_K + 2 : WB_K;              // staged X rows
-    __shared__ __attribute__((aligned(16))) short sA[2][ND][WB_K][WB_LD];
-    __shared__ __attribute__((aligned(16))) short sB[2][XR][WB_LD];          // (tap dx reads rows dx .. dx + 31 of the 34)
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = wg_wave();
-    const int wm = wave >> 1, wn = wave & 1;
-    const int n_ci_tiles = (p.Cin + WG_T - 1) / WG_T;
-    const int co0 = blockIdx.x * WG_T;
-    const int ci0 = (blockIdx.y % n_ci_tiles) * WG_T;
-    const int tsel = blockIdx.y / n_ci_tiles;             // K3: kernel row 0..2; else the tap index
-    const int dy = K3 ? tsel - 1 : tsel / p.kw - p.pad;
-    const int dx1 = K3 ? 0 : tsel % p.kw - p.pad;
-    const int m_begin = blockIdx.z * p.chunk, m_end = min(p.M, m_begin + p.chunk);
-    const int lr = tid >> 3, lc = (tid & 7) * 8;          // this thread stages row lr, columns lc .. lc + 7 of both tiles
-    f32x4 acc[ND][2][2];
-#pragma unroll
-    for (int d = 0; d < ND; ++d)
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) acc[d][a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // operands through buffer descriptors sized to this block's rows (see k_wgrad3): rows / column groups outside read as zeros in
-    // hardware, the row's image coordinates are carried from step to step
-    const int xshift = K3 ? dy * p.W - 1 : dy * p.W + dx1;
-    const int x_first = max(0, m_begin + xshift);
-    const int x_last = min(p.M, m_end + xshift + WB_K + (K3 ? 2 : 0));             // exclusive
-    const __amdgpu_buffer_rsrc_t rz = make_rsrc(p.dz + (size_t)m_begin * p.dz_ld, (unsigned)(m_end - m_begin) * (unsigned)p.dz_ld * 4u);
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x + (size_t)x_first * p.x_ld, (unsigned)max(x_last - x_first, 0) * (unsigned)p.x_ld * 4u);
-    constexpr unsigned OOB = 0x80000000u;
-    const unsigned z0 = (unsigned)(lr * p.dz_ld + p.dz_coff + co0 + lc) * 4u;
-    const unsigned x0 = (unsigned)((m_begin + lr + xshift - x_first) * p.x_ld + p.x_coff + ci0 + lc) * 4u;
-    unsigned vz0 = co0 + lc < p.Cout ? z0 : OOB, vz1 = co0 + lc + 4 < p.Cout ? z0 + 16u : OOB;
-    unsigned vx0 = ci0 + lc < p.Cin ? x0 : OOB, vx1 = ci0 + lc + 4 < p.Cin ? x0 + 16u : OOB;
-    const unsigned step_z = (unsigned)(WB_K * p.dz_ld) * 4u, step_x = (unsigned)(WB_K * p.x_ld) * 4u;
-    unsigned vy0 = K3 && lr < 2 && vx0 != OOB ? vx0 + step_x : OOB, vy1 = K3 && lr < 2 && vx1 != OOB ? vx1 + step_x : OOB;
-    const bool coords = K3 || p.kh * p.kw > 1;
-    int xq = 0, yq = 0;
-    if (coords) { xq = (m_begin + lr) % p.W; yq = ((m_begin + lr) / p.W) % p.H; }
-    auto bl = [&](const __amdgpu_buffer_rsrc_t& r, unsigned v) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)v, 0, 0)); };
-    f32x4 za, zb, xa, xb, ya, yb;                          // dZ row, X row, (K3) the extra X row of threads lr < 2
-    int msk = 0;
-    auto load = [&](int) {
-        za = bl(rz, vz0); zb = bl(rz, vz1);
-        if constexpr (K3) {
-            const int ys = yq + dy;
-            msk = (ys >= 0 && ys < p.H) ? ((xq > 0 ? 1 : 0) | 2 | (xq + 1 < p.W ? 4 : 0)) : 0;     // (rows behind m_end read dZ = 0: any mask)
-            xa = bl(rx, vx0); xb = bl(rx, vx1);
-            ya = bl(rx, vy0); yb = bl(rx, vy1);
-            vy0 += step_x; vy1 += step_x;
-        } else {
-            bool xv = true;
-            if (coords) {
-                const int ys = yq + dy, xs = xq + dx1;
-                xv = ys >= 0 && ys < p.H && xs >= 0 && xs < p.W;
-            }
-            xa = bl(rx, xv ? vx0 : OOB); xb = bl(rx, xv ? vx1 : OOB);
-        }
-        if (coords) {
-            xq += WB_K;
-            while (xq >= p.W) { xq -= p.W; if (++yq == p.H) yq = 0; }
-        }
-        vz0 += step_z; vz1 += step_z; vx0 += step_x; vx1 += step_x;
-    };
-    load(m_begin);
-    const bool do_b = p.db != nullptr && blockIdx.y == 0;
-    f32x4 bs0 = {0.f, 0.f, 0.f, 0.f}, bs1 = bs0;
-    int buf = 0;
-    auto kloop = [&](auto TMc, auto TNc) {                       // (see k_wgrad: only the 16 x 16 tiles with real channels are multiplied)
-    constexpr int TM = decltype(TMc)::value, TN = decltype(TNc)::value;
-    for (int m0 = m_begin; m0 < m_end; m0 += WB_K) {
-        if (do_b) { bs0 += za; bs1 += zb; }
-        if constexpr (K3) {
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                const bool on = (msk >> d) & 1;
-                const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-                *reinterpret_cast<s16x8v*>(&sA[buf][d][lr][lc]) = pack_bf16x8(on ? za : z, on ? zb : z);
-            }
-            *reinterpret_cast<s16x8v*>(&sB[buf][lr][lc]) = pack_bf16x8(xa, xb);
-            if (lr < 2) *reinterpret_cast<s16x8v*>(&sB[buf][WB_K + lr][lc]) = pack_bf16x8(ya, yb);
-        } else {
-            *reinterpret_cast<s16x8v*>(&sA[buf][0][lr][lc]) = pack_bf16x8(za, zb);
-            *reinterpret_cast<s16x8v*>(&sB[buf][lr][lc]) = pack_bf16x8(xa, xb);
-        }
-        __syncthreads();
-        if (m0 + WB_K < m_end) load(m0 + WB_K);                  // next step's global loads fly under this step's MFMAs
-        if constexpr (TM > 0 && TN > 0) {
-#pragma unroll
-            for (int d = 0; d < ND; ++d) {
-                bf16x8_t a[TM], b[TN];
-#pragma unroll
-                for (int t = 0; t < TM; ++t) a[t] = wb_frag(&sA[buf][d][0][wm * 32 + t * 16]);
-#pragma unroll
-                for (int t = 0; t < TN; ++t) b[t] = wb_frag(&sB[buf][K3 ? d : 0][wn * 32 + t * 16]);     // tap dx: the X rows shifted by d
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                    for (int tn = 0; tn < TN; ++tn)
-                        acc[d][tm][tn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[tm], b[tn], acc[d][tm][tn], 0, 0, 0);
-            }
-        }
-        buf ^= 1;                                                // the other buffer was last read two barriers ago
-    }
-    };
-    WG_DISPATCH(kloop, wg_live(p.Cout, co0 + wm * 32), wg_live(p.Cin, ci0 + wn * 32));
-    const int taps = p.kh * p.kw;
-    float* slab = p.slab + (size_t)blockIdx.z * p.slab_stride;
-    if (do_b) {                                                  // column sums of the fp32 dZ rows this block staged: 32 rows meet in LDS
-        __syncthreads();
-        float* red = reinterpret_cast<float*>(&sA[0][0][0][0]);  // [32][64] floats = 8 KB of the 13.8+ KB staging area
-        *reinterpret_cast<f32x4*>(red + lr * 64 + lc) = bs0;
-        *reinterpret_cast<f32x4*>(red + lr * 64 + lc + 4) = bs1;
-        __syncthreads();
-        if (tid < 64 && co0 + tid < p.Cout) {
-            float sacc = red[tid];
-#pragma unroll
-            for (int r = 1; r < 32; ++r) sacc += red[r * 64 + tid];
-            if (p.dw) {
-                float* o = p.db + co0 + tid;
-                *o = p.beta_b != 0.0f ? p.beta_b * *o + sacc : sacc;
-            } else {
-                slab[(size_t)p.Cout * taps * p.Cin + co0 + tid] = sacc;
-            }
-        }
-    }
-    // D: column = lane & 15 (ci), row = (lane >> 4) * 4 + reg (co)
-#pragma unroll
-    for (int d = 0; d < ND; ++d) {
-        const int tap = K3 ? tsel * 3 + d : tsel;
-#pragma unroll
-        for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn) {
-                const int ci = ci0 + wn * 32 + tn * 16 + (lane & 15);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int co = co0 + wm * 32 + tm * 16 + (lane >> 4) * 4 + r;
-                    if (co < p.Cout && ci < p.Cin) {
-                        if (p.dw) {
-                            float* o = p.dw + ((size_t)co * p.Cin + ci) * taps + tap;
-                            *o = p.beta != 0.0f ? p.beta * *o + acc[d][tm][tn][r] : acc[d][tm][tn][r];
-                        } else {
-                            slab[((size_t)co * taps + tap) * p.Cin + ci] = acc[d][tm][tn][r];
-                        }
-                    }
-                }
-            }
-    }
-}
-
-// dw_oihw[co][ci][tap] = beta * dw + sum_z slab[z][co][tap][ci].  Fixed summation order: slab z belongs to group z % G, every group is
-// summed ascending by one thread, the G partial sums are added ascending (deterministic for a given S).  One thread = (4 consecutive
-// ci, one group): 16-byte slab loads, G x as many loads in flight as one thread per output has -- the 1x1 layers split their rows 192-745
-// ways (few tiles), and a single chain per output made their reductions 26-96 us of pure latency.
-template <int G>
-__global__ __launch_bounds__(256) void k_wgrad_reduce(const float* __restrict__ slab, int S, int Cout, int taps, int Cin, float beta,
-                                                      float* __restrict__ dw, long long stride, float* __restrict__ db, float beta_b) {
-    __shared__ __attribute__((aligned(16))) float part[256 * 4];
-    constexpr int PER = 256 / G;                                  // outputs quads per block
-    const long long nw = (long long)Cout * taps * Cin;
-    const long long n = nw + (db ? Cout : 0);                     // the slabs' bias part follows their weight part
-    const int q = threadIdx.x % PER, g = threadIdx.x / PER;
-    const long long i = ((long long)blockIdx.x * PER + q) * 4;
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    if (i < n)
-        for (int z = g; z < S; z += G) s += *reinterpret_cast<const f32x4*>(slab + (size_t)z * stride + i);
-    if (G > 1) {
-        *reinterpret_cast<f32x4*>(part + threadIdx.x * 4) = s;
-        __syncthreads();
-        if (g != 0) return;
-#pragma unroll
-        for (int k = 1; k < G; ++k) s += *reinterpret_cast<const f32x4*>(part + (k * PER + q) * 4);
-    }
-    if (i >= n) return;
-    if (i >= nw) {                                               // bias gradient
-        float* o = db + (i - nw);
-        if (beta_b != 0.0f) s += beta_b * *reinterpret_cast<const f32x4*>(o);
-        *reinterpret_cast<f32x4*>(o) = s;
-        return;
-    }
-    const int ci = (int)(i % Cin), tap = (int)((i / Cin) % taps), co = (int)(i / ((long long)Cin * taps));
-    float* o = dw + ((size_t)co * Cin + ci) * taps + tap;
-    if (taps == 1) {
-        f32x4 v = s;
-        if (beta != 0.0f) v += beta * *reinterpret_cast<const f32x4*>(o);
-        *reinterpret_cast<f32x4*>(o) = v;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) o[(size_t)k * taps] = beta != 0.0f ? beta * o[(size_t)k * taps] + s[k] : s[k];
     }
 }
 
@@ -989,78 +451,6 @@ extern "C" int ore_pack_conv_weights_multi_fwd(const ore_pack_job* jobs_dev, int
     hipLaunchKernelGGL(k_pack_weight_multi, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, jobs_dev, n_jobs,
                        (long long)total);
     return ore_launch_status("k_pack_weight_multi");
-}
-
-// blocks of one split: k_wgrad3 (3x3) owns the three dx taps of a kernel row per block
-static int wgrad_tiles(int Cin, int Cout, int kh, int kw) {
-    return ceil_div(Cout, WG_T) * ceil_div(Cin, WG_T) * (kh == 3 && kw == 3 ? 3 : kh * kw);
-}
-
-extern "C" size_t ore_conv_wgrad_workspace_floats(int32_t rows, int32_t Cin, int32_t Cout, int32_t kh, int32_t kw) {
-    const long long per = (long long)Cout * kh * kw * Cin + Cout;      // (+ the bias part of a slab, whether or not it is asked for)
-    const int tiles = wgrad_tiles(Cin, Cout, kh, kw);
-    int S = max(1, min(ceil_div(WG_BLOCKS, tiles), ceil_div(rows, 128)));
-    return (size_t)(per * S);
-}
-
-extern "C" int ore_conv2d_wgrad_bias_fwd(const float* x, int32_t x_ld, int32_t x_coff, const float* dz, int32_t dz_ld, int32_t dz_coff,
-                                         int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t kh, int32_t kw, int32_t pad,
-                                         float* dw_oihw, float beta, float* db, float beta_b, float* workspace, size_t workspace_floats,
-                                         void* stream) {
-    ORE_CHECK_ARG(x && dz && dw_oihw && workspace, "ore_conv2d_wgrad_fwd: null pointer");
-    ORE_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && kh > 0 && kw > 0 && kh == 2 * pad + 1 && kw == 2 * pad + 1,
-                  "ore_conv2d_wgrad_fwd: stride-1 'same' convolutions only (k = 2*pad+1)");
-    ORE_CHECK_ARG(Cin % 4 == 0 && Cout % 4 == 0 && x_ld % 4 == 0 && dz_ld % 4 == 0 && x_coff % 4 == 0 && dz_coff % 4 == 0 &&
-                  x_coff + Cin <= x_ld && dz_coff + Cout <= dz_ld, "ore_conv2d_wgrad_fwd: channel counts/offsets must be multiples of 4 and fit ld");
-    const long long M = (long long)B * H * W;
-    ORE_CHECK_ARG(M < (1ll << 31), "ore_conv2d_wgrad_fwd: too many rows");
-    // (the kernels address a block's rows through 32-bit buffer offsets: a chunk of rows + its halo must span less than 2^31 bytes --
-    // with the <= 1536-block row split that is a tensor of several hundred GB)
-    const long long pw = (long long)Cout * kh * kw * Cin;
-    const long long per = pw + Cout;                                   // slab = weight part + bias part
-    const int tiles = wgrad_tiles(Cin, Cout, kh, kw);
-    int S = max(1, min(ceil_div(WG_BLOCKS, tiles), ceil_div((int)M, 128)));
-    { const long long cap = (long long)(workspace_floats / (size_t)per); if (cap < S) S = (int)cap; }
-    if (S < 1) { ore_set_error("ore_conv2d_wgrad_fwd: workspace too small (%zu < %lld floats)", workspace_floats, per); return ORE_ENOMEM; }
-    WgradP p{};
-    p.x = x; p.x_ld = x_ld; p.x_coff = x_coff; p.dz = dz; p.dz_ld = dz_ld; p.dz_coff = dz_coff;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.kh = kh; p.kw = kw; p.pad = pad;
-    const bool bfm = ore_conv_get_precision() == ORE_CONV_BF16;        // bf16 MFMA build: 32-row steps
-    p.M = (int)M; p.chunk = round_up(ceil_div((int)M, S), bfm ? WB_K : WG_K);
-    S = ceil_div((int)M, p.chunk);
-    ORE_CHECK_ARG(((long long)p.chunk + 2ll * W + 64) * (long long)max(x_ld, dz_ld) * 4 < (1ll << 31),
-                  "ore_conv2d_wgrad_fwd: a row split of %d rows x %d floats exceeds the 2 GiB a block addresses (give more workspace)", p.chunk, max(x_ld, dz_ld));
-    p.slab = workspace; p.slab_stride = per;
-    p.db = db; p.beta_b = beta_b;
-    if (S == 1) { p.dw = dw_oihw; p.beta = beta; }
-    p.bf16 = ore_conv_get_precision() == ORE_CONV_BF16;   // the STORAGE mode (2) is an engine property, plain calls stay fp32 (ore_hip.h)
-    ore_flop_count_add(2.0 * (double)M * Cout * Cin * kh * kw);
-    hipStream_t st = (hipStream_t)stream;
-    if (bfm && kh == 3 && kw == 3) hipLaunchKernelGGL(k_wgrad_bf<true>, dim3(ceil_div(Cout, WG_T), ceil_div(Cin, WG_T) * 3, S), dim3(256), 0, st, p);
-    else if (bfm) hipLaunchKernelGGL(k_wgrad_bf<false>, dim3(ceil_div(Cout, WG_T), ceil_div(Cin, WG_T) * kh * kw, S), dim3(256), 0, st, p);
-    else if (kh == 3 && kw == 3) hipLaunchKernelGGL(k_wgrad3, dim3(ceil_div(Cout, WG_T), ceil_div(Cin, WG_T) * 3, S), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(k_wgrad, dim3(ceil_div(Cout, WG_T), ceil_div(Cin, WG_T) * kh * kw, S), dim3(256), 0, st, p);
-    int rc = ore_launch_status("k_wgrad");
-    if (rc || S == 1) return rc;
-    // slab groups per output: enough threads to fill the chip and enough independent loads per output to hide the latency
-    const long long quads = (pw + (db ? Cout : 0)) / 4;
-    if (S >= 64 && quads <= 65536)
-        hipLaunchKernelGGL(k_wgrad_reduce<16>, dim3((unsigned)((quads + 15) / 16)), dim3(256), 0, st, workspace, S, Cout, kh * kw, Cin, beta, dw_oihw,
-                           per, db, beta_b);
-    else if (S >= 16)
-        hipLaunchKernelGGL(k_wgrad_reduce<4>, dim3((unsigned)((quads + 63) / 64)), dim3(256), 0, st, workspace, S, Cout, kh * kw, Cin, beta, dw_oihw,
-                           per, db, beta_b);
-    else
-        hipLaunchKernelGGL(k_wgrad_reduce<1>, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, workspace, S, Cout, kh * kw, Cin, beta, dw_oihw,
-                           per, db, beta_b);
-    return ore_launch_status("k_wgrad_reduce");
-}
-
-extern "C" int ore_conv2d_wgrad_fwd(const float* x, int32_t x_ld, int32_t x_coff, const float* dz, int32_t dz_ld, int32_t dz_coff,
-                                    int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t kh, int32_t kw, int32_t pad,
-                                    float* dw_oihw, float beta, float* workspace, size_t workspace_floats, void* stream) {
-    return ore_conv2d_wgrad_bias_fwd(x, x_ld, x_coff, dz, dz_ld, dz_coff, B, H, W, Cin, Cout, kh, kw, pad, dw_oihw, beta, nullptr, 0.0f, workspace,
-                                     workspace_floats, stream);
 }
 
 extern "C" int ore_relu_affine_bwd(const float* dy, int32_t dy_ld, int32_t dy_coff, const float* y, int32_t y_ld, int32_t y_coff,

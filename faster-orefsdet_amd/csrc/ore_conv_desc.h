@@ -39,7 +39,7 @@ __host__ __device__ __forceinline__ constexpr unsigned chunk_off(ChunkFmt f, uns
 // device side
 // =====================================================================================================================================
 
-// (make_rsrc, the descriptor itself, is in ore_common.h: the weight-gradient kernels of ore_bwd.hip use it too)
+// (make_rsrc, the descriptor itself, is in ore_common.h: the weight-gradient kernels of ore_conv_wgrad.hip use it too)
 // 16 bytes per lane into registers: base + voff (range-checked) + soff (not checked)
 __device__ __forceinline__ f32x4 bload(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));

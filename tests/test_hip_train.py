@@ -245,7 +245,7 @@ def test_wgrad_with_fused_bias_gradient(oh, B, H, W, Cin, Cout, k):
     """ore_conv2d_wgrad_bias_fwd: weight gradient and bias gradient (column sums of dZ) from ONE launch, with and without a row split
     (the first shape runs unsplit and writes both outputs directly), against torch.autograd of F.conv2d.  The widths that are not
     multiples of 64 leave 16 x 16 tiles of a block without real channels; the waves owning them skip their matrix instructions
-    (wg_live in ore_bwd.hip) and the result must not notice."""
+    (wg_live in ore_conv_wgrad.hip) and the result must not notice."""
     g = torch.Generator().manual_seed(B * 7 + H + Cin + Cout + k)
     x = torch.randn(B, Cin, H, W, generator=g)
     w = (torch.randn(Cout, Cin, k, k, generator=g) * 0.05).requires_grad_(True)

@@ -1,4 +1,4 @@
-"""Every launch form of the conv weight gradient (ore_conv2d_wgrad_bias_fwd, csrc/ore_bwd.hip) against a float64 reference.
+"""Every launch form of the conv weight gradient (ore_conv2d_wgrad_bias_fwd, csrc/ore_conv_wgrad.hip) against a float64 reference.
 
 One entry point computes every conv weight gradient of the training step.  Depending on the kernel size and the precision mode it
 runs k_wgrad, k_wgrad3, k_wgrad_bf<false> or k_wgrad_bf<true>.  Depending on the row split S it writes dW / db itself (S == 1) or

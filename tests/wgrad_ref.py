@@ -1,4 +1,4 @@
-"""Restatement of the conv weight-gradient launch (csrc/ore_bwd.hip, ore_conv2d_wgrad_bias_fwd) and its float64 reference.
+"""Restatement of the conv weight-gradient launch (csrc/ore_conv_wgrad.hip, ore_conv2d_wgrad_bias_fwd) and its float64 reference.
 
 `wgrad_plan` mirrors the host dispatch: how many row splits S the launch uses, how many rows each split owns, and which reduce
 (`k_wgrad_reduce<G>`) sums the slabs.  `wgrad_ref` computes dW and db in float64 as GEMMs over shifted windows, and `wgrad_check`
@@ -22,7 +22,7 @@ import math
 
 import torch
 
-WG_BLOCKS = 1536        # the build-time target of blocks per launch (ORE_WG_BLOCKS in ore_bwd.hip)
+WG_BLOCKS = 1536        # the build-time target of blocks per launch (ORE_WG_BLOCKS in ore_conv_wgrad.hip)
 WG_T = 64               # block tile: 64 output x 64 input channels of one tap
 U = 2.0 ** -24          # unit roundoff of fp32
 
@@ -111,7 +111,7 @@ def bound_c(plan):
 
 
 def bf16_rne(t):
-    """fp32 -> bf16 -> fp32, round to nearest even, as bf16_rne / to_bf16x4 in the kernels (finite inputs)."""
+    """fp32 -> bf16 -> fp32, round to nearest even, as to_bf16x4 in the kernels (finite inputs)."""
     u = t.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
     u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
     u = torch.where(u >= 2 ** 31, u - 2 ** 32, u)

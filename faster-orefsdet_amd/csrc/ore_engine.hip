@@ -30,6 +30,9 @@ struct Conv {
     int Cin = 0, Cout = 0, k = 1, stride = 1, pad = 0, relu_cout = 0;
 };
 
+// depthwise-separable unit of the *-dw-* bodies (ore_dwpw_fwd): depthwise taps [C][9], pointwise weights [C][C], folded FrozenBN
+struct DwUnit { float* w_dw = nullptr; float* w_pw = nullptr; float* scale = nullptr; float* shift = nullptr; int C = 0, stride = 1; };
+
 struct Buf { float* p = nullptr; int ld = 0; size_t rows = 0; };
 
 struct Geo { int B, H, W, Hp, Wp; int h[6], w[6]; };  // h[1]=Hp/2 (stem), h[2]=Hp/4 ... h[5]=Hp/32
@@ -53,7 +56,14 @@ struct ore_engine {
     // weights
     float* stem1_w = nullptr; float* stem1_scale = nullptr; float* stem1_shift = nullptr;
     Conv stem2, stem3;
-    struct Stage { Conv layer[8]; Conv concat; float* fc_w = nullptr; float* fc_b = nullptr; int in_ch, conv_ch, out_ch, cat_ch; } stage[4];
+    struct Stage { Conv layer[8]; Conv concat; float* fc_w = nullptr; float* fc_b = nullptr; int in_ch, conv_ch, out_ch, cat_ch;
+                   DwUnit dw[8]; Conv reduction; bool has_reduction = false; } stage[4];
+    // depthwise bodies (ore_engine_set_depthwise): stem_2 / stem_3 and the stage layers are DwUnits, a stage whose input width differs
+    // from its layer width has a 1x1 conv_reduction whose output (red[s], [M][conv_ch]) feeds layer 0 and is not part of the concat
+    bool depthwise = false;
+    DwUnit dstem2, dstem3;
+    Buf red[4];
+    float* dw_scratch = nullptr; size_t dw_scratch_floats = 0;   // depthwise output of the units the planner runs unfused (ore_dwpw_planned_fwd)
     Conv lateral[3], output[3], conv3, tower, pred;      // pred.scale/shift are [3 levels][16]
     float* out_wino3 = nullptr; float* out_shift3 = nullptr; size_t out_wino_stride = 0;   // the three FPN output convs as ONE per-level Winograd launch: [3][U], [3][F] bias
     uint16_t* out_wh3 = nullptr; size_t out_wh_stride = 0;                                 // bf16 storage: [3][packed bf16 weights] for the weight-stationary kernel
@@ -204,6 +214,30 @@ int make_conv_bn(ore_engine* e, const std::string& name, int Cin, int Cout, int 
     return make_wino(e, c);
 }
 
+// name/dw_conv3x3 [C,1,3,3] + name/pw_conv1x1 [C,C,1,1] + name/pw_norm (d2z:modeling/backbone/vovnet.py:110-130); fp32 whatever the mode
+int make_dw_unit(ore_engine* e, const std::string& name, int C, int stride, DwUnit* u) {
+    const HostTensor *wd, *wp, *g, *b, *m, *v;
+    int rc;
+    ORE_CHECK_ARG(C % 16 == 0, "ore_engine_finalize: depthwise unit %s of %d channels (a multiple of 16)", name.c_str(), C);
+    if ((rc = need(e, name + "/dw_conv3x3.weight", &wd, {C, 1, 3, 3}))) return rc;
+    if ((rc = need(e, name + "/pw_conv1x1.weight", &wp, {C, C, 1, 1}))) return rc;
+    if ((rc = need(e, name + "/pw_norm.weight", &g, {C}))) return rc;
+    if ((rc = need(e, name + "/pw_norm.bias", &b, {C}))) return rc;
+    if ((rc = need(e, name + "/pw_norm.running_mean", &m, {C}))) return rc;
+    if ((rc = need(e, name + "/pw_norm.running_var", &v, {C}))) return rc;
+    std::vector<float> packed(ore_packed_weight_floats(C, C, 1, 1));
+    ore_pack_conv_weight_host(wp->v.data(), C, C, 1, 1, packed.data());
+    std::vector<float> sc(C), sh(C);
+    for (int n = 0; n < C; ++n) {
+        sc[n] = g->v[n] * (1.0f / sqrtf(v->v[n] + 1e-5f));
+        sh[n] = b->v[n] - m->v[n] * sc[n];
+    }
+    if ((rc = e->upload(&u->w_dw, wd->v)) || (rc = e->upload(&u->w_pw, packed))) return rc;
+    if ((rc = e->upload(&u->scale, sc)) || (rc = e->upload(&u->shift, sh))) return rc;
+    u->C = C; u->stride = stride;
+    return ORE_OK;
+}
+
 int make_conv_bias(ore_engine* e, const std::string& name, int Cin, int Cout, int k, int relu, Conv* c) {
     const HostTensor *w, *b;
     int rc;
@@ -294,6 +328,18 @@ struct Run {
         if (prof && ea && eb) { (void)hipEventRecord(eb, st); e->spans.push_back({ia, ia + 1, fl, ore_last_wino() ? fl / 2.25 : fl}); }
         flops += fl;
     }
+    void dwpw(const DwUnit& u, const float* in, int in_ld, int in_coff, int B, int H, int W, float* out, int out_ld, int out_coff) {
+        if (rc) return;
+        const int Ho = (H - 1) / u.stride + 1, Wo = (W - 1) / u.stride + 1;
+        const double fl = ore_dwpw_flops((int64_t)B * Ho * Wo, u.C);
+        hipEvent_t ea = nullptr, eb = nullptr;
+        size_t ia = 0;
+        if (prof) { ia = e->ev_used; ea = e->next_event(); eb = e->next_event(); if (ea) (void)hipEventRecord(ea, st); }
+        rc = ore_dwpw_planned_fwd(in, in_ld, in_coff, B, H, W, u.C, u.stride, u.w_dw, u.w_pw, u.scale, u.shift, out, out_ld, out_coff,
+                                  e->dw_scratch, e->dw_scratch_floats, st);
+        if (prof && ea && eb) { (void)hipEventRecord(eb, st); e->spans.push_back({ia, ia + 1, fl, fl}); }
+        flops += fl;
+    }
 };
 
 int lvl_row0(const Geo& g, int l) {   // first row of pyramid level l (0 = p3) in the level-major matrices
@@ -313,8 +359,13 @@ int run_backbone(ore_engine* e, const void* img, int is_u8, const Geo& g, hipStr
                                 e->stem1_shift, c.stem_ch[0], e->s1.p, e->s1.ld, 0, st);
     if (rc) return rc;
     r.flops += 2.0 * g.B * g.h[1] * g.w[1] * 27.0 * c.stem_ch[0];
-    r.conv(e->stem2, e->s1.p, e->s1.ld, 0, g.B, g.h[1], g.w[1], e->s2.p, e->s2.ld, 0);
-    r.conv(e->stem3, e->s2.p, e->s2.ld, 0, g.B, g.h[1], g.w[1], e->cat[0].p, e->cat[0].ld, 0);
+    if (e->depthwise) {
+        r.dwpw(e->dstem2, e->s1.p, e->s1.ld, 0, g.B, g.h[1], g.w[1], e->s2.p, e->s2.ld, 0);
+        r.dwpw(e->dstem3, e->s2.p, e->s2.ld, 0, g.B, g.h[1], g.w[1], e->cat[0].p, e->cat[0].ld, 0);
+    } else {
+        r.conv(e->stem2, e->s1.p, e->s1.ld, 0, g.B, g.h[1], g.w[1], e->s2.p, e->s2.ld, 0);
+        r.conv(e->stem3, e->s2.p, e->s2.ld, 0, g.B, g.h[1], g.w[1], e->cat[0].p, e->cat[0].ld, 0);
+    }
     bool lat_scaled_ok[3] = {false, false, false};         // this forward wrote lat_scaled[l] (bs = 1 with the fused column sums)
     bool pooled_next = false;                              // the gate kernel of the previous stage already pooled into this stage's buffer
     for (int s = 0; s < 4 && !r.rc; ++s) {
@@ -329,7 +380,20 @@ int run_backbone(ore_engine* e, const void* img, int is_u8, const Geo& g, hipStr
             if (r.rc) break;
         }
         int src = 0, dst = S.in_ch;
-        for (int i = 0; i < c.layers_per_block; ++i) {
+        if (e->depthwise) {
+            const float* in = cat.p;
+            int in_ld = cat.ld;
+            if (S.has_reduction) {
+                r.conv(S.reduction, cat.p, cat.ld, 0, g.B, g.h[k], g.w[k], e->red[s].p, e->red[s].ld, 0);
+                in = e->red[s].p; in_ld = e->red[s].ld;
+            }
+            for (int i = 0; i < c.layers_per_block; ++i) {
+                r.dwpw(S.dw[i], in, in_ld, src, g.B, g.h[k], g.w[k], cat.p, cat.ld, dst);
+                in = cat.p; in_ld = cat.ld;
+                src = dst; dst += S.conv_ch;
+            }
+        }
+        for (int i = 0; i < c.layers_per_block && !e->depthwise; ++i) {
             r.conv(S.layer[i], cat.p, cat.ld, src, g.B, g.h[k], g.w[k], cat.p, cat.ld, dst);
             src = dst; dst += S.conv_ch;
         }
@@ -663,6 +727,13 @@ extern "C" int ore_engine_set_support(ore_engine* e, int32_t level, const float*
     return ORE_OK;
 }
 
+extern "C" int ore_engine_set_depthwise(ore_engine* e, int32_t on) {
+    ORE_CHECK_ARG(e && !e->finalized, "ore_engine_set_depthwise: call it before ore_engine_finalize");
+    ORE_CHECK_ARG(!on || !e->sb(), "ore_engine_set_depthwise: a bf16-storage engine has no depthwise body (the depthwise units are fp32 only)");
+    e->depthwise = on != 0;
+    return ORE_OK;
+}
+
 extern "C" int ore_engine_finalize(ore_engine* e) {
     ORE_CHECK_ARG(e && !e->finalized, "ore_engine_finalize: bad state");
     ORE_CHECK_ARG(!e->sb() || e->cfg.max_batch == 1, "ore_engine_finalize: a bf16-storage engine takes one image per pass (max_batch = 1)");
@@ -682,8 +753,16 @@ extern "C" int ore_engine_finalize(ore_engine* e) {
         for (int n = 0; n < C0; ++n) { sc[n] = g->v[n] * (1.0f / sqrtf(v->v[n] + 1e-5f)); sh[n] = b->v[n] - m->v[n] * sc[n]; }
         if ((rc = e->upload(&e->stem1_w, w->v)) || (rc = e->upload(&e->stem1_scale, sc)) || (rc = e->upload(&e->stem1_shift, sh))) return rc;
     }
-    if ((rc = make_conv_bn(e, bu + "stem.stem_2", c.stem_ch[0], c.stem_ch[1], 3, 1, &e->stem2))) return rc;
-    if ((rc = make_conv_bn(e, bu + "stem.stem_3", c.stem_ch[1], c.stem_ch[2], 3, 2, &e->stem3))) return rc;
+    ORE_CHECK_ARG(!e->depthwise || !e->sb(), "ore_engine_finalize: a bf16-storage engine has no depthwise body (the depthwise units are fp32 only)");
+    if (e->depthwise) {
+        ORE_CHECK_ARG(c.stem_ch[0] == c.stem_ch[1] && c.stem_ch[1] == c.stem_ch[2], "ore_engine_finalize: a depthwise stem keeps its width (%d, %d, %d)",
+                      c.stem_ch[0], c.stem_ch[1], c.stem_ch[2]);
+        if ((rc = make_dw_unit(e, bu + "stem.stem_2", c.stem_ch[1], 1, &e->dstem2))) return rc;
+        if ((rc = make_dw_unit(e, bu + "stem.stem_3", c.stem_ch[2], 2, &e->dstem3))) return rc;
+    } else {
+        if ((rc = make_conv_bn(e, bu + "stem.stem_2", c.stem_ch[0], c.stem_ch[1], 3, 1, &e->stem2))) return rc;
+        if ((rc = make_conv_bn(e, bu + "stem.stem_3", c.stem_ch[1], c.stem_ch[2], 3, 2, &e->stem3))) return rc;
+    }
     int cin = c.stem_ch[2];
     for (int s = 0; s < 4; ++s) {
         auto& S = e->stage[s];
@@ -693,7 +772,13 @@ extern "C" int ore_engine_finalize(ore_engine* e) {
         S.in_ch = cin; S.conv_ch = c.stage_conv_ch[s]; S.out_ch = c.stage_out_ch[s];
         S.cat_ch = cin + c.layers_per_block * S.conv_ch;
         int ci = cin;
-        for (int i = 0; i < c.layers_per_block; ++i) {
+        if (e->depthwise) {
+            S.has_reduction = cin != S.conv_ch;
+            if (S.has_reduction && (rc = make_conv_bn(e, pre + "conv_reduction." + mod + "_reduction_0", cin, S.conv_ch, 1, 1, &S.reduction))) return rc;
+            for (int i = 0; i < c.layers_per_block; ++i)
+                if ((rc = make_dw_unit(e, pre + "layers." + std::to_string(i) + "." + mod + "_" + std::to_string(i), S.conv_ch, 1, &S.dw[i]))) return rc;
+        }
+        for (int i = 0; i < c.layers_per_block && !e->depthwise; ++i) {
             if ((rc = make_conv_bn(e, pre + "layers." + std::to_string(i) + "." + mod + "_" + std::to_string(i), ci, S.conv_ch, 3, 1, &S.layer[i]))) return rc;
             ci = S.conv_ch;
         }
@@ -770,11 +855,19 @@ extern "C" int ore_engine_finalize(ore_engine* e) {
         const size_t M = B * g.h[k] * g.w[k];
         if ((rc = alloc_buf(e, &e->cat[s], M, e->stage[s].cat_ch))) return rc;
         if ((rc = alloc_buf(e, &e->sout[s], M, e->stage[s].out_ch))) return rc;
+        if (e->stage[s].has_reduction && (rc = alloc_buf(e, &e->red[s], M, e->stage[s].conv_ch))) return rc;
+        if (e->depthwise && ore_dwpw_prefers_composition((int64_t)M, e->stage[s].conv_ch, 1))
+            e->dw_scratch_floats = std::max(e->dw_scratch_floats, M * (size_t)e->stage[s].conv_ch);
         if ((rc = e->dalloc(&e->gate[s], B * e->stage[s].out_ch))) return rc;
         if (s >= 1 && (rc = e->dalloc(&e->lat_scaled[s - 1], (size_t)round_up(e->cfg.fpn_ch, 16) * e->stage[s].out_ch))) return rc;
         if ((size_t)e->stage[s].out_ch > cmax) cmax = e->stage[s].out_ch;
         const size_t cs = (M / 16 + 1) * (size_t)e->stage[s].out_ch;     // worst case: 16-row tiles
         if (cs > cs_need) cs_need = cs;
+    }
+    if (e->depthwise) {
+        const size_t m1 = B * g.h[1] * g.w[1];                       // stem_2 (stem_3 has stride 2: always fused)
+        if (ore_dwpw_prefers_composition((int64_t)m1, c.stem_ch[1], 1)) e->dw_scratch_floats = std::max(e->dw_scratch_floats, m1 * (size_t)c.stem_ch[1]);
+        if (e->dw_scratch_floats && (rc = e->dalloc(&e->dw_scratch, e->dw_scratch_floats))) return rc;
     }
     size_t rows_all = 0;
     for (int l = 0; l < 3; ++l) rows_all += (size_t)B * g.h[l + 3] * g.w[l + 3];

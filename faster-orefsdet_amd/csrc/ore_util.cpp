@@ -42,5 +42,7 @@ extern "C" int ore_flop_counter_read(double* flops, int64_t* calls, int32_t rese
     if (reset) { g_flops.store(0.0, std::memory_order_relaxed); g_flop_calls.store(0, std::memory_order_relaxed); }
     return ORE_OK;
 }
+// one depthwise-separable unit (csrc/ore_conv_dw.hip): 9 multiply-adds per element for the 3x3, C per element for the 1x1
+extern "C" double ore_dwpw_flops(int64_t rows, int32_t C) { return 2.0 * (double)rows * (double)C * (9.0 + (double)C); }
 extern "C" int32_t ore_det_record_rows(void) { return ORE_DET_RECORD_ROWS; }
 extern "C" int ore_version(void) { return 601; }   // round*100 + revision: bumped whenever a kernel on the eval path changes (bench.py keys the PMC traffic file on it)

@@ -1,5 +1,6 @@
 """VoVNet-eSE backbone on the HIP kernels (module tree / parameter names of d2z:modeling/backbone/vovnet.py so
-reference checkpoints load: `stem.stem_1/conv.weight`, `stage3.OSA3_1.layers.0.OSA3_1_0/norm.running_var`, ...).
+reference checkpoints load: `stem.stem_1/conv.weight`, `stage3.OSA3_1.layers.0.OSA3_1_0/norm.running_var`, ...; in the depthwise
+bodies `...OSA3_1_0/dw_conv3x3.weight`, `...OSA3_1_0/pw_norm.running_var`, `...conv_reduction.OSA3_1_reduction_0/conv.weight`).
 
 Compute is NHWC: each OSA block owns ONE concat buffer, its 3x3 layers write channel slices of it (no torch.cat),
 the eSE gate is folded into the consumers where possible, the max-pool is ceil-mode like the reference."""
@@ -13,8 +14,12 @@ import torch.nn as nn
 from detectron2.layers import FrozenBatchNorm2d, ShapeSpec, get_norm, nhwc_view, _require_gpu
 from . import BACKBONE_REGISTRY, Backbone
 
-# d2z:modeling/backbone/vovnet.py:28-96 (non-depthwise bodies; the *-dw-* bodies are not on the path)
+# d2z:modeling/backbone/vovnet.py:28-96.  dw=True: the depthwise bodies (vovnet.py:28-48), whose 3x3 layers are _DwUnit
 _STAGE_SPECS = {
+    "V-19-slim-dw-eSE": dict(stem=[64, 64, 64], stage_conv_ch=[64, 80, 96, 112], stage_out_ch=[112, 256, 384, 512],
+                             layer_per_block=3, block_per_stage=[1, 1, 1, 1], dw=True),
+    "V-19-dw-eSE": dict(stem=[64, 64, 64], stage_conv_ch=[128, 160, 192, 224], stage_out_ch=[256, 512, 768, 1024],
+                        layer_per_block=3, block_per_stage=[1, 1, 1, 1], dw=True),
     "V-19-slim-eSE": dict(stem=[64, 64, 128], stage_conv_ch=[64, 80, 96, 112], stage_out_ch=[112, 256, 384, 512],
                           layer_per_block=3, block_per_stage=[1, 1, 1, 1]),
     "V-19-eSE": dict(stem=[64, 64, 128], stage_conv_ch=[128, 160, 192, 224], stage_out_ch=[256, 512, 768, 1024],
@@ -68,6 +73,39 @@ class _Unit(nn.Sequential):
                              shift=sh, relu_cout=conv.out_channels, w_wino=U, **kw)
 
 
+def _dw_conv_bn_relu(name, ch, stride, norm):
+    """d2z vovnet.py:110-130 `dw_conv3x3`: depthwise 3x3 (carries the stride) -> pointwise 1x1 -> norm -> ReLU, nothing in between."""
+    return [(f"{name}/dw_conv3x3", nn.Conv2d(ch, ch, 3, stride, 1, groups=ch, bias=False)),
+            (f"{name}/pw_conv1x1", nn.Conv2d(ch, ch, 1, 1, 0, bias=False)),
+            (f"{name}/pw_norm", get_norm(norm, ch)), (f"{name}/pw_relu", nn.ReLU(inplace=True))]
+
+
+class _DwUnit(nn.Sequential):
+    """depthwise 3x3 + pointwise 1x1 + FrozenBN + ReLU as ONE fused HIP launch (orehip.dwpw); fp32 in every precision mode."""
+
+    def __init__(self, name, ch, stride, norm):
+        super().__init__(OrderedDict(_dw_conv_bn_relu(name, ch, stride, norm)))
+        self._n = name
+        self._cache = None
+
+    def parts(self):
+        m = self._modules
+        return m[self._n + "/dw_conv3x3"], m[self._n + "/pw_conv1x1"], m[self._n + "/pw_norm"]
+
+    def hip(self, x_nhwc, in_coff=0, out=None, out_coff=0):
+        import orehip
+        dw, pw, bn = self.parts()
+        assert isinstance(bn, FrozenBatchNorm2d), "the HIP path folds FrozenBN only (MODEL.VOVNET.NORM=FrozenBN)"
+        assert x_nhwc.dtype == torch.float32, "the depthwise units have no bf16 storage form"
+        key = (dw.weight.data_ptr(), dw.weight._version, pw.weight.data_ptr(), pw.weight._version, bn.weight._version,
+               bn.running_var._version, str(pw.weight.device))
+        if self._cache is None or self._cache[0] != key:
+            sc, sh = bn.scale_shift()
+            self._cache = (key, dw.weight.detach().contiguous(), orehip.pack_conv_weight(pw.weight), sc.contiguous(), sh.contiguous())
+        _, wd, wp, sc, sh = self._cache
+        return orehip.dwpw(x_nhwc, wd, wp, dw.out_channels, dw.stride[0], sc, sh, in_coff=in_coff, out=out, out_coff=out_coff)
+
+
 class eSEModule(nn.Module):
     def __init__(self, channel):
         super().__init__()
@@ -102,11 +140,44 @@ class _OSA_module(nn.Module):
         return y, self.ese.gate(y)
 
 
+class _OSA_module_dw(nn.Module):
+    """OSA block of the depthwise bodies (d2z vovnet.py:284-332 with depthwise=True): when in_ch != stage_ch a 1x1 `conv_reduction`
+    feeds layer 0 (it is NOT part of the concat); the layers are stage_ch -> stage_ch depthwise units; concat = [x, l0, l1, l2]."""
+    identity = False
+
+    def __init__(self, in_ch, stage_ch, concat_ch, layer_per_block, module_name, norm):
+        super().__init__()
+        self.in_ch, self.stage_ch, self.n = in_ch, stage_ch, layer_per_block
+        self.layers = nn.ModuleList(_DwUnit(f"{module_name}_{i}", stage_ch, 1, norm) for i in range(layer_per_block))
+        self.has_reduction = in_ch != stage_ch
+        if self.has_reduction:
+            self.conv_reduction = _Unit(f"{module_name}_reduction_0", in_ch, stage_ch, 1, 1, norm)
+        self.cat_ch = in_ch + layer_per_block * stage_ch
+        self.concat = _Unit(f"{module_name}_concat", self.cat_ch, concat_ch, 1, 1, norm)
+        self.ese = eSEModule(concat_ch)
+
+    def hip(self, cat_buf):
+        """cat_buf [B,H,W,cat_ch] with the block input already in channels [0,in_ch). Returns (pre-gate out, gate)."""
+        src_buf, src, dst = cat_buf, 0, self.in_ch
+        if self.has_reduction:
+            src_buf = self.conv_reduction.hip(cat_buf, in_coff=0, Cin=self.in_ch)
+        for layer in self.layers:
+            layer.hip(src_buf, in_coff=src, out=cat_buf, out_coff=dst)
+            src_buf, src, dst = cat_buf, dst, dst + self.stage_ch
+        y = self.concat.hip(cat_buf)
+        return y, self.ese.gate(y)
+
+
 class _OSA_stage(nn.Sequential):
-    def __init__(self, in_ch, stage_ch, concat_ch, block_per_stage, layer_per_block, stage_num, norm):
+    def __init__(self, in_ch, stage_ch, concat_ch, block_per_stage, layer_per_block, stage_num, norm, dw=False):
         super().__init__()
         if stage_num != 2:
             self.add_module("Pooling", nn.MaxPool2d(kernel_size=3, stride=2, ceil_mode=True))
+        if dw:
+            assert block_per_stage == 1, "the reference has no multi-block depthwise body"
+            self.add_module(f"OSA{stage_num}_1", _OSA_module_dw(in_ch, stage_ch, concat_ch, layer_per_block, f"OSA{stage_num}_1", norm))
+            self.pool = stage_num != 2
+            return
         self.add_module(f"OSA{stage_num}_1", _OSA_module(in_ch, stage_ch, concat_ch, layer_per_block, f"OSA{stage_num}_1", False, norm))
         for i in range(block_per_stage - 1):
             name = f"OSA{stage_num}_{i + 2}"
@@ -114,7 +185,7 @@ class _OSA_stage(nn.Sequential):
         self.pool = stage_num != 2
 
     def blocks(self):
-        return [m for m in self.children() if isinstance(m, _OSA_module)]
+        return [m for m in self.children() if isinstance(m, (_OSA_module, _OSA_module_dw))]
 
 
 class VoVNet(Backbone):
@@ -123,11 +194,17 @@ class VoVNet(Backbone):
         norm = cfg.MODEL.VOVNET.NORM
         spec = _STAGE_SPECS[cfg.MODEL.VOVNET.CONV_BODY]
         self.spec = spec
+        self.body = cfg.MODEL.VOVNET.CONV_BODY
         stem_ch = spec["stem"]
         self._out_features = out_features
         stem = _conv_bn_relu("stem_1", input_ch, stem_ch[0], 3, 2, norm)
-        stem += _conv_bn_relu("stem_2", stem_ch[0], stem_ch[1], 3, 1, norm)
-        stem += _conv_bn_relu("stem_3", stem_ch[1], stem_ch[2], 3, 2, norm)
+        self.dw = bool(spec.get("dw", False))
+        if self.dw:
+            stem += _dw_conv_bn_relu("stem_2", stem_ch[1], 1, norm)
+            stem += _dw_conv_bn_relu("stem_3", stem_ch[2], 2, norm)
+        else:
+            stem += _conv_bn_relu("stem_2", stem_ch[0], stem_ch[1], 3, 1, norm)
+            stem += _conv_bn_relu("stem_3", stem_ch[1], stem_ch[2], 3, 2, norm)
         self.add_module("stem", nn.Sequential(OrderedDict(stem)))
         self._stem_units = None
         stride = 4
@@ -139,7 +216,7 @@ class VoVNet(Backbone):
             name = f"stage{i + 2}"
             self.stage_names.append(name)
             self.add_module(name, _OSA_stage(in_ch[i], spec["stage_conv_ch"][i], spec["stage_out_ch"][i],
-                                             spec["block_per_stage"][i], spec["layer_per_block"], i + 2, norm))
+                                             spec["block_per_stage"][i], spec["layer_per_block"], i + 2, norm, dw=self.dw))
             self._out_feature_channels[name] = spec["stage_out_ch"][i]
             if i != 0:
                 stride *= 2
@@ -183,6 +260,13 @@ class VoVNet(Backbone):
     def _unit(self, name):
         if self._stem_units is None:
             self._stem_units = {}
+        if name not in self._stem_units and self.dw:
+            u = _DwUnit.__new__(_DwUnit)
+            nn.Module.__init__(u)
+            u._n, u._cache = name, None
+            for part in ("/dw_conv3x3", "/pw_conv1x1", "/pw_norm"):
+                u._modules[name + part] = self.stem._modules[name + part]
+            self._stem_units[name] = u
         if name not in self._stem_units:
             conv, bn = self.stem._modules[name + "/conv"], self.stem._modules[name + "/norm"]
             u = _Unit.__new__(_Unit)
@@ -197,12 +281,15 @@ class VoVNet(Backbone):
         bindings (orehip.autograd.OSAFn: forward + data/weight-gradient kernels) when gradients are enabled.
         raw_norm: see stem_hip (the fused-preprocess entry used by the training forward)."""
         import orehip
+        if self.dw and self.frozen_storage == "bf16":
+            raise ValueError("frozen_storage='bf16' with a depthwise body (%s): the depthwise units have no bf16 storage form; "
+                             "use 'auto' or 'fp32'" % self.body)
         _require_gpu(x, "VoVNet")
         grad_on = torch.is_grad_enabled()
         outputs = {}
         # bf16 storage for the frozen stages: only when something trainable follows (a training forward) -- eval goes through the engine
         want16 = self.frozen_storage == "bf16" or (self.frozen_storage == "auto" and orehip.get_conv_precision() == "bf16")
-        st16 = want16 and grad_on and not any(p.requires_grad for p in self.stem.parameters())
+        st16 = want16 and grad_on and not any(p.requires_grad for p in self.stem.parameters()) and not self.dw
         fdt = torch.bfloat16 if st16 else torch.float32
 
         def new_cat(B_, H_, W_, ch):
@@ -297,6 +384,19 @@ class VoVNet(Backbone):
                     x_in = cat0[..., : blk.in_ch].contiguous()
             else:
                 x_in = full
+            if self.dw:
+                def fold(unit):
+                    conv, bn = unit.parts()
+                    sc, sh = bn.scale_shift()
+                    return (conv.weight, sc.contiguous(), sh.contiguous())
+                layers = []
+                for unit in blk.layers:
+                    dwc, pwc, bn = unit.parts()
+                    sc, sh = bn.scale_shift()
+                    layers.append((dwc.weight, pwc.weight, sc.contiguous(), sh.contiguous()))
+                y = A.osa_block_dw(x_in, fold(blk.conv_reduction) if blk.has_reduction else None, layers, fold(blk.concat))
+                full = A.ese(y, blk.ese.fc.weight, blk.ese.fc.bias)
+                continue
             layers = []
             for unit in list(blk.layers) + [blk.concat]:
                 conv, bn = unit.parts()

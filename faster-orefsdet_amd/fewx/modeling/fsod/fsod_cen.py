@@ -369,7 +369,7 @@ class CenterNet2Detector(nn.Module):
                               fpn_ch=c["fpn_ch"], strides=c["strides"], pixel_mean=c["pixel_mean"], pixel_std=c["pixel_std"],
                               score_thresh=c["score_thresh"], pre_topk=c["pre_topk"], nms_thresh=c["nms_thresh"],
                               post_topk=c["post_topk"], max_batch=max_batch, max_h=max_hw[0], max_w=max_hw[1],
-                              device=dev.index or 0)
+                              device=dev.index or 0, depthwise=bool(spec.get("dw", False)))
         finally:
             orehip.set_conv_precision(prev)
         e.load_state_dict(self.state_dict())

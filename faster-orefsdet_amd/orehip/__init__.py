@@ -2372,6 +2372,77 @@ def conv2d_wgrad(x: torch.Tensor, dz: torch.Tensor, k: int, *, x_coff: int = 0, 
     return (out, db) if want_bias else out
 
 
+def _dw_out(x: torch.Tensor, C: int, stride: int, out: Optional[torch.Tensor]) -> torch.Tensor:
+    B, H, W, _ = x.shape
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if out is None:
+        out = torch.empty(B, Ho, Wo, C, device=x.device, dtype=torch.float32)
+    _f32(out)
+    assert out.shape[:3] == (B, Ho, Wo), (tuple(out.shape), (B, Ho, Wo))
+    return out
+
+
+def dwpw(x: torch.Tensor, w_dw: torch.Tensor, w_pw_packed: torch.Tensor, C: int, stride: int = 1, scale=None, shift=None, *,
+         in_coff: int = 0, out: Optional[torch.Tensor] = None, out_coff: int = 0, fused: Optional[bool] = None) -> torch.Tensor:
+    """One depthwise-separable unit of the *-dw-* VoVNet bodies in one launch (ore_dwpw_fwd): depthwise 3x3 (stride 1 | 2, pad 1) ->
+    pointwise 1x1 -> scale / shift (folded FrozenBN) -> ReLU.  x [B,H,W,ld] NHWC fp32, channels [in_coff, in_coff + C) are read;
+    w_dw [C,1,3,3]; w_pw_packed = pack_conv_weight of the [C,C,1,1] weight; channels [out_coff, out_coff + C) of `out` are written
+    (x and out may be one buffer when the slices do not overlap).  fp32 in every conv precision mode.
+    fused=None: the library's planner (ore_dwpw_planned_fwd) -- the fused launch, except at stride 1 with rows * C >= 2^22 (dwpw_prefers_composition:
+    stem_2 at 640x640), where the depthwise conv goes through a scratch tensor to the 1x1 conv launch; fused=True: always k_dwpw."""
+    _f32(x); _f32(w_dw); _f32(w_pw_packed)
+    assert w_dw.numel() == C * 9 and w_pw_packed.numel() == C * C, (tuple(w_dw.shape), w_pw_packed.numel(), C)
+    assert out is None or out.data_ptr() != x.data_ptr() or in_coff + C <= out_coff or out_coff + C <= in_coff, "overlapping slices"
+    out = _dw_out(x, C, stride, out)
+    B, H, W, ld = x.shape
+    rows = out.shape[0] * out.shape[1] * out.shape[2]
+    if fused is None and dwpw_prefers_composition(rows, C, stride):
+        scratch = torch.empty(rows * C, device=x.device, dtype=torch.float32)
+        _chk(lib().ore_dwpw_planned_fwd(_ptr(x), ld, in_coff, B, H, W, C, stride, _ptr(w_dw), _ptr(w_pw_packed), _ptr(scale), _ptr(shift),
+                                        _ptr(out), out.shape[-1], out_coff, _ptr(scratch), scratch.numel(), _stream()), "ore_dwpw_planned_fwd")
+        return out
+    assert fused is not False or not dwpw_prefers_composition(rows, C, stride), "fused=False: the planner's choice is the only unfused form"
+    _chk(lib().ore_dwpw_fwd(_ptr(x), ld, in_coff, B, H, W, C, stride, _ptr(w_dw), _ptr(w_pw_packed), _ptr(scale), _ptr(shift), _ptr(out),
+                            out.shape[-1], out_coff, _stream()), "ore_dwpw_fwd")
+    return out
+
+
+def dwpw_prefers_composition(rows: int, C: int, stride: int = 1) -> bool:
+    """True where orehip.dwpw / the engine run a unit as k_dw3x3 + the 1x1 conv launch instead of k_dwpw (ore_dwpw_prefers_composition)."""
+    return bool(lib().ore_dwpw_prefers_composition(int(rows), int(C), int(stride)))
+
+
+def dw3x3(x: torch.Tensor, w_dw: torch.Tensor, C: int, stride: int = 1, *, in_coff: int = 0, out: Optional[torch.Tensor] = None,
+          out_coff: int = 0, dgrad: bool = False, accumulate: bool = False) -> torch.Tensor:
+    """The depthwise 3x3 alone (ore_dw3x3_fwd), slices as in dwpw.  dgrad: mirrored taps = the data gradient of a stride-1 unit (x is
+    then dT); stride 2 is refused there.  accumulate: out[..., slice] += result."""
+    _f32(x); _f32(w_dw)
+    assert w_dw.numel() == C * 9
+    out = _dw_out(x, C, stride, out)
+    B, H, W, ld = x.shape
+    _chk(lib().ore_dw3x3_fwd(_ptr(x), ld, in_coff, B, H, W, C, stride, _ptr(w_dw), int(bool(dgrad)), _ptr(out), out.shape[-1], out_coff,
+                             int(bool(accumulate)), _stream()), "ore_dw3x3_fwd")
+    return out
+
+
+def dw3x3_wgrad(x: torch.Tensor, dt: torch.Tensor, C: int, *, x_coff: int = 0, dt_coff: int = 0, out: Optional[torch.Tensor] = None,
+                beta: float = 0.0) -> torch.Tensor:
+    """x [B,H,W,x_ld], dt [B,H,W,dt_ld] -> dW [C,1,3,3] of the stride-1 depthwise conv (ore_dw3x3_wgrad_fwd): deterministic, fixed split
+    and combine order.  out / beta: dW = beta * out + ... in place.  The workspace is the weight-gradient one (allocated outside any
+    capture by the first eager call, like conv2d_wgrad's)."""
+    _f32(x); _f32(dt)
+    B, H, W, xld = x.shape
+    assert dt.shape[:3] == (B, H, W)
+    if out is None:
+        out = torch.empty(C, 1, 3, 3, device=x.device, dtype=torch.float32)
+        beta = 0.0
+    assert out.numel() == C * 9 and out.is_contiguous() and out.dtype == torch.float32
+    ws = _wgrad_ws(x.device, lib().ore_dw3x3_wgrad_workspace_floats(B * H * W, C))
+    _chk(lib().ore_dw3x3_wgrad_fwd(_ptr(x), xld, x_coff, _ptr(dt), dt.shape[-1], dt_coff, B, H, W, C, _ptr(out), beta, _ptr(ws), ws.numel(),
+                                   _stream()), "ore_dw3x3_wgrad_fwd")
+    return out
+
+
 def relu_affine_bwd(dy: torch.Tensor, y: torch.Tensor, scale: Optional[torch.Tensor] = None, *, dy_coff: int = 0, y_coff: int = 0,
                     Cc: Optional[int] = None, out: Optional[torch.Tensor] = None, out_coff: int = 0) -> torch.Tensor:
     """dZ = dY * (Y > 0) * scale over channel slices of NHWC/row-major buffers (last dim = ld)."""
@@ -2640,7 +2711,9 @@ class Engine:
     def __init__(self, *, stem=(64, 64, 128), conv=(64, 80, 96, 112), out=(112, 256, 384, 512), layers=3, fpn_ch=128,
                  strides=(8, 16, 32), pixel_mean=(103.530, 116.280, 123.675), pixel_std=(1.0, 1.0, 1.0),
                  score_thresh=1e-5, pre_topk=1000, nms_thresh=0.6, post_topk=256, max_batch=1, max_h=640, max_w=640,
-                 device: int = 0):
+                 device: int = 0, depthwise: bool = False):
+        """depthwise: one of the *-dw-* bodies (stem (64, 64, 64)): stem_2 / stem_3 and the stage layers are depthwise-separable units
+        (ore_dwpw_fwd), load_state_dict takes the reference's dw names.  Refused (OreError) in the bf16 storage mode."""
         cfg = ModelCfg()
         cfg.stem_ch[:] = stem
         cfg.stage_conv_ch[:] = conv
@@ -2657,6 +2730,9 @@ class Engine:
         self.fpn_ch = fpn_ch
         self._h = C.c_void_p()
         _chk(lib().ore_engine_create(C.byref(cfg), device, C.byref(self._h)), "ore_engine_create")
+        self.depthwise = bool(depthwise)
+        if self.depthwise:
+            _chk(lib().ore_engine_set_depthwise(self._h, 1), "ore_engine_set_depthwise")
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:

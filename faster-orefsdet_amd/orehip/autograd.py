@@ -6,6 +6,8 @@ order (what `losses.backward()` does in d2z:engine/train_loop.py:279).  Every FL
                 the data-gradient weight layout, ore_conv2d_wgrad_fwd, ore_colsum_fwd
     OSAFn       one whole OSA block over its concat buffer (d2z:modeling/backbone/vovnet.py:310-332): layers write channel
                 slices, the backward walks the slices of ONE gradient buffer (no torch.cat / split)
+    OSADwFn     the same for the depthwise bodies (orehip/autograd_dw.py, re-exported here): ore_dwpw_fwd per unit, ore_dw3x3_fwd /
+                ore_dw3x3_wgrad_fwd and the 1x1 conv entry points in the backward
     RoiAlignFn  ore_roi_align_fwd | ore_roi_align_bwd
     CenterNetLossFn  ore_centernet_losses_fwd | ore_centernet_losses_bwd (normalisers stay on device)
 Weights are repacked on device (ore_pack_conv_weight_fwd) at most once per optimizer step and layout.
@@ -664,3 +666,7 @@ CN_HP = dict(gamma=2.0, beta=4.0, sigmoid_clamp=1e-4, ignore_high_fp=0.85, alpha
 def centernet_losses(head, reg_targets, hm_targets, pos_inds, pos_count, hp=None, with_counts: bool = False):
     out = CenterNetLossFn.apply(head, reg_targets, hm_targets, pos_inds, pos_count, hp or CN_HP)
     return (out[:3], out[3:].detach()) if with_counts else out[:3]
+
+
+# the OSA block of the depthwise VoVNet bodies (orehip/autograd_dw.py), part of this module's interface
+from orehip.autograd_dw import OSADwFn, osa_block_dw  # noqa: E402,F401

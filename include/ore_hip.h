@@ -460,6 +460,48 @@ int ore_colsum_fwd(const float* x, int32_t ld, int32_t coff, int64_t rows, int32
 int ore_colsum_segments_fwd(const float* x, int32_t ld, int32_t coff, int32_t segments, int64_t rows_per_segment, int32_t C,
                             float beta, float* out, float* workspace, size_t workspace_floats, void* stream);
 
+/* ------------------------------------------------------------------ depthwise-separable units (the *-dw-* VoVNet bodies) */
+/* d2z:modeling/backbone/vovnet.py:110-130 `dw_conv3x3`: Conv2d(C, C, 3, stride, 1, groups=C, bias=False) -> Conv2d(C, C, 1, bias=False) ->
+ * FrozenBN -> ReLU, nothing between the two convs.  All three entry points are fp32 whatever the process-wide conv precision is (the
+ * reference has no reduced-precision path to pin a bf16 form to), read channels [coff, coff + C) of NHWC rows of `ld` floats (the
+ * concat-slice convention of ore_conv_desc; ld and coff multiples of 4), treat everything outside an image as zero -- the halo of a
+ * border row never comes from the neighbouring image of the batch or from the channels beside the slice -- and enqueue on `stream`
+ * without synchronising.  w_dw is the Conv2d weight [C][1][3][3] as it is; pad is 1; Ho = (H - 1) / stride + 1.
+ *
+ * ore_dwpw_fwd: the whole unit in ONE launch (k_dwpw): out[b,oy,ox,out_coff + n] = relu(scale[n] * sum_k w_pw[n][k] * dw(in)[b,oy,ox,k]
+ *   + shift[n]); the depthwise result is formed per chunk of up to 64 channels in LDS and fed to v_mfma_f32_16x16x4_f32, it never goes
+ *   to memory.
+ *   C % 16 == 0, C <= 1024, stride 1 or 2; w_pw [C][C] row-major = ore_pack_conv_weight_host of the 1x1 weight; scale / shift [C] or
+ *   NULL (1 / 0).  Input and output may be slices of the same buffer when they do not overlap (the OSA chain).
+ *   Counted by ore_flop_counter_read as ore_dwpw_flops(rows, C) = 2 * rows * C * (9 + C), rows = B * Ho * Wo.
+ * ore_dw3x3_fwd: the depthwise conv alone (k_dw3x3), C % 4 == 0.  dgrad = 1: taps mirrored, i.e. the data gradient dX of a stride-1
+ *   unit from dT -- stride 2 is refused there with ORE_EINVAL: the only stride-2 unit of the bodies, stem_3, is frozen at every
+ *   FREEZE_AT the reference trains with.  accumulate = 1: out += result (the gradient of a concat slice that already holds a sum).
+ * ore_dw3x3_wgrad_fwd: dw[c][ky][kx] = beta * dw + sum_{b,y,x} x[b,y+ky-1,x+kx-1,c] * dt[b,y,x,c] (stride 1).  Deterministic, no float
+ *   atomics: the pixels are cut into parts of 256 whatever the device, each part summed in a fixed order into the workspace
+ *   (ore_dw3x3_wgrad_workspace_floats(B * H * W, C) floats, the caller's), then the parts in order by a second launch.  beta = 0
+ *   does not read dw. */
+/* Base pointers of in / out (and w_pw, scale, shift of ore_dwpw_fwd) must be 16-byte aligned; an input and an output slice that share a
+ * buffer must lie side by side in every row (same ld) -- anything else returns ORE_EINVAL.
+ * ore_dwpw_planned_fwd: ore_dwpw_fwd, except where ore_dwpw_prefers_composition(rows, C, stride) -- stride 1 and rows * C >= 2^22, the one
+ *   regime where the fused launch measured slower (stem_2 at 640x640) -- where it runs k_dw3x3 into `scratch` (the caller's, >= rows * C
+ *   floats, else ORE_ENOMEM) and the 1x1 conv launch in fp32.  The engine and orehip.dwpw go through it.  The unfused path sets the
+ *   process-wide conv precision (ore_conv_set_precision) to fp32 around that launch and restores it: like every call that depends on
+ *   that mode, it must not run concurrently with another host thread that sets or relies on a different mode. */
+int32_t ore_dwpw_prefers_composition(int64_t rows, int32_t C, int32_t stride);
+int ore_dwpw_planned_fwd(const float* in, int32_t ld_in, int32_t in_coff, int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride,
+                         const float* w_dw, const float* w_pw, const float* scale, const float* shift, float* out, int32_t ld_out,
+                         int32_t out_coff, float* scratch, size_t scratch_floats, void* stream);
+double ore_dwpw_flops(int64_t rows, int32_t C);
+int ore_dwpw_fwd(const float* in, int32_t ld_in, int32_t in_coff, int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride,
+                 const float* w_dw, const float* w_pw, const float* scale, const float* shift, float* out, int32_t ld_out,
+                 int32_t out_coff, void* stream);
+int ore_dw3x3_fwd(const float* in, int32_t ld_in, int32_t in_coff, int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride,
+                  const float* w_dw, int32_t dgrad, float* out, int32_t ld_out, int32_t out_coff, int32_t accumulate, void* stream);
+size_t ore_dw3x3_wgrad_workspace_floats(int64_t rows, int32_t C);
+int ore_dw3x3_wgrad_fwd(const float* x, int32_t x_ld, int32_t x_coff, const float* dt, int32_t dt_ld, int32_t dt_coff, int32_t B, int32_t H,
+                        int32_t W, int32_t C, float* dw, float beta, float* workspace, size_t workspace_floats, void* stream);
+
 /* Depthwise support correlation with gradients (ref:fewx/modeling/fsod/fsod_cen.py:229-245, training branch).
  * k_per_image = 0: one support kernel set k11 [C], k13 / k31 [C][3] for all B images; 1: every image its own ([B][C], [B][C][3]) --
  * a training batch, where each query image comes with its own support crops.
@@ -543,6 +585,14 @@ int ore_engine_set_tensor(ore_engine* e, const char* name, const float* data_hos
 /* Cached support prototypes [128][s][s] for level 3/4/5 (support_feature.pkl 'p3','p4','p5'), host. */
 int ore_engine_set_support(ore_engine* e, int32_t level, const float* proto_chw_host, int32_t C, int32_t s);
 int ore_engine_finalize(ore_engine* e);   /* fold BN, pack weights, upload */
+/* The depthwise bodies (V-19-slim-dw-eSE, V-19-dw-eSE; d2z:modeling/backbone/vovnet.py:28-48): call with on = 1 BEFORE ore_engine_finalize
+ * (a setter, so that ore_model_cfg keeps its layout).  finalize then needs the reference's depthwise names -- stem.stem_2/dw_conv3x3,
+ * /pw_conv1x1, /pw_norm; stageK.OSAK_1.layers.i.OSAK_1_i/dw_conv3x3 ...; stageK.OSAK_1.conv_reduction.OSAK_1_reduction_0/conv, /norm where
+ * a stage's input width differs from stage_conv_ch -- builds stem_2 / stem_3 and every stage layer as one ore_dwpw_fwd launch, and holds
+ * one extra [rows][stage_conv_ch] buffer per stage for the reduction's output (it feeds layer 0 and is not part of the concat).
+ * ore_engine_last_flops counts a unit as ore_dwpw_flops.  The units are fp32 in every conv precision; an engine created in the bf16
+ * STORAGE mode refuses with ORE_EINVAL (here and in finalize). */
+int ore_engine_set_depthwise(ore_engine* e, int32_t on);
 /* Optional second stage (CustomCascadeROIHeads, eval) inside the same forward/graph; call after finalize.  W_host [fc_dim]
  * [pooled*pooled*fpn_ch] (k ordered [pos][channel]) and b_host [fc_dim] are the pre-composed DSA-mix + flatten + fc1 chain
  * (ref:fewx/modeling/fsod/fsod_roi_heads.py:500-520; orehip.compose_roi_head builds them from the state_dict and the cached

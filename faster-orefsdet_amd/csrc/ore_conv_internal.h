@@ -156,4 +156,10 @@ int launch_kw(const ConvP& p, const ConvPlan& pl, hipStream_t st);       // k_co
 // ore_conv_gd.hip: the second-stage GEMM as a K split over blocks (called directly, not planned)
 int conv_gd_splitk(const float* in, int in_ld, const float* w, int M, int K, int Cout16, float* parts, int S, hipStream_t st);
 
+// ore_conv_wgrad.hip: dw_oihw[co][ci][tap] = beta * dw + sum_z slab[z][co][tap][ci] over S slabs `stride` floats apart, in the fixed order of
+// k_wgrad_reduce<G> (G by S and the output size); db / beta_b: the bias part behind every slab's weight part, or null.  Also used by
+// ore_conv_s2grad.hip (taps = 9; taps = 1 with "Cin" = 27 for the flat [Cout][27] gradient of stem_1).
+int launch_wgrad_reduce(const float* slab, int S, int Cout, int taps, int Cin, float beta, float* dw_oihw, long long stride, float* db,
+                        float beta_b, hipStream_t st);
+
 }  // namespace oreconv

@@ -8,7 +8,7 @@
 //   k_wgrad_bf<K3>     the same two forms on the bf16 MFMA (ore_conv_set_precision(ORE_CONV_BF16))
 //   k_wgrad_reduce<G>  the slab sum, G groups of slabs per output
 // Pinned against float64 in every launch form by tests/test_hip_wgrad.py (the host dispatch restated in tests/wgrad_ref.py).
-#include "ore_common.h"
+#include "ore_conv_internal.h"
 #include <stdlib.h>
 
 namespace {
@@ -547,6 +547,21 @@ static int wgrad_split(int rows, int Cin, int Cout, int kh, int kw) {
     return max(1, min(ceil_div(WG_BLOCKS, wgrad_tiles(Cin, Cout, kh, kw)), ceil_div(rows, 128)));
 }
 
+// The ordered slab sum of a row-split weight gradient (k_wgrad_reduce<G>), shared with ore_conv_s2grad.hip through ore_conv_internal.h
+int oreconv::launch_wgrad_reduce(const float* slab, int S, int Cout, int taps, int Cin, float beta, float* dw_oihw, long long stride, float* db,
+                                 float beta_b, hipStream_t st) {
+    const long long pw = (long long)Cout * taps * Cin;
+    // slab groups per output: enough threads to fill the chip and enough independent loads per output to hide the latency
+    const long long quads = (pw + (db ? Cout : 0)) / 4;
+    const int G = S >= 64 && quads <= 65536 ? 16 : S >= 16 ? 4 : 1;
+    const int per_block = 256 / G;                                     // output quads per block
+    void (*const reduce)(const float*, int, int, int, int, float, float*, long long, float*, float) =
+        G == 1 ? k_wgrad_reduce<1> : G == 16 ? k_wgrad_reduce<16> : k_wgrad_reduce<4>;   // (instantiated, and so emitted, as <16>, <4>, <1>)
+    hipLaunchKernelGGL(reduce, dim3((unsigned)((quads + per_block - 1) / per_block)), dim3(256), 0, st, slab, S, Cout, taps, Cin, beta,
+                       dw_oihw, stride, db, beta_b);
+    return ore_launch_status("k_wgrad_reduce");
+}
+
 extern "C" size_t ore_conv_wgrad_workspace_floats(int32_t rows, int32_t Cin, int32_t Cout, int32_t kh, int32_t kw) {
     const long long per = (long long)Cout * kh * kw * Cin + Cout;      // (+ the bias part of a slab, whether or not it is asked for)
     return (size_t)(per * wgrad_split(rows, Cin, Cout, kh, kw));
@@ -589,15 +604,7 @@ extern "C" int ore_conv2d_wgrad_bias_fwd(const float* x, int32_t x_ld, int32_t x
     hipLaunchKernelGGL(kernel, dim3(ceil_div(Cout, WG_T), ceil_div(Cin, WG_T) * (k3 ? 3 : kh * kw), S), dim3(256), 0, st, p);
     int rc = ore_launch_status("k_wgrad");
     if (rc || S == 1) return rc;
-    // slab groups per output: enough threads to fill the chip and enough independent loads per output to hide the latency
-    const long long quads = (pw + (db ? Cout : 0)) / 4;
-    const int G = S >= 64 && quads <= 65536 ? 16 : S >= 16 ? 4 : 1;
-    const int per_block = 256 / G;                                     // output quads per block
-    void (*const reduce)(const float*, int, int, int, int, float, float*, long long, float*, float) =
-        G == 1 ? k_wgrad_reduce<1> : G == 16 ? k_wgrad_reduce<16> : k_wgrad_reduce<4>;   // (instantiated, and so emitted, as <16>, <4>, <1>)
-    hipLaunchKernelGGL(reduce, dim3((unsigned)((quads + per_block - 1) / per_block)), dim3(256), 0, st, workspace, S, Cout, kh * kw, Cin, beta,
-                       dw_oihw, per, db, beta_b);
-    return ore_launch_status("k_wgrad_reduce");
+    return oreconv::launch_wgrad_reduce(workspace, S, Cout, kh * kw, Cin, beta, dw_oihw, per, db, beta_b, st);
 }
 
 extern "C" int ore_conv2d_wgrad_fwd(const float* x, int32_t x_ld, int32_t x_coff, const float* dz, int32_t dz_ld, int32_t dz_coff,

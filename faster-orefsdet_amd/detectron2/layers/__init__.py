@@ -129,21 +129,30 @@ class Conv2d(nn.Conv2d):
     def forward(self, x):
         _require_gpu(x, "Conv2d")
         if torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad):
-            # training: the autograd bindings (forward + data/weight-gradient kernels); stride-1 'same' convolutions only
+            # training: the autograd bindings (forward + data/weight-gradient kernels); stride-1 'same' convolutions, and 3x3 / stride 2 / pad 1
             from orehip import autograd as A
             k = self.kernel_size[0]
-            if not (self.groups == 1 and self.dilation == (1, 1) and self.stride == (1, 1) and self.padding == (k // 2, k // 2)
-                    and self.kernel_size[1] == k and self.in_channels % 16 == 0):
-                raise NotImplementedError("the HIP backward kernels cover stride-1 'same' convolutions with Cin % 16 == 0 "
-                                          "(every trainable conv of finetune_vovnet.yaml)")
+            plain = self.groups == 1 and self.dilation == (1, 1) and self.kernel_size[1] == k and self.in_channels % 16 == 0
+            same = plain and self.stride == (1, 1) and self.padding == (k // 2, k // 2)
+            s2 = plain and k == 3 and self.stride == (2, 2) and self.padding == (1, 1) and self.out_channels % 4 == 0
+            if not (same or s2):
+                raise NotImplementedError("the HIP backward kernels cover stride-1 'same' convolutions and 3x3 / stride 2 / pad 1 ones (those with "
+                                          "Cout % 4 == 0), with groups = 1, dilation = 1 and Cin % 16 == 0 (every trainable conv of the fsod "
+                                          "configs); other strides, paddings, grouped and dilated convolutions have no backward kernel")
             relu = self.activation is not None
             if isinstance(self.norm, FrozenBatchNorm2d):
                 assert self.bias is None, "conv + FrozenBN has no bias in the reference"
                 sc, sh = self.norm.scale_shift()
-                y = A.conv(nhwc_view(x), self.weight, None, sc.contiguous(), sh.contiguous(), relu)
+                if s2:
+                    y = A.conv_s2(nhwc_view(x), self.weight, sc.contiguous(), sh.contiguous(), relu)
+                else:
+                    y = A.conv(nhwc_view(x), self.weight, None, sc.contiguous(), sh.contiguous(), relu)
             else:
                 assert self.norm is None, "only FrozenBN can be folded into the HIP conv epilogue"
-                y = A.conv(nhwc_view(x), self.weight, self.bias, None, None, relu)
+                if s2:
+                    y = A.conv_s2(nhwc_view(x), self.weight, None, None, relu, self.bias)
+                else:
+                    y = A.conv(nhwc_view(x), self.weight, self.bias, None, None, relu)
             return y.permute(0, 3, 1, 2)
         return self.forward_nhwc(nhwc_view(x)).permute(0, 3, 1, 2)
 

@@ -301,21 +301,33 @@ class VoVNet(Backbone):
             # the block has not written yet -- against zero weights, and 0 x (a NaN bit pattern of fresh memory) would be NaN
             flat = torch.zeros(B_ * H_ * W_ * ch + 32, device=x.device, dtype=torch.bfloat16)
             return flat[:-32].view(B_, H_, W_, ch)
-        with torch.no_grad():
-            y = self.stem_hip(x, raw_norm, out_bf16=st16)
-            y = self._unit("stem_2").hip(y)
-            first = getattr(self, "stage2").blocks()[0]
-            B, H, W, _ = y.shape
-            Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-            cat = new_cat(B, Ho, Wo, first.cat_ch)
-            self._unit("stem_3").hip(y, out=cat, out_coff=0)
+        first = getattr(self, "stage2").blocks()[0]
+        # FREEZE_AT 0: the stem trains (orehip.autograd.StemFn: the frozen path's launches forward, the stride-2 / stem_1 gradient kernels backward)
+        stem_train = grad_on and any(p.requires_grad for p in self.stem.parameters())
+        x_stem, cat = None, None
+        if stem_train and self.dw:
+            raise NotImplementedError(
+                "MODEL.BACKBONE.FREEZE_AT: 0 with the depthwise body %s: its stem_3 is a stride-2 depthwise unit, and ore_dw3x3_fwd refuses the "
+                "stride-2 data gradient (dgrad = 1, stride = 2: ORE_EINVAL), so the stem cannot train; use FREEZE_AT >= 1 or a dense body" % self.body)
+        if stem_train:
+            x_stem = self._stem_train(x, raw_norm, first.cat_ch)
+        else:
+            with torch.no_grad():
+                y = self.stem_hip(x, raw_norm, out_bf16=st16)
+                y = self._unit("stem_2").hip(y)
+                B, H, W, _ = y.shape
+                Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+                cat = new_cat(B, Ho, Wo, first.cat_ch)
+                self._unit("stem_3").hip(y, out=cat, out_coff=0)
         if "stem" in self._out_features:
-            outputs["stem"] = cat[..., : first.in_ch].float().permute(0, 3, 1, 2)
+            outputs["stem"] = (x_stem if stem_train else cat[..., : first.in_ch].float()).permute(0, 3, 1, 2)
         prev, gate, full = None, None, None      # prev = pre-gate block output (frozen path), full = gated output (train path)
         for name in self.stage_names:
             stage = getattr(self, name)
             blocks = stage.blocks()
             train = grad_on and any(p.requires_grad for p in stage.parameters())
+            if x_stem is not None and full is None and not train:
+                raise NotImplementedError("a trainable stem in front of a frozen stage 2 is not a configuration of the reference (FREEZE_AT)")
             if train:
                 if prev is not None and prev.dtype == torch.bfloat16:      # the frozen / trainable seam: fp32 from here on
                     with torch.no_grad():
@@ -330,7 +342,8 @@ class VoVNet(Backbone):
                     if name in self._out_features:
                         outputs[name] = full.permute(0, 3, 1, 2)
                     continue
-                full = self._stage_train(stage, blocks, cat if prev is None and full is None else None, prev, gate, full)
+                full = self._stage_train(stage, blocks, cat if prev is None and full is None else None, prev, gate, full,
+                                         x0=x_stem if prev is None and full is None else None)
                 prev, gate = None, None
                 if name in self._out_features:
                     outputs[name] = full.permute(0, 3, 1, 2)
@@ -365,9 +378,21 @@ class VoVNet(Backbone):
                     outputs[name] = fullp.permute(0, 3, 1, 2)
         return outputs
 
-    def _stage_train(self, stage, blocks, cat0, prev, gate, full, pooled=False):
+    def _stem_train(self, x, raw_norm, cat_ch):
+        """The stem with trainable weights (dense bodies): one StemFn node; returns stage 2's input [B,H/4,W/4,C3], carrying gradient."""
+        from orehip import autograd as A
+        folds = []
+        for name in ("stem_1", "stem_2", "stem_3"):
+            conv, bn = self.stem._modules[name + "/conv"], self.stem._modules[name + "/norm"]
+            assert isinstance(bn, FrozenBatchNorm2d), "the HIP path folds FrozenBN only (MODEL.VOVNET.NORM=FrozenBN)"
+            sc, sh = bn.scale_shift()
+            folds.append((conv.weight, sc.contiguous(), sh.contiguous()))
+        return A.stem(x, self.stem_hip, raw_norm, cat_ch, folds[0][1], folds[0][0], folds[1], folds[2])
+
+    def _stage_train(self, stage, blocks, cat0, prev, gate, full, pooled=False, x0=None):
         """One trainable stage: max-pool, OSA blocks through OSAFn, eSE.  The input comes either from a frozen stage
-        (prev, gate: no gradient needed) or from the previous trainable stage (`full`, carries gradient)."""
+        (prev, gate: no gradient needed), from the previous trainable stage (`full`, carries gradient) or, for stage 2, from the stem:
+        frozen (cat0, the concat buffer stem_3 wrote) or trainable (x0, carries gradient)."""
         import orehip
         import torch.nn.functional as F
         from orehip import autograd as A
@@ -381,7 +406,7 @@ class VoVNet(Backbone):
                     with torch.no_grad():
                         x_in = orehip.maxpool3x3s2(prev, gate) if stage.pool else (orehip.scale_channels(prev, gate) if gate is not None else prev)
                 else:
-                    x_in = cat0[..., : blk.in_ch].contiguous()
+                    x_in = x0 if x0 is not None else cat0[..., : blk.in_ch].contiguous()
             else:
                 x_in = full
             if self.dw:

@@ -2372,6 +2372,91 @@ def conv2d_wgrad(x: torch.Tensor, dz: torch.Tensor, k: int, *, x_coff: int = 0, 
     return (out, db) if want_bias else out
 
 
+def _s2_out_hw(H: int, W: int) -> Tuple[int, int]:
+    return (H - 1) // 2 + 1, (W - 1) // 2 + 1
+
+
+# The stride-2 gradient kernels address a tensor through 32-bit byte offsets and refuse one of 2 GiB or more (ORE_EINVAL).  The bindings
+# therefore hand them the batch in groups of whole images whose tensors stay below this many bytes (a margin of 1 MiB for the rows a last
+# step may name): one group -- one launch, as ever -- for everything but the support batch of a very large step.  A weight gradient adds the
+# groups in order with beta = 1, so it stays deterministic; the order of that sum then depends on the grouping, i.e. on the shapes alone.
+_S2_MAX_BYTES = (1 << 31) - (1 << 20)
+
+
+def _s2_image_groups(B: int, *bytes_per_image: int) -> List[Tuple[int, int]]:
+    nb = max(1, min(B, _S2_MAX_BYTES // max(bytes_per_image)))
+    return [(b0, min(B, b0 + nb)) for b0 in range(0, B, nb)]
+
+
+def conv2d_wgrad_s2(x: torch.Tensor, dz: torch.Tensor, *, x_coff: int = 0, Cin: Optional[int] = None, dz_coff: int = 0,
+                    Cout: Optional[int] = None, out: Optional[torch.Tensor] = None, beta: float = 0.0,
+                    workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [B,H,W,x_ld], dz [B,Ho,Wo,dz_ld] NHWC -> dW [Cout,Cin,3,3] of the 3x3 / stride 2 / pad 1 conv (ore_conv2d_wgrad_s2_fwd, fp32 in
+    every precision mode, deterministic).  out / beta: dW = beta * out + ... in place.  The workspace is the weight-gradient one
+    (allocated outside any capture by the first eager call, reused); `workspace`: the caller's instead (a smaller one caps the row split)."""
+    _f32(x); _f32(dz)
+    B, H, W, xld = x.shape
+    dld = dz.shape[-1]
+    assert tuple(dz.shape[:3]) == (B, *_s2_out_hw(H, W)), (tuple(dz.shape), tuple(x.shape))
+    Cin = Cin if Cin is not None else xld - x_coff
+    Cout = Cout if Cout is not None else dld - dz_coff
+    if out is None:
+        out = torch.empty(Cout, Cin, 3, 3, device=x.device, dtype=torch.float32)
+        beta = 0.0
+    assert out.shape == (Cout, Cin, 3, 3) and out.is_contiguous() and out.dtype == torch.float32
+    for i, (b0, b1) in enumerate(_s2_image_groups(B, H * W * xld * 4, dz.shape[1] * dz.shape[2] * dld * 4)):
+        rows = (b1 - b0) * dz.shape[1] * dz.shape[2]
+        ws = workspace if workspace is not None else _wgrad_ws(x.device, lib().ore_conv_wgrad_s2_workspace_floats(rows, Cin, Cout))
+        _chk(lib().ore_conv2d_wgrad_s2_fwd(_ptr(x[b0:b1]), xld, x_coff, _ptr(dz[b0:b1]), dld, dz_coff, b1 - b0, H, W, Cin, Cout, _ptr(out),
+                                           beta if i == 0 else 1.0, _ptr(ws), ws.numel(), _stream()), "ore_conv2d_wgrad_s2_fwd")
+    return out
+
+
+def conv2d_dgrad_s2(dz: torch.Tensor, w_oihw: torch.Tensor, H: int, W: int, *, dz_coff: int = 0, out: Optional[torch.Tensor] = None,
+                    out_coff: int = 0) -> torch.Tensor:
+    """dz [B,Ho,Wo,dz_ld], w [Cout,Cin,3,3] -> dX [B,H,W,Cin] of the 3x3 / stride 2 / pad 1 conv over an H x W input
+    (ore_conv2d_dgrad_s2_fwd: parity decomposition, fp32, deterministic).  out / out_coff: write channels [out_coff, out_coff + Cin) of a
+    wider buffer.  The packed weights live in the weight-gradient workspace (stream-ordered behind whatever used it last)."""
+    _f32(dz); _f32(w_oihw)
+    Cout, Cin = w_oihw.shape[:2]
+    assert tuple(w_oihw.shape[2:]) == (3, 3)
+    B = dz.shape[0]
+    assert tuple(dz.shape[1:3]) == _s2_out_hw(H, W) and dz_coff + Cout <= dz.shape[-1], (tuple(dz.shape), H, W)
+    if out is None:
+        out = torch.empty(B, H, W, Cin, device=dz.device, dtype=torch.float32)
+    _f32(out)
+    assert tuple(out.shape[:3]) == (B, H, W)
+    ws = _wgrad_ws(dz.device, lib().ore_conv_dgrad_s2_workspace_floats(Cin, Cout))
+    for b0, b1 in _s2_image_groups(B, dz.shape[1] * dz.shape[2] * dz.shape[-1] * 4, H * W * out.shape[-1] * 4):
+        _chk(lib().ore_conv2d_dgrad_s2_fwd(_ptr(dz[b0:b1]), dz.shape[-1], dz_coff, _ptr(w_oihw), b1 - b0, H, W, Cin, Cout, _ptr(out[b0:b1]),
+                                           out.shape[-1], out_coff, _ptr(ws), ws.numel(), _stream()), "ore_conv2d_dgrad_s2_fwd")
+    return out
+
+
+def stem1_wgrad(img: torch.Tensor, Hp: int, Wp: int, mean: Sequence[float], std: Sequence[float], dz: torch.Tensor, *, dz_coff: int = 0,
+                Cout: Optional[int] = None, out: Optional[torch.Tensor] = None, beta: float = 0.0,
+                workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """img [B,3,H,W] uint8 or fp32 (planar, raw), dz [B,Hp/2,Wp/2,dz_ld] -> dW [Cout,3,3,3] of stem_1 (ore_stem1_wgrad_fwd): the
+    normalisation and the zero padding to (Hp, Wp) are formed on the fly as in stem1().  out / beta: dW = beta * out + ... in place."""
+    assert img.is_contiguous() and img.dtype in (torch.uint8, torch.float32)
+    _f32(dz)
+    B, _, H, W = img.shape
+    assert tuple(dz.shape[:3]) == (B, Hp // 2, Wp // 2), (tuple(dz.shape), Hp, Wp)
+    Cout = Cout if Cout is not None else dz.shape[-1] - dz_coff
+    if out is None:
+        out = torch.empty(Cout, 3, 3, 3, device=img.device, dtype=torch.float32)
+        beta = 0.0
+    assert out.numel() == Cout * 27 and out.is_contiguous() and out.dtype == torch.float32
+    m = (C.c_float * 3)(*mean)
+    s = (C.c_float * 3)(*std)
+    for i, (b0, b1) in enumerate(_s2_image_groups(B, (Hp // 2) * (Wp // 2) * dz.shape[-1] * 4, 3 * H * W * img.element_size())):
+        rows = (b1 - b0) * (Hp // 2) * (Wp // 2)
+        ws = workspace if workspace is not None else _wgrad_ws(img.device, lib().ore_stem1_wgrad_workspace_floats(rows, Cout))
+        _chk(lib().ore_stem1_wgrad_fwd(_ptr(img[b0:b1]), int(img.dtype == torch.uint8), b1 - b0, H, W, Hp, Wp, m, s, _ptr(dz[b0:b1]), dz.shape[-1],
+                                       dz_coff, Cout, _ptr(out), beta if i == 0 else 1.0, _ptr(ws), ws.numel(), _stream()), "ore_stem1_wgrad_fwd")
+    return out
+
+
 def _dw_out(x: torch.Tensor, C: int, stride: int, out: Optional[torch.Tensor]) -> torch.Tensor:
     B, H, W, _ = x.shape
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1

@@ -8,6 +8,8 @@ order (what `losses.backward()` does in d2z:engine/train_loop.py:279).  Every FL
                 slices, the backward walks the slices of ONE gradient buffer (no torch.cat / split)
     OSADwFn     the same for the depthwise bodies (orehip/autograd_dw.py, re-exported here): ore_dwpw_fwd per unit, ore_dw3x3_fwd /
                 ore_dw3x3_wgrad_fwd and the 1x1 conv entry points in the backward
+    ConvS2Fn    conv 3x3 / stride 2 / pad 1 and StemFn, the trainable stem of a dense body (orehip/autograd_stem.py, re-exported here):
+                ore_conv2d_wgrad_s2_fwd, ore_conv2d_dgrad_s2_fwd, ore_stem1_wgrad_fwd in the backward
     RoiAlignFn  ore_roi_align_fwd | ore_roi_align_bwd
     CenterNetLossFn  ore_centernet_losses_fwd | ore_centernet_losses_bwd (normalisers stay on device)
 Weights are repacked on device (ore_pack_conv_weight_fwd) at most once per optimizer step and layout.
@@ -670,3 +672,5 @@ def centernet_losses(head, reg_targets, hm_targets, pos_inds, pos_count, hp=None
 
 # the OSA block of the depthwise VoVNet bodies (orehip/autograd_dw.py), part of this module's interface
 from orehip.autograd_dw import OSADwFn, osa_block_dw  # noqa: E402,F401
+# the stride-2 conv and the trainable stem (orehip/autograd_stem.py), likewise
+from orehip.autograd_stem import ConvS2Fn, StemFn, conv_s2, stem  # noqa: E402,F401

@@ -450,6 +450,39 @@ int ore_conv2d_wgrad_fwd(const float* x, int32_t x_ld, int32_t x_coff, const flo
 int ore_conv2d_wgrad_bias_fwd(const float* x, int32_t x_ld, int32_t x_coff, const float* dz, int32_t dz_ld, int32_t dz_coff, int32_t B,
                               int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t kh, int32_t kw, int32_t pad, float* dw_oihw,
                               float beta, float* db, float beta_b, float* workspace, size_t workspace_floats, void* stream);
+/* ---- the stride-2 convolutions of the stem (MODEL.BACKBONE.FREEZE_AT: 0; csrc/ore_conv_s2grad.hip) ----
+ * 3x3, stride 2, pad 1: X is [B,H,W,.], dZ is [B,Ho,Wo,.] with Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1 (H, W are always the INPUT's).
+ * All three entry points are fp32 whatever the process-wide conv precision is (ore_conv_set_precision; like the depthwise units there is
+ * no reduced-precision reference to pin another form to), deterministic (no float atomics, fixed summation order), enqueue on `stream`
+ * without synchronising, use only the caller's workspace (capturable), treat everything outside an image as zero, read / write channel
+ * slices [coff, coff + C) of rows of `ld` floats (ld, coff multiples of 4), return ORE_EINVAL for shapes they do not cover (a tensor
+ * of 2 GiB or more included) and ORE_ENOMEM for a workspace that is too small, and are counted by ore_flop_counter_read.
+ * Held to float64 references on an MI355X by tests/test_hip_s2grad.py; what was measured, and when: DESIGN.md 7n.
+ * ore_conv2d_wgrad_s2_fwd: dw_oihw[co][ci][ky][kx] = beta * dw_oihw + sum_{b,oy,ox} dz[b,oy,ox,co] * x[b,2oy+ky-1,2ox+kx-1,ci].  Cin, Cout
+ *   multiples of 4.  fp32 MFMA on a 64 x 64 (co x ci) tile; the rows B * Ho * Wo are split over blocks into slabs of the workspace
+ *   (ore_conv_wgrad_s2_workspace_floats(rows, Cin, Cout) floats for the full split; less caps the split, down to one slab of
+ *   Cout * 9 * Cin floats) which the reduce launch of ore_conv2d_wgrad_fwd adds in a fixed order.  beta = 0 does not read dw_oihw.
+ * ore_conv2d_dgrad_s2_fwd: dx[b,y,x,ci] = sum_{ky,kx,co} dz[b,(y+1-ky)/2,(x+1-kx)/2,co] * w_oihw[co][ci][ky][kx] over the taps whose two
+ *   quotients are integers inside the map.  Cin, Cout multiples of 4.  The pixels of each (y mod 2, x mod 2) class are one GEMM with
+ *   K = taps x Cout, taps = 1 / 2 / 2 / 4; one launch for the four classes, after a small launch that packs the weights as
+ *   [tap][Cout][Cin] into the workspace (ore_conv_dgrad_s2_workspace_floats(Cin, Cout) = 9 * Cin * Cout floats).  Every element of the
+ *   dx slice is written (no accumulation).
+ * ore_stem1_wgrad_fwd: dw[co][27] = beta * dw + the weight gradient of stem_1 (ore_stem1_fwd) from the raw planar image [B][3][H][W]
+ *   (uint8 or fp32): (x - mean) / std and the zero padding to (Hp, Wp) are formed on the fly, as in the forward; dz is [B,Hp/2,Wp/2,.].
+ *   Hp, Wp even, Cout a multiple of 16; mean3_host / std3_host are HOST floats.  Workspace: ore_stem1_wgrad_workspace_floats(rows, Cout),
+ *   rows = B * Hp/2 * Wp/2 (less caps the split).  stem_1 has no data gradient. */
+size_t ore_conv_wgrad_s2_workspace_floats(int32_t rows, int32_t Cin, int32_t Cout);
+int ore_conv2d_wgrad_s2_fwd(const float* x, int32_t x_ld, int32_t x_coff, const float* dz, int32_t dz_ld, int32_t dz_coff, int32_t B,
+                            int32_t H, int32_t W, int32_t Cin, int32_t Cout, float* dw_oihw, float beta, float* workspace,
+                            size_t workspace_floats, void* stream);
+size_t ore_conv_dgrad_s2_workspace_floats(int32_t Cin, int32_t Cout);
+int ore_conv2d_dgrad_s2_fwd(const float* dz, int32_t dz_ld, int32_t dz_coff, const float* w_oihw, int32_t B, int32_t H, int32_t W,
+                            int32_t Cin, int32_t Cout, float* dx, int32_t dx_ld, int32_t dx_coff, float* workspace,
+                            size_t workspace_floats, void* stream);
+size_t ore_stem1_wgrad_workspace_floats(int32_t rows, int32_t Cout);
+int ore_stem1_wgrad_fwd(const void* img, int32_t img_is_u8, int32_t B, int32_t H, int32_t W, int32_t Hp, int32_t Wp,
+                        const float* mean3_host, const float* std3_host, const float* dz, int32_t dz_ld, int32_t dz_coff,
+                        int32_t Cout, float* dw, float beta, float* workspace, size_t workspace_floats, void* stream);
 int ore_relu_affine_bwd(const float* dy, int32_t dy_ld, int32_t dy_coff, const float* y, int32_t y_ld, int32_t y_coff,
                         const float* scale, int64_t rows, int32_t C, float* dz, int32_t dz_ld, int32_t dz_coff, void* stream);
 /* out[c] = beta * out[c] + sum_rows x[row][coff + c]; workspace >= ceil(rows/64) * C floats. */

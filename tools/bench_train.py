@@ -42,6 +42,7 @@ def main():
     ap.add_argument("--nesterov", action="store_true", help="SOLVER.NESTEROV (default: the config's, off)")
     ap.add_argument("--config", default="finetune_vovnet.yaml", help="a file of configs/fsod (finetune_vovnet_dw.yaml: the depthwise body, with "
                     "the synthetic weights of tests/vovnet_dw_ref.py)")
+    ap.add_argument("--freeze-at", type=int, default=None, help="MODEL.BACKBONE.FREEZE_AT (default: the config's, 3; 0 also trains the stem)")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -64,6 +65,8 @@ def main():
         cfg.SOLVER.CLIP_GRADIENTS.NORM_TYPE = a.norm_type
     if a.nesterov:
         cfg.SOLVER.NESTEROV = True
+    if a.freeze_at is not None:
+        cfg.MODEL.BACKBONE.FREEZE_AT = a.freeze_at
     cfg.freeze()
     torch.manual_seed(0)
     m = build_model(cfg)

@@ -10,7 +10,8 @@ The operands carry per-channel scales from 1e-3 to 1e3, so the channels of dX sp
 Launchers and how this module reaches them:
   automatic plan (the shape matrix and edge classes; test_reached_cells pins the exact set): fp32 k_conv3x3_wino, k_conv3x3_wino_nu,
     k_conv3x3_patch<4>, k_conv_kd, k_conv_gs, k_conv_kw, k_conv_igemm; bf16 k_conv3x3_patch<4>, k_conv_kw, k_conv_igemm.  The
-    production replay lands on the launcher each recorded call ran (forward calls add k_conv_gd);
+    production replay lands on the launcher each recorded call ran (forward calls add k_conv_gd); its stride-2 and input-affine calls
+    and every returned column sum are held to the forward contract of tests/fwdconv_ref.py;
   forced through ore_conv_set_plan_override at a data-gradient shape (test_forced_launcher), the hook confirming each:
     k_conv3x3_patch<8>, k_conv3x3_patch_db, k_conv3x3_ws<2,64>, k_conv3x3_ws<2,128>, k_conv_gd, k_conv_rf, and k_conv3x3_patch<4>,
     k_conv_kw, k_conv_gs, k_conv_igemm at other shapes; explicit split-K 2, 3, 7, 17 on k_conv_igemm (test_explicit_splitk).
@@ -24,6 +25,7 @@ import pytest
 import torch
 
 import dgrad_ref as DR
+import fwdconv_ref as FR
 
 pytestmark = pytest.mark.gpu
 
@@ -40,16 +42,21 @@ def oh():
     return orehip
 
 
+class _Plans(list):
+    bm = 0          # rows of a block tile in the last plan (the row tiles of the column sums)
+
+
 @contextlib.contextmanager
 def _planned(oh):
     """Each ore_conv2d_fwd call made inside the block first asks ore_conv_plan about the same descriptor; the answers, in order."""
     L = oh.lib()
-    real, plans = L.ore_conv2d_fwd, []
+    real, plans = L.ore_conv2d_fwd, _Plans()
 
     def fwd(d, stream):
         pl = oh.ConvPlan()
         assert L.ore_conv_plan(d, 0, None, None, 0, C.byref(pl)) == 0, L.ore_last_error()
         plans.append((oh.CONV_LAUNCHERS[pl.launcher], pl.splitk))
+        plans.bm = pl.bm
         return real(d, stream)
 
     L.ore_conv2d_fwd = fwd
@@ -341,6 +348,35 @@ def test_relu_affine_bwd_bitwise(oh):
 
 
 # ---- production replay ----------------------------------------------------------------------------------------------------------
+@contextlib.contextmanager
+def _spying(oh, calls, phase):
+    """Inside the block every fp32 orehip.conv2d call is recorded in calls: signature -> [count, {the launchers it ran on}]."""
+    real = oh.conv2d
+
+    def spy(x, w_packed, Cout, k, stride=1, pad=None, **kw2):
+        res = real(x, w_packed, Cout, k, stride, pad, **kw2)
+        if x.dtype != torch.float32:
+            return res
+        B, H, W, ld = x.shape
+        out = kw2.get("out")
+        add = kw2.get("add")
+        sig = (phase[0], B, H, W, ld, kw2.get("in_coff", 0), kw2.get("Cin") or ld - kw2.get("in_coff", 0), Cout, k, stride,
+               k // 2 if pad is None else pad, out.shape[-1] if out is not None else Cout, kw2.get("out_coff", 0),
+               kw2.get("scale") is not None, kw2.get("shift") is not None, int(kw2.get("relu_cout", 0)), kw2.get("in_mul") is not None,
+               add.shape[-1] if add is not None else 0, kw2.get("w_wino") is not None, int(kw2.get("splitk", 0)),
+               bool(kw2.get("want_colsum", False)), kw2.get("in_add") is not None, bool(kw2.get("in_relu", False)))
+        e = calls.setdefault(sig, [0, set()])
+        e[0] += 1
+        e[1].add(oh.conv_last_launch())
+        return res
+
+    oh.conv2d = spy
+    try:
+        yield
+    finally:
+        oh.conv2d = real
+
+
 def _spy_step(oh, batch):
     """Every distinct orehip.conv2d call of one eager training step: forward-pass calls marked "fwd", backward-pass calls "dgrad";
     each with the launcher it ran."""
@@ -379,50 +415,47 @@ def _spy_step(oh, batch):
         inst = Instances(hw)
         inst.gt_boxes, inst.gt_classes = Boxes(gt), torch.zeros(len(gt), dtype=torch.int64)
         data.append({"image": img, "instances": inst, "support_images": sup, "support_bboxes": sbox.numpy()})
-    calls = {}
-    real = oh.conv2d
-    phase = ["fwd"]
-
-    def spy(x, w_packed, Cout, k, stride=1, pad=None, **kw2):
-        res = real(x, w_packed, Cout, k, stride, pad, **kw2)
-        if x.dtype != torch.float32:
-            return res
-        B, H, W, ld = x.shape
-        out = kw2.get("out")
-        add = kw2.get("add")
-        sig = (phase[0], B, H, W, ld, kw2.get("in_coff", 0), kw2.get("Cin") or ld - kw2.get("in_coff", 0), Cout, k, stride,
-               k // 2 if pad is None else pad, out.shape[-1] if out is not None else Cout, kw2.get("out_coff", 0),
-               kw2.get("scale") is not None, kw2.get("shift") is not None, int(kw2.get("relu_cout", 0)), kw2.get("in_mul") is not None,
-               add.shape[-1] if add is not None else 0, kw2.get("w_wino") is not None, int(kw2.get("splitk", 0)),
-               bool(kw2.get("want_colsum", False)))
-        e = calls.setdefault(sig, [0, set()])
-        e[0] += 1
-        e[1].add(oh.conv_last_launch())
-        return res
-
-    oh.conv2d = spy
-    try:
+    calls, phase = {}, ["fwd"]
+    with _spying(oh, calls, phase):
         losses = train_forward(m, data, **kw)
         torch.cuda.synchronize()
         phase[0] = "dgrad"
         sum(losses.values()).backward()
         torch.cuda.synchronize()
-    finally:
-        oh.conv2d = real
     del m
     return calls
 
 
+def _fwd_ref_images(images, xv, wl, stride, pad, bf16, scale, shift, relu_cout, mul, iadd, in_relu, add, wino, dev):
+    """fwdconv_ref.fwd_ref of these images (None: all), one image at a time, as rows [n, Cout]."""
+    B, H, W, Cin = xv.shape
+    to = lambda t: None if t is None else t.to(dev)
+    wl, scale, shift = to(wl), to(scale), to(shift)
+    refs, mags = [], []
+    for b in (range(B) if images is None else images):
+        r, m = FR.fwd_ref(to(xv[b]).reshape(-1, Cin), wl, [(H, W)], 1, stride=stride, pad=pad, bf16=bf16, scale=scale, shift=shift,
+                          relu_cout=relu_cout, in_mul=to(mul[b:b + 1]) if mul is not None else None,
+                          in_add=to(iadd[b:b + 1]) if iadd is not None else None, in_relu=in_relu,
+                          add=to(add[b:b + 1, ..., :wl.shape[0]]) if add is not None else None, wino=wino)
+        refs.append(r)
+        mags.append(m)
+    return torch.cat(refs, 0), torch.cat(mags, 0)
+
+
 def _replay(oh, mode, calls, batch):
     bf16 = mode == "bf16"
-    reached, skipped, n = set(), 0, 0
+    reached, skipped, n, nfwd, ncs = set(), 0, 0, 0, 0
     dclasses = set()
     for i, (sig, (count, launches)) in enumerate(sorted(calls.items())):
         (ph, B, H, W, ld, in_coff, Cin, Cout, k, stride, pad, out_ld, out_coff, has_sc, has_sh, relu_cout, in_mul, add_ld, has_wino,
-         splitk, colsum) = sig
-        if stride != 1 or pad != k // 2 or in_mul or len(launches) != 1:
+         splitk, colsum, has_in_add, in_relu) = sig
+        if len(launches) != 1:
             skipped += 1
             continue
+        fwd_only = stride != 1 or pad != k // 2 or in_mul   # forward-only forms: the float64 contract of tests/fwdconv_ref.py
+        nfwd += fwd_only
+        exact = in_mul and bf16                             # (operands whose affine is exact in fp32: fwdconv_ref's docstring)
+        Ho, Wo = FR.out_hw(H, W, k, stride, pad)
         launch = next(iter(launches))
         if ph == "dgrad":
             dclasses.add((Cin, Cout, k))
@@ -430,7 +463,19 @@ def _replay(oh, mode, calls, batch):
         sx = 10.0 ** (torch.rand(Cin, generator=gen, device="cuda") * 6 - 3)
         x = torch.full((B, H, W, ld), NAN, device="cuda")
         xv = torch.randn(B, H, W, Cin, generator=gen, device="cuda") * sx
+        if exact:
+            sx = 2.0 ** (torch.rand(Cin, generator=gen, device="cuda") * 9 - 5)
+            xv = ((torch.randn(B, H, W, Cin, generator=gen, device="cuda") * sx * 64).round() / 64).clamp(-63, 63)
         x[..., in_coff:in_coff + Cin] = xv
+        mul = iadd = None
+        if in_mul:
+            sign = torch.where(torch.rand(B, Cin, generator=gen, device="cuda") < 0.3, -1.0, 1.0)
+            mul = sign * (2.0 ** torch.randint(-2, 3, (B, Cin), generator=gen, device="cuda").float() if exact
+                          else torch.rand(B, Cin, generator=gen, device="cuda") + 0.5)
+            if has_in_add:
+                iadd = torch.randn(B, Cin, generator=gen, device="cuda") * sx * mul.abs()
+                iadd = ((iadd * 64).round() / 64).clamp(-63, 63) if exact else iadd
+            assert not exact or FR.affine_is_exact(xv.reshape(-1, Cin), mul, iadd, B, [(H, W)]), sig
         sw = 10.0 ** (torch.rand(Cout, generator=gen, device="cuda") * 6 - 3)
         wl = torch.randn(Cout, Cin, k, k, generator=gen, device="cuda") * sw.view(-1, 1, 1, 1) / (Cin * k * k) ** 0.5
         pw = oh.pack_conv_weight_dev(wl)
@@ -439,24 +484,38 @@ def _replay(oh, mode, calls, batch):
         shift = torch.randn(Cout, generator=gen, device="cuda") * float(sw.mean()) if has_sh else None
         add = None
         if add_ld:
-            add = torch.randn(B, (H + 1) // 2, (W + 1) // 2, add_ld, generator=gen, device="cuda") * float(sw.mean())
-        out = torch.full((B, H, W, out_ld), NAN, device="cuda")
+            add = torch.randn(B, (Ho + 1) // 2, (Wo + 1) // 2, add_ld, generator=gen, device="cuda") * float(sw.mean())
+        out = torch.full((B, Ho, Wo, out_ld), NAN, device="cuda")
         with _planned(oh) as plans:
-            res = oh.conv2d(x, pw, Cout, k, 1, pad, in_coff=in_coff, Cin=Cin, scale=scale, shift=shift, relu_cout=relu_cout, add=add,
-                            out=out, out_coff=out_coff, splitk=splitk, w_wino=ww, want_colsum=colsum)
+            res = oh.conv2d(x, pw, Cout, k, stride, pad, in_coff=in_coff, Cin=Cin, scale=scale, shift=shift, relu_cout=relu_cout, add=add,
+                            out=out, out_coff=out_coff, splitk=splitk, w_wino=ww, want_colsum=colsum, in_mul=mul, in_add=iadd,
+                            in_relu=in_relu)
         got_l = oh.conv_last_launch()
         assert got_l == launch, (sig, launch, got_l)
         assert plans == [got_l], (sig, plans, got_l)
         out = res[0] if colsum else res
         assert bool(out[..., :out_coff].isnan().all()) and bool(out[..., out_coff + Cout:].isnan().all()), ("wrote outside its slice", sig)
-        images, rows = _subset(B, H, W, k, B * H * W * Cin * Cout * k * k)
+        images, rows = _subset(B, Ho, Wo, k, B * Ho * Wo * Cin * Cout * k * k)
         wt = wl.transpose(0, 1).flip(2, 3).contiguous()          # the conv x -> out as a data-gradient-oriented weight
         name, S = got_l
         wino = name.startswith("k_conv3x3_wino")
-        dev = "cuda" if B * H * W * Cin * Cout * k * k > 2e7 else "cpu"
-        ref, mag = DR.dgrad_ref(xv, wt, bf16=bf16, device=dev, images=images, rows=rows, scale=scale, shift=shift, add=add,
-                                relu=relu_cout, wino=wino)
-        d = DR.depth(k * k * Cin, S, wino_cin=Cin if wino else None)
+        dev = "cuda" if B * Ho * Wo * Cin * Cout * k * k > 2e7 else "cpu"
+        fwd_args = (xv, wl, stride, pad, bf16, scale, shift, relu_cout, mul, iadd, in_relu, add, wino, dev)
+        if fwd_only:
+            rows = None
+            ref, mag = _fwd_ref_images(images, *fwd_args)
+            d = FR.fwd_depth(k * k * Cin, S, affine=bool(in_mul), bf16=bf16)
+        else:
+            ref, mag = DR.dgrad_ref(xv, wt, bf16=bf16, device=dev, images=images, rows=rows, scale=scale, shift=shift, add=add,
+                                    relu=relu_cout, wino=wino)
+            d = DR.depth(k * k * Cin, S, wino_cin=Cin if wino else None)
+        if colsum:                                            # the returned column sums against the float64 sum over ALL pixels
+            cs = res[1]
+            assert cs.shape == (-(-B * Ho * Wo // plans.bm), DR.c16(Cout)), (sig, cs.shape, plans.bm)
+            full = (ref, mag) if images is None and rows is None else _fwd_ref_images(None, *fwd_args)
+            r_cs = FR.colsum_check(cs, full[0], full[1], d, plans.bm, Cout)
+            assert r_cs <= 1, (sig, got_l, "column sums", r_cs)
+            ncs += 1
         g = out[..., out_coff:out_coff + Cout]
         if images is not None:
             g = g[images]
@@ -468,8 +527,10 @@ def _replay(oh, mode, calls, batch):
         assert r["hard"] <= 1 and r["rms"] <= 1, (sig, got_l, r)
         reached.add((ph, name))
         n += 1
-    print(f"\n{mode} bs{batch}: {len(calls)} distinct conv2d calls ({sum(c for c, _ in calls.values())} launches), {n} replayed, "
-          f"{skipped} skipped (stride 2 / input affine); launchers {sorted(reached)}")
+    print(f"\n{mode} bs{batch}: {len(calls)} distinct conv2d calls ({sum(c for c, _ in calls.values())} launches), {n} replayed "
+          f"({nfwd} stride 2 / input affine through fwdconv_ref, {ncs} with column sums), {skipped} skipped (ran on more than one "
+          f"launcher); launchers {sorted(reached)}")
+    _replay.counts = {"replayed": n, "fwd_only": nfwd, "colsum": ncs, "skipped": skipped}
     return dclasses
 
 
@@ -483,3 +544,24 @@ def test_production_replay(oh, mode, batch):
     print(f"dgrad classes {sorted(dclasses)}")
     assert dclasses <= model, sorted(dclasses - model)
     assert model <= dclasses, sorted(model - dclasses)
+
+
+def test_replay_of_the_forward_forms_a_training_step_lacks(oh, mode):
+    """The replay on the forward forms of the inference engine that no training step of this configuration calls: the eSE concat conv
+    with fused column sums (1x1, one image and two), the consumer of an eSE gate (in_mul alone), a GroupNorm fold (in_mul, in_add,
+    in_relu) and a 3x3 stride-2 layer with a slice output.  Recorded through the same spy, so every branch of _replay runs in both
+    modes whatever the step contains."""
+    z = lambda *s: torch.zeros(*s, device="cuda")
+    calls = {}
+    with _spying(oh, calls, ["fwd"]):
+        for B, H, W, Cin, Cout in ((1, 20, 19, 352, 256), (2, 9, 11, 64, 48)):
+            pw = oh.pack_conv_weight_dev(z(Cout, Cin, 1, 1))
+            oh.conv2d(z(B, H, W, Cin), pw, Cout, 1, scale=z(Cout), shift=z(Cout), relu_cout=Cout, want_colsum=True)
+        pw = oh.pack_conv_weight_dev(z(96, 64, 3, 3))
+        oh.conv2d(z(2, 13, 10, 96), pw, 96, 3, in_coff=16, Cin=64, scale=z(96), shift=z(96), relu_cout=96, in_mul=z(2, 64))
+        oh.conv2d(z(2, 13, 10, 64), pw, 96, 3, shift=z(96), relu_cout=50, in_mul=z(2, 64), in_add=z(2, 64), in_relu=True)
+        pw = oh.pack_conv_weight_dev(z(128, 64, 3, 3))
+        oh.conv2d(z(2, 14, 17, 64), pw, 128, 3, 2, scale=z(128), shift=z(128), relu_cout=128, out=z(2, 7, 9, 160), out_coff=32)
+    assert len(calls) == 5
+    _replay(oh, mode, calls, 0)
+    assert _replay.counts == {"replayed": 5, "fwd_only": 3, "colsum": 2, "skipped": 0}, _replay.counts

@@ -9,6 +9,9 @@
 //
 // The OSA concat, the eSE product, the FPN upsample+add, torch.cat((attn,q)) and the GroupNorm output
 // are never materialised.  Reference call sites: include/ore_hip.h.
+//
+// Deep bodies (ore_engine_set_blocks: V-39 / V-57 / V-99-eSE): a stage runs blocks[s] OSA blocks; the blocks j >= 2 add their input
+// to their output (identity blocks) and end in ONE launch each at one image per pass (ore_ese_gate_residual_fwd), DESIGN.md 7o.
 #include <map>
 #include <string>
 #include <vector>
@@ -56,8 +59,17 @@ struct ore_engine {
     // weights
     float* stem1_w = nullptr; float* stem1_scale = nullptr; float* stem1_shift = nullptr;
     Conv stem2, stem3;
+    // an identity block (block j >= 2 of a stage): Cin = the stage's out_ch, concat width out_ch + layers_per_block * conv_ch
+    struct Block { Conv layer[8]; Conv concat; float* fc_w = nullptr; float* fc_b = nullptr; int cat_ch = 0; };
     struct Stage { Conv layer[8]; Conv concat; float* fc_w = nullptr; float* fc_b = nullptr; int in_ch, conv_ch, out_ch, cat_ch;
-                   DwUnit dw[8]; Conv reduction; bool has_reduction = false; } stage[4];
+                   DwUnit dw[8]; Conv reduction; bool has_reduction = false; std::vector<Block> more; } stage[4];
+    // deep bodies (ore_engine_set_blocks): stage s runs blocks[s] OSA blocks.  Block 1 works in cat[s] as ever; the identity blocks
+    // alternate between the two concat buffers icat[s][0 | 1] (block j in icat[s][j & 1]; the second exists from three blocks on):
+    // the tail of block j reads its identity from the buffer it ran in and writes the first slice of the other one, so two
+    // suffice for any depth.  Every concat conv of such a stage writes ycat[s]; the last tail writes sout[s], gate[s] holds ones.
+    int blocks[4] = {1, 1, 1, 1};
+    Buf icat[4][2], ycat[4];
+    float* gate_blk = nullptr;                           // [B][C] eSE gate of the block in flight (multi-block stages)
     // depthwise bodies (ore_engine_set_depthwise): stem_2 / stem_3 and the stage layers are DwUnits, a stage whose input width differs
     // from its layer width has a 1x1 conv_reduction whose output (red[s], [M][conv_ch]) feeds layer 0 and is not part of the concat
     bool depthwise = false;
@@ -373,10 +385,11 @@ int run_backbone(ore_engine* e, const void* img, int is_u8, const Geo& g, hipStr
         const int k = s + 2;
         Buf& cat = e->cat[s];
         if (s > 0 && !pooled_next) {
+            const float* pool_mul = e->blocks[s - 1] > 1 ? nullptr : e->gate[s - 1];   // a stage that ends in an identity block is whole
             r.rc = sb ? ore_maxpool3x3s2_bf16_fwd(reinterpret_cast<const uint16_t*>(e->sout[s - 1].p), e->sout[s - 1].ld, 0, g.B, g.h[k - 1],
                                                   g.w[k - 1], S.in_ch, e->gate[s - 1], reinterpret_cast<uint16_t*>(cat.p), cat.ld, 0, st)
                       : ore_maxpool3x3s2_fwd(e->sout[s - 1].p, e->sout[s - 1].ld, 0, g.B, g.h[k - 1], g.w[k - 1], S.in_ch,
-                                             e->gate[s - 1], cat.p, cat.ld, 0, st);
+                                             pool_mul, cat.p, cat.ld, 0, st);
             if (r.rc) break;
         }
         int src = 0, dst = S.in_ch;
@@ -398,11 +411,45 @@ int run_backbone(ore_engine* e, const void* img, int is_u8, const Geo& g, hipStr
             src = dst; dst += S.conv_ch;
         }
         int cs_rows = 0;
-        r.conv(S.concat, cat.p, cat.ld, 0, g.B, g.h[k], g.w[k], e->sout[s].p, e->sout[s].ld, 0, nullptr, nullptr, 0, nullptr, 0, 0,
+        const int nblk = e->blocks[s];
+        Buf& y1 = nblk > 1 ? e->ycat[s] : e->sout[s];
+        r.conv(S.concat, cat.p, cat.ld, 0, g.B, g.h[k], g.w[k], y1.p, y1.ld, 0, nullptr, nullptr, 0, nullptr, 0, 0,
                g.B == 1 ? e->colsum : nullptr, &cs_rows);   // eSE average pool fused into the concat conv's epilogue
         if (r.rc) break;
         pooled_next = false;
-        if (cs_rows > 0 && s < 3 && (s == 0 || e->lat_scaled[s - 1])) {
+        if (nblk > 1) {
+            // Deep stage.  The tail of block j -- eSE gate, product, identity add (j >= 2), and the copy into the first slice of the
+            // concat buffer of block j + 1 (or into the stage's output map) -- is one launch at one image per pass, fed by the concat
+            // conv's fused column sums; with more images the gate comes from ore_ese_gate_fwd and the tail is ore_scale_residual_fwd.
+            const int HW = g.h[k] * g.w[k], C = S.out_ch;
+            const Buf* cur = &cat;                          // the concat buffer block j ran in; its first C channels are the identity
+            for (int j = 1; j <= nblk && !r.rc; ++j) {
+                const float* fw = j == 1 ? S.fc_w : S.more[j - 2].fc_w;
+                const float* fb = j == 1 ? S.fc_b : S.more[j - 2].fc_b;
+                const float* idn = j == 1 ? nullptr : cur->p;
+                const Buf& dstb = j < nblk ? e->icat[s][(j + 1) & 1] : e->sout[s];
+                if (cs_rows > 0)
+                    r.rc = ore_ese_gate_residual_fwd(e->colsum, cs_rows, HW, C, fw, fb, e->gate_blk, e->ycat[s].p, e->ycat[s].ld, 0, idn,
+                                                     cur->ld, 0, dstb.p, dstb.ld, 0, st);
+                else {
+                    r.rc = ore_ese_gate_fwd(e->ycat[s].p, e->ycat[s].ld, 0, g.B, HW, C, fw, fb, e->gate_blk, e->ese_ws, st);
+                    if (!r.rc)
+                        r.rc = ore_scale_residual_fwd(e->ycat[s].p, e->ycat[s].ld, 0, e->gate_blk, idn, cur->ld, 0, g.B, HW, C, dstb.p,
+                                                      dstb.ld, 0, st);
+                }
+                if (r.rc || j == nblk) break;
+                const ore_engine::Block& Bn = S.more[j - 1];  // block j + 1
+                int bsrc = 0, bdst = C;
+                for (int i = 0; i < c.layers_per_block; ++i) {
+                    r.conv(Bn.layer[i], dstb.p, dstb.ld, bsrc, g.B, g.h[k], g.w[k], dstb.p, dstb.ld, bdst);
+                    bsrc = bdst; bdst += S.conv_ch;
+                }
+                cs_rows = 0;
+                r.conv(Bn.concat, dstb.p, dstb.ld, 0, g.B, g.h[k], g.w[k], e->ycat[s].p, e->ycat[s].ld, 0, nullptr, nullptr, 0, nullptr, 0,
+                       0, g.B == 1 ? e->colsum : nullptr, &cs_rows);
+                cur = &dstb;
+            }
+        } else if (cs_rows > 0 && s < 3 && (s == 0 || e->lat_scaled[s - 1])) {
             // bs = 1, a stage followed by the max-pool: gate + the gate-scaled lateral weight of this stage + the pooled, gated input of
             // the next stage (written into its concat buffer) in one launch
             Buf& nx = e->cat[s + 1];
@@ -447,8 +494,8 @@ int run_backbone(ore_engine* e, const void* img, int is_u8, const Geo& g, hipStr
         } else if (sb) {
             ore_set_error("bf16-storage engine: the lateral needs the gate-scaled weights (one image per pass)"); r.rc = ORE_EINVAL;
         } else {
-            r.conv(e->lateral[l], e->sout[s].p, e->sout[s].ld, 0, g.B, g.h[k], g.w[k], lat[l], F, 0, e->gate[s], nullptr, 0,
-                   add, F, 0);
+            r.conv(e->lateral[l], e->sout[s].p, e->sout[s].ld, 0, g.B, g.h[k], g.w[k], lat[l], F, 0,
+                   e->blocks[s] > 1 ? nullptr : e->gate[s], nullptr, 0, add, F, 0);
         }
         if (!grouped)
             r.conv(e->output[l], lat[l], F, 0, g.B, g.h[k], g.w[k], e->at(e->pcat.p, (size_t)lvl_row0(g, l) * 2 * F), 2 * F, F);
@@ -730,7 +777,22 @@ extern "C" int ore_engine_set_support(ore_engine* e, int32_t level, const float*
 extern "C" int ore_engine_set_depthwise(ore_engine* e, int32_t on) {
     ORE_CHECK_ARG(e && !e->finalized, "ore_engine_set_depthwise: call it before ore_engine_finalize");
     ORE_CHECK_ARG(!on || !e->sb(), "ore_engine_set_depthwise: a bf16-storage engine has no depthwise body (the depthwise units are fp32 only)");
+    ORE_CHECK_ARG(!on || (e->blocks[0] == 1 && e->blocks[1] == 1 && e->blocks[2] == 1 && e->blocks[3] == 1),
+                  "ore_engine_set_depthwise: this engine has identity blocks (ore_engine_set_blocks): there is no deep depthwise body");
     e->depthwise = on != 0;
+    return ORE_OK;
+}
+
+extern "C" int ore_engine_set_blocks(ore_engine* e, const int32_t blocks[4]) {
+    ORE_CHECK_ARG(e && blocks && !e->finalized, "ore_engine_set_blocks: call it before ore_engine_finalize");
+    bool deep = false;
+    for (int s = 0; s < 4; ++s) {
+        ORE_CHECK_ARG(blocks[s] >= 1 && blocks[s] <= 16, "ore_engine_set_blocks: %d blocks in stage %d (1 to 16)", blocks[s], s + 2);
+        deep = deep || blocks[s] > 1;
+    }
+    ORE_CHECK_ARG(!deep || !e->depthwise, "ore_engine_set_blocks: a depthwise engine has one block per stage (there is no deep depthwise body)");
+    ORE_CHECK_ARG(!deep || !e->sb(), "ore_engine_set_blocks: a bf16-storage engine has one block per stage (the identity blocks are fp32 only)");
+    for (int s = 0; s < 4; ++s) e->blocks[s] = blocks[s];
     return ORE_OK;
 }
 
@@ -787,6 +849,22 @@ extern "C" int ore_engine_finalize(ore_engine* e) {
         if ((rc = need(e, pre + "ese.fc.weight", &fw, {S.out_ch, S.out_ch, 1, 1}))) return rc;
         if ((rc = need(e, pre + "ese.fc.bias", &fb, {S.out_ch}))) return rc;
         if ((rc = e->upload(&S.fc_w, fw->v)) || (rc = e->upload(&S.fc_b, fb->v))) return rc;
+        S.more.resize(e->blocks[s] - 1);
+        for (int j = 2; j <= e->blocks[s]; ++j) {          // identity blocks: OSAk_j, Cin = out_ch
+            ore_engine::Block& Bk = S.more[j - 2];
+            const std::string bm = "OSA" + std::to_string(k) + "_" + std::to_string(j);
+            const std::string bp = bu + "stage" + std::to_string(k) + "." + bm + ".";
+            Bk.cat_ch = S.out_ch + c.layers_per_block * S.conv_ch;
+            int bi = S.out_ch;
+            for (int i = 0; i < c.layers_per_block; ++i) {
+                if ((rc = make_conv_bn(e, bp + "layers." + std::to_string(i) + "." + bm + "_" + std::to_string(i), bi, S.conv_ch, 3, 1, &Bk.layer[i]))) return rc;
+                bi = S.conv_ch;
+            }
+            if ((rc = make_conv_bn(e, bp + "concat." + bm + "_concat", Bk.cat_ch, S.out_ch, 1, 1, &Bk.concat))) return rc;
+            if ((rc = need(e, bp + "ese.fc.weight", &fw, {S.out_ch, S.out_ch, 1, 1}))) return rc;
+            if ((rc = need(e, bp + "ese.fc.bias", &fb, {S.out_ch}))) return rc;
+            if ((rc = e->upload(&Bk.fc_w, fw->v)) || (rc = e->upload(&Bk.fc_b, fb->v))) return rc;
+        }
         cin = S.out_ch;
     }
     const int F = c.fpn_ch;
@@ -859,7 +937,15 @@ extern "C" int ore_engine_finalize(ore_engine* e) {
         if (e->depthwise && ore_dwpw_prefers_composition((int64_t)M, e->stage[s].conv_ch, 1))
             e->dw_scratch_floats = std::max(e->dw_scratch_floats, M * (size_t)e->stage[s].conv_ch);
         if ((rc = e->dalloc(&e->gate[s], B * e->stage[s].out_ch))) return rc;
-        if (s >= 1 && (rc = e->dalloc(&e->lat_scaled[s - 1], (size_t)round_up(e->cfg.fpn_ch, 16) * e->stage[s].out_ch))) return rc;
+        if (e->blocks[s] > 1) {
+            // a deep stage: the concat convs' output map, one or two identity concat buffers, and a gate of ones (the stage-output
+            // contract: "stageK" x "gateK" is the stage's output; nothing writes this gate again).  No gate-scaled lateral weight.
+            const int icw = e->stage[s].out_ch + c.layers_per_block * e->stage[s].conv_ch;
+            if ((rc = alloc_buf(e, &e->ycat[s], M, e->stage[s].out_ch)) || (rc = alloc_buf(e, &e->icat[s][0], M, icw))) return rc;
+            if (e->blocks[s] > 2 && (rc = alloc_buf(e, &e->icat[s][1], M, icw))) return rc;
+            const std::vector<float> ones(B * e->stage[s].out_ch, 1.0f);
+            ORE_HIP(hipMemcpy(e->gate[s], ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice));
+        } else if (s >= 1 && (rc = e->dalloc(&e->lat_scaled[s - 1], (size_t)round_up(e->cfg.fpn_ch, 16) * e->stage[s].out_ch))) return rc;
         if ((size_t)e->stage[s].out_ch > cmax) cmax = e->stage[s].out_ch;
         const size_t cs = (M / 16 + 1) * (size_t)e->stage[s].out_ch;     // worst case: 16-row tiles
         if (cs > cs_need) cs_need = cs;
@@ -882,6 +968,7 @@ extern "C" int ore_engine_finalize(ore_engine* e) {
     if ((rc = e->dalloc(&e->ws, e->ws_floats))) return rc;
     ORE_HIP(hipMemset(e->ws, 0, e->ws_floats * sizeof(float)));   // arrival counters start at zero and reset themselves
     if ((rc = e->dalloc(&e->ese_ws, B * (ORE_ESE_PARTS + 1) * cmax))) return rc;
+    if (std::any_of(e->blocks, e->blocks + 4, [](int n) { return n > 1; }) && (rc = e->dalloc(&e->gate_blk, B * cmax))) return rc;
     e->colsum_floats = cs_need;
     if ((rc = e->dalloc(&e->colsum, cs_need))) return rc;
     if ((rc = e->dalloc(&e->gn_ws, (rows_all / 64 + 3 * B + 8) * 64 * 2))) return rc;

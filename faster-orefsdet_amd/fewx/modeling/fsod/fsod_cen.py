@@ -360,7 +360,10 @@ class CenterNet2Detector(nn.Module):
         from detectron2.modeling.backbone.vovnet import _STAGE_SPECS
         c = self._cfg_engine
         spec = _STAGE_SPECS[c["body"]]
-        assert all(b == 1 for b in spec["block_per_stage"]), "the fused engine covers one OSA block per stage (V-19 bodies)"
+        blocks = tuple(spec["block_per_stage"])
+        if any(b > 1 for b in blocks) and self.conv_operands == "bf16s":
+            raise ValueError(f"MODEL.VOVNET.CONV_BODY {c['body']} has identity blocks {blocks}: the engine has no bf16 storage form "
+                             "of them (conv_operands 'bf16s')")
         dev = self.device
         assert dev.type == "cuda", "CenterNet2Detector inference runs on the MI355X only"
         prev = orehip.set_conv_precision(self.conv_operands)      # the engine keeps the mode in force at its creation
@@ -369,7 +372,7 @@ class CenterNet2Detector(nn.Module):
                               fpn_ch=c["fpn_ch"], strides=c["strides"], pixel_mean=c["pixel_mean"], pixel_std=c["pixel_std"],
                               score_thresh=c["score_thresh"], pre_topk=c["pre_topk"], nms_thresh=c["nms_thresh"],
                               post_topk=c["post_topk"], max_batch=max_batch, max_h=max_hw[0], max_w=max_hw[1],
-                              device=dev.index or 0, depthwise=bool(spec.get("dw", False)))
+                              device=dev.index or 0, depthwise=bool(spec.get("dw", False)), blocks=blocks)
         finally:
             orehip.set_conv_precision(prev)
         e.load_state_dict(self.state_dict())

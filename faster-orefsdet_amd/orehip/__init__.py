@@ -455,6 +455,42 @@ def scale_channels(x: torch.Tensor, gate: torch.Tensor) -> torch.Tensor:
     return y
 
 
+def _rows_ld(t: torch.Tensor) -> Tuple[int, int]:
+    """(rows, ld) of a contiguous fp32 [..., ld] map."""
+    _f32(t)
+    return t.numel() // t.shape[-1], t.shape[-1]
+
+
+def ese_gate_residual(part: torch.Tensor, fc_w: torch.Tensor, fc_b: torch.Tensor, y: torch.Tensor, x: Optional[torch.Tensor],
+                      out: torch.Tensor, y_coff: int = 0, x_coff: int = 0, out_coff: int = 0) -> torch.Tensor:
+    """The tail of an OSA identity block for one image in one launch (ore_ese_gate_residual_fwd): the gate [1, C] from the concat
+    conv's fused column sums `part` [P, C], and out[..., out_coff + c] = y[..., y_coff + c] * gate[c] + x[..., x_coff + c] over the
+    rows of the maps ([..., ld] each, the same row count).  x = None: out = y * gate.  Returns the gate; `out` is written in place."""
+    _f32(part)
+    P, Cc = part.shape
+    HW, y_ld = _rows_ld(y)
+    rows_o, out_ld = _rows_ld(out)
+    assert rows_o == HW and (x is None or _rows_ld(x)[0] == HW), "y, x and out have the same rows"
+    gate = torch.empty(1, Cc, device=part.device, dtype=torch.float32)
+    _chk(lib().ore_ese_gate_residual_fwd(_ptr(part), P, HW, Cc, _ptr(_f32(fc_w.reshape(Cc, Cc))), _ptr(_f32(fc_b)), _ptr(gate), _ptr(y), y_ld,
+                                         y_coff, _ptr(x), 0 if x is None else x.shape[-1], x_coff, _ptr(out), out_ld, out_coff, _stream()),
+         "ore_ese_gate_residual_fwd")
+    return gate
+
+
+def scale_residual(y: torch.Tensor, gate: torch.Tensor, x: Optional[torch.Tensor], out: torch.Tensor, y_coff: int = 0, x_coff: int = 0,
+                   out_coff: int = 0) -> torch.Tensor:
+    """The same tail for B images with the gates given (ore_scale_residual_fwd): y, x, out [B, ..., ld], gate [B, C]."""
+    _f32(gate)
+    B, Cc = gate.shape
+    rows, y_ld = _rows_ld(y)
+    rows_o, out_ld = _rows_ld(out)
+    assert y.shape[0] == B and rows % B == 0 and rows_o == rows and (x is None or _rows_ld(x)[0] == rows), "y, x and out have the same rows"
+    _chk(lib().ore_scale_residual_fwd(_ptr(y), y_ld, y_coff, _ptr(gate), _ptr(x), 0 if x is None else x.shape[-1], x_coff, B, rows // B, Cc,
+                                      _ptr(out), out_ld, out_coff, _stream()), "ore_scale_residual_fwd")
+    return out
+
+
 def support_kernels(proto_chw: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     _f32(proto_chw)
     Cc, s, s2 = proto_chw.shape
@@ -2796,9 +2832,12 @@ class Engine:
     def __init__(self, *, stem=(64, 64, 128), conv=(64, 80, 96, 112), out=(112, 256, 384, 512), layers=3, fpn_ch=128,
                  strides=(8, 16, 32), pixel_mean=(103.530, 116.280, 123.675), pixel_std=(1.0, 1.0, 1.0),
                  score_thresh=1e-5, pre_topk=1000, nms_thresh=0.6, post_topk=256, max_batch=1, max_h=640, max_w=640,
-                 device: int = 0, depthwise: bool = False):
+                 device: int = 0, depthwise: bool = False, blocks: Sequence[int] = (1, 1, 1, 1)):
         """depthwise: one of the *-dw-* bodies (stem (64, 64, 64)): stem_2 / stem_3 and the stage layers are depthwise-separable units
-        (ore_dwpw_fwd), load_state_dict takes the reference's dw names.  Refused (OreError) in the bf16 storage mode."""
+        (ore_dwpw_fwd), load_state_dict takes the reference's dw names.  Refused (OreError) in the bf16 storage mode.
+        blocks: OSA blocks per stage (ore_engine_set_blocks): (1, 1, 2, 2) is V-39-eSE, (1, 1, 4, 3) V-57-eSE, (1, 3, 9, 3) V-99-eSE, with
+        layers=5; load_state_dict then also takes the names of the identity blocks OSAk_2 ...  Refused (OreError) for a depthwise
+        engine, in the bf16 storage mode, and for a count outside 1..16."""
         cfg = ModelCfg()
         cfg.stem_ch[:] = stem
         cfg.stage_conv_ch[:] = conv
@@ -2818,6 +2857,10 @@ class Engine:
         self.depthwise = bool(depthwise)
         if self.depthwise:
             _chk(lib().ore_engine_set_depthwise(self._h, 1), "ore_engine_set_depthwise")
+        self.blocks = tuple(int(b) for b in blocks)
+        assert len(self.blocks) == 4, blocks
+        if any(b != 1 for b in self.blocks):
+            _chk(lib().ore_engine_set_blocks(self._h, _i32s(self.blocks)), "ore_engine_set_blocks")
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:

@@ -626,6 +626,17 @@ int ore_engine_finalize(ore_engine* e);   /* fold BN, pack weights, upload */
  * ore_engine_last_flops counts a unit as ore_dwpw_flops.  The units are fp32 in every conv precision; an engine created in the bf16
  * STORAGE mode refuses with ORE_EINVAL (here and in finalize). */
 int ore_engine_set_depthwise(ore_engine* e, int32_t on);
+/* The deep bodies (V-39-eSE, V-57-eSE, V-99-eSE; d2z:modeling/backbone/vovnet.py:50-96): blocks[s] OSA blocks in stage s + 2, each 1..16;
+ * call BEFORE ore_engine_finalize (a setter, so that ore_model_cfg keeps its layout).  All ones is the default and leaves every pass as
+ * it was, launch for launch.  finalize then needs, for the identity blocks j = 2..blocks[s], the reference's names
+ * stageK.OSAK_j.layers.i.OSAK_j_i/conv|norm, stageK.OSAK_j.concat.OSAK_j_concat/conv|norm and stageK.OSAK_j.ese.fc.{weight,bias}
+ * (layer 0 of such a block has Cin = stage_out_ch, its concat width is stage_out_ch + layers_per_block * stage_conv_ch).  The tail of
+ * an identity block is ONE launch at one image per pass (ore_ese_gate_residual_fwd), two at more (ore_ese_gate_fwd +
+ * ore_scale_residual_fwd).  Stage-output contract: buffer "stageK" times buffer "gateK" is the stage's output; a stage that ends in an
+ * identity block holds the full output in "stageK" and ones in "gateK" (its FPN lateral runs on the unscaled weights, the max-pool
+ * behind it without a multiplier), a one-block stage of the same engine keeps its folds.  Refused with ORE_EINVAL and the reason: a
+ * depthwise engine (the reference has no deep depthwise body), an engine created in the bf16 STORAGE mode, a count outside 1..16. */
+int ore_engine_set_blocks(ore_engine* e, const int32_t blocks[4]);
 /* Optional second stage (CustomCascadeROIHeads, eval) inside the same forward/graph; call after finalize.  W_host [fc_dim]
  * [pooled*pooled*fpn_ch] (k ordered [pos][channel]) and b_host [fc_dim] are the pre-composed DSA-mix + flatten + fc1 chain
  * (ref:fewx/modeling/fsod/fsod_roi_heads.py:500-520; orehip.compose_roi_head builds them from the state_dict and the cached
@@ -712,6 +723,20 @@ int ore_ese_gate_pool_fwd(const float* part, int32_t P, int32_t HW, int32_t C, c
 int ore_ese_gate_pool_bf16_fwd(const float* part, int32_t P, int32_t HW, int32_t C, const float* fc_w, const float* fc_b, float* gate,
                                const float* w_packed_f32, int32_t w_rows, uint16_t* w_scaled_bf16, const uint16_t* x, int32_t x_ld,
                                int32_t x_coff, int32_t H, int32_t W, uint16_t* out, int32_t out_ld, int32_t out_coff, void* stream);
+/* The tail of an OSA identity block (d2z:modeling/backbone/vovnet.py:310-332: eSE product + `xt += identity_feat`) for ONE image in
+ * ONE launch: gate[C] from the concat conv's fused column sums part[P][C] (the arithmetic of ore_ese_gate_from_colsum_fwd for one
+ * image), and out[r][out_coff + c] = y[r][y_coff + c] * gate[c] + x[r][x_coff + c] for all HW rows (one rounding: fmaf).  y is the concat
+ * conv's output, x the block's identity (the first C channels of its own concat buffer), out the first slice of the next block's
+ * concat buffer or the stage's output map.  x == NULL: out = y * gate (the tail of block 1 in front of an identity block).  C % 4 == 0,
+ * C <= 4096; every ld / coff a multiple of 4 with coff + C <= ld; y, x, out, part, gate 16-byte aligned; out must not overlap y or x
+ * (side by side in the rows of one buffer is fine).  No atomics: the bits do not depend on scheduling. */
+int ore_ese_gate_residual_fwd(const float* part, int32_t P, int32_t HW, int32_t C, const float* fc_w, const float* fc_b, float* gate,
+                              const float* y, int32_t y_ld, int32_t y_coff, const float* x, int32_t x_ld, int32_t x_coff, float* out,
+                              int32_t out_ld, int32_t out_coff, void* stream);
+/* The same tail for B images of rows_per_image rows with the gates given, gate_bc[B][C] (ore_ese_gate_fwd): the same arithmetic element
+ * by element, the same argument rules. */
+int ore_scale_residual_fwd(const float* y, int32_t y_ld, int32_t y_coff, const float* gate_bc, const float* x, int32_t x_ld, int32_t x_coff,
+                           int32_t B, int32_t rows_per_image, int32_t C, float* out, int32_t out_ld, int32_t out_coff, void* stream);
 int ore_roi_align_bf16_fwd(const uint16_t* const* feat, const int32_t* ld, const int32_t* coff, const int32_t* H, const int32_t* W,
                            const float* scales_host, int32_t n_levels, int32_t min_level, int32_t C, int32_t pooled, const float* boxes,
                            const int32_t* n_dev, int32_t n_host, int32_t cap, float* out, void* stream);

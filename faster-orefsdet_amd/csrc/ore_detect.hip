@@ -971,7 +971,7 @@ __global__ __launch_bounds__(256) void k_nms_prep(const float* __restrict__ boxe
                                                   const int* __restrict__ n_dev, float* s_boxes, float* s_scores, int* s_order,
                                                   int* n_out) {
     extern __shared__ float sc[];
-    const int n = n_dev ? *n_dev : n_host;
+    const int n = n_dev ? min(*n_dev, n_host) : n_host;      // a device count is clamped to the capacity (sc[] holds n_host floats)
     for (int i = threadIdx.x; i < n; i += 256) sc[i] = scores[i];
     __syncthreads();
     const int e = blockIdx.x * 16 + (threadIdx.x >> 4), sub = threadIdx.x & 15;

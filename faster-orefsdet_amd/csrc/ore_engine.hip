@@ -1379,7 +1379,8 @@ extern "C" int ore_engine_buffer(ore_engine* e, const char* name, void** ptr, in
         if (base == "final_scores") return set(e->fin_scores_of(ib), e->roi_cap, 1, 1, 0);
         if (base == "final_count") return set(e->fin_count + ib * 4, 4, 1, 1, 0);
         if (base == "final_classes") return set(e->fin_pack + ib * rcap * 28 + rcap * 20, e->roi_cap, 1, 1, 0);   // N-way pass: slot 0
-        if (n == "roi_h") return set(e->roi_h, e->roi_cap, e->roi_fc, e->roi_fc, 0);
+        // K-split mode leaves the fc1 rows in roi_hp partial sums and never writes roi_h: the name is unknown there
+        if (n == "roi_h" && e->roi_ksplit <= 1) return set(e->roi_h, e->roi_cap, e->roi_fc, e->roi_fc, 0);
         // the predictor's per-ROI rows BEFORE the score filter / NMS (row r = proposal r of the image the second stage ran last on)
         const oreroi::PredictWs L = oreroi::predict_ws_layout(e->roi_cap);
         if (n == "roi_raw_boxes") return set((float*)((char*)e->roi_ws + L.raw_boxes), e->roi_cap, 4, 4, 0);

@@ -1217,6 +1217,19 @@ extern "C" int ore_roi_predict_post_fwd(const float* h, int32_t C, const float* 
                                     fin_count, host_count, workspace, workspace_bytes, stream);
 }
 
+// The engine's launch form behind the C ABI (h_parts >= 1: h = [h_parts][cap][C] raw sums): forwarded unchanged.
+extern "C" int ore_roi_predict_parts_fwd(const float* h, int32_t C, const float* cls_w, const float* cls_b, const float* box_w,
+                                         const float* box_b, const float* boxes, const int32_t* n_dev, int32_t n_host, int32_t cap,
+                                         const float* reg_weights4_host, float img_h, float img_w, float score_thresh, float nms_thresh,
+                                         int32_t topk, float* det_boxes, float* det_scores, int64_t* det_src, int32_t* det_count,
+                                         const float* post_dev, float* fin_boxes, float* fin_scores, int32_t* fin_count,
+                                         int32_t* host_count, void* workspace, size_t workspace_bytes, void* stream,
+                                         int32_t h_parts, const float* h_bias) {
+    return oreroi::roi_predict_post(h, C, h_parts, h_bias, cls_w, cls_b, box_w, box_b, boxes, n_dev, n_host, cap, reg_weights4_host, img_h, img_w,
+                                    score_thresh, nms_thresh, topk, det_boxes, det_scores, det_src, det_count, post_dev, fin_boxes, fin_scores,
+                                    fin_count, host_count, workspace, workspace_bytes, stream);
+}
+
 // The same with the fc1 rows still in K-split partial sums (h = [h_parts][cap][C] raw sums, h_bias [C]): the engine's second stage.
 int oreroi::roi_predict_post(const float* h, int32_t C, int32_t h_parts, const float* h_bias, const float* cls_w, const float* cls_b,
                              const float* box_w, const float* box_b, const float* boxes, const int32_t* n_dev, int32_t n_host, int32_t cap,

@@ -883,19 +883,34 @@ def roi_align_bwd(dout: torch.Tensor, feats_like: Sequence[torch.Tensor], boxes:
 
 
 def roi_predict(h: torch.Tensor, cls_w, cls_b, box_w, box_b, boxes: torch.Tensor, reg_weights, image_hw, score_thresh: float,
-                nms_thresh: float, topk: int, n_dev: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-    cap, Cc = h.shape
+                nms_thresh: float, topk: int, n_dev: Optional[torch.Tensor] = None, parts: int = 0, bias: Optional[torch.Tensor] = None,
+                post: Optional[torch.Tensor] = None, pin: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """h [cap, C] fc1 rows, or with parts >= 1 the K-split partial sums [parts, cap, C] (bias [C] or None) that the engine's second
+    stage hands over (ore_roi_predict_parts_fwd).  post: device {sx, sy, out_w, out_h} -> detector_postprocess in the same launch,
+    returned as "fin_boxes" / "fin_scores" / "fin_count".  pin: device int32 tensor of >= 4 words: word 0 receives the final count,
+    words 2..3 hold the 64-bit device address of a record tensor (boxes | scores | int64 classes, see the header) or 0."""
+    cap, Cc = h.shape[-2:]
+    if h.dim() != (3 if parts >= 1 else 2) or (parts >= 1 and h.shape[0] != parts):
+        raise OreError(f"roi_predict: h {tuple(h.shape)} with parts={parts}")
+    if pin is not None and (pin.dtype != torch.int32 or pin.numel() < 4):
+        raise OreError("roi_predict: pin must hold at least 4 int32 words")
     n = boxes.shape[0]
     dev = h.device
     o = {"boxes": torch.zeros(cap, 4, device=dev), "scores": torch.zeros(cap, device=dev),
          "src": torch.zeros(cap, dtype=torch.int64, device=dev), "count": torch.zeros(1, dtype=torch.int32, device=dev)}
+    if post is not None:
+        o.update({"fin_boxes": torch.zeros(cap, 4, device=dev), "fin_scores": torch.zeros(cap, device=dev),
+                  "fin_count": torch.zeros(1, dtype=torch.int32, device=dev)})
     wsb = lib().ore_roi_predict_workspace_bytes(cap)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
     rw = (C.c_float * 4)(*reg_weights)
     b = boxes.float().contiguous() if n else torch.zeros(1, 4, device=dev)
-    _chk(lib().ore_roi_predict_fwd(_ptr(_f32(h)), Cc, _ptr(_f32(cls_w)), _ptr(_f32(cls_b)), _ptr(_f32(box_w)), _ptr(_f32(box_b)), _ptr(b),
-                                   _ptr(n_dev), n, cap, rw, image_hw[0], image_hw[1], score_thresh, nms_thresh, topk, _ptr(o["boxes"]),
-                                   _ptr(o["scores"]), _ptr(o["src"]), _ptr(o["count"]), _ptr(ws), wsb, _stream()), "ore_roi_predict_fwd")
+    _chk(lib().ore_roi_predict_parts_fwd(_ptr(_f32(h)), Cc, _ptr(_f32(cls_w)), _ptr(_f32(cls_b)), _ptr(_f32(box_w)), _ptr(_f32(box_b)), _ptr(b),
+                                         _ptr(n_dev), n, cap, rw, image_hw[0], image_hw[1], score_thresh, nms_thresh, topk, _ptr(o["boxes"]),
+                                         _ptr(o["scores"]), _ptr(o["src"]), _ptr(o["count"]), _ptr(_f32(post)) if post is not None else None,
+                                         _ptr(o.get("fin_boxes")), _ptr(o.get("fin_scores")), _ptr(o.get("fin_count")), _ptr(pin),
+                                         _ptr(ws), wsb, _stream(), parts, _ptr(_f32(bias)) if bias is not None else None),
+         "ore_roi_predict_parts_fwd")
     o["_ws"] = ws
     return o
 

@@ -269,7 +269,8 @@ size_t ore_nms_workspace_bytes(int32_t n);
 int ore_nms_fwd(const float* boxes, const float* scores, int32_t n, float thr, int64_t* keep_idx,
                 int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
-/* NMS with the box count on the device (capacity cap): lets a producer kernel feed the NMS without a host sync. */
+/* NMS with the box count on the device (capacity cap): lets a producer kernel feed the NMS without a host sync.  boxes / scores hold
+ * cap rows; *n_dev is clamped to cap (a larger count runs the NMS of the first cap rows). */
 int ore_nms_device_n_fwd(const float* boxes, const float* scores, const int32_t* n_dev, int32_t cap, float thr,
                          int64_t* keep_idx, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
@@ -334,6 +335,17 @@ int ore_roi_predict_post_fwd(const float* h, int32_t C, const float* cls_w, cons
                              int32_t topk, float* det_boxes, float* det_scores, int64_t* det_src, int32_t* det_count,
                              const float* post_dev, float* fin_boxes, float* fin_scores, int32_t* fin_count,
                              int32_t* host_count, void* workspace, size_t workspace_bytes, void* stream);
+/* The same with the fc1 rows still in K-split partial sums, the form the engine's second stage launches: h_parts >= 1 means h is
+ * [h_parts][cap][C] raw sums and row r = ReLU(h_bias + h[0][r] + h[1][r] + ...) added in that order (h_bias [C] device, NULL = 0;
+ * every slice holds cap rows, rows at and beyond the count are summed and never used); cap <= 512 only.  h_parts = 0 is
+ * ore_roi_predict_post_fwd (h_bias unused). */
+int ore_roi_predict_parts_fwd(const float* h, int32_t C, const float* cls_w, const float* cls_b, const float* box_w,
+                              const float* box_b, const float* boxes, const int32_t* n_dev, int32_t n_host, int32_t cap,
+                              const float* reg_weights4_host, float img_h, float img_w, float score_thresh, float nms_thresh,
+                              int32_t topk, float* det_boxes, float* det_scores, int64_t* det_src, int32_t* det_count,
+                              const float* post_dev, float* fin_boxes, float* fin_scores, int32_t* fin_count,
+                              int32_t* host_count, void* workspace, size_t workspace_bytes, void* stream,
+                              int32_t h_parts, const float* h_bias);
 
 /* ------------------------------------------------------------------ training targets / losses - */
 /* CenterNet2 proposal-generator ground truth for only_proposal=True (class-agnostic), on device.

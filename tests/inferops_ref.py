@@ -586,10 +586,10 @@ INFER_OPS = {
 NOT_COVERED = {
     "k_correlation_classes": "internal N-way fan-out: bit-identical per class to k_correlation in tests/test_hip_nway.py",
     "k_copy_cols": "plain copy of a channel slice, part of the N-way pass: bitwise in tests/test_hip_nway.py",
-    "k_roi_predict": "bit-exact against the C twin (oracle/ref_decode.c) in tests/test_hip_parity.py",
-    "k_roi_predict_mb": "bit-exact against the C twin",
-    "k_roi_finalize": "bit-exact against the C twin",
-    "k_roi_tail": "bit-exact against the C twin",
+    "k_roi_predict": "bit-exact against the C twin (oracle/ref_decode.c): the GENERAL form of tests/test_hip_roitail.py (tests/roitail_ref.py)",
+    "k_roi_predict_mb": "bit-exact against the C twin: the FUSED64 and FUSED8 (K-split partials) forms of tests/test_hip_roitail.py",
+    "k_roi_finalize": "bit-exact against the C twin: the GENERAL form of tests/test_hip_roitail.py",
+    "k_roi_tail": "bit-exact against the C twin: both fused forms of tests/test_hip_roitail.py, every hard decision a case class of its own",
     "k_roi_merge_classes": "bit-exact against the C twin (tests/test_hip_nway.py)",
     "k_roi_align_bwd": "training: held to float64 in tests/test_hip_trainloss.py (tests/trainloss_ref.py roi_align_bwd_ref)",
     "k_roi_align_bwd_col": "training: held to float64 in tests/test_hip_trainloss.py (tests/trainloss_ref.py roi_align_bwd_ref)",

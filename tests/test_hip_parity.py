@@ -1522,6 +1522,9 @@ def test_eval_end_to_end_vs_reference_run(ore, golden, tmp_path):
         assert (np.abs(raw_s[which[both]] - ref_s[both]) <= 1e-3 * ref_s[both] + 1e-6).all()
         # second stage decisions: score > 0.05 -> NMS 0.9 -> the best 100, in output coordinates (detector_postprocess scales by 300/320)
         okf = e.buffer("roi_ok")[:n_prop, 0].cpu().numpy() != 0
+        # this engine runs fc1 K-split (8192 -> 128, cap 320): the rows exist only as partial sums, so the never-written "roi_h" is no buffer
+        with pytest.raises(ore.OreError, match="unknown buffer 'roi_h'"):
+            e.buffer("roi_h")
         s2 = guided_nms_explain(raw_b[okf] * (300.0 / W), raw_s[okf], rb, rs, 0.9, max_out=100, box_tol=5e-2, score_rtol=1e-3, drop_empty=True)
         assert s2["unexplained"] == [], (i, "detections", s2["unexplained"][:6])
         print(f"image {i}: {int(ok.sum())}/{len(ok)} detections match row for row; near-tie decisions used: proposals {s1['ambiguous']}, "

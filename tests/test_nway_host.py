@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from roitail_ref import scale_clip_drop
+
 
 def merge_classes(dets, class_ids, topk, in_hw, out_hw):
     """dets: per class slot (boxes [n,4] f32, scores [n] f32), each list score-descending as the per-class second stage leaves it.
@@ -21,10 +23,7 @@ def merge_classes(dets, class_ids, topk, in_hw, out_hw):
     B, S, Cl = B[order], S[order], Cl[order]
     (H, W), (oh, ow) = in_hw, out_hw
     sx, sy = np.float32(ow / W), np.float32(oh / H)
-    B = B * np.array([sx, sy, sx, sy], np.float32)
-    B[:, 0::2] = np.minimum(np.maximum(B[:, 0::2], np.float32(0)), np.float32(ow))
-    B[:, 1::2] = np.minimum(np.maximum(B[:, 1::2], np.float32(0)), np.float32(oh))
-    keep = ((B[:, 2] - B[:, 0]) > 0) & ((B[:, 3] - B[:, 1]) > 0)
+    B, keep = scale_clip_drop(B, sx, sy, ow, oh)          # the arithmetic k_roi_tail's postprocess is held to as well
     return B[keep], S[keep], Cl[keep]
 
 

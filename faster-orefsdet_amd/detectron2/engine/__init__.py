@@ -55,10 +55,11 @@ class SimpleTrainer:
         data_time = time.perf_counter() - start
         if getattr(self, "graph_step", False):
             # opt-in (trainer.graph_step = True; single process, the HIP detector): the whole iteration -- forward, losses, backward, clip
-            # + SGD -- captured once and replayed as one hipGraph (fewx.solver.GraphedTrainStep; eager while it warms up or cannot capture)
+            # + SGD -- captured once and replayed as one hipGraph (fewx.solver.GraphedTrainStep; eager while it warms up or cannot capture).
+            # trainer.graph_step_options: its keyword arguments, e.g. {"max_graphs": 8, "recur": 1} for a multi-scale schedule
             if self.__dict__.get("_graphed") is None:
                 from fewx.solver import GraphedTrainStep
-                self._graphed = GraphedTrainStep(self.model, self.optimizer)
+                self._graphed = GraphedTrainStep(self.model, self.optimizer, **(getattr(self, "graph_step_options", None) or {}))
             loss_dict = self._graphed(data)
             self.flush_metrics(keep=self.metrics_lag - 1)
             self.last_losses = {k: v.detach().clone() for k, v in loss_dict.items()}   # (the graph's loss buffers are rewritten by the next replay)

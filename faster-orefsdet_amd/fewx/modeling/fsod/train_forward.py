@@ -439,10 +439,11 @@ def train_forward(model, batched_inputs, perm: Optional[Callable[[int], torch.Te
                       fused_preprocess=fused_preprocess)
 
 
-def stage_inputs(model, batched_inputs, gt_capacity: Optional[int] = None) -> Dict:
+def stage_inputs(model, batched_inputs, gt_capacity: Optional[int] = None, images: bool = True) -> Dict:
     """Every host -> device upload of a call (pinned, asynchronous), so nothing in the core waits for the stream to drain:
     imgs / sups (lists, as given), gts (list of [n_i,4]), gtp [B,G,4] + gt_n [B] int64 (zero padded to the batch maximum, or to
-    `gt_capacity` rows: the fixed-shape form of a captured step), sbx [B*N,4]."""
+    `gt_capacity` rows: the fixed-shape form of a captured step), sbx [B*N,4].  `images=False`: the boxes only (a captured mixed-size
+    step uploads its images as one slab, orehip.batch_canvas_plan)."""
     import orehip
     dev = model.device
     N = model.support_way * model.support_shot
@@ -458,17 +459,19 @@ def stage_inputs(model, batched_inputs, gt_capacity: Optional[int] = None) -> Di
         assert gtp.shape[1] <= gt_capacity
         if gtp.shape[1] < gt_capacity:
             gtp = F.pad(gtp, (0, 0, 0, gt_capacity - gtp.shape[1]))
-    imgs = [orehip.to_device(item["image"], dev) for item in batched_inputs]
-    sups = [orehip.to_device(item["support_images"], dev) for item in batched_inputs]
-    for s_ in sups:
-        assert s_.shape[0] == N, "support_images must hold SUPPORT_WAY * SUPPORT_SHOT crops"
+    for item in batched_inputs:
+        assert item["support_images"].shape[0] == N, "support_images must hold SUPPORT_WAY * SUPPORT_SHOT crops"
+    imgs = [orehip.to_device(item["image"], dev) for item in batched_inputs] if images else None
+    sups = [orehip.to_device(item["support_images"], dev) for item in batched_inputs] if images else None
     return dict(imgs=imgs, sups=sups, gts=gts, gtp=gtp.contiguous(), gt_n=gt_n, sbx=sbx)
 
 
 def train_core(model, st: Dict, perm=None, return_aux: bool = False, roi_override=None, cn_norm_avg=None, fused_preprocess: bool = True,
                static: bool = False):
     """train_forward behind its uploads.  `static`: the inputs are the fixed buffers of a captured step (st["xq"] / st["xs"] stacked raw
-    images, gtp / gt_n / sbx; no per-image lists) -- nothing in here may then touch host memory or depend on a host-known count."""
+    images, gtp / gt_n / sbx; no per-image lists; or, for images of several sizes, st["canvas_buf"] / st["canvas_geom"]: the step's slab
+    and table of orehip.batch_canvas_plan on the device and its geometry, in place of xq / xs) -- nothing in here may then touch host
+    memory or depend on a host-known count."""
     import orehip
     from orehip import autograd as A
     dev = model.device
@@ -481,11 +484,19 @@ def train_core(model, st: Dict, perm=None, return_aux: bool = False, roi_overrid
     gts = st.get("gts")
     graph = getattr(model, "train_graph", False) and not static
     if static:
-        B = int(st["xq"].shape[0])
         # inside a captured step: the packed copies are rebuilt by launches that belong to the graph (as in _DensePart)
         A.weights_changed()
         A.prepack(list(model.parameters()))
-        outs = dense_part(model, st["xq"], st["xs"], raw=True)
+        geom = st.get("canvas_geom")
+        if geom is None:
+            B = int(st["xq"].shape[0])
+            outs = dense_part(model, st["xq"], st["xs"], raw=True)
+        else:
+            # images of several sizes: st["canvas_buf"] holds the step's raw images and their table; ONE launch writes the two canvases
+            # the mixed-size branch below builds with per-image torch ops (the sizes are read on the device: the launch is replayed)
+            B = int(geom.n_query)
+            xq, xs = orehip.batch_canvas(st["canvas_buf"], geom, mean, std)
+            outs = dense_part(model, xq, xs)
     else:
         imgs, sups = st["imgs"], st["sups"]
         B = len(imgs)

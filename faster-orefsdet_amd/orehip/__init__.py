@@ -1170,6 +1170,156 @@ def support_crops(frames, boxes, frame_index=None, size: int = 240, context: int
 
 
 # ---------------------------------------------------------------------------------------------------
+# batch canvases of a training step ("batch canvas v1", include/ore_hip.h; csrc/ore_batch_canvas.hip)
+# ---------------------------------------------------------------------------------------------------
+BATCH_CANVAS_JOB_INTS = 8                                # ORE_BATCH_CANVAS_JOB_INTS
+_BCJ_SRC, _BCJ_H, _BCJ_W, _BCJ_DST, _BCJ_HC, _BCJ_WC = 0, 2, 3, 4, 6, 7
+
+
+class BatchCanvasGeom(tuple):
+    """What of a batch-canvas plan is a launch argument -- and therefore fixed in a captured launch: (n_query, (Hq, Wq), query_u8,
+    n_support, (Hs, Ws), support_u8, table_bytes, slab_bytes).  Two plans with equal geometry are served by the same launch."""
+    __slots__ = ()
+    n_query = property(lambda s: s[0])
+    q_canvas = property(lambda s: s[1])
+    q_u8 = property(lambda s: s[2])
+    n_support = property(lambda s: s[3])
+    s_canvas = property(lambda s: s[4])
+    s_u8 = property(lambda s: s[5])
+    table_bytes = property(lambda s: s[6])
+    slab_bytes = property(lambda s: s[7])
+
+    @property
+    def out_floats(self) -> int:
+        return self.n_query * 3 * self.q_canvas[0] * self.q_canvas[1] + self.n_support * 3 * self.s_canvas[0] * self.s_canvas[1]
+
+
+class BatchCanvasPlan:
+    """One step's raw images packed for ore_batch_canvas_fwd: `host` = ONE pinned uint8 buffer [table | slab] (the table: one row of
+    BATCH_CANVAS_JOB_INTS int32 words per job, query rows first; the slab: every image planar at its own size, each at a 16-byte
+    boundary), `used` = the bytes of it that a step has to upload, `table` = the rows as an int32 [jobs, 8] view of the buffer,
+    `geom` = the launch's fixed arguments."""
+
+    def __init__(self, host, used, table, geom):
+        self.host, self.used, self.table, self.geom = host, int(used), table, geom
+
+
+def _canvas_group(images, what: str):
+    """A group's images as a flat list of [3, h, w] host tensors of one dtype (a [N, 3, h, w] tensor counts as N images), and the
+    tensors as given, each with the index of its first image: [(first, [n, 3, h, w])]."""
+    flat, blocks = [], []
+    for t in images:
+        t = torch.as_tensor(t)
+        if t.is_cuda:
+            raise ValueError(f"batch_canvas_plan packs host images; a {what} image lives on {t.device}")
+        blocks.append((len(flat), t if t.dim() == 4 else t[None]))
+        if t.dim() == 4:
+            flat.extend(t[i] for i in range(t.shape[0]))
+        else:
+            flat.append(t)
+    for t in flat:
+        if t.dim() != 3 or t.shape[0] != 3 or t.shape[1] < 1 or t.shape[2] < 1:
+            raise ValueError(f"batch_canvas_plan takes [3, h, w] images, not a {what} image of shape {tuple(t.shape)}")
+        if t.dtype not in (torch.uint8, torch.float32):
+            raise ValueError(f"batch_canvas_plan takes raw uint8 or fp32 images, not a {what} image of {t.dtype}")
+        if t.dtype != flat[0].dtype:
+            raise ValueError(f"batch_canvas_plan: the {what} images mix {flat[0].dtype} and {t.dtype}; one dtype per group")
+    return flat, blocks
+
+
+def batch_canvas_plan(queries, supports=(), div: int = 32, q_canvas: Optional[Tuple[int, int]] = None,
+                      s_canvas: Optional[Tuple[int, int]] = None, capacity: Optional[Tuple[int, int]] = None,
+                      full_slab: bool = False) -> BatchCanvasPlan:
+    """Host plan of one step's batch canvases: the query images (a list of [3, h, w] host tensors, sizes may differ) and the support
+    crops (a list of [3, h, w] or [N, 3, h, w] host tensors) packed into one pinned buffer, table and slab together, so that ONE
+    host-to-device copy per step replaces one upload per image.  A group's canvas is its largest height and width rounded up to `div`
+    (ImageList.from_tensors), or `q_canvas` / `s_canvas` as given.  `capacity` = (query jobs, support jobs) of the launch (default: the
+    images given); rows beyond the images given are empty jobs, whose canvases come out all zero.  `full_slab`: the slab is sized for
+    images that fill their canvases -- the geometry, and with it the launch, then depends on nothing but the canvases, the capacities
+    and the dtypes (a captured launch).  ValueError: an image larger than its canvas, two dtypes within a group, more images than the
+    capacity, an image on the device."""
+    both = [_canvas_group(queries, "query"), _canvas_group(supports, "support")]
+    groups, blocks = [b[0] for b in both], [b[1] for b in both]
+    cap =[len(groups[0]), len(groups[1])] if capacity is None else [int(capacity[0]), int(capacity[1])]
+    canv, u8 = [], []
+    for g, (imgs, given, what) in enumerate(zip(groups, (q_canvas, s_canvas), ("query", "support"))):
+        if len(imgs) > cap[g]:
+            raise ValueError(f"batch_canvas_plan: {len(imgs)} {what} images, the capacity is {cap[g]}")
+        if given is not None:
+            Hc, Wc = int(given[0]), int(given[1])
+        elif imgs:
+            Hc, Wc = (-(-max(int(t.shape[d]) for t in imgs) // div) * div for d in (1, 2))
+        else:
+            Hc, Wc = 0, 0
+        for i, t in enumerate(imgs):
+            if t.shape[1] > Hc or t.shape[2] > Wc:
+                raise ValueError(f"batch_canvas_plan: {what} image {i} of {t.shape[1]} x {t.shape[2]} is larger than its {Hc} x {Wc} canvas")
+        if cap[g] and (Hc < 1 or Wc < 4 or Wc % 4 or max(Hc, Wc) > 8192):
+            raise ValueError(f"batch_canvas_plan: {what} canvas {Hc} x {Wc} (sides 1 .. 8192, the width a multiple of 4)")
+        canv.append((Hc, Wc))
+        u8.append(bool(imgs[0].dtype == torch.uint8) if imgs else True)
+    if cap[0] + cap[1] < 1 or cap[0] + cap[1] > 65535:
+        raise ValueError(f"batch_canvas_plan: {cap[0]} + {cap[1]} jobs (1 .. 65535 in all)")
+    up16 = lambda n: (n + 15) // 16 * 16                 # noqa: E731
+    esz = [1 if u else 4 for u in u8]
+    table_bytes = up16((cap[0] + cap[1]) * BATCH_CANVAS_JOB_INTS * 4)
+    packed = sum(up16(3 * int(t.shape[1]) * int(t.shape[2]) * esz[g]) for g in range(2) for t in groups[g])
+    slab_bytes = sum(cap[g] * up16(3 * canv[g][0] * canv[g][1] * esz[g]) for g in range(2)) if full_slab else max(packed, 16)
+    geom = BatchCanvasGeom((cap[0], canv[0], u8[0], cap[1], canv[1], u8[1], table_bytes, slab_bytes))
+    host = torch.empty(table_bytes + slab_bytes, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    table = host[:(cap[0] + cap[1]) * BATCH_CANVAS_JOB_INTS * 4].view(torch.int32).view(cap[0] + cap[1], BATCH_CANVAS_JOB_INTS)
+    jobs = cap[0] + cap[1]
+    rows = np.zeros((jobs, BATCH_CANVAS_JOB_INTS), dtype=np.int64)
+    first = (0, cap[0])
+    for g in range(2):
+        j0, n = first[g], len(groups[g])
+        rows[j0:j0 + n, _BCJ_H] = [int(t.shape[1]) for t in groups[g]]
+        rows[j0:j0 + n, _BCJ_W] = [int(t.shape[2]) for t in groups[g]]
+        rows[j0:j0 + cap[g], _BCJ_HC], rows[j0:j0 + cap[g], _BCJ_WC] = canv[g]
+        rows[j0:j0 + cap[g], _BCJ_DST] = (first[g] and cap[0] * 3 * canv[0][0] * canv[0][1]) + np.arange(cap[g]) * (3 * canv[g][0] * canv[g][1])
+    nbytes = 3 * rows[:, _BCJ_H] * rows[:, _BCJ_W] * np.repeat(esz, cap)
+    src = np.concatenate([[0], np.cumsum((nbytes + 15) // 16 * 16)])                     # every image at a 16-byte boundary
+    rows[:, _BCJ_SRC] = src[:-1]
+    for at in (_BCJ_SRC, _BCJ_DST):
+        rows[:, at + 1], rows[:, at] = rows[:, at] >> 32, rows[:, at] & 0xffffffff
+    table.copy_(torch.from_numpy(rows.astype(np.uint32).view(np.int32)))
+    for g in range(2):
+        for i0, t in blocks[g]:                                                           # a tensor of crops whose images tile the slab: one copy
+            n, j = int(t.shape[0]), first[g] + i0
+            nb = int(nbytes[j])
+            for k in ([None] if nb % 16 == 0 or n == 1 else range(n)):
+                a = table_bytes + int(src[j + (k or 0)])
+                piece = host[a:a + (n if k is None else 1) * nb]
+                piece = (piece if u8[g] else piece.view(torch.float32)).view(-1, *t.shape[1:])
+                piece.copy_(t if k is None else t[k:k + 1])
+    return BatchCanvasPlan(host, table_bytes + int(src[-1]), table, geom)
+
+
+def batch_canvas(buf: torch.Tensor, geom: BatchCanvasGeom, pixel_mean: torch.Tensor, pixel_std: torch.Tensor,
+                 out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The query and the support canvas of a step from ONE launch (ore_batch_canvas_fwd): buf = the device copy of a BatchCanvasPlan's
+    buffer (`plan.host[:plan.used]` at its start; a buffer of a captured launch is written again before every replay), geom = the
+    plan's geometry, pixel_mean / pixel_std = the model's buffers on the device.  Returns (xq [n_query, 3, Hq, Wq], xs [n_support, 3, Hs,
+    Ws]) fp32, both views of `out` (allocated if not given): (float(raw) - mean) / std inside every image, +0.0 in the padding -- the
+    tensors the mixed-size branch of train_forward.train_core builds with a handful of torch ops per image."""
+    assert buf.is_cuda and buf.dtype == torch.uint8 and buf.is_contiguous() and buf.numel() >= geom.table_bytes + geom.slab_bytes, \
+        "batch_canvas: buf is the uint8 device buffer [table | slab] of the plan's geometry"
+    mean, std = _f32(pixel_mean.reshape(-1)), _f32(pixel_std.reshape(-1))
+    assert mean.numel() == 3 and std.numel() == 3 and mean.device == buf.device and std.device == buf.device
+    n = geom.out_floats
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=buf.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= n
+    with torch.cuda.device(buf.device):
+        _chk(lib().ore_batch_canvas_fwd(buf.data_ptr() + geom.table_bytes, geom.slab_bytes, _ptr(buf), geom.n_query, geom.q_canvas[0],
+                                        geom.q_canvas[1], int(geom.q_u8), geom.n_support, geom.s_canvas[0], geom.s_canvas[1], int(geom.s_u8),
+                                        _ptr(mean), _ptr(std), _ptr(out), out.numel(), _stream()), "ore_batch_canvas_fwd")
+    flat = out.view(-1)
+    nq = geom.n_query * 3 * geom.q_canvas[0] * geom.q_canvas[1]
+    return (flat[:nq].view(geom.n_query, 3, *geom.q_canvas), flat[nq:n].view(geom.n_support, 3, *geom.s_canvas))
+
+
+# ---------------------------------------------------------------------------------------------------
 # test-time augmentation tail (csrc/ore_tta.hip): flipped variants, per-variant collection, the merge
 # ---------------------------------------------------------------------------------------------------
 TTA_MAX_CANDIDATES = 8192                                # rows one ore_tta_merge_fwd takes (include/ore_hip.h)

@@ -1186,6 +1186,33 @@ int ore_tile_collect_fwd(const float* boxes, const float* scores, const int64_t*
                          float margin, float* pool_boxes, float* pool_scores, int64_t* pool_classes, int32_t* pool_n, int32_t pool_cap,
                          int32_t* src_counts, int32_t* src_dropped, int32_t source, void* stream);
 
+/* ------------------------------------------------------------------ batch canvases ------------ */
+/* "batch canvas v1": the input tensors of a training step built from its raw images in one launch -- ImageList.from_tensors
+ * (d2z:structures/image_list.py) behind the normalisation (ref:fewx/modeling/fsod/fsod_cen.py:540-551), for images whose sizes differ.
+ * slab: the raw images of the step on the device, each planar [3][h][w] and contiguous at its own size, uint8 or fp32.  table: one row
+ * of ORE_BATCH_CANVAS_JOB_INTS int32 words per image (ORE_BCJ_*): the byte offset of the image inside the slab (low, high word; an fp32
+ * image at a multiple of 4), h, w, the float offset of its canvas inside `out` (low, high; a multiple of 4), and the canvas Hc, Wc.
+ * Rows 0 .. n_query - 1 are the query images (canvas Hq x Wq, raw uint8 if query_u8 else raw fp32), rows n_query .. n_query +
+ * n_support - 1 the support crops (Hs x Ws, support_u8); a group may be empty.  pixel_mean / pixel_std: 3 floats each on the device.
+ * Canvas cell (c, y, x) of an image = (float(raw) - mean[c]) / std[c], the subtraction and the correctly rounded division each rounded
+ * on its own, where y < h and x < w, and +0.0f elsewhere; planar NCHW fp32.  Sizes and offsets are read from the table ON THE DEVICE:
+ * only the job counts and the canvas sizes are launch arguments, so a captured launch serves any later contents of slab and table.
+ * Every cell of every canvas a valid row names is written exactly once.  Whatever the table holds, nothing outside [slab, slab +
+ * slab_bytes) is read and nothing outside [out, out + out_floats) is written: a row whose canvas is not the launch's, or does not lie
+ * inside `out`, is skipped; a row whose image does not lie inside the slab or its canvas gives an all-zero canvas.
+ * ORE_EINVAL: slab or out not 16-byte aligned, slab_bytes no multiple of 4, no job or more than 65535, a canvas side outside 1 .. 8192
+ * or a canvas width that is no multiple of 4, out_floats smaller than the canvases. */
+#define ORE_BATCH_CANVAS_JOB_INTS 8
+#define ORE_BCJ_SRC 0     /* byte offset inside the slab: low, high word */
+#define ORE_BCJ_H 2
+#define ORE_BCJ_W 3
+#define ORE_BCJ_DST 4     /* float offset inside out: low, high word */
+#define ORE_BCJ_HC 6
+#define ORE_BCJ_WC 7
+int ore_batch_canvas_fwd(const void* slab, size_t slab_bytes, const int32_t* table, int32_t n_query, int32_t Hq, int32_t Wq,
+                         int32_t query_u8, int32_t n_support, int32_t Hs, int32_t Ws, int32_t support_u8,
+                         const float* pixel_mean, const float* pixel_std, float* out, size_t out_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

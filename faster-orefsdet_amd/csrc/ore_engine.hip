@@ -113,6 +113,13 @@ struct ore_engine {
     float* roi_hp = nullptr; int roi_ksplit = 1;       // K-split partial sums of the second-stage GEMM [roi_ksplit][roi_cap][roi_fc]
     float* det_boxes = nullptr; float* det_scores = nullptr; int64_t* det_src = nullptr; int32_t* det_count = nullptr;
     void* roi_ws = nullptr; size_t roi_ws_bytes = 0;
+    // cascade (ore_engine_set_roi_cascade): stage k >= 1 of CustomCascadeROIHeads -- its composed fc1, predictor and regression weights
+    // (stage 0 is the set above), the boxes handed from stage to stage (ping-pong), the running score sum and the dead-row bytes
+    int roi_stages = 1;
+    float* casc_W[ORE_MAX_CASCADE] = {}; float* casc_b[ORE_MAX_CASCADE] = {}; float* casc_cls_w[ORE_MAX_CASCADE] = {};
+    float* casc_cls_b[ORE_MAX_CASCADE] = {}; float* casc_box_w[ORE_MAX_CASCADE] = {}; float* casc_box_b[ORE_MAX_CASCADE] = {};
+    float casc_reg_w[ORE_MAX_CASCADE][4] = {};
+    float* casc_boxes[2] = {}; float* casc_sum = nullptr; uint8_t* casc_dead = nullptr;
     // detector_postprocess inside the graph (ore_engine_detect_fwd): device {sx, sy, out_w, out_h} per image slot, the postprocessed
     // detections, and a pinned host word the count is copied into behind the graph
     float* post = nullptr; float post_host[4] = {1.f, 1.f, 0.f, 0.f};
@@ -126,6 +133,7 @@ struct ore_engine {
     float* k11s = nullptr, *k13s = nullptr, *k31s = nullptr;   // [slot][3][C], [slot][3][C][3], [slot][3][C][3]
     bool slot_support_set[ORE_MAX_CLASSES][3] = {};
     float* roi_W_slot[ORE_MAX_CLASSES] = {}; float* roi_b_slot[ORE_MAX_CLASSES] = {};   // composed DSA-mix + fc1 of each class
+    float* casc_W_slot[ORE_MAX_CLASSES][ORE_MAX_CASCADE] = {}; float* casc_b_slot[ORE_MAX_CLASSES][ORE_MAX_CASCADE] = {};   // stages >= 1
     char* det_ws_slots = nullptr;                        // detection-tail workspaces of slots 1.. (slot 0 uses det_ws)
     // graph cache (K: class count of an N-way pass, 0 = the single-class / batch passes)
     hipStream_t cap_stream = nullptr;
@@ -603,14 +611,63 @@ int run_detect_classes(ore_engine* e, const Geo& g, hipStream_t st, int K) {
 
 // image b (scratch roi_feat / roi_h / roi_ws is shared: stream order).  class_slot: the N-way pass -- block b = class slot b with that
 // class's composed fc1, detections to det_*#b only (the merge kernel does the postprocess and publishes the count)
+// One stage of the second stage up to the fc1 rows: ROIAlign of `boxes` and the pre-composed GEMM (K-split partial sums or finished rows).
+static int run_roi_rows(ore_engine* e, const Geo& g, hipStream_t st, double* flops, int b, float* roi_W, float* roi_b, const float* out_boxes,
+                        const int32_t* counts);
+
 int run_roi(ore_engine* e, const Geo& g, hipStream_t st, double* flops, int b = 0, bool class_slot = false) {
     const ore_model_cfg& c = e->cfg;
-    float* roi_W = class_slot ? e->roi_W_slot[b] : e->roi_W;
-    float* roi_b = class_slot ? e->roi_b_slot[b] : e->roi_b;
-    const int F = c.fpn_ch;
     const size_t cap = (size_t)3 * c.pre_topk, rcap = (size_t)e->roi_cap;
     float* out_boxes = e->out_boxes + b * cap * 4;
     int32_t* counts = e->counts + b * 4;
+    const int S = e->roi_ksplit, NS = e->roi_stages;
+    const float* h = S > 1 ? e->roi_hp : e->roi_h;
+    *flops = 0.0;
+    // the cascade: stage k pools the boxes stage k - 1 decoded (detached, clipped), with its own composed fc1 and predictor; the
+    // foreground probabilities add up in casc_sum in stage order, the last stage averages them and runs the tail
+    const float* boxes_k = out_boxes;
+    for (int k = 0; k < NS - 1; ++k) {
+        float* W_k = k == 0 ? (class_slot ? e->roi_W_slot[b] : e->roi_W) : (class_slot ? e->casc_W_slot[b][k] : e->casc_W[k]);
+        float* b_k = k == 0 ? (class_slot ? e->roi_b_slot[b] : e->roi_b) : (class_slot ? e->casc_b_slot[b][k] : e->casc_b[k]);
+        double fl = 0.0;
+        int rc = run_roi_rows(e, g, st, &fl, b, W_k, b_k, boxes_k, counts);
+        if (rc) return rc;
+        *flops += fl;
+        float* next = e->casc_boxes[k & 1];
+        rc = ore_roi_cascade_refine_fwd(h, e->roi_fc, S > 1 ? S : 0, S > 1 ? b_k : nullptr, k == 0 ? e->roi_cls_w : e->casc_cls_w[k],
+                                        k == 0 ? e->roi_cls_b : e->casc_cls_b[k], k == 0 ? e->roi_box_w : e->casc_box_w[k],
+                                        k == 0 ? e->roi_box_b : e->casc_box_b[k], boxes_k, counts + 1, 0, e->roi_cap,
+                                        k == 0 ? e->roi_reg_w : e->casc_reg_w[k], (float)g.H, (float)g.W, next, e->casc_sum, e->casc_dead,
+                                        k > 0 ? 1 : 0, st);
+        if (rc) return rc;
+        boxes_k = next;
+    }
+    const int kl = NS - 1;
+    float* roi_W = kl == 0 ? (class_slot ? e->roi_W_slot[b] : e->roi_W) : (class_slot ? e->casc_W_slot[b][kl] : e->casc_W[kl]);
+    float* roi_b = kl == 0 ? (class_slot ? e->roi_b_slot[b] : e->roi_b) : (class_slot ? e->casc_b_slot[b][kl] : e->casc_b[kl]);
+    double fl = 0.0;
+    int rc = run_roi_rows(e, g, st, &fl, b, roi_W, roi_b, boxes_k, counts);
+    if (rc) return rc;
+    *flops += fl;
+    if (kl == 0)
+        return oreroi::roi_predict_post(h, e->roi_fc, S > 1 ? S : 0, S > 1 ? roi_b : nullptr, e->roi_cls_w, e->roi_cls_b,
+                                        e->roi_box_w, e->roi_box_b, out_boxes, counts + 1, 0,
+                                        e->roi_cap, e->roi_reg_w, (float)g.H, (float)g.W, e->roi_score_thresh, e->roi_nms_thresh, e->roi_topk,
+                                        e->det_boxes + b * rcap * 4, e->det_scores + b * rcap, e->det_src + b * rcap, e->det_count + b * 4,
+                                        class_slot ? nullptr : e->post, e->fin_boxes_of(b), e->fin_scores_of(b), e->fin_count + b * 4,
+                                        b == 0 && !class_slot ? e->pin_count_dev : nullptr, e->roi_ws, e->roi_ws_bytes, st);
+    return ore_roi_predict_cascade_fwd(h, e->roi_fc, e->casc_cls_w[kl], e->casc_cls_b[kl], e->casc_box_w[kl], e->casc_box_b[kl], boxes_k,
+                                       counts + 1, 0, e->roi_cap, e->casc_reg_w[kl], (float)g.H, (float)g.W, e->roi_score_thresh,
+                                       e->roi_nms_thresh, e->roi_topk, e->det_boxes + b * rcap * 4, e->det_scores + b * rcap,
+                                       e->det_src + b * rcap, e->det_count + b * 4, class_slot ? nullptr : e->post, e->fin_boxes_of(b),
+                                       e->fin_scores_of(b), e->fin_count + b * 4, b == 0 && !class_slot ? e->pin_count_dev : nullptr,
+                                       e->roi_ws, e->roi_ws_bytes, st, S > 1 ? S : 0, S > 1 ? roi_b : nullptr, e->casc_sum, e->casc_dead, NS);
+}
+
+static int run_roi_rows(ore_engine* e, const Geo& g, hipStream_t st, double* flops, int b, float* roi_W, float* roi_b, const float* out_boxes,
+                        const int32_t* counts) {
+    const ore_model_cfg& c = e->cfg;
+    const int F = c.fpn_ch;
     const float* feat[3]; int ld[3], coff[3], H[3], W[3]; float sc[3];
     for (int l = 0; l < 3; ++l) {
         feat[l] = e->at(e->pcat.p, ((size_t)lvl_row0(g, l) + (size_t)b * g.h[l + 3] * g.w[l + 3]) * 2 * F); ld[l] = 2 * F; coff[l] = F;
@@ -644,12 +701,7 @@ int run_roi(ore_engine* e, const Geo& g, hipStream_t st, double* flops, int b = 
         if (r.rc) return r.rc;
         *flops = r.flops;
     }
-    return oreroi::roi_predict_post(S > 1 ? e->roi_hp : e->roi_h, e->roi_fc, S > 1 ? S : 0, S > 1 ? roi_b : nullptr, e->roi_cls_w, e->roi_cls_b,
-                                    e->roi_box_w, e->roi_box_b, out_boxes, counts + 1, 0,
-                                    e->roi_cap, e->roi_reg_w, (float)g.H, (float)g.W, e->roi_score_thresh, e->roi_nms_thresh, e->roi_topk,
-                                    e->det_boxes + b * rcap * 4, e->det_scores + b * rcap, e->det_src + b * rcap, e->det_count + b * 4,
-                                    class_slot ? nullptr : e->post, e->fin_boxes_of(b), e->fin_scores_of(b), e->fin_count + b * 4,
-                                    b == 0 && !class_slot ? e->pin_count_dev : nullptr, e->roi_ws, e->roi_ws_bytes, st);
+    return ORE_OK;
 }
 
 }  // namespace
@@ -709,8 +761,51 @@ extern "C" int ore_engine_set_roi_head(ore_engine* e, const float* W_host, const
     e->roi_fc = fc_dim; e->roi_pooled = pooled; e->roi_topk = topk; e->roi_score_thresh = score_thresh; e->roi_nms_thresh = nms_thresh;
     for (int i = 0; i < 4; ++i) e->roi_reg_w[i] = reg_weights4_host[i];
     e->roi_set = true;
+    e->roi_stages = 1;
     for (auto& gk : e->graphs) (void)hipGraphExecDestroy(gk.exec);   // captured graphs did not contain the second stage
     e->graphs.clear();
+    ORE_HIP(hipDeviceSynchronize());
+    return ORE_OK;
+}
+
+extern "C" int ore_engine_set_roi_cascade(ore_engine* e, int32_t n_stages, const float* const* W_host, const float* const* b_host,
+                                          int32_t fc_dim, int32_t pooled, const float* const* cls_w_host, const float* const* cls_b_host,
+                                          const float* const* box_w_host, const float* const* box_b_host, const float* reg_weights4_host,
+                                          float score_thresh, float nms_thresh, int32_t topk) {
+    ORE_CHECK_ARG(e && W_host && b_host && cls_w_host && cls_b_host && box_w_host && box_b_host && reg_weights4_host,
+                  "ore_engine_set_roi_cascade: null pointer");
+    ORE_CHECK_ARG(n_stages >= 1 && n_stages <= ORE_MAX_CASCADE, "ore_engine_set_roi_cascade: %d cascade stages: the engine runs 1 .. %d", n_stages,
+                  ORE_MAX_CASCADE);
+    for (int k = 0; k < n_stages; ++k)
+        ORE_CHECK_ARG(W_host[k] && b_host[k] && cls_w_host[k] && cls_b_host[k] && box_w_host[k] && box_b_host[k],
+                      "ore_engine_set_roi_cascade: stage %d of %d: null pointer", k, n_stages);
+    // stage 0 is the single-stage head: same buffers, same launches (n_stages = 1 is ore_engine_set_roi_head)
+    int rc = ore_engine_set_roi_head(e, W_host[0], b_host[0], fc_dim, pooled, cls_w_host[0], cls_b_host[0], box_w_host[0], box_b_host[0],
+                                     reg_weights4_host, score_thresh, nms_thresh, topk);
+    if (rc || n_stages == 1) return rc;
+    const size_t K = (size_t)pooled * pooled * e->cfg.fpn_ch, cap = (size_t)e->roi_cap;
+    auto up = [&](float** dst, const float* src, size_t n) -> int {
+        if (!*dst && (rc = e->dalloc(dst, n))) return rc;
+        ORE_HIP(hipMemcpy(*dst, src, n * sizeof(float), hipMemcpyHostToDevice));
+        return ORE_OK;
+    };
+    for (int k = 1; k < n_stages; ++k) {
+        if ((rc = up(&e->casc_W[k], W_host[k], (size_t)fc_dim * K)) || (rc = up(&e->casc_b[k], b_host[k], fc_dim)) ||
+            (rc = up(&e->casc_cls_w[k], cls_w_host[k], 2 * (size_t)fc_dim)) || (rc = up(&e->casc_cls_b[k], cls_b_host[k], 2)) ||
+            (rc = up(&e->casc_box_w[k], box_w_host[k], 4 * (size_t)fc_dim)) || (rc = up(&e->casc_box_b[k], box_b_host[k], 4)))
+            return rc;
+        for (int i = 0; i < 4; ++i) e->casc_reg_w[k][i] = reg_weights4_host[4 * k + i];
+    }
+    if (!e->casc_sum) {
+        if ((rc = e->dalloc(&e->casc_boxes[0], cap * 4)) || (rc = e->dalloc(&e->casc_boxes[1], cap * 4)) || (rc = e->dalloc(&e->casc_sum, cap)) ||
+            (rc = e->dalloc(&e->casc_dead, cap)))
+            return rc;
+        ORE_HIP(hipMemset(e->casc_boxes[0], 0, cap * 16));
+        ORE_HIP(hipMemset(e->casc_boxes[1], 0, cap * 16));
+        ORE_HIP(hipMemset(e->casc_sum, 0, cap * 4));
+        ORE_HIP(hipMemset(e->casc_dead, 0, cap));
+    }
+    e->roi_stages = n_stages;
     ORE_HIP(hipDeviceSynchronize());
     return ORE_OK;
 }
@@ -1151,6 +1246,9 @@ static int eval_classes(ore_engine* e, const void* img, int32_t is_u8, int32_t H
         for (int l = 0; l < 3; ++l)
             ORE_CHECK_ARG(e->slot_support_set[k][l], "N-way pass: class slot %d has no support prototype for level %d (ore_engine_set_support_slot)", k, l + 3);
         ORE_CHECK_ARG(!e->roi_set || e->roi_W_slot[k], "N-way pass: class slot %d has no second-stage support (ore_engine_set_roi_support_slot)", k);
+        for (int sk = 1; sk < e->roi_stages && e->roi_set; ++sk)
+            ORE_CHECK_ARG(e->casc_W_slot[k][sk], "N-way pass: class slot %d has no second-stage support for stage %d of the %d cascade stages "
+                          "(ore_engine_set_roi_support_slot_stage)", k, sk, e->roi_stages);
     }
     int rc = check_geo(e, K, H, W);
     if (rc) return rc;
@@ -1266,6 +1364,24 @@ extern "C" int ore_engine_set_roi_support_slot(ore_engine* e, int32_t slot, cons
     if (!e->roi_W_slot[slot] && ((rc = e->dalloc(&e->roi_W_slot[slot], fc * K)) || (rc = e->dalloc(&e->roi_b_slot[slot], fc)))) return rc;
     ORE_HIP(hipMemcpy(e->roi_W_slot[slot], W_host, fc * K * sizeof(float), hipMemcpyHostToDevice));
     ORE_HIP(hipMemcpy(e->roi_b_slot[slot], b_host, fc * sizeof(float), hipMemcpyHostToDevice));
+    drop_class_graphs(e);
+    return ORE_OK;
+}
+
+extern "C" int ore_engine_set_roi_support_slot_stage(ore_engine* e, int32_t slot, int32_t stage, const float* W_host, const float* b_host) {
+    if (stage == 0) return ore_engine_set_roi_support_slot(e, slot, W_host, b_host);
+    ORE_CHECK_ARG(e && e->roi_set && e->k11s && W_host && b_host,
+                  "ore_engine_set_roi_support_slot_stage: needs ore_engine_set_roi_cascade and ore_engine_set_classes (n >= 1) first, pointers non-null");
+    ORE_CHECK_ARG(slot >= 0 && slot < e->n_slots, "ore_engine_set_roi_support_slot_stage: slot %d outside [0, %d)", slot, e->n_slots);
+    ORE_CHECK_ARG(stage > 0 && stage < e->roi_stages, "ore_engine_set_roi_support_slot_stage: stage %d outside the engine's %d cascade stages", stage,
+                  e->roi_stages);
+    ORE_HIP(hipSetDevice(e->device));
+    const size_t K = (size_t)e->roi_pooled * e->roi_pooled * e->cfg.fpn_ch, fc = (size_t)e->roi_fc;
+    int rc;
+    if (!e->casc_W_slot[slot][stage] && ((rc = e->dalloc(&e->casc_W_slot[slot][stage], fc * K)) || (rc = e->dalloc(&e->casc_b_slot[slot][stage], fc))))
+        return rc;
+    ORE_HIP(hipMemcpy(e->casc_W_slot[slot][stage], W_host, fc * K * sizeof(float), hipMemcpyHostToDevice));
+    ORE_HIP(hipMemcpy(e->casc_b_slot[slot][stage], b_host, fc * sizeof(float), hipMemcpyHostToDevice));
     drop_class_graphs(e);
     return ORE_OK;
 }

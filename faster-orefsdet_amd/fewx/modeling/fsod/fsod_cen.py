@@ -382,8 +382,13 @@ class CenterNet2Detector(nn.Module):
         e.finalize()
         rh = self.roi_heads
         if "rcnn_8" in self.support_dict and hasattr(rh, "bbox_reg_weights"):
-            e.set_roi_head(self.state_dict(), self.support_dict["rcnn_8"][cls_id], rh.bbox_reg_weights, rh.test_score_thresh,
-                           rh.test_nms_thresh, rh.test_topk)
+            stages = getattr(rh, "bbox_reg_weights_per_stage", (rh.bbox_reg_weights,))
+            if len(stages) > 1:                       # the cascade: len(ROI_BOX_CASCADE_HEAD.IOUS) stages inside the engine's graph
+                e.set_roi_cascade(self.state_dict(), self.support_dict["rcnn_8"][cls_id], stages, rh.test_score_thresh,
+                                  rh.test_nms_thresh, rh.test_topk)
+            else:
+                e.set_roi_head(self.state_dict(), self.support_dict["rcnn_8"][cls_id], rh.bbox_reg_weights, rh.test_score_thresh,
+                               rh.test_nms_thresh, rh.test_topk)
         if classes:
             sd = self.state_dict()
             e.set_classes(classes)

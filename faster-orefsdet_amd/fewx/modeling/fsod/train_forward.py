@@ -214,39 +214,109 @@ def label_and_sample(rh, proposals: torch.Tensor, gt_boxes: torch.Tensor, perm: 
     return sampled, boxes[sampled].contiguous(), labels[sampled], roi_gt
 
 
+class _ScaleGradient(torch.autograd.Function):
+    """Identity whose gradient is scaled (d2z:modeling/roi_heads/cascade_rcnn.py:20-28): 1/K on every stage's pooled query features."""
+
+    @staticmethod
+    def forward(ctx, x, scale):
+        ctx.scale = scale
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g * ctx.scale, None
+
+
+def _cascade_stages(rh) -> int:
+    return len(rh.box_head)
+
+
+def _stage_weights(rh, k: int):
+    return rh.bbox_reg_weights_per_stage[k] if hasattr(rh, "bbox_reg_weights_per_stage") else rh.bbox_reg_weights
+
+
+@torch.no_grad()
+def cascade_relabel_rows(rh, k: int, boxes, deltas, gt_boxes, image_hw):
+    """The seam in front of stage k >= 1 for the rows of ONE image, as the reference's training does it (cascade_rcnn.py:231-307):
+    decode with stage k - 1's weights, clip, DROP the empty rows, match against the ground truth at IOUS[k] -- one launch of
+    ore_cascade_relabel_fwd and the compaction of its valid rows.  Returns (boxes, labels, matched gt, kept row indices)."""
+    import orehip
+    dev = boxes.device
+    R = boxes.shape[0]
+    G = int(gt_boxes.shape[0])
+    hw = orehip.to_device(torch.tensor([[float(image_hw[0]), float(image_hw[1])]]), dev)
+    gtp = gt_boxes.float().reshape(1, G, 4).contiguous()
+    gt_n = orehip.to_device(torch.tensor([G], dtype=torch.int64), dev)
+    b2, l2, g2, v2 = orehip.cascade_relabel(boxes.detach().float().reshape(1, R, 4).contiguous(), deltas.detach().reshape(1, R, 4).contiguous(),
+                                            torch.ones(1, R, dtype=torch.bool, device=dev), hw, gtp, gt_n, _stage_weights(rh, k - 1),
+                                            float(rh.iou_thresholds[k]))
+    keep = torch.nonzero(v2[0]).squeeze(1)
+    return b2[0][keep].contiguous(), l2[0][keep], g2[0][keep], keep
+
+
 def roi_stage_losses(rh, qf: List[torch.Tensor], sup8: torch.Tensor, roi_boxes, roi_labels, roi_gt, strides,
-                     roi_image: Optional[torch.Tensor] = None, rois_per_image: Optional[List[int]] = None):
-    """_run_stage + CustomFastRCNNOutputLayers.losses for the single cascade stage (ref:fewx/modeling/fsod/fsod_roi_heads.py:459-520,
+                     roi_image: Optional[torch.Tensor] = None, rois_per_image: Optional[List[int]] = None, gt_boxes=None, image_hw=None):
+    """_run_stage + CustomFastRCNNOutputLayers.losses for every cascade stage (ref:fewx/modeling/fsod/fsod_roi_heads.py:404-520,
     custom_fast_rcnn.py:52-81).  One image: qf[l] [H,W,C] query pyramid (NHWC), sup8 [N, P*P*C] pooled support features ordered
     [pos][c].  B images in one pass: qf[l] [B,H,W,C], sup8 [B,N,P*P*C], the ROIs of all images concatenated with roi_image [R]
     (int32 image of each ROI) and rois_per_image (host ints); each image's losses keep their own 1/R_b normaliser and the result is
-    the mean over the images."""
+    the mean over the images.  K = len(IOUS) > 1 stages: gt_boxes ([G,4], or a list of B of them) and image_hw ((h, w), or a list of B)
+    feed the seam between the stages (cascade_relabel_rows: rows whose refined box clips to nothing are dropped, as the reference
+    does); the result holds loss_cls_stage{k} / loss_box_reg_stage{k} of every stage, each normalised by its own row count, and the
+    aux dict the LAST stage's tensors plus `stages`: per stage (boxes, labels, matched gt)."""
+    K = _cascade_stages(rh)
+    assert K == 1 or (gt_boxes is not None and image_hw is not None), f"{K} cascade stages: roi_stage_losses needs gt_boxes and image_hw"
+    losses, stages, aux = {}, [], None
+    for k in range(K):
+        if k > 0:
+            d = aux["deltas"]
+            if roi_image is None:
+                roi_boxes, roi_labels, roi_gt, _ = cascade_relabel_rows(rh, k, roi_boxes, d, gt_boxes, image_hw)
+            else:
+                per, o = [], 0
+                for b, n in enumerate(rois_per_image):
+                    per.append(cascade_relabel_rows(rh, k, roi_boxes[o:o + n], d[o:o + n], gt_boxes[b], image_hw[b]))
+                    o += n
+                roi_boxes, roi_labels, roi_gt = (torch.cat([p[i] for p in per], 0) for i in range(3))
+                rois_per_image = [int(p[0].shape[0]) for p in per]
+                roi_image = torch.cat([torch.full((n,), b, dtype=torch.int32, device=roi_boxes.device) for b, n in enumerate(rois_per_image)])
+        l_k, aux = _roi_stage_losses_one(rh, k, qf, sup8, roi_boxes, roi_labels, roi_gt, strides, roi_image, rois_per_image)
+        losses.update(l_k)
+        stages.append((roi_boxes, roi_labels, roi_gt))
+    aux["stages"] = stages
+    return losses, aux
+
+
+def _roi_stage_losses_one(rh, k, qf, sup8, roi_boxes, roi_labels, roi_gt, strides, roi_image, rois_per_image):
+    """Stage k of roi_stage_losses on its own rows."""
     from orehip import autograd as A
     R = roi_boxes.shape[0]
     C = qf[0].shape[-1]
     P = rh.pooler_resolution
+    K = _cascade_stages(rh)
+    sg = (lambda t: _ScaleGradient.apply(t, 1.0 / K)) if K > 1 else (lambda t: t)
     if roi_image is None:
-        x = A.roi_align(qf, roi_boxes, strides, P).reshape(R * P * P, C)                # rows ordered [roi][pos], channels last
+        x = sg(A.roi_align(qf, roi_boxes, strides, P)).reshape(R * P * P, C)            # rows ordered [roi][pos], channels last
         s = sup8.mean(0, True).reshape(P * P, C)
         s_exp = s.unsqueeze(0).expand(R, P * P, C).reshape(R * P * P, C)
         s2_exp = A.linear(s, rh.conv2.weight.flatten(1), rh.conv2.bias).unsqueeze(0).expand(R, P * P, C // 2).reshape(R * P * P, C // 2)
     else:
         B = sup8.shape[0]
         img = roi_image.long()
-        x = A.roi_align_batched(qf, roi_boxes, roi_image, strides, P).reshape(R * P * P, C)
+        x = sg(A.roi_align_batched(qf, roi_boxes, roi_image, strides, P)).reshape(R * P * P, C)
         s = sup8.mean(1).reshape(B * P * P, C)                                          # each image's own support prototype
         s_exp = s.reshape(B, P * P, C)[img].reshape(R * P * P, C)
         s2_exp = A.linear(s, rh.conv2.weight.flatten(1), rh.conv2.bias).reshape(B, P * P, C // 2)[img].reshape(R * P * P, C // 2)
     a = A.linear(torch.cat((x, s_exp), 1), rh.conv3.weight.flatten(1), rh.conv3.bias) + \
         torch.cat((A.linear(x, rh.conv1.weight.flatten(1), rh.conv1.bias), s2_exp), 1)
     a = a.reshape(R, P * P, C).permute(0, 2, 1).reshape(R, C * P * P)                   # NCHW flatten order of fc1's weight
-    fc1 = rh.box_head[0].fc1
+    fc1 = rh.box_head[k].fc1
     h = A.linear(a.contiguous(), fc1.weight, fc1.bias, True)
-    pr = rh.box_predictor[0]
+    pr = rh.box_predictor[k]
     scores = A.linear(h, pr.cls_score.weight, pr.cls_score.bias)
     deltas = A.linear(h, pr.bbox_pred.weight, pr.bbox_pred.bias)
     fg = torch.nonzero(roi_labels == 0).squeeze(1)
-    tgt = get_deltas(roi_boxes[fg], roi_gt[fg], rh.bbox_reg_weights)
+    tgt = get_deltas(roi_boxes[fg], roi_gt[fg], _stage_weights(rh, k))
     if roi_image is None:
         loss_cls = F.cross_entropy(scores, roi_labels, reduction="mean")
         loss_box = (deltas[fg] - tgt).abs().sum() / max(roi_labels.numel(), 1)           # smooth_l1, beta = 0
@@ -254,7 +324,7 @@ def roi_stage_losses(rh, qf: List[torch.Tensor], sup8: torch.Tensor, roi_boxes, 
         w = torch.tensor([1.0 / (max(n, 1) * len(rois_per_image)) for n in rois_per_image], device=scores.device)[img]
         loss_cls = (F.cross_entropy(scores, roi_labels, reduction="none") * w).sum()
         loss_box = ((deltas[fg] - tgt).abs().sum(1) * w[fg]).sum()
-    return {"loss_cls_stage0": loss_cls, "loss_box_reg_stage0": loss_box}, dict(scores=scores, deltas=deltas, h=h)
+    return {f"loss_cls_stage{k}": loss_cls, f"loss_box_reg_stage{k}": loss_box}, dict(scores=scores, deltas=deltas, h=h)
 
 
 def first_stage_batch(pg, heads: List[torch.Tensor], gts: Optional[List[torch.Tensor]], norm_avg: Optional[torch.Tensor] = None,
@@ -367,14 +437,38 @@ def _roi_image(B: int, R: int, dev) -> torch.Tensor:
     return _ROI_IMAGE[key]
 
 
-def roi_stage_losses_padded(rh, qf: List[torch.Tensor], sup8: torch.Tensor, boxes, labels, gt, valid, strides):
-    """_run_stage + CustomFastRCNNOutputLayers.losses for the single cascade stage (ref:fewx/modeling/fsod/fsod_roi_heads.py:459-520,
+def roi_stage_losses_padded(rh, qf: List[torch.Tensor], sup8: torch.Tensor, boxes, labels, gt, valid, strides, gtp=None, gt_n=None,
+                            img_hw=None):
+    """_run_stage + CustomFastRCNNOutputLayers.losses for every cascade stage (ref:fewx/modeling/fsod/fsod_roi_heads.py:404-520,
     custom_fast_rcnn.py:52-81) for B images in ONE pass, fixed shapes, no host sync: qf[l] [B,H,W,C] query pyramid (NHWC), sup8
     [B,N,P*P*C] pooled support features, boxes / gt [B,R,4], labels [B,R] (0 fg / 1 bg), valid [B,R].  Every image's losses keep their
     own 1/R_b normaliser (R_b = its valid rows) and the result is the mean over the images (= the gradient-averaged data-parallel
-    result of B single-image ranks)."""
+    result of B single-image ranks).  K = len(IOUS) > 1 stages: gtp [B,G,4] / gt_n [B] int64 / img_hw [B,2] fp32 (h, w), all on the
+    device, feed ONE launch of ore_cascade_relabel_fwd between two stages; a row whose refined box clips to nothing turns into a
+    padding row (valid 0) where the eager form drops it, so each stage's normaliser is its own count of valid rows."""
+    import orehip
+    K = _cascade_stages(rh)
+    assert K == 1 or (gtp is not None and gt_n is not None and img_hw is not None), \
+        f"{K} cascade stages: roi_stage_losses_padded needs gtp, gt_n and img_hw"
+    losses, stages, aux = {}, [], None
+    for k in range(K):
+        if k > 0:
+            with torch.no_grad():
+                B, R = labels.shape
+                boxes, labels, gt, valid = orehip.cascade_relabel(boxes.contiguous(), aux["deltas"].detach().reshape(B, R, 4).contiguous(), valid, img_hw,
+                                                                  gtp, gt_n, _stage_weights(rh, k - 1), float(rh.iou_thresholds[k]))
+        l_k, aux = _roi_stage_losses_padded_one(rh, k, qf, sup8, boxes, labels, gt, valid, strides)
+        losses.update(l_k)
+        stages.append((boxes, labels, gt, valid))
+    aux["stages"] = stages
+    return losses, aux
+
+
+def _roi_stage_losses_padded_one(rh, k, qf, sup8, boxes, labels, gt, valid, strides):
+    """Stage k of roi_stage_losses_padded on its own rows."""
     from orehip import autograd as A
     B, R = labels.shape
+    K = _cascade_stages(rh)
     C = qf[0].shape[-1]
     P = rh.pooler_resolution
     dev = boxes.device
@@ -382,7 +476,10 @@ def roi_stage_losses_padded(rh, qf: List[torch.Tensor], sup8: torch.Tensor, boxe
     img = rimg.long()
     RT = B * R
     bx, lb, gtf, vf = boxes.reshape(RT, 4), labels.reshape(RT), gt.reshape(RT, 4), valid.reshape(RT)
-    x = A.roi_align_batched(qf, bx, rimg, strides, P).reshape(RT * P * P, C)            # rows ordered [roi][pos], channels last
+    x = A.roi_align_batched(qf, bx, rimg, strides, P)                                   # rows ordered [roi][pos], channels last
+    if K > 1:
+        x = _ScaleGradient.apply(x, 1.0 / K)
+    x = x.reshape(RT * P * P, C)
     s = sup8.mean(1).reshape(B * P * P, C)                                              # each image's own support prototype
     # the ROIs of image b are rows b*R .. (b+1)*R: broadcasting its prototype is an expand (backward = one sum over R), not a gather
     s_exp = s.reshape(B, 1, P * P, C).expand(B, R, P * P, C).reshape(RT * P * P, C)
@@ -391,17 +488,17 @@ def roi_stage_losses_padded(rh, qf: List[torch.Tensor], sup8: torch.Tensor, boxe
     a = A.linear(torch.cat((x, s_exp), 1), rh.conv3.weight.flatten(1), rh.conv3.bias) + \
         torch.cat((A.linear(x, rh.conv1.weight.flatten(1), rh.conv1.bias), s2_exp), 1)
     # fc1 reads the NCHW flatten [c][pos] of the reference; the rows here are [pos][c]: permute the 4 MB weight, not the activations
-    fc1 = rh.box_head[0].fc1
+    fc1 = rh.box_head[k].fc1
     w1 = fc1.weight.reshape(fc1.weight.shape[0], C, P * P).permute(0, 2, 1).reshape(fc1.weight.shape[0], P * P * C)
     h = A.linear(a.reshape(RT, P * P * C), w1, fc1.bias, True)
-    pr = rh.box_predictor[0]
+    pr = rh.box_predictor[k]
     scores = A.linear(h, pr.cls_score.weight, pr.cls_score.bias)
     deltas = A.linear(h, pr.bbox_pred.weight, pr.bbox_pred.bias)
     # both losses and their gradients from ONE launch (ore_roi_losses_fwd): w_i = valid_i / (n_b * B), n_b = an image's valid rows;
     # cross-entropy over the two classes; |deltas - get_deltas(box, gt)| on the foreground rows (smooth_l1 with beta = 0; background and
     # padding rows have no target) -- what ~50 element-wise launches and ~40 more in their backward computed
-    loss_cls, loss_box = A.roi_losses(scores, deltas, bx, gtf, lb, vf, B, R, rh.bbox_reg_weights)
-    return {"loss_cls_stage0": loss_cls, "loss_box_reg_stage0": loss_box}, dict(scores=scores, deltas=deltas, h=h)
+    loss_cls, loss_box = A.roi_losses(scores, deltas, bx, gtf, lb, vf, B, R, _stage_weights(rh, k))
+    return {f"loss_cls_stage{k}": loss_cls, f"loss_box_reg_stage{k}": loss_box}, dict(scores=scores, deltas=deltas, h=h)
 
 
 def _pad_stack(ts: List[torch.Tensor], width: int, dev):
@@ -547,7 +644,24 @@ def train_core(model, st: Dict, perm=None, return_aux: bool = False, roi_overrid
         boxes, labels, roi_gt, valid = sample_rois_device(rh, prop, prop_n, gtp, gt_n)
     # ---- second stage of all B images in one pass: support rcnn_8 features (one box per support crop), DSA mix, fc1, predictor, losses
     sup8 = A.roi_align_batched(sf_levels, sbx, _roi_image(B * N, 1, dev), pg.strides, rh.pooler_resolution)
-    l_roi, a2 = roi_stage_losses_padded(rh, qf, sup8.reshape(B, N, -1), boxes, labels, roi_gt, valid, pg.strides)
+    img_hw = None
+    if _cascade_stages(rh) > 1:
+        # the size every image's refined boxes are clipped to between the stages, [B,2] (h, w) on the device without a host copy
+        if static and st.get("canvas_geom") is not None:
+            tab = st["canvas_buf"][:B * orehip.BATCH_CANVAS_JOB_INTS * 4].view(torch.int32).view(B, orehip.BATCH_CANVAS_JOB_INTS)
+            img_hw = torch.stack((tab[:, orehip._BCJ_H], tab[:, orehip._BCJ_W]), 1).float().contiguous()
+        else:
+            sizes = [tuple(st["xq"].shape[-2:])] * B if static else [tuple(i.shape[-2:]) for i in st["imgs"]]
+            img_hw = torch.empty(B, 2, device=dev)
+            if all(s_ == sizes[0] for s_ in sizes):
+                img_hw[:, 0].fill_(float(sizes[0][0]))
+                img_hw[:, 1].fill_(float(sizes[0][1]))
+            else:
+                for b, (h_, w_) in enumerate(sizes):
+                    img_hw[b, 0].fill_(float(h_))
+                    img_hw[b, 1].fill_(float(w_))
+    l_roi, a2 = roi_stage_losses_padded(rh, qf, sup8.reshape(B, N, -1), boxes, labels, roi_gt, valid, pg.strides, gtp=gtp, gt_n=gt_n,
+                                        img_hw=img_hw)
     losses = {**l_roi, **l_rpn}
     if return_aux:                                           # (host syncs from here on: only for callers that ask)
         nv = valid.sum(1).tolist()

@@ -884,12 +884,17 @@ def roi_align_bwd(dout: torch.Tensor, feats_like: Sequence[torch.Tensor], boxes:
 
 def roi_predict(h: torch.Tensor, cls_w, cls_b, box_w, box_b, boxes: torch.Tensor, reg_weights, image_hw, score_thresh: float,
                 nms_thresh: float, topk: int, n_dev: Optional[torch.Tensor] = None, parts: int = 0, bias: Optional[torch.Tensor] = None,
-                post: Optional[torch.Tensor] = None, pin: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                post: Optional[torch.Tensor] = None, pin: Optional[torch.Tensor] = None, score_sum: Optional[torch.Tensor] = None,
+                dead: Optional[torch.Tensor] = None, n_stages: int = 1) -> Dict[str, torch.Tensor]:
     """h [cap, C] fc1 rows, or with parts >= 1 the K-split partial sums [parts, cap, C] (bias [C] or None) that the engine's second
     stage hands over (ore_roi_predict_parts_fwd).  post: device {sx, sy, out_w, out_h} -> detector_postprocess in the same launch,
     returned as "fin_boxes" / "fin_scores" / "fin_count".  pin: device int32 tensor of >= 4 words: word 0 receives the final count,
-    words 2..3 hold the 64-bit device address of a record tensor (boxes | scores | int64 classes, see the header) or 0."""
+    words 2..3 hold the 64-bit device address of a record tensor (boxes | scores | int64 classes, see the header) or 0.
+    n_stages > 1: the last stage of a cascade (ore_roi_predict_cascade_fwd) with score_sum [cap] fp32 / dead [cap] uint8 of
+    roi_cascade_refine; the candidate score is (score_sum + s) * float32(1 / n_stages)."""
     cap, Cc = h.shape[-2:]
+    if n_stages > 1 and (score_sum is None or dead is None or score_sum.numel() < cap or dead.numel() < cap or dead.dtype != torch.uint8):
+        raise OreError(f"roi_predict: {n_stages} cascade stages need score_sum [cap] fp32 and dead [cap] uint8 of the stages before the last")
     if h.dim() != (3 if parts >= 1 else 2) or (parts >= 1 and h.shape[0] != parts):
         raise OreError(f"roi_predict: h {tuple(h.shape)} with parts={parts}")
     if pin is not None and (pin.dtype != torch.int32 or pin.numel() < 4):
@@ -905,14 +910,68 @@ def roi_predict(h: torch.Tensor, cls_w, cls_b, box_w, box_b, boxes: torch.Tensor
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
     rw = (C.c_float * 4)(*reg_weights)
     b = boxes.float().contiguous() if n else torch.zeros(1, 4, device=dev)
-    _chk(lib().ore_roi_predict_parts_fwd(_ptr(_f32(h)), Cc, _ptr(_f32(cls_w)), _ptr(_f32(cls_b)), _ptr(_f32(box_w)), _ptr(_f32(box_b)), _ptr(b),
-                                         _ptr(n_dev), n, cap, rw, image_hw[0], image_hw[1], score_thresh, nms_thresh, topk, _ptr(o["boxes"]),
-                                         _ptr(o["scores"]), _ptr(o["src"]), _ptr(o["count"]), _ptr(_f32(post)) if post is not None else None,
-                                         _ptr(o.get("fin_boxes")), _ptr(o.get("fin_scores")), _ptr(o.get("fin_count")), _ptr(pin),
-                                         _ptr(ws), wsb, _stream(), parts, _ptr(_f32(bias)) if bias is not None else None),
-         "ore_roi_predict_parts_fwd")
+    args = (_ptr(_f32(h)), Cc, _ptr(_f32(cls_w)), _ptr(_f32(cls_b)), _ptr(_f32(box_w)), _ptr(_f32(box_b)), _ptr(b),
+            _ptr(n_dev), n, cap, rw, image_hw[0], image_hw[1], score_thresh, nms_thresh, topk, _ptr(o["boxes"]),
+            _ptr(o["scores"]), _ptr(o["src"]), _ptr(o["count"]), _ptr(_f32(post)) if post is not None else None,
+            _ptr(o.get("fin_boxes")), _ptr(o.get("fin_scores")), _ptr(o.get("fin_count")), _ptr(pin),
+            _ptr(ws), wsb, _stream(), parts, _ptr(_f32(bias)) if bias is not None else None)
+    if n_stages == 1 and score_sum is None and dead is None:
+        _chk(lib().ore_roi_predict_parts_fwd(*args), "ore_roi_predict_parts_fwd")
+    else:
+        _chk(lib().ore_roi_predict_cascade_fwd(*args, _ptr(_f32(score_sum)) if score_sum is not None else None, _ptr(dead), int(n_stages)),
+             "ore_roi_predict_cascade_fwd")
     o["_ws"] = ws
     return o
+
+
+def roi_cascade_refine(h: torch.Tensor, cls_w, cls_b, box_w, box_b, boxes: torch.Tensor, reg_weights, image_hw,
+                       n_dev: Optional[torch.Tensor] = None, parts: int = 0, bias: Optional[torch.Tensor] = None,
+                       score_sum: Optional[torch.Tensor] = None, dead: Optional[torch.Tensor] = None):
+    """One intermediate cascade stage (ore_roi_cascade_refine_fwd): h as roi_predict takes it, boxes [n,4] the stage's proposals.
+    score_sum / dead None: the first stage (both are created and written); given: added into / kept sticky.
+    Returns (next boxes [n,4], score_sum [cap], dead [cap] uint8)."""
+    cap, Cc = h.shape[-2:]
+    if h.dim() != (3 if parts >= 1 else 2) or (parts >= 1 and h.shape[0] != parts):
+        raise OreError(f"roi_cascade_refine: h {tuple(h.shape)} with parts={parts}")
+    if (score_sum is None) != (dead is None):
+        raise OreError("roi_cascade_refine: score_sum and dead come together")
+    n = boxes.shape[0]
+    dev = h.device
+    acc = 0 if score_sum is None else 1
+    if score_sum is None:
+        score_sum = torch.zeros(cap, device=dev)
+        dead = torch.zeros(cap, dtype=torch.uint8, device=dev)
+    if score_sum.numel() < cap or dead.numel() < cap or dead.dtype != torch.uint8:
+        raise OreError("roi_cascade_refine: score_sum [cap] fp32 and dead [cap] uint8")
+    nxt = torch.zeros(cap, 4, device=dev)
+    rw = (C.c_float * 4)(*reg_weights)
+    b = boxes.float().contiguous() if n else torch.zeros(1, 4, device=dev)
+    _chk(lib().ore_roi_cascade_refine_fwd(_ptr(_f32(h)), Cc, parts, _ptr(_f32(bias)) if bias is not None else None, _ptr(_f32(cls_w)),
+                                          _ptr(_f32(cls_b)), _ptr(_f32(box_w)), _ptr(_f32(box_b)), _ptr(b), _ptr(n_dev), n, cap, rw,
+                                          image_hw[0], image_hw[1], _ptr(nxt), _ptr(_f32(score_sum)), _ptr(dead), acc, _stream()),
+         "ore_roi_cascade_refine_fwd")
+    return nxt[:n] if n_dev is None else nxt, score_sum, dead
+
+
+def cascade_relabel(boxes: torch.Tensor, deltas: torch.Tensor, valid: torch.Tensor, img_hw: torch.Tensor, gtp: torch.Tensor,
+                    gt_n: torch.Tensor, reg_weights, iou_thr: float):
+    """The training seam between two cascade stages for B images x R rows in one launch (ore_cascade_relabel_fwd): boxes / deltas [B,R,4]
+    of the producing stage, valid [B,R] bool, img_hw [B,2] fp32 (h, w) on the device, gtp [B,G,4] + gt_n [B] int64, reg_weights of the
+    producing stage, iou_thr of the consuming one -> (boxes' [B,R,4], labels [B,R] int64 (0 fg / 1 bg), matched gt [B,R,4], valid' [B,R])."""
+    B, R, _ = boxes.shape
+    G = gtp.shape[1]
+    dev = boxes.device
+    assert deltas.shape == (B, R, 4) and valid.shape == (B, R) and valid.dtype == torch.bool and img_hw.shape == (B, 2)
+    assert gt_n.dtype == torch.int64 and gt_n.numel() == B and gtp.dim() == 3 and gtp.shape[0] == B
+    ob = torch.empty(B, R, 4, device=dev, dtype=torch.float32)
+    og = torch.empty(B, R, 4, device=dev, dtype=torch.float32)
+    ol = torch.empty(B, R, device=dev, dtype=torch.int64)
+    ov = torch.empty(B, R, device=dev, dtype=torch.bool)
+    rw = (C.c_float * 4)(*[float(v) for v in reg_weights])
+    _chk(lib().ore_cascade_relabel_fwd(_ptr(_f32(boxes)), _ptr(_f32(deltas)), _ptr(valid.contiguous()), _ptr(_f32(img_hw)),
+                                       _ptr(_f32(gtp)) if G else None, _ptr(gt_n), B, R, G, rw, float(iou_thr), _ptr(ob), _ptr(ov), _ptr(ol),
+                                       _ptr(og), _stream()), "ore_cascade_relabel_fwd")
+    return ob, ol, og, ov
 
 
 def to_device(t: torch.Tensor, dev) -> torch.Tensor:
@@ -2962,11 +3021,12 @@ def event_pair_overhead_us(reps: int = 200) -> float:
     return float(v.value)
 
 
-def compose_roi_head(sd, support_8: torch.Tensor, prefix: str = "roi_heads."):
+def compose_roi_head(sd, support_8: torch.Tensor, prefix: str = "roi_heads.", stage: int = 0):
     """The eval second stage between ROIAlign and fc1's ReLU is linear in the pooled features:
          a = conv3(cat(x, s)) + cat(conv1(x), conv2(s));  h = relu(fc1(flatten(a)))        (fsod_roi_heads.py:500-520)
     so it folds, once per (weights, support set), into h = relu(W' x_flat + b') with x_flat ordered [pos][channel]
-    (the ROIAlign kernel's output order).  Returns (W' [fc, 64*C] fp32, b' [fc] fp32) on the CPU; done in fp64."""
+    (the ROIAlign kernel's output order).  Returns (W' [fc, 64*C] fp32, b' [fc] fp32) on the CPU; done in fp64.
+    stage: which box_head[stage].fc1 of a cascade closes the chain (conv1 / conv2 / conv3 are shared by the stages)."""
     f64 = torch.float64
     W3 = sd[prefix + "conv3.weight"].detach().cpu().to(f64).flatten(1)
     b3 = sd[prefix + "conv3.bias"].detach().cpu().to(f64)
@@ -2974,8 +3034,8 @@ def compose_roi_head(sd, support_8: torch.Tensor, prefix: str = "roi_heads."):
     b1 = sd[prefix + "conv1.bias"].detach().cpu().to(f64)
     W2 = sd[prefix + "conv2.weight"].detach().cpu().to(f64).flatten(1)
     b2 = sd[prefix + "conv2.bias"].detach().cpu().to(f64)
-    fw = sd[prefix + "box_head.0.fc1.weight"].detach().cpu().to(f64)
-    fb = sd[prefix + "box_head.0.fc1.bias"].detach().cpu().to(f64)
+    fw = sd[prefix + f"box_head.{int(stage)}.fc1.weight"].detach().cpu().to(f64)
+    fb = sd[prefix + f"box_head.{int(stage)}.fc1.bias"].detach().cpu().to(f64)
     Cc = W1.shape[1]
     P = fw.shape[1] // Cc
     s = support_8.detach().cpu().to(torch.float32).mean(0).to(f64).reshape(Cc, P)        # mean over shots in fp32 like the reference
@@ -3068,8 +3128,13 @@ class Engine:
     def set_roi_support(self, sd, support_8: torch.Tensor, slot: int, prefix: str = "roi_heads.") -> None:
         """The second stage of N-way class slot `slot`: DSA-mix + flatten + fc1 composed with that class's rcnn_8 support features
         (compose_roi_head), after set_roi_head() and set_classes()."""
-        Wp, bp = compose_roi_head(sd, support_8, prefix)
-        _chk(lib().ore_engine_set_roi_support_slot(self._h, int(slot), Wp.data_ptr(), bp.data_ptr()), "ore_engine_set_roi_support_slot")
+        for k in range(getattr(self, "roi_stages", 1)):          # a cascade engine: every stage's fc1 composed with the class's features
+            Wp, bp = compose_roi_head(sd, support_8, prefix, stage=k)
+            if k == 0:
+                _chk(lib().ore_engine_set_roi_support_slot(self._h, int(slot), Wp.data_ptr(), bp.data_ptr()), "ore_engine_set_roi_support_slot")
+            else:
+                _chk(lib().ore_engine_set_roi_support_slot_stage(self._h, int(slot), k, Wp.data_ptr(), bp.data_ptr()),
+                     "ore_engine_set_roi_support_slot_stage")
 
     def finalize(self) -> None:
         _chk(lib().ore_engine_finalize(self._h), "ore_engine_finalize")
@@ -3086,7 +3151,37 @@ class Engine:
         _chk(lib().ore_engine_set_roi_head(self._h, Wp.data_ptr(), bp.data_ptr(), Wp.shape[0], pooled, cw.data_ptr(), cb.data_ptr(),
                                            bw.data_ptr(), bb.data_ptr(), rw, score_thresh, nms_thresh, topk), "ore_engine_set_roi_head")
         self.has_roi = True
+        self.roi_stages = 1
         self._det_cap = min(max(int(topk), 1), 320)        # rows of the result tensors ore_engine_detect_fwd fills
+
+    def set_roi_cascade(self, sd, support_8: torch.Tensor, reg_weights, score_thresh: float = 0.0, nms_thresh: float = 0.9, topk: int = 100,
+                        prefix: str = "roi_heads.") -> None:
+        """The second stage as a cascade of len(reg_weights) stages (ore_engine_set_roi_cascade): reg_weights = one 4-tuple per stage
+        (MODEL.ROI_BOX_CASCADE_HEAD.BBOX_REG_WEIGHTS); box_head.k.fc1 is composed per stage, box_predictor.k uploaded per stage.  One
+        stage is set_roi_head: the same launches."""
+        K = len(reg_weights)
+        if K < 1 or any(len(w) != 4 for w in reg_weights):
+            raise OreError(f"set_roi_cascade: reg_weights must hold one 4-tuple per stage, got {reg_weights!r}")
+        if prefix + f"box_head.{K - 1}.fc1.weight" not in sd:
+            raise OreError(f"set_roi_cascade: {K} cascade stages asked for, the state dict has no {prefix}box_head.{K - 1}")
+        f = lambda k: sd[prefix + k].detach().float().cpu().contiguous()      # noqa: E731
+        keep, cols = [], [[] for _ in range(6)]
+        for k in range(K):
+            Wp, bp = compose_roi_head(sd, support_8, prefix, stage=k)
+            ts = (Wp, bp, f(f"box_predictor.{k}.cls_score.weight"), f(f"box_predictor.{k}.cls_score.bias"),
+                  f(f"box_predictor.{k}.bbox_pred.weight"), f(f"box_predictor.{k}.bbox_pred.bias"))
+            assert ts[2].shape[0] == 2 and ts[4].shape[0] == 4, "one foreground class, class-agnostic box regression"
+            keep.append(ts)
+            for c, t in zip(cols, ts):
+                c.append(t.data_ptr())
+        arrs = [(C.c_void_p * K)(*c) for c in cols]
+        pooled = int(round((keep[0][0].shape[1] // self.fpn_ch) ** 0.5))
+        rw = (C.c_float * (4 * K))(*[float(v) for w in reg_weights for v in w])
+        _chk(lib().ore_engine_set_roi_cascade(self._h, K, arrs[0], arrs[1], keep[0][0].shape[0], pooled, arrs[2], arrs[3], arrs[4], arrs[5], rw,
+                                              score_thresh, nms_thresh, topk), "ore_engine_set_roi_cascade")
+        self.has_roi = True
+        self.roi_stages = K
+        self._det_cap = min(max(int(topk), 1), 320)
 
     def detections(self, b: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """(boxes [k,4], scores [k], source proposal index [k]) of the second stage for image b -- one sync to read the count."""

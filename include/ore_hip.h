@@ -347,6 +347,43 @@ int ore_roi_predict_parts_fwd(const float* h, int32_t C, const float* cls_w, con
                               int32_t* host_count, void* workspace, size_t workspace_bytes, void* stream,
                               int32_t h_parts, const float* h_bias);
 
+/* The cascade: CustomCascadeROIHeads with K = len(ROI_BOX_CASCADE_HEAD.IOUS) > 1 stages (ref:fewx/modeling/fsod/fsod_roi_heads.py:404-457,
+ * d2z:modeling/roi_heads/cascade_rcnn.py:163-307).
+ * One INTERMEDIATE eval stage in one launch.  The fc1 rows in either form of ore_roi_predict_parts_fwd (h [cap][C] finished, or h_parts >= 1
+ * raw K-split sums [h_parts][cap][C] + h_bias, added in slice order, then bias, then ReLU); per row below the count: the stage's two
+ * logits and four deltas (the C twin's fmaf order), the softmax foreground probability s, apply_deltas with reg_weights4_host and the
+ * log(1000/16) clamp, the clip to (img_h, img_w).  next_boxes [cap][4] receives the clipped box (the next stage's proposal), score_sum
+ * [cap] receives s (accumulate = 0, the first stage) or score_sum + s (1); dead [cap] is a sticky byte: set when the unclipped box or s is
+ * not finite (the reference's Boxes.clip aborts there), kept once set (accumulate = 1); a dead row's next box is (0,0,0,0) and its sum 0,
+ * and the last stage drops it.  Rows at and beyond the count are not written and never read by a later kernel.  Domain: that of the fused
+ * tail, cap <= 512 and C <= 210; anything else is ORE_EINVAL. */
+int ore_roi_cascade_refine_fwd(const float* h, int32_t C, int32_t h_parts, const float* h_bias, const float* cls_w,
+                               const float* cls_b, const float* box_w, const float* box_b, const float* boxes,
+                               const int32_t* n_dev, int32_t n_host, int32_t cap, const float* reg_weights4_host, float img_h,
+                               float img_w, float* next_boxes, float* score_sum, uint8_t* dead, int32_t accumulate, void* stream);
+/* The LAST stage: ore_roi_predict_parts_fwd with the candidate score (score_sum[r] + s_last[r]) * (float)(1.0 / n_stages) -- the fp32 sum
+ * in stage order times the fp32-rounded reciprocal, as the reference averages -- and dead rows failing the filter; threshold, NMS, top-k,
+ * detector_postprocess, the pinned count word and the caller's record are unchanged.  n_stages = 1 (score_sum = dead = NULL) launches what
+ * ore_roi_predict_parts_fwd launches.  n_stages > 1: cap <= 512 and C <= 210 only. */
+int ore_roi_predict_cascade_fwd(const float* h, int32_t C, const float* cls_w, const float* cls_b, const float* box_w,
+                                const float* box_b, const float* boxes, const int32_t* n_dev, int32_t n_host, int32_t cap,
+                                const float* reg_weights4_host, float img_h, float img_w, float score_thresh, float nms_thresh,
+                                int32_t topk, float* det_boxes, float* det_scores, int64_t* det_src, int32_t* det_count,
+                                const float* post_dev, float* fin_boxes, float* fin_scores, int32_t* fin_count,
+                                int32_t* host_count, void* workspace, size_t workspace_bytes, void* stream,
+                                int32_t h_parts, const float* h_bias, const float* score_sum, const uint8_t* dead,
+                                int32_t n_stages);
+/* The TRAINING seam between stage k - 1 and stage k for B images x R rows in one launch (no host sync, fixed shapes, no atomics; a
+ * sibling of ore_sample_rois_fwd).  boxes / deltas [B][R][4] of the producing stage (deltas detached), valid [B][R] bytes, img_hw [B][2]
+ * device (h, w) of every image, gtp [B][G][4] with gt_n [B] (0 <= G <= 256), reg_weights4_host of the PRODUCING stage, iou_thr of the
+ * CONSUMING stage.  out_boxes = apply_deltas + clip to the row's image; out_valid = valid and finite and not empty after the clip (the
+ * reference removes empty boxes in training); labels 0 (IoU with the matched ground truth >= iou_thr) / 1; gt = the matched box (max
+ * IoU, first index on ties; pairwise_iou: inter > 0 ? inter / (a_gt + a_box - inter) : 0); no ground truth: label 1, gt zeros.  Rows that
+ * are not valid: box (0,0,8,8), label 1, valid 0, gt zeros (the padding contract of ore_sample_rois_fwd).  out_boxes may be boxes. */
+int ore_cascade_relabel_fwd(const float* boxes, const float* deltas, const uint8_t* valid, const float* img_hw, const float* gtp,
+                            const int64_t* gt_n, int32_t B, int32_t R, int32_t G, const float* reg_weights4_host, float iou_thr,
+                            float* out_boxes, uint8_t* out_valid, int64_t* labels, float* gt, void* stream);
+
 /* ------------------------------------------------------------------ training targets / losses - */
 /* CenterNet2 proposal-generator ground truth for only_proposal=True (class-agnostic), on device.
  * ref:fewx/modeling/fsod/fsod_rpn.py:803-901 (_get_ground_truth), :904-956 (_get_label_inds), :959-989 (assign_fpn_level /
@@ -657,6 +694,18 @@ int ore_engine_set_blocks(ore_engine* e, const int32_t blocks[4]);
 int ore_engine_set_roi_head(ore_engine* e, const float* W_host, const float* b_host, int32_t fc_dim, int32_t pooled,
                             const float* cls_w_host, const float* cls_b_host, const float* box_w_host, const float* box_b_host,
                             const float* reg_weights4_host, float score_thresh, float nms_thresh, int32_t topk);
+/* The same for a cascade of n_stages = len(ROI_BOX_CASCADE_HEAD.IOUS) stages (1 .. ORE_MAX_CASCADE): host arrays of n_stages
+ * host pointers -- W_host[k] / b_host[k] the composed chain with box_head[k].fc1 (orehip.compose_roi_head(stage=k)), cls_* / box_* of
+ * box_predictor[k] -- and reg_weights4_host [n_stages][4].  The second stage then loops: ROIAlign(boxes_k) -> the fc1 GEMM (same K-split) ->
+ * ore_roi_cascade_refine_fwd for k < n_stages - 1, ore_roi_predict_cascade_fwd for the last; the one-image pass, the folded batch pass
+ * and the N-way class slots all run it (a class slot needs ore_engine_set_roi_support_slot_stage for every stage; a pass with one
+ * missing is refused with the stage count in the message).  n_stages = 1 IS ore_engine_set_roi_head: the same launches.  The GEMMs
+ * stay fp32 in the bf16 modes.  A later ore_engine_set_roi_head returns the engine to one stage. */
+#define ORE_MAX_CASCADE 4
+int ore_engine_set_roi_cascade(ore_engine* e, int32_t n_stages, const float* const* W_host, const float* const* b_host,
+                               int32_t fc_dim, int32_t pooled, const float* const* cls_w_host, const float* const* cls_b_host,
+                               const float* const* box_w_host, const float* const* box_b_host, const float* reg_weights4_host,
+                               float score_thresh, float nms_thresh, int32_t topk);
 
 /* Backbone+FPN only: img [B][3][H][W] (u8 or f32, device) -> p3,p4,p5 NHWC device pointers owned by the engine. */
 int ore_engine_backbone_fwd(ore_engine* e, const void* img, int32_t img_is_u8, int32_t B, int32_t H, int32_t W,
@@ -791,6 +840,8 @@ int ore_engine_eval_batch_fwd(ore_engine* e, const void* img, int32_t img_is_u8,
 int ore_engine_set_classes(ore_engine* e, int32_t n, const int64_t* class_ids_host);
 int ore_engine_set_support_slot(ore_engine* e, int32_t slot, int32_t level, const float* proto_chw_host, int32_t C, int32_t s);
 int ore_engine_set_roi_support_slot(ore_engine* e, int32_t slot, const float* W_host, const float* b_host);
+/* Stage `stage` of a cascade engine's class slot (stage 0 = ore_engine_set_roi_support_slot). */
+int ore_engine_set_roi_support_slot_stage(ore_engine* e, int32_t slot, int32_t stage, const float* W_host, const float* b_host);
 int ore_engine_detect_classes_begin(ore_engine* e, const void* img, int32_t img_is_u8, int32_t H, int32_t W, int32_t out_h, int32_t out_w,
                                     void* out_record, void* stream);
 int ore_engine_eval_classes_fwd(ore_engine* e, const void* img, int32_t img_is_u8, int32_t H, int32_t W, int32_t use_graph, void* stream);

@@ -76,7 +76,10 @@ typedef struct ore_conv_desc {
                            * are bf16 tensors (ld / coff count ELEMENTS), accumulation, scale / shift and colsum stay fp32, the output is
                            * rounded once (nearest even) when it is stored and colsum sums the ROUNDED values.  ORE_ST_BF16_F32OUT: the
                            * same with an fp32 `out` (the detection head's outputs).  The input buffer must extend 32 bytes past its
-                           * last row when Cin % 32 == 16 (the last K chunk of a row reads 16 channels further, against zero weights). */
+                           * last row when Cin % 32 == 16 (the last K chunk of a row reads 16 channels further, against zero weights).
+                           * Both bf16 modes need in_ld and in_coff in multiples of 8 elements (16-byte aligned input slices) and take no
+                           * input affine: a call with in_mul returns ORE_EINVAL.  Column sums with an fp32 `out` do not run on k_conv_kd
+                           * (k_conv_kw takes the call). */
     int64_t w_wino_level_stride; /* ore_conv2d_levels_fwd only.  0: all levels share the weights.  Otherwise the levels are DIFFERENT layers of
                            * one shape (the three FPN output convs, d2z:modeling/backbone/fpn.py:139-145): level l's Winograd weights start
                            * l * w_wino_level_stride floats after w_wino, its scale / shift l * ep_stride floats after scale / shift; `w` is

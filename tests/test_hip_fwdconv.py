@@ -11,7 +11,8 @@ tests/test_fwdconv_host.py shows on the CPU that the bounds pass an fp32 emulati
 Every case forces its launcher through orehip.conv_overrides, asserts that conv_last_launch() names it and that ore_conv_plan
 predicted it, takes d from the split that ran, and launches twice (bitwise equal).  Every input is a slice of a wider NaN-filled
 allocation with NaN rows in front of and behind it, the per-channel vectors have NaN guards and NaN past Cout, and everything outside
-the output slice must come back bitwise unchanged.  fp32 storage only; operand precision fp32 and bf16.
+the output slice must come back bitwise unchanged.  fp32 storage only (bf16 storage: tests/test_hip_bf16s_conv.py); operand precision
+fp32 and bf16.
 
 ORE_FWDCONV_LOG=<file>: append the worst hard, rms and column-sum ratios per (mode, launcher, class) to that file."""
 import ctypes as C

@@ -471,7 +471,8 @@ extern "C" int ore_centernet_targets_fwd(int32_t n_levels, const int32_t* H, con
                                          const float* gt_boxes, const int32_t* gt_count, int32_t max_n, const float* soi_host,
                                          float hm_min_overlap, float min_radius, float* reg_targets, float* hm_targets,
                                          int64_t* pos_inds, int32_t* pos_count, void* stream) {
-    ORE_CHECK_ARG(H && W && stride && gt_boxes && gt_count && soi_host && reg_targets && hm_targets && pos_inds && pos_count,
+    // pos_inds and pos_count both null: the caller takes its positives from ore_centernet_more_pos_fwd, k_cn_pos_inds is not launched
+    ORE_CHECK_ARG(H && W && stride && gt_boxes && gt_count && soi_host && reg_targets && hm_targets && !pos_inds == !pos_count,
                   "ore_centernet_targets_fwd: null pointer");
     ORE_CHECK_ARG(n_levels >= 1 && n_levels <= 4 && B >= 1 && max_n >= 1 && max_n <= MAXN, "ore_centernet_targets_fwd: 1..4 levels, <= %d objects/image", MAXN);
     TgtP p{};
@@ -486,7 +487,7 @@ extern "C" int ore_centernet_targets_fwd(int32_t n_levels, const int32_t* H, con
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_cn_targets, dim3(ceil_div(maxhw, 256), n_levels * B), dim3(256), 0, st, p);
     int rc = ore_launch_status("k_cn_targets");
-    if (rc) return rc;
+    if (rc || !pos_inds) return rc;
     hipLaunchKernelGGL(k_cn_pos_inds, dim3(1), dim3(1024), 0, st, p, (long long*)pos_inds, pos_count);
     return ore_launch_status("k_cn_pos_inds");
 }

@@ -27,8 +27,16 @@ class CenterNet(nn.Module):
         self.post_nms_topk_train, self.post_nms_topk_test = c.POST_NMS_TOPK_TRAIN, c.POST_NMS_TOPK_TEST
         self.nms_thresh_train, self.nms_thresh_test = c.NMS_TH_TRAIN, c.NMS_TH_TEST
         self.only_proposal, self.with_agn_hm, self.not_nms = c.ONLY_PROPOSAL, c.WITH_AGN_HM, c.NOT_NMS
-        if not (self.only_proposal and self.with_agn_hm) or self.not_nms or c.CENTER_NMS or c.MORE_POS:
-            raise NotImplementedError("CenterNet: only ONLY_PROPOSAL + WITH_AGN_HM with NMS is built (finetune_vovnet.yaml)")
+        if not (self.only_proposal and self.with_agn_hm) or self.not_nms or c.CENTER_NMS:
+            raise NotImplementedError("CenterNet: only ONLY_PROPOSAL + WITH_AGN_HM with NMS is built (finetune_vovnet.yaml, with or "
+                                      "without MORE_POS); NOT_NMS and CENTER_NMS are not")
+        # MORE_POS (ref fsod_rpn.py:664-669, :1213-1343): training positives from the 3x3 block around every centre cell; no effect on eval
+        self.more_pos, self.more_pos_thresh, self.more_pos_topk = bool(c.MORE_POS), float(c.MORE_POS_THRESH), int(c.MORE_POS_TOPK)
+        if self.more_pos and not 1 <= self.more_pos_topk <= 9 * len(self.strides):
+            raise ValueError(f"MODEL.CENTERNET.MORE_POS_TOPK = {self.more_pos_topk}: set it to 1 .. {9 * len(self.strides)} "
+                             f"(9 candidates on each of the {len(self.strides)} levels of FPN_STRIDES)")
+        if self.more_pos and not self.more_pos_thresh > 0:
+            raise ValueError(f"MODEL.CENTERNET.MORE_POS_THRESH = {self.more_pos_thresh}: set it above 0 (the reference ships 0.2)")
         # training-side hyper-parameters (fewx/modeling/fsod/train_forward.py)
         self.hm_focal_alpha, self.hm_focal_beta, self.loss_gamma = c.HM_FOCAL_ALPHA, c.HM_FOCAL_BETA, c.LOSS_GAMMA
         self.reg_weight, self.not_norm_reg, self.pos_weight, self.neg_weight = c.REG_WEIGHT, c.NOT_NORM_REG, c.POS_WEIGHT, c.NEG_WEIGHT

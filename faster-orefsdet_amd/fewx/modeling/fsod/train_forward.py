@@ -165,6 +165,14 @@ def graphed_dense_part(model, xq, xs):
     return g(xq, xs) if g is not None else dense_part(model, xq, xs)
 
 
+def _more_pos_arg(pg, rows: torch.Tensor):
+    """MORE_POS (ref:fewx/modeling/fsod/fsod_rpn.py:664-669): the positives are chosen from the detached fp32 head rows, on the step's
+    stream; None when the switch is off."""
+    if not getattr(pg, "more_pos", False):
+        return None
+    return rows.detach(), float(pg.more_pos_thresh), int(pg.more_pos_topk)
+
+
 def first_stage(pg, heads: List[torch.Tensor], gt_boxes: torch.Tensor):
     """CenterNet.forward, training branch, after the head (ref:fewx/modeling/fsod/fsod_rpn.py:658-700): ground truth, the three
     losses, and the proposals with the *_TRAIN thresholds, WITHOUT a host sync.  heads[l] [1,H,W,16] (0..3 ltrb after Scale+ReLU,
@@ -174,7 +182,8 @@ def first_stage(pg, heads: List[torch.Tensor], gt_boxes: torch.Tensor):
     dev = heads[0].device
     shapes = [tuple(h.shape[1:3]) for h in heads]
     rows = torch.cat([h.reshape(-1, h.shape[-1]) for h in heads], 0)
-    tg = orehip.centernet_targets([gt_boxes], shapes, pg.strides, pg.sizes_of_interest, pg.hm_min_overlap, pg.min_radius, device=dev)
+    tg = orehip.centernet_targets([gt_boxes], shapes, pg.strides, pg.sizes_of_interest, pg.hm_min_overlap, pg.min_radius, device=dev,
+                                  more_pos=_more_pos_arg(pg, rows))
     hp = dict(gamma=pg.loss_gamma, beta=pg.hm_focal_beta, sigmoid_clamp=pg.sigmoid_clamp, ignore_high_fp=pg.ignore_high_fp,
               alpha=pg.hm_focal_alpha, pos_weight=pg.pos_weight, neg_weight=pg.neg_weight, reg_weight=pg.reg_weight)
     l3 = A.centernet_losses(rows, tg["reg_targets"], tg["hm_targets"], tg["pos_inds"], tg["pos_count"], hp)
@@ -340,7 +349,8 @@ def first_stage_batch(pg, heads: List[torch.Tensor], gts: Optional[List[torch.Te
     shapes = [tuple(h.shape[1:3]) for h in heads]
     rows = torch.cat([h.reshape(-1, h.shape[-1]) for h in heads], 0)       # level-major, the images of a level in order: the targets' rows
     # `padded` = (boxes [B,G,4], counts [B] int32) on the device: the fixed-shape form a captured step uses
-    tg = orehip.centernet_targets(gts, shapes, pg.strides, pg.sizes_of_interest, pg.hm_min_overlap, pg.min_radius, device=dev, padded=padded)
+    tg = orehip.centernet_targets(gts, shapes, pg.strides, pg.sizes_of_interest, pg.hm_min_overlap, pg.min_radius, device=dev, padded=padded,
+                                  more_pos=_more_pos_arg(pg, rows))
     hp = dict(gamma=pg.loss_gamma, beta=pg.hm_focal_beta, sigmoid_clamp=pg.sigmoid_clamp, ignore_high_fp=pg.ignore_high_fp,
               alpha=pg.hm_focal_alpha, pos_weight=pg.pos_weight, neg_weight=pg.neg_weight, reg_weight=pg.reg_weight, images=B,
               norm_avg=norm_avg)

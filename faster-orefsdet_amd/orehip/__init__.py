@@ -2369,9 +2369,13 @@ def heatmap_host(frame_hwc_u8, levels, in_hw=None, *, out=None, lut="jet", alpha
 
 def centernet_targets(gt_boxes: Sequence[torch.Tensor], shapes: Sequence[Tuple[int, int]], strides=(8, 16, 32),
                       soi=((0, 64), (48, 192), (128, 1000000)), hm_min_overlap: float = 0.8, min_radius: float = 4.0,
-                      device=None, padded: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+                      device=None, padded: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                      more_pos: Optional[Tuple[torch.Tensor, float, int]] = None) -> Dict[str, torch.Tensor]:
     """CenterNet._get_ground_truth (ref:fewx/modeling/fsod/fsod_rpn.py:803-901) on device.  gt_boxes: per image [N_i,4]; or
-    `padded` = (boxes [B,G,4] fp32, counts [B] int32) already on the device (fixed shapes: a captured training step)."""
+    `padded` = (boxes [B,G,4] fp32, counts [B] int32) already on the device (fixed shapes: a captured training step).
+    `more_pos` = (head rows [rows, ld >= 4] fp32 in the targets' row order, MORE_POS_THRESH, MORE_POS_TOPK): pos_inds / pos_count are
+    the reference's _add_more_pos list (:1213-1343; ore_centernet_more_pos_fwd, capacity B * max_n * L * 9) instead of one centre per
+    (object, level that cares); the same stream, no host sync."""
     dev = torch.device(device or "cuda")
     L = len(strides)
     if padded is not None:
@@ -2395,14 +2399,29 @@ def centernet_targets(gt_boxes: Sequence[torch.Tensor], shapes: Sequence[Tuple[i
             gt = to_device(gt, dev)
         cnt = to_device(torch.tensor(ns, dtype=torch.int32), dev)
     rows = sum(B * h * w for h, w in shapes)
+    if more_pos is not None:
+        head, mp_thresh, mp_topk = more_pos
+        head = head.detach()
+        if not (head.is_cuda and head.dtype == torch.float32 and head.dim() == 2 and head.shape[0] == rows and head.shape[1] >= 4
+                and head.stride(1) == 1 and head.stride(0) >= head.shape[1]):
+            raise OreError(f"centernet_targets: more_pos takes the [{rows}, >= 4] fp32 head rows on the device, got "
+                           f"{tuple(head.shape)} {head.dtype} {head.device}")
     o = {"reg_targets": torch.empty(rows, 4, device=dev), "hm_targets": torch.empty(rows, device=dev),
-         "pos_inds": torch.zeros(B * max_n * L, dtype=torch.int64, device=dev), "pos_count": torch.zeros(1, dtype=torch.int32, device=dev)}
+         "pos_inds": torch.zeros(B * max_n * L * (9 if more_pos is not None else 1), dtype=torch.int64, device=dev),
+         "pos_count": torch.zeros(1, dtype=torch.int32, device=dev)}
     Hs = (C.c_int32 * L)(*[h for h, _ in shapes]); Ws = (C.c_int32 * L)(*[w for _, w in shapes]); St = (C.c_int32 * L)(*strides)
     so = (C.c_float * (2 * L))(*[float(v) for r in soi for v in r])
-    _chk(lib().ore_centernet_targets_fwd(L, Hs, Ws, St, B, _ptr(gt), _ptr(cnt), max_n, so, hm_min_overlap, min_radius,
-                                         _ptr(o["reg_targets"]), _ptr(o["hm_targets"]), _ptr(o["pos_inds"]), _ptr(o["pos_count"]),
-                                         _stream()), "ore_centernet_targets_fwd")
-    o["_keep"] = (gt, cnt)
+    if more_pos is None:
+        _chk(lib().ore_centernet_targets_fwd(L, Hs, Ws, St, B, _ptr(gt), _ptr(cnt), max_n, so, hm_min_overlap, min_radius,
+                                             _ptr(o["reg_targets"]), _ptr(o["hm_targets"]), _ptr(o["pos_inds"]), _ptr(o["pos_count"]),
+                                             _stream()), "ore_centernet_targets_fwd")
+    else:
+        _chk(lib().ore_centernet_targets_fwd(L, Hs, Ws, St, B, _ptr(gt), _ptr(cnt), max_n, so, hm_min_overlap, min_radius,
+                                             _ptr(o["reg_targets"]), _ptr(o["hm_targets"]), None, None, _stream()), "ore_centernet_targets_fwd")
+        _chk(lib().ore_centernet_more_pos_fwd(L, Hs, Ws, St, B, _ptr(gt), _ptr(cnt), max_n, so, _ptr(head), int(head.stride(0)),
+                                              float(mp_thresh), int(mp_topk), _ptr(o["pos_inds"]), _ptr(o["pos_count"]), _stream()),
+             "ore_centernet_more_pos_fwd")
+    o["_keep"] = (gt, cnt) if more_pos is None else (gt, cnt, head)
     return o
 
 

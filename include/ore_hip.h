@@ -393,11 +393,24 @@ int ore_cascade_relabel_fwd(const float* boxes, const float* deltas, const uint8
  * assign_reg_fpn), :992-1003 (_get_reg_targets), :1038-1046 (_create_agn_heatmaps_from_dist), :1049-1065 (get_center3x3).
  * Rows are the reference's "level first" order [level][image][y][x].  gt_boxes [B][max_n][4] (x1,y1,x2,y2; max_n <= 128),
  * gt_count [B] device; soi_host [n_levels][2].  Outputs: reg_targets [rows][4] (ltrb / stride, or -1e8/stride where no object
- * owns the location), hm_targets [rows], pos_inds [<= B*max_n*n_levels] in (image, object, level) order, pos_count [1]. */
+ * owns the location), hm_targets [rows], pos_inds [<= B*max_n*n_levels] in (image, object, level) order, pos_count [1]; pos_inds and
+ * pos_count may both be NULL: the positives are then left to ore_centernet_more_pos_fwd. */
 int ore_centernet_targets_fwd(int32_t n_levels, const int32_t* H, const int32_t* W, const int32_t* stride, int32_t B,
                               const float* gt_boxes, const int32_t* gt_count, int32_t max_n, const float* soi_host,
                               float hm_min_overlap, float min_radius, float* reg_targets, float* hm_targets,
                               int64_t* pos_inds, int32_t* pos_count, void* stream);
+/* MORE_POS positives (ref:fewx/modeling/fsod/fsod_rpn.py:664-669, :1213-1343 _add_more_pos / _get_c33_inds), the list that replaces
+ * pos_inds of ore_centernet_targets_fwd when MODEL.CENTERNET.MORE_POS is set.  Levels, boxes and counts as there.  Per object, level l
+ * and neighbour k = 0..8 (dx = k % 3 - 1, dy = k / 3 - 1) of the centre cell: the GIoU loss between head[row][0..3] (fp32 ltrb
+ * prediction, head_ld >= 4) and the centre regression shifted by (dx, dy) stride units; 1e8 where the neighbour lies outside the map or
+ * a shifted side is negative; 0 at k = 4 of a level that cares for the object and holds its centre cell.  The object keeps the candidates
+ * STRICTLY below min(more_pos_topk-th smallest of its 9 * n_levels losses (NaN above every number), more_pos_thresh).
+ * pos_inds [capacity B * max_n * n_levels * 9]: the kept rows in (image, object, level, k) order, duplicates kept; pos_count [1].
+ * 1 <= more_pos_topk <= 9 * n_levels, more_pos_thresh > 0.  One launch on `stream`, no host sync, the same list run to run. */
+int ore_centernet_more_pos_fwd(int32_t n_levels, const int32_t* H, const int32_t* W, const int32_t* stride, int32_t B,
+                               const float* gt_boxes, const int32_t* gt_count, int32_t max_n, const float* soi_host,
+                               const float* head, int32_t head_ld, float more_pos_thresh, int32_t more_pos_topk,
+                               int64_t* pos_inds, int32_t* pos_count, void* stream);
 /* Loss sums of CenterNet.losses (ref:fewx/modeling/fsod/fsod_rpn.py:702-779) with with_agn_hm + only_proposal:
  * head [rows][head_ld]: columns 0..3 = ltrb prediction (after Scale + ReLU), column 4 = agnostic heatmap logit.
  * sums4 = { sum GIoU loss over rows with max(reg_target) >= 0   (ref:CenterNet2/centernet/modeling/layers/iou_loss.py:10-63),

@@ -43,6 +43,7 @@ def main():
     ap.add_argument("--config", default="finetune_vovnet.yaml", help="a file of configs/fsod (finetune_vovnet_dw.yaml: the depthwise body, with "
                     "the synthetic weights of tests/vovnet_dw_ref.py)")
     ap.add_argument("--freeze-at", type=int, default=None, help="MODEL.BACKBONE.FREEZE_AT (default: the config's, 3; 0 also trains the stem)")
+    ap.add_argument("--more-pos", action="store_true", help="MODEL.CENTERNET.MORE_POS: the 3x3 centre positives chosen on the GPU (default: the config's, off)")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -67,6 +68,8 @@ def main():
         cfg.SOLVER.NESTEROV = True
     if a.freeze_at is not None:
         cfg.MODEL.BACKBONE.FREEZE_AT = a.freeze_at
+    if a.more_pos:
+        cfg.MODEL.CENTERNET.MORE_POS = True
     cfg.freeze()
     torch.manual_seed(0)
     m = build_model(cfg)
@@ -144,8 +147,8 @@ def main():
                                      "bucket_bytes": 4 * opt.bucket.size},
                           "optimizer": {"clip_type": opt.clip_type, "norm_type": opt.norm_type, "nesterov": opt.nesterov,
                                         "clip_value": opt.clip_value, "parameters": len(opt.bucket.numels)},
-                          "train_graph": bool(a.graph), "train_graph_error": m.__dict__.get("_ore_train_graph_error"),
-                          "whole_step_graph": None if stepper is None else {"replays": stepper.replays, "eager_steps": stepper.eager_steps, "error": stepper.error},
+                          "more_pos": bool(cfg.MODEL.CENTERNET.MORE_POS), "train_graph": bool(a.graph), "train_graph_error": m.__dict__.get("_ore_train_graph_error"),
+                          "whole_step_graph": None if stepper is None else {"captures": stepper.captures, "replays": stepper.replays, "eager_steps": stepper.eager_steps, "error": stepper.error},
                           "losses": {k: float(v.detach()) for k, v in losses.items()}}))
     if world > 1:
         dist.destroy_process_group()

@@ -1460,6 +1460,11 @@ extern "C" int ore_engine_buffer(ore_engine* e, const char* name, void** ptr, in
         if (n == "stage" + std::to_string(s + 2)) return set(e->sout[s].p, rows, e->stage[s].out_ch, e->sout[s].ld, 0);  // pre-gate
         if (n == "gate" + std::to_string(s + 2)) return set(e->gate[s], g.B, e->stage[s].out_ch, e->stage[s].out_ch, 0);
         if (n == "cat" + std::to_string(s + 2)) return set(e->cat[s].p, rows, e->stage[s].cat_ch, e->cat[s].ld, 0);
+        // read-back of the buffers a pass reuses (tests that hold a launch on the engine's own inputs); each exists only where the body has it
+        if (n == "ycat" + std::to_string(s + 2) && e->ycat[s].p) return set(e->ycat[s].p, rows, e->stage[s].out_ch, e->ycat[s].ld, 0);
+        if (n == "icat" + std::to_string(s + 2) && e->icat[s][0].p) return set(e->icat[s][0].p, rows, e->icat[s][0].ld, e->icat[s][0].ld, 0);
+        if (n == "icat" + std::to_string(s + 2) + "b" && e->icat[s][1].p) return set(e->icat[s][1].p, rows, e->icat[s][1].ld, e->icat[s][1].ld, 0);
+        if (n == "red" + std::to_string(s + 2) && e->red[s].p) return set(e->red[s].p, rows, e->stage[s].conv_ch, e->red[s].ld, 0);
     }
     for (int l = 0; l < 3; ++l) {
         const std::string k = std::to_string(l + 3);

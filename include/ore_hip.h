@@ -153,7 +153,22 @@ int ore_conv_plan(const ore_conv_desc* d, int32_t n_levels, const int32_t* H, co
  * operands, v_mfma_f32_16x16x4_f32.  ORE_CONV_BF16: tensors stay fp32 in HBM and LDS, both operands are rounded to bf16 (nearest
  * even) as they are fed to v_mfma_f32_16x16x16_bf16, fp32 accumulation and epilogue.  stem_1 (Cin = 3), the depthwise
  * correlation, GroupNorm, top-k / NMS and the second-stage GEMM of an engine always run in fp32.  An engine keeps the mode that was
- * in force when it was created. */
+ * in force when it was created.
+ * What an ENGINE's pass rounds in this mode, launch by launch (tests/test_hip_bf16_engine.py holds each launch to it on the engine's own
+ * buffers, tests/bf16_engine_ref.py is the contract in float64):
+ *   - rounded (both operands, as they enter the conv): stem_2, stem_3, every OSA layer and concat conv, the 1x1 reduction conv of a
+ *     depthwise stage, the FPN laterals, conv3 and the head's tower conv.  An input fold -- relu(x * mul + add), the eSE gate as
+ *     in_mul -- is computed in fp32 and rounded AFTER it;
+ *   - fp32, nothing rounded: stem_1, the max-pools, the eSE gates, the depthwise-separable units (taps and pointwise), the identity-block
+ *     tails, the correlation, GroupNorm + ReLU + the head's (l,t,r,b | hm) conv (one VALU kernel), everything behind the head;
+ *   - the three FPN output convs run as ONE per-level Winograd launch (w_wino_level_stride), and a per-level Winograd launch multiplies
+ *     in fp32 whatever this mode says: the engine's p3 .. p5 are conv_fp32(lat, W), nearer to the fp32 network than the mode asks for.
+ *     A plain ore_conv2d_fwd call of the same layer rounds its operands;
+ *   - with ONE image per pass the eSE gate of a one-block stage reaches its FPN lateral folded into the weight (the gate kernel writes
+ *     fp32(g * W), the lateral is a plain conv on it): conv(round(x), round(fp32(g * W))).  With more images per pass the gate is the
+ *     conv's input multiplier: conv(round(fp32(x * g)), round(W)).  A one-image pass and a batched pass of the same image therefore
+ *     differ at the laterals by a bf16 rounding in this mode (2e-3 .. 6e-3 of the map), whereas in fp32 they differ by summation order
+ *     only.  (A stage that ends in an identity block holds its whole output: its lateral is a plain rounded conv in both passes.) */
 #define ORE_CONV_FP32 0
 #define ORE_CONV_BF16 1
 /* ORE_CONV_BF16S -- bf16 STORAGE (BASELINE configs[4] as a byte-saving path): an engine created under this mode keeps every activation
@@ -863,7 +878,14 @@ int ore_engine_detect_classes_begin(ore_engine* e, const void* img, int32_t img_
 int ore_engine_eval_classes_fwd(ore_engine* e, const void* img, int32_t img_is_u8, int32_t H, int32_t W, int32_t use_graph, void* stream);
 /* Named device buffers: "p3","p4","p5" (NHWC, ld=2*fpn_ch, coff=fpn_ch), "pos3".."pos5", "head3".."head5",
  * "pre_boxes","pre_scores","pre_loc","keep_idx","counts","out_boxes","out_scores", "stage2".."stage5", ...
- * Returns device pointer and fills dims[0..3] = {rows(H*W*B), channels, ld, coff}. */
+ * Returns device pointer and fills dims[0..3] = {rows(H*W*B), channels, ld, coff}.
+ * Read-only names of the buffers a pass reuses, for tests that hold a launch on the engine's own inputs (K = 2..5; each name exists
+ * only where the body has the buffer, ORE_ENOENT otherwise):
+ *   "ycatK"  a stage of more than one block: the output map of its concat convs (after a pass: the LAST block's, before its tail);
+ *   "icatK"  the same stage: the concat buffer of the identity blocks with an even number (block 2, 4, ...): channels [0, out_ch) are the
+ *            identity = the tail of the block before, then the block's layers; "icatKb": the buffer of blocks 3, 5, ... (from three
+ *            blocks on).  After a pass each holds the last block that ran in it;
+ *   "redK"   a depthwise stage with a 1x1 reduction conv: its output map [M][conv_ch], the input of unit 0. */
 int ore_engine_buffer(ore_engine* e, const char* name, void** dev_ptr, int64_t dims[4]);
 /* Algorithmic FLOPs of the dense part of the last forward (2*MAC of every conv), for roofline accounting. */
 double ore_engine_last_flops(ore_engine* e);

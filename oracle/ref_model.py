@@ -44,7 +44,17 @@ VOVNET_SPECS = {
 # (BASELINE configs[4]; the reference has no reduced-precision path, so this mode is pinned by construction only): both operands of
 # every MFMA convolution -- all VoVNet/FPN convs except stem_1, conv3, the CenterNet head convs -- are rounded to bf16 (nearest
 # even) at the point where they enter the convolution; accumulation, FrozenBN, eSE, GroupNorm, the depthwise correlation and
-# everything after the head stay fp32.
+# everything after the head stay fp32.  An input fold (relu(x * mul + add), the eSE gate as the conv's input multiplier) is computed in
+# fp32 and rounded after it.  Two statements of the mode belong to an ENGINE's eval pass alone (operand_precision("bf16",
+# engine_pass=...); tests/bf16_engine_ref.py holds every launch to them on the engine's own buffers):
+#   * the three FPN output convs of an engine run as ONE per-level Winograd launch, and that launch multiplies in fp32 in this mode
+#     (nearer to the fp32 network than the mode asks for); a plain conv call of the same layer rounds its operands;
+#   * with ONE image per pass the eSE gate of a one-block stage reaches its FPN lateral folded into the weight,
+#     conv(round(x), round(fp32(g * W))) (`_ore_gated`, the mechanism of the storage mode); with more images it is the conv's input
+#     multiplier, conv(round(fp32(x * g)), round(W)).  A one-image pass and a batched pass of the same image therefore differ at the
+#     laterals by a bf16 rounding in this mode (2e-3 .. 6e-3 of the map), whereas in fp32 they differ by summation order only.
+#   (The last step of the head -- GroupNorm + ReLU + the (l,t,r,b | hm) conv -- is one fp32 VALU kernel in the engine; the oracle's
+#   whole-network statement rounds that conv's operands, inside the whole-network bound.)
 # "bf16s" restates ORE_CONV_BF16S, the bf16 STORAGE mode of an engine: every activation that travels between two kernels is a bf16 tensor
 # -- the producer rounds its fp32 result once, nearest even (`_st`) --, conv weights are bf16; stem_1's arithmetic, FrozenBN / bias, the
 # eSE pool and gate, GroupNorm statistics, the depthwise correlation's arithmetic and the head OUTPUTS stay fp32.  Two folds of the
@@ -52,6 +62,7 @@ VOVNET_SPECS = {
 # FPN lateral as a weight, round(W * g) (the pair rides on the gated tensor: `_ore_gated`).
 _OPERANDS = "fp32"
 _LINEARS = False
+_ENGINE_PASS = None    # "one" | "batch": an engine's eval pass in the bf16-operand mode (see above); None: the kernels' statement
 FROZEN_STAGES = 2      # stage index k <= FROZEN_STAGES + 1 is frozen: stem + stage2 + stage3 (FREEZE_AT = 3, d2z vovnet.py:455-468)
 
 
@@ -80,19 +91,24 @@ class operand_precision:
     stages of the backbone (stem, stage 2, stage 3 at FREEZE_AT = 3 -- 70 image-equivalents of a bs-16 step, no gradients) run in the
     STORAGE form: every map between two of their kernels is a bf16 tensor (`_st`), the eSE gate reaches the max-pool as
     round(max(x) * g); what leaves them -- the gated stage-3 map (bf16 value x fp32 gate, an fp32 tensor) and stage 4's pooled input
-    (a bf16 map) -- is consumed by the trainable layers in their operand-rounding form."""
+    (a bf16 map) -- is consumed by the trainable layers in their operand-rounding form.
+    engine_pass="one" | "batch" (mode "bf16", eval): the statement of an ENGINE's pass with one image / with more -- the FPN output
+    convs in fp32, and for "one" the gate folded into the lateral's weight (the header comment of this file has both sentences);
+    None (default) is the statement of the conv kernels and of a batched lateral."""
 
-    def __init__(self, mode: str, train: bool = False):
+    def __init__(self, mode: str, train: bool = False, engine_pass=None):
         assert mode in ("fp32", "bf16", "bf16s")
-        self.mode, self.train = mode, train
+        assert engine_pass in (None, "one", "batch") and (engine_pass is None or (mode == "bf16" and not train))
+        self.mode, self.train, self.engine_pass = mode, train, engine_pass
 
     def __enter__(self):
-        global _OPERANDS, _LINEARS
-        self.saved, _OPERANDS, _LINEARS = (_OPERANDS, _LINEARS), self.mode, self.train and self.mode == "bf16"
+        global _OPERANDS, _LINEARS, _ENGINE_PASS
+        self.saved = (_OPERANDS, _LINEARS, _ENGINE_PASS)
+        _OPERANDS, _LINEARS, _ENGINE_PASS = self.mode, self.train and self.mode == "bf16", self.engine_pass
 
     def __exit__(self, *exc):
-        global _OPERANDS, _LINEARS
-        _OPERANDS, _LINEARS = self.saved
+        global _OPERANDS, _LINEARS, _ENGINE_PASS
+        _OPERANDS, _LINEARS, _ENGINE_PASS = self.saved
 
 
 def _rnd(t: Tensor) -> Tensor:
@@ -196,7 +212,7 @@ def ese(x: Tensor, sd: SD, prefix: str) -> Tensor:
     s = F.conv2d(s, sd[prefix + "fc.weight"], sd[prefix + "fc.bias"])
     s = F.relu6(s + 3.0) / 6.0
     y = x * s
-    if _OPERANDS == "bf16s":
+    if _OPERANDS == "bf16s" or _ENGINE_PASS == "one":
         y._ore_gated = (x, s)          # lets fpn() fold the gate into the lateral weight; lives and dies with y (no global table)
     return y
 
@@ -258,15 +274,18 @@ def fpn(feats: Mapping[str, Tensor], sd: SD, prefix: str = "backbone.",
     res: Dict[str, Tensor] = {}
     prev = None
     for name, st in reversed(list(zip(in_features, stages))):
-        if _OPERANDS == "bf16s" and hasattr(feats[name], "_ore_gated"):   # the gate rides on the lateral's weight: conv(x, round(W * g))
-            xs, gs = feats[name]._ore_gated
-            lat = F.conv2d(xs, _rnd(sd[f"{prefix}fpn_lateral{st}.weight"] * gs.view(1, -1, 1, 1)), sd[f"{prefix}fpn_lateral{st}.bias"])
+        if (_OPERANDS == "bf16s" or _ENGINE_PASS == "one") and hasattr(feats[name], "_ore_gated"):
+            xs, gs = feats[name]._ore_gated                                # the gate rides on the lateral's weight: conv(x, round(W * g))
+            lat = F.conv2d(_rnd(xs), _rnd(sd[f"{prefix}fpn_lateral{st}.weight"] * gs.view(1, -1, 1, 1)), sd[f"{prefix}fpn_lateral{st}.bias"])
         else:
             lat = dense_conv(feats[name], sd[f"{prefix}fpn_lateral{st}.weight"], sd[f"{prefix}fpn_lateral{st}.bias"])
         if prev is not None:
             lat = lat + F.interpolate(prev, scale_factor=2.0, mode="nearest")
         lat = _st(lat)
         prev = lat
+        if _ENGINE_PASS is not None:                                       # an engine's grouped Winograd launch: fp32 in the operand mode
+            res[f"p{st}"] = F.conv2d(lat, sd[f"{prefix}fpn_output{st}.weight"], sd[f"{prefix}fpn_output{st}.bias"], padding=1)
+            continue
         res[f"p{st}"] = _st(dense_conv(lat, sd[f"{prefix}fpn_output{st}.weight"],
                                        sd[f"{prefix}fpn_output{st}.bias"], padding=1))
     return {k: res[k] for k in sorted(res)}

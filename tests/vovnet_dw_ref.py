@@ -10,6 +10,12 @@ What the bodies are (d2z:modeling/backbone/vovnet.py:28-48, 110-130, 284-332, ch
   stem   stem_1 the ordinary 3 -> 64 3x3 stride-2 conv, stem_2 a unit at stride 1, stem_3 a unit at stride 2
   block  if in_ch != stage_ch a 1x1 conv_reduction (+ norm + ReLU) feeds layer 0 and is NOT part of the concat; three units;
          concat [x, l0, l1, l2] -> 1x1 -> eSE; ceil-mode 3x3 stride-2 max-pool in front of stages 3..5
+
+The bf16-operand mode (include/ore_hip.h ORE_CONV_BF16) of these bodies, `with operand_precision("bf16"):` -- the units are fp32 whatever
+the mode (depthwise taps AND the pointwise conv: ore_dwpw_fwd never rounds), stem_1 is fp32 as in every body, and the convs that run on
+the matrix cores -- a stage's 1x1 reduction conv and its 1x1 concat conv, the FPN convs -- round both operands to bf16 where they enter
+the conv.  `engine_pass="one" | "batch"` selects the statement of an engine's pass (oracle/ref_model.py: the FPN output convs fp32, the
+one-image lateral with the gate folded into its weight).  Outside the scope nothing here changes.
 """
 from __future__ import annotations
 
@@ -90,6 +96,12 @@ def synth_state_dict_dw(seed: int = 0, body: str = "V-19-slim-dw-eSE") -> Dict[s
 
 
 # ------------------------------------------------------------------------------------------------ the network
+def operand_precision(mode: str, engine_pass=None):
+    """The oracle's scope (oracle.ref_model.operand_precision): one switch for the dense and the depthwise bodies."""
+    from oracle import ref_model as R
+    return R.operand_precision(mode, engine_pass=engine_pass)
+
+
 def _bn(x, sd, name, eps=1e-5):
     sc = sd[name + ".weight"] / torch.sqrt(sd[name + ".running_var"] + eps)
     sh = sd[name + ".bias"] - sd[name + ".running_mean"] * sc
@@ -97,18 +109,26 @@ def _bn(x, sd, name, eps=1e-5):
 
 
 def conv_bn_relu(x, sd, name, stride, pad):
-    return F.relu(_bn(F.conv2d(x, sd[name + "/conv.weight"], None, stride, pad), sd, name + "/norm"))
+    from oracle import ref_model as R
+    if name.endswith("stem.stem_1"):                         # Cin = 3: fp32 in every mode
+        return F.relu(_bn(F.conv2d(x, sd[name + "/conv.weight"], None, stride, pad), sd, name + "/norm"))
+    return F.relu(_bn(R.dense_conv(x, sd[name + "/conv.weight"], None, stride, pad), sd, name + "/norm"))   # reduction / concat: an MFMA conv
 
 
 def dw_unit(x, sd, name, stride):
+    """fp32 in every operand mode: neither the taps nor the pointwise operands are rounded."""
     c = x.shape[1]
     t = F.conv2d(x, sd[name + "/dw_conv3x3.weight"], None, stride, 1, groups=c)
     return F.relu(_bn(F.conv2d(t, sd[name + "/pw_conv1x1.weight"]), sd, name + "/pw_norm"))
 
 
 def ese(x, sd, prefix):
-    s = F.conv2d(F.adaptive_avg_pool2d(x, 1), sd[prefix + "fc.weight"], sd[prefix + "fc.bias"])
-    return x * (F.relu6(s + 3.0) / 6.0)
+    from oracle import ref_model as R
+    s = F.relu6(F.conv2d(F.adaptive_avg_pool2d(x, 1), sd[prefix + "fc.weight"], sd[prefix + "fc.bias"]) + 3.0) / 6.0
+    y = x * s
+    if R._ENGINE_PASS == "one":
+        y._ore_gated = (x, s)                                # the one-image lateral folds the gate into its weight (ref_model.fpn)
+    return y
 
 
 def osa_stage_dw(x, sd, k: int, layers: int = 3, prefix: str = P):
@@ -142,7 +162,10 @@ def vovnet_dw(x, sd, prefix: str = P) -> Dict[str, torch.Tensor]:
 
 def backbone_fpn_dw(x, sd) -> Dict[str, torch.Tensor]:
     """p3 / p4 / p5 (d2z:modeling/backbone/fpn.py:113-154, TOP_LEVELS 0, fuse "sum", bias, no norm)."""
+    from oracle import ref_model as R
     f = vovnet_dw(x, sd)
+    if R._OPERANDS != "fp32":
+        return R.fpn(f, sd)                                  # the mode's statement of the FPN is the dense bodies'
     res, prev = {}, None
     for st in (5, 4, 3):
         lat = F.conv2d(f[f"stage{st}"], sd[f"backbone.fpn_lateral{st}.weight"], sd[f"backbone.fpn_lateral{st}.bias"])

@@ -15,30 +15,14 @@
 //             track its place behind the rows; the new list, the header and ids_out are written from registers and LDS.  Every read of
 //             the state precedes a barrier that precedes every write of it.
 // Compiled with -ffp-contract=off: the IoU is single fp32 operations, each rounded on its own (the expression of ore_proposal_recall).
-#include "ore_block.h"
+#include "ore_track.h"                               // the state's layout and the IoU, shared with ore_track_wide.hip
 
 namespace {
 
 constexpr int TR_MAX_ROWS = ORE_DET_RECORD_ROWS;
 constexpr int TR_MAX_T = ORE_TRACK_MAX_TRACKS;       // threads of the block: one per track slot
 constexpr int TR_WORDS = (TR_MAX_ROWS + 63) / 64;    // 64-bit words of a row mask
-constexpr int TR_HEADER = 32;                        // bytes: m, capacity (int32), next_id, frames, dropped (int64)
 static_assert(TR_MAX_ROWS <= TR_MAX_T && TR_MAX_T % 64 == 0 && TR_MAX_T <= 1024, "one thread per row and per track slot");
-
-struct Header { int32_t m, capacity; int64_t next_id, frames, dropped; };
-static_assert(sizeof(Header) == TR_HEADER, "the documented header");
-struct State { Header* hd; float* boxes; int64_t* classes; int64_t* ids; int32_t* ttl; };
-__host__ __device__ inline State track_state(void* p, int capacity) {
-    char* c = static_cast<char*>(p);
-    State s;
-    s.hd = reinterpret_cast<Header*>(c);
-    s.boxes = reinterpret_cast<float*>(c + TR_HEADER);
-    s.classes = reinterpret_cast<int64_t*>(c + TR_HEADER + (size_t)capacity * 16);
-    s.ids = s.classes + capacity;
-    s.ttl = reinterpret_cast<int32_t*>(s.ids + capacity);
-    return s;
-}
-inline size_t track_state_bytes(int capacity) { return ((size_t)TR_HEADER + (size_t)capacity * 36 + 15) & ~(size_t)15; }
 
 struct UpdArgs {
     void* state; int32_t capacity;
@@ -105,12 +89,7 @@ __global__ __launch_bounds__(TR_MAX_T) void k_track_update(const UpdArgs a) {
     const float tarea = (tb.z - tb.x) * (tb.w - tb.y);
     __syncthreads();
 
-    auto iou_with = [&](int d) -> float {
-        const f32x4 b = s_box[d];
-        const float iw = fminf(tb.z, b.z) - fmaxf(tb.x, b.x), ih = fminf(tb.w, b.w) - fmaxf(tb.y, b.y);
-        const float inter = (iw > 0.0f && ih > 0.0f) ? iw * ih : 0.0f;
-        return inter > 0.0f ? inter / ((tarea + s_area[d]) - inter) : 0.0f;
-    };
+    auto iou_with = [&](int d) -> float { return track_iou(tb, tarea, s_box[d], s_area[d]); };
 
     // ---- scan: the candidate rows of this track
     unsigned long long cand[TR_WORDS];

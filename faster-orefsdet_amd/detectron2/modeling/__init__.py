@@ -27,4 +27,5 @@ def build_model(cfg):
     return model
 
 
-from .test_time_augmentation import DatasetMapperTTA, GeneralizedRCNNWithTTA  # noqa: E402,F401
+from .test_time_augmentation import DatasetMapperTTA  # noqa: E402,F401
+from .tta_tracking import GeneralizedRCNNWithTTA  # noqa: E402,F401  (test_time_augmentation's wrapper, plus track=)

@@ -7,7 +7,8 @@ The whole frame stays on the device: one upload, one gather launch that writes e
 (orehip.tile_gather_u8), one device resize for the full-frame pass (orehip.resize_bilinear_u8), one engine replay per pass -- `fold`
 tiles per pass through Engine.eval_forward_batch -- with the rows of every image collected behind it (ore_tile_collect_fwd: seam rule,
 offset, appended at a device-side offset) and one merge (ore_tta_merge_fwd), all queued on the current stream; the host waits once, for
-the merged count.  With support_classes set (N-way) the engine's merged rows exist only in the record of a finished pass, so the host
+the merged count.  With track= the merged rows get ids that persist from frame to frame (orehip.WideBoxTracker, association contract
+"track v1"): the update is queued behind the merge, on the merged record and its device-side count, before that one wait.  With support_classes set (N-way) the engine's merged rows exist only in the record of a finished pass, so the host
 polls once per source.
 
 Seam rule: a tile row whose box comes within `margin` pixels of a tile side that is not a frame side is taken to be the fragment of an
@@ -19,7 +20,7 @@ import numpy as np
 import torch
 from torch import nn
 
-__all__ = ["TiledInference", "check_tiling_limits"]
+__all__ = ["TiledInference", "check_tiling_limits", "merge_tracker"]
 
 FRAME_MAX_SIDE = 8192                      # ore_tile_gather_u8_fwd / ore_resize_bilinear_u8_fwd
 MAX_TILES = 128                            # ore_tile_gather_u8_fwd
@@ -74,9 +75,37 @@ def check_tiling_limits(frame_hw, plan, full_hw, rows):
                          "full_frame=False")
 
 
+def merge_tracker(who, track, rows, device):
+    """The tracker behind a merge that keeps `rows` record rows, from a wrapper's track= argument: None / False -> None; True -> an
+    orehip.WideBoxTracker on `device` sized for the merge (max_rows = rows, capacity = rows live rows plus as many survivors, within
+    the kernel's limit); a tracker object as given, if it is on `device` and takes `rows` rows."""
+    import orehip
+    if track is None or track is False:
+        return None
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if track is True:
+        return orehip.WideBoxTracker(device, capacity=min(2 * rows, orehip.TRACK_WIDE_MAX_TRACKS), max_rows=rows)
+    if not isinstance(track, orehip.BoxTracker) or track.device != device:
+        raise ValueError(f"{who}: track is None, True or an orehip.BoxTracker / WideBoxTracker on the model's device {device}")
+    if rows > track._row_limit():
+        raise ValueError(f"{who}: the merge keeps {rows} rows, the tracker takes {track._row_limit()}; use an orehip.WideBoxTracker "
+                         f"with max_rows >= {rows}")
+    return track
+
+
+def enqueue_track(tracker, p):
+    """The tracker's update behind a merge, on the current stream: reads the merged record's views and its device-side count."""
+    import orehip
+    boxes, scores, classes = orehip.record_views(p.rec, p.rows, p.rows)
+    return tracker.update(boxes, scores, classes, p.count)
+
+
 class _Pending:
-    """One frame between `_enqueue` and `_finish`: the result record, its device count, the output size, the pool and the plan."""
-    __slots__ = ("rec", "count", "rows", "out_hw", "pool", "plan", "full_hw")
+    """One frame between `_enqueue` and `_finish`: the result record, its device count, the output size, the pool and the plan; with
+    a tracker, the ids of the record's rows."""
+    __slots__ = ("rec", "count", "rows", "out_hw", "pool", "plan", "full_hw", "ids")
 
 
 class _Slot:
@@ -97,9 +126,13 @@ class TiledInference(nn.Module):
     MODEL.ROI_HEADS.NMS_THRESH_TEST.  Per source the rows are those `model.inference([{"image": source}], do_postprocess=False)`
     returns.  The wrapper owns its engines -- one of `fold` images at the tile's size, one at the resized frame's -- keyed like
     model.engine() and rebuilt when the key changes; the model's own cached engine is left alone.  Frames the device cannot run
-    (check_tiling_limits) are a ValueError before any GPU work; no source is ever skipped."""
+    (check_tiling_limits) are a ValueError before any GPU work; no source is ever skipped.
 
-    def __init__(self, cfg, model, tile=(640, 640), overlap=128, margin=2.0, full_frame=True, fold=1, max_detections=None):
+    track=True follows the merged detections from frame to frame in the order of the calls: an orehip.WideBoxTracker sized for
+    max_detections, on the model's device (or pass a tracker of your own).  The result's Instances then carries track_ids, and
+    track_stats() counts the tracks started.  The frame still has one host wait."""
+
+    def __init__(self, cfg, model, tile=(640, 640), overlap=128, margin=2.0, full_frame=True, fold=1, max_detections=None, track=None):
         super().__init__()
         from fewx.modeling.fsod.fsod_cen import CenterNet2Detector
         while not isinstance(model, CenterNet2Detector) and isinstance(getattr(model, "module", None), nn.Module):
@@ -124,6 +157,13 @@ class TiledInference(nn.Module):
         self.test_size = (int(cfg.INPUT.MIN_SIZE_TEST), int(cfg.INPUT.MAX_SIZE_TEST))
         self._slots = {}
         self._pools = {}
+        self.tracker = merge_tracker("TiledInference", track, self.topk + (self.topk & 1), model.device)
+
+    def track_stats(self):
+        """BoxTracker.stats() of the frames so far: tracks, started (the particle count), frames, dropped.  One host sync."""
+        if self.tracker is None:
+            return {"tracks": 0, "started": 0, "frames": 0, "dropped": 0}
+        return self.tracker.stats()
 
     # ---- plan and limits (host) ---------------------------------------------------------------------------------
     def _rows(self):
@@ -230,6 +270,8 @@ class TiledInference(nn.Module):
         res.pred_boxes = Boxes(boxes)
         res.scores = scores
         res.pred_classes = classes
+        if p.ids is not None:
+            res.track_ids = p.ids[:k]
         return {"instances": res}
 
     # ---- the device path ----------------------------------------------------------------------------------------
@@ -285,4 +327,5 @@ class TiledInference(nn.Module):
             p = _Pending()
             p.rec, p.count = orehip.tta_merge(pool, h, w, SCORE_THRESH, self.nms_thresh, self.topk)
             p.rows, p.out_hw, p.pool, p.plan, p.full_hw = self.topk + (self.topk & 1), (h, w), pool, plan, full_hw
+            p.ids = enqueue_track(self.tracker, p) if self.tracker is not None else None
             return p

@@ -1818,16 +1818,19 @@ def overlay_host(frame_hwc_u8, boxes, scores, classes=None, n=None, *, out=None,
 # Detection tracking (csrc/ore_track.hip; association contract "track v1", include/ore_hip.h).  BoxTracker holds the state and runs the
 # kernel, track_host is the numpy statement of the same contract: both give the same ids and the same state.
 TRACK_MAX_TRACKS = 1024                                    # ORE_TRACK_MAX_TRACKS
+TRACK_WIDE_MAX_TRACKS, TRACK_WIDE_MAX_ROWS = 16384, 8192   # ORE_TRACK_WIDE_MAX_TRACKS, ORE_TRACK_WIDE_MAX_ROWS (csrc/ore_track_wide.hip)
+TRACK_WIDE_DEFAULTS = {"capacity": 4096, "max_rows": 2048, "iou_thresh": 0.6, "ttl": 8, "class_aware": True, "score_thresh": 0.0}
 TRACK_DEFAULTS = {"capacity": 1024, "iou_thresh": 0.6, "ttl": 8, "class_aware": True, "score_thresh": 0.0}
 _TRACK_HEADER = 32                                         # bytes: int32 m, capacity; int64 next_id, frames, dropped
 
 
-def _track_params(who: str, capacity, iou_thresh, ttl, class_aware, score_thresh) -> dict:
-    """The parameters of a tracker, checked against the limits of ore_track_update_fwd; the thresholds as the fp32 the kernel takes."""
+def _track_params(who: str, capacity, iou_thresh, ttl, class_aware, score_thresh, max_tracks: int = TRACK_MAX_TRACKS) -> dict:
+    """The parameters of a tracker, checked against the limits of ore_track_update_fwd (max_tracks = TRACK_WIDE_MAX_TRACKS: of
+    ore_track_wide_update_fwd); the thresholds as the fp32 the kernel takes."""
     with np.errstate(over="ignore"):
         iou, sc = np.float32(iou_thresh), np.float32(score_thresh)
-    if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or not 1 <= capacity <= TRACK_MAX_TRACKS:
-        raise OreError(f"{who}: capacity {capacity!r} (1 .. {TRACK_MAX_TRACKS})")
+    if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or not 1 <= capacity <= max_tracks:
+        raise OreError(f"{who}: capacity {capacity!r} (1 .. {max_tracks})")
     if isinstance(ttl, bool) or not isinstance(ttl, (int, np.integer)) or not 1 <= ttl <= 1 << 20:
         raise OreError(f"{who}: ttl {ttl!r} (1 .. {1 << 20})")
     if not (np.isfinite(iou) and iou >= 0):
@@ -1844,13 +1847,15 @@ def track_state_empty(capacity: int = 1024) -> dict:
 
 
 def track_host(state, boxes, scores, classes=None, n=None, *, capacity: int = 1024, iou_thresh: float = 0.6, ttl: int = 8,
-               class_aware: bool = True, score_thresh: float = 0.0):
+               class_aware: bool = True, score_thresh: float = 0.0, wide: bool = False):
     """One update of the association contract "track v1" (include/ore_hip.h) on the host, numpy fp32 one operation at a time: what
-    ore_track_update_fwd computes, bit for bit.  state: a dict {boxes [m, 4] fp32, classes, ids [m] int64, ttl [m] int32, m, next_id,
+    ore_track_update_fwd computes, bit for bit.  wide=True: the same code with the limits of ore_track_wide_update_fwd (capacity up to
+    16384, up to 8192 rows) -- what that computes, bit for bit.  state: a dict {boxes [m, 4] fp32, classes, ids [m] int64, ttl [m] int32, m, next_id,
     frames, dropped} (None: the empty state); boxes [rows, 4], scores [rows], classes [rows] or None (all 0), n = rows taken (None: all).
     Returns (ids [rows] int64 with -1 for rows that are not live, the new state); `state` is left as it was."""
     as_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else (None if t is None else np.asarray(t))
-    p = _track_params("track_host", capacity, iou_thresh, ttl, class_aware, score_thresh)
+    p = _track_params("track_host", capacity, iou_thresh, ttl, class_aware, score_thresh, TRACK_WIDE_MAX_TRACKS if wide else TRACK_MAX_TRACKS)
+    max_rows = TRACK_WIDE_MAX_ROWS if wide else int(lib().ore_det_record_rows())
     st = track_state_empty() if state is None else state
     m = int(st["m"])
     tb = np.asarray(as_np(st["boxes"]), dtype=np.float32).reshape(-1, 4)[:m]
@@ -1858,8 +1863,8 @@ def track_host(state, boxes, scores, classes=None, n=None, *, capacity: int = 10
     b = np.ascontiguousarray(np.asarray(as_np(boxes), dtype=np.float32)).reshape(-1, 4)
     s = np.asarray(as_np(scores), dtype=np.float32).reshape(-1)
     rows = len(s)
-    if rows > int(lib().ore_det_record_rows()) or len(b) != rows:
-        raise OreError(f"track_host: {len(b)} boxes, {rows} scores (at most {int(lib().ore_det_record_rows())} rows)")
+    if rows > max_rows or len(b) != rows:
+        raise OreError(f"track_host: {len(b)} boxes, {rows} scores (at most {max_rows} rows)")
     c = np.zeros(rows, dtype=np.int64) if classes is None else np.asarray(as_np(classes), dtype=np.int64).reshape(-1)
     n = rows if n is None else min(max(int(n), 0), rows)
     with np.errstate(all="ignore"):
@@ -1916,9 +1921,21 @@ class BoxTracker:
     tracker, and the frames are associated in the order of the calls.  device "cpu" (or host tensors' tracker) runs track_host instead:
     the same ids."""
 
+    # what WideBoxTracker replaces: the limits, the three entry points, the workspace
+    MAX_TRACKS = TRACK_MAX_TRACKS
+    _STATE_BYTES, _RESET, _UPDATE = "ore_track_state_bytes", "ore_track_reset", "ore_track_update_fwd"
+    _host_kw: dict = {}
+
+    def _row_limit(self) -> int:
+        return int(lib().ore_det_record_rows())
+
+    def _workspace(self):
+        """(address or None, bytes) of the update's workspace."""
+        return None, 0
+
     def __init__(self, device, *, capacity: int = 1024, iou_thresh: float = 0.6, ttl: int = 8, class_aware: bool = True,
                  score_thresh: float = 0.0):
-        self.params = _track_params("BoxTracker", capacity, iou_thresh, ttl, class_aware, score_thresh)
+        self.params = _track_params(type(self).__name__, capacity, iou_thresh, ttl, class_aware, score_thresh, self.MAX_TRACKS)
         self.capacity = self.params["capacity"]
         self.device = torch.device(device)
         self._host = None if self.device.type == "cuda" else track_state_empty()
@@ -1926,7 +1943,7 @@ class BoxTracker:
         if self._host is None:
             if self.device.index is None:
                 self.device = torch.device("cuda", torch.cuda.current_device())
-            nbytes = int(lib().ore_track_state_bytes(self.capacity))
+            nbytes = int(getattr(lib(), self._STATE_BYTES)(self.capacity))
             with torch.cuda.device(self.device):
                 self._buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
                 self._event = torch.cuda.Event()
@@ -1958,7 +1975,7 @@ class BoxTracker:
             return
         with torch.cuda.device(self.device):
             cur = self._ordered()
-            _chk(lib().ore_track_reset(_ptr(self._buf), self.capacity, cur), "ore_track_reset")
+            _chk(getattr(lib(), self._RESET)(_ptr(self._buf), self.capacity, cur), self._RESET)
             self._updated(cur)
 
     def update(self, boxes, scores=None, classes=None, n_dev=None, *, out=None):
@@ -1979,7 +1996,7 @@ class BoxTracker:
             raise OreError("BoxTracker.update takes boxes and scores, or one Instances")
         if self._host is not None:
             n = int(n_dev.reshape(-1)[0]) if torch.is_tensor(n_dev) else n_dev
-            ids, self._host = track_host(self._host, boxes, scores, classes, n, **self.params)
+            ids, self._host = track_host(self._host, boxes, scores, classes, n, **self.params, **self._host_kw)
             ids = torch.from_numpy(ids)
             if out is not None:
                 out.copy_(ids)
@@ -1995,8 +2012,8 @@ class BoxTracker:
                 (rows == 0 or (boxes.stride(1) == 1 and boxes.stride(0) == 4)) and
                 (rows <= 1 or (scores.stride(0) == 1 and (classes is None or classes.stride(0) == 1)))):
             raise OreError("BoxTracker.update: boxes [n, 4] fp32, scores [n] fp32, classes [n] int64, rows contiguous")
-        if rows > int(lib().ore_det_record_rows()):
-            raise OreError(f"BoxTracker.update: {rows} rows (at most {int(lib().ore_det_record_rows())})")
+        if rows > self._row_limit():
+            raise OreError(f"{type(self).__name__}.update: {rows} rows (at most {self._row_limit()})")
         n_host = rows
         if n_dev is not None and not torch.is_tensor(n_dev):
             n_host, n_dev = min(max(int(n_dev), 0), rows), None
@@ -2010,10 +2027,11 @@ class BoxTracker:
                 raise OreError("BoxTracker.update: out is a contiguous int64 tensor [n] on the tracker's device")
             p = self.params
             cur = self._ordered()
-            _chk(lib().ore_track_update_fwd(_ptr(self._buf), self.capacity, _ptr(boxes) if rows else None, _ptr(scores) if rows else None,
-                                            _ptr(classes) if rows else None, _ptr(n_dev), n_host, rows, float(p["score_thresh"]),
-                                            float(p["iou_thresh"]), p["ttl"], int(p["class_aware"]), _ptr(out) if rows else None, None, 0,
-                                            cur), "ore_track_update_fwd")
+            ws, ws_bytes = self._workspace()
+            _chk(getattr(lib(), self._UPDATE)(_ptr(self._buf), self.capacity, _ptr(boxes) if rows else None, _ptr(scores) if rows else None,
+                                              _ptr(classes) if rows else None, _ptr(n_dev), n_host, rows, float(p["score_thresh"]),
+                                              float(p["iou_thresh"]), p["ttl"], int(p["class_aware"]), _ptr(out) if rows else None, ws,
+                                              ws_bytes, cur), self._UPDATE)
             self._updated(cur)
         return out
 
@@ -2048,6 +2066,46 @@ class BoxTracker:
         raw = self._buf[:_TRACK_HEADER].cpu().numpy()
         nxt, frames, dropped = (int(v) for v in raw[8:32].view(np.int64))
         return {"tracks": int(raw[:4].view(np.int32)[0]), "started": nxt, "frames": frames, "dropped": dropped}
+
+
+class WideBoxTracker(BoxTracker):
+    """BoxTracker for the rows of a tiled or TTA merge: up to 16384 tracks and 8192 rows per update (csrc/ore_track_wide.hip), the same
+    contract "track v1", the same ids and the same state as BoxTracker wherever both take the input.
+
+        tracker = WideBoxTracker(device)                   # capacity=4096, max_rows=2048, iou_thresh=0.6, ttl=8, ...
+        ids = tracker.update(boxes, scores, classes, n_dev)   # two launches on the current stream, no sync
+
+    max_rows is the most rows one update takes; it sizes the workspace (candidate bits of every track x row tile, the copy of the old
+    list).  Everything else -- update, reset, state, state_host, stats, the Instances form, out=, n_dev, the ordering across streams
+    -- is BoxTracker's.  device "cpu" runs track_host(wide=True)."""
+
+    MAX_TRACKS = TRACK_WIDE_MAX_TRACKS
+    _STATE_BYTES, _RESET, _UPDATE = "ore_track_wide_state_bytes", "ore_track_wide_reset", "ore_track_wide_update_fwd"
+    _host_kw = {"wide": True}
+
+    def __init__(self, device, *, capacity: int = 4096, max_rows: int = 2048, iou_thresh: float = 0.6, ttl: int = 8,
+                 class_aware: bool = True, score_thresh: float = 0.0):
+        if isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or not 0 <= max_rows <= TRACK_WIDE_MAX_ROWS:
+            raise OreError(f"WideBoxTracker: max_rows {max_rows!r} (0 .. {TRACK_WIDE_MAX_ROWS})")
+        self.max_rows = int(max_rows)
+        self._ws = None
+        super().__init__(device, capacity=capacity, iou_thresh=iou_thresh, ttl=ttl, class_aware=class_aware, score_thresh=score_thresh)
+        if self._host is None:
+            self._ws_bytes = int(lib().ore_track_wide_workspace_bytes(self.capacity, self.max_rows))
+            with torch.cuda.device(self.device):
+                self._ws = torch.empty(max(self._ws_bytes, 256), dtype=torch.uint8, device=self.device)
+
+    def _row_limit(self) -> int:
+        return self.max_rows
+
+    def _workspace(self):
+        return _ptr(self._ws), self._ws_bytes
+
+    def _ordered(self) -> int:
+        cur = super()._ordered()
+        if self._ws is not None and self._event_stream is not None and self._event_stream != cur:
+            self._ws.record_stream(torch.cuda.current_stream(self.device))
+        return cur
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -75,15 +75,20 @@ class TiledPredictor:
 
     builds the model as DefaultPredictor does (cfg.MODEL.WEIGHTS, the metadata of cfg.DATASETS.TEST[0]) and wraps it in
     fewx.modeling.TiledInference(cfg, model, **tiling).  The frame is BGR [h, w, 3] uint8 (numpy array, CPU or device tensor);
-    cfg.INPUT.FORMAT == "RGB" exchanges the channels on the device."""
+    cfg.INPUT.FORMAT == "RGB" exchanges the channels on the device.  track=True (or an orehip tracker) follows the merged detections
+    across the frames in the order of the calls: outputs["instances"].track_ids, and track_stats() counts the tracks started."""
 
-    def __init__(self, cfg, **tiling):
+    def __init__(self, cfg, track=None, **tiling):
         from fewx.modeling import TiledInference
         self.predictor = DefaultPredictor(cfg)
         self.cfg, self.model = self.predictor.cfg, self.predictor.model
         self.metadata = getattr(self.predictor, "metadata", None)
         self.input_format = self.predictor.input_format
-        self.tiled = TiledInference(self.cfg, self.model, **tiling)
+        self.tiled = TiledInference(self.cfg, self.model, track=track, **tiling)
+
+    def track_stats(self):
+        """TiledInference.track_stats(): tracks, started (the particle count), frames, dropped.  One host sync."""
+        return self.tiled.track_stats()
 
     def __call__(self, original_image):
         return self.tiled([{"image_raw": original_image, "swap_rb": self.input_format == "RGB"}])[0]

@@ -1187,6 +1187,25 @@ int ore_track_update_fwd(void* state, int32_t capacity, const float* boxes, cons
                          const int32_t* n_dev, int32_t n_host, int32_t max_rows, float score_thresh, float iou_thresh, int32_t ttl,
                          int32_t class_aware, int64_t* ids_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The wide form: the same contract "track v1" -- the same state buffer, the same ids and the same new list for the same inputs -- for
+ * the rows a tiled or TTA merge hands over: up to ORE_TRACK_WIDE_MAX_ROWS rows (the merge pool's 8192) and ORE_TRACK_WIDE_MAX_TRACKS
+ * tracks (that many live rows plus as many survivors) per update.  Two launches on `stream`, no host synchronisation, no allocation:
+ * the candidate bits of every (track, row) tile on the whole chip, then the matching and the new list in one workgroup.  The parameters
+ * are ore_track_update_fwd's; `workspace` is a 256-byte aligned device buffer of at least ore_track_wide_workspace_bytes(capacity,
+ * max_rows) bytes (0 for arguments out of range), disjoint from the state, ids_out and the row arrays; its contents mean nothing
+ * between calls.  ore_track_wide_state_bytes is ore_track_state_bytes with the wide limit (0 beyond it); a buffer written by the one
+ * form may be handed to the other while capacity and max_rows fit both.
+ * Limits (ORE_EINVAL before any launch): capacity 1 .. ORE_TRACK_WIDE_MAX_TRACKS, max_rows 0 .. ORE_TRACK_WIDE_MAX_ROWS, ttl 1 ..
+ * 1 << 20, iou_thresh finite and >= 0, score_thresh not NaN, boxes 16-byte aligned, a workspace that is too small. */
+#define ORE_TRACK_WIDE_MAX_TRACKS 16384
+#define ORE_TRACK_WIDE_MAX_ROWS 8192
+size_t ore_track_wide_state_bytes(int32_t capacity);
+size_t ore_track_wide_workspace_bytes(int32_t capacity, int32_t max_rows);
+int ore_track_wide_reset(void* state, int32_t capacity, void* stream);
+int ore_track_wide_update_fwd(void* state, int32_t capacity, const float* boxes, const float* scores, const int64_t* classes,
+                              const int32_t* n_dev, int32_t n_host, int32_t max_rows, float score_thresh, float iou_thresh, int32_t ttl,
+                              int32_t class_aware, int64_t* ids_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ heat maps ----------------- */
 /* Heat maps of a detection pass drawn over an interleaved [h][w][3] uint8 frame on the device (ref:demo_visualizer.py Have_a_Look /
  * visualize_grid_attention_v2; ref:fewx/modeling/fsod/debug.py debug_test): where the class-agnostic objectness fired, where the

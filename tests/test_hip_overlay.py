@@ -129,6 +129,24 @@ def test_two_runs_are_bit_equal(ore):
     assert np.array_equal(a, guarded_draw(ore, img, b, s, c, **kw)) and np.array_equal(a, want)
 
 
+def test_33_palettes_evict_the_oldest_tables(ore):
+    """The table cache holds 32: 33 distinct two-colour palettes (beside the atlas and the names) push the oldest tables out, the atlas
+    and the first palette among them, and a draw with the first palette afterwards uploads them again -- overlay_host's bytes every time."""
+    h, w = 32, 48
+    img = frame(h, w, 17)
+    b, s, c = OR.cases(h, w, seed=h + w, rows=6)
+    pals = [np.array([[7 * i + 1, 255 - 5 * i, 90], [3 * i, 40 + i, 200 - 2 * i]], np.uint8) for i in range(33)]
+    assert len({p.tobytes() for p in pals}) == 33
+    ore._OVERLAY_TABLES.clear()
+    for pal in pals + pals[:1]:
+        kw = dict(line_width=1, text_scale=1, names=NAMES, palette=pal, color_by="class")
+        want = ore.overlay_host(img, b, s, c, **kw)
+        assert (want != img).any()
+        assert np.array_equal(guarded_draw(ore, img, b, s, c, **kw), want)
+        assert len(ore._OVERLAY_TABLES) <= ore._OVERLAY_TABLES_MAX == 32
+    assert len(ore._OVERLAY_TABLES) == 32
+
+
 def test_limits_are_errors(ore):
     img = torch.zeros(16, 16, 3, dtype=torch.uint8, device="cuda")
     b = torch.tensor([[1.0, 1.0, 9.0, 9.0]], device="cuda")

@@ -46,7 +46,8 @@ for ev in prof.events():
         continue
     site = "?"
     for fr in (ev.stack or []):
-        if ("faster-orefsdet_amd" in fr or "/bench.py" in fr) and "orehip/__init__" not in fr:
+        # the binding's modules are not a call site; the autograd layers above them are
+        if ("faster-orefsdet_amd" in fr or "/bench.py" in fr) and ("orehip/" not in fr or "orehip/autograd" in fr):
             site = fr.split("faster-orefsdet_amd/")[-1][:90]
             break
     if site == "?":                                       # no Python frames (this torch build): the operand shapes tell the call site

@@ -5,7 +5,9 @@
 --heatmap objectness | attention | <buffer>[:<channel>] (p4, pos3:17, ...) lays that heat map of the detection pass under the boxes
 (--heatmap-alpha, --heatmap-colormap jet | gray).  --track follows the detections from frame to frame (ids that persist, boxes coloured and
 labelled by them) over a video, or over several --input images taken as a sequence in the given order, and prints the number of tracks
-started.  Images are decoded with Pillow and drawn on the device.  Video (--video-input, --webcam) needs OpenCV to decode and to show frames;
+started.  --track-motion belt (with --track) is for a scene that moves as one, a conveyor belt: the frame's shift is voted from the boxes
+and the tracks are moved by it before they are matched (--belt-radius: the largest shift per frame in pixels, --belt-bin: pixels per
+histogram bin), and the mean shift per frame is printed beside the tracks started.  Images are decoded with Pillow and drawn on the device.  Video (--video-input, --webcam) needs OpenCV to decode and to show frames;
 this package neither ships nor requires it, and the two flags say so when it is missing.
 --support-json ANN.json --support-root DIR [--shots N] enrols every category of a COCO json from its annotated images (under DIR) before
 the first frame: support crops and prototypes are computed on the device, in place of a support_feature.pkl.  With more than one
@@ -31,6 +33,12 @@ def get_parser():
     parser.add_argument("--heatmap-colormap", default="jet", choices=("jet", "gray"), help="the heat map's colour table (default: %(default)s)")
     parser.add_argument("--track", action="store_true", help="follow the detections across the frames: ids that persist, colours and labels by id; "
                         "needs --video-input, --webcam or several --input frames (a sequence in the given order); prints the tracks started")
+    parser.add_argument("--track-motion", choices=("belt",), default=None, help="with --track: 'belt' votes the one shift the whole frame shares "
+                        "and moves the tracks by it before matching (a conveyor belt); prints the mean shift per frame as well")
+    parser.add_argument("--belt-radius", type=int, default=None, metavar="PX", help="with --track-motion belt: the largest shift per frame and axis "
+                        "in pixels (default: 128; at most 64 bins of --belt-bin)")
+    parser.add_argument("--belt-bin", type=int, default=None, choices=(1, 2, 4, 8, 16), metavar="PX", help="with --track-motion belt: pixels per "
+                        "histogram bin, 1, 2, 4, 8 or 16 (default: 2)")
     parser.add_argument("--support-json", metavar="ANN.json", help="enrol every category of this COCO annotation file as a support class before "
                         "the first frame (instead of support_feature.pkl); needs --support-root")
     parser.add_argument("--support-root", metavar="DIR", help="the directory of the images --support-json names")
@@ -144,6 +152,15 @@ def main(argv=None):
         sys.exit("demo.py: --track needs a sequence: --video-input, --webcam or at least two --input frames")
     elif not args.output:
         sys.exit("demo.py: --input needs --output: pictures are written to files, there is no window to show them in")
+    if args.track_motion and not args.track:
+        sys.exit("demo.py: --track-motion goes with --track")
+    if (args.belt_radius is not None or args.belt_bin is not None) and args.track_motion != "belt":
+        sys.exit("demo.py: --belt-radius and --belt-bin go with --track-motion belt")
+    belt = {k: v for k, v in (("radius", args.belt_radius), ("bin", args.belt_bin)) if v is not None}
+    if args.track_motion == "belt":
+        bin_, radius = belt.get("bin", 2), belt.get("radius", 128)
+        if radius < 1 or -(-radius // bin_) > 64:
+            sys.exit(f"demo.py: --belt-radius {radius} at --belt-bin {bin_} is outside 1 .. {64 * bin_} (64 bins a side); use a larger bin")
     if bool(args.support_json) != bool(args.support_root) or (args.shots is not None and not args.support_json):
         sys.exit("demo.py: --support-json and --support-root go together (and --shots with them)")
     if args.shots is not None and args.shots < 1:
@@ -157,7 +174,10 @@ def main(argv=None):
         heatmap = heatmap_args(heatmap, "--heatmap")          # the flags alone, before anything is built
     except ValueError as err:
         sys.exit(f"demo.py: {err}")
-    demo = VisualizationDemo(setup_cfg(args), heatmap=heatmap, track=args.track)
+    if args.track_motion == "belt":
+        demo = VisualizationDemo(setup_cfg(args), heatmap=heatmap, track="belt", belt=belt)
+    else:
+        demo = VisualizationDemo(setup_cfg(args), heatmap=heatmap, track=args.track)
     if args.support_json:
         enrol_support(demo.predictor.model, args, log)
     if video:
@@ -167,7 +187,13 @@ def main(argv=None):
     else:
         run_images(demo, args, log)
     if args.track:
-        print(f"tracks started: {demo.track_stats()['started']}")
+        stats = demo.track_stats()
+        if args.track_motion == "belt":
+            k = max(stats["frames"], 1)
+            print(f"tracks started: {stats['started']}; mean shift per frame: ({stats.get('travel', (0, 0))[0] / k:.1f}, {stats.get('travel', (0, 0))[1] / k:.1f}) px "
+                  f"over {stats['frames']} frames, {stats.get('coasted', 0)} coasted")
+        else:
+            print(f"tracks started: {stats['started']}")
 
 
 if __name__ == "__main__":

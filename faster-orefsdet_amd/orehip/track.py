@@ -162,6 +162,13 @@ class BoxTracker:
         self._event.record(torch.cuda.current_stream(self.device))
         self._event_stream = cur
 
+    def _before_update(self, boxes, scores, classes, n_dev, n_host: int, rows: int, cur: int) -> None:
+        """What a subclass enqueues on the update's stream `cur` in front of the update, once every check of the rows has passed and
+        the stream follows the last update (orehip/belt.py moves the tracks here).  Nothing, in this class."""
+
+    def _before_host(self, boxes, scores, classes, n) -> None:
+        """The same in front of track_host, for a tracker on the host."""
+
     def reset(self) -> None:
         """The empty state: no tracks, next_id 0, the counters 0.  Enqueued on the current stream (device) like an update."""
         if self._host is not None:
@@ -190,6 +197,7 @@ class BoxTracker:
             raise OreError("BoxTracker.update takes boxes and scores, or one Instances")
         if self._host is not None:
             n = int(n_dev.reshape(-1)[0]) if torch.is_tensor(n_dev) else n_dev
+            self._before_host(boxes, scores, classes, n)
             ids, self._host = track_host(self._host, boxes, scores, classes, n, **self.params, **self._host_kw)
             ids = torch.from_numpy(ids)
             if out is not None:
@@ -222,6 +230,7 @@ class BoxTracker:
             p = self.params
             cur = self._ordered()
             ws, ws_bytes = self._workspace()
+            self._before_update(boxes, scores, classes, n_dev, n_host, rows, cur)
             _chk(getattr(lib(), self._UPDATE)(_ptr(self._buf), self.capacity, _ptr(boxes) if rows else None, _ptr(scores) if rows else None,
                                               _ptr(classes) if rows else None, _ptr(n_dev), n_host, rows, float(p["score_thresh"]),
                                               float(p["iou_thresh"]), p["ttl"], int(p["class_aware"]), _ptr(out) if rows else None, ws,

@@ -310,11 +310,19 @@ class VisualizationDemo:
     heatmap=kind -- "objectness", "attention", "<buffer>[:<channel>]", or a dict (heatmap_args) -- lays that heat map of the detection
     pass under the boxes; None (the default) draws the boxes alone.  track=True follows the detections across the frames of
     run_on_video (an orehip.BoxTracker, reset at the start of every call): ids that persist, boxes coloured and labelled by them;
-    track_stats() then counts the tracks started.  run_on_image ignores it."""
+    track_stats() then counts the tracks started.  track="belt" is the same with an orehip.BeltTracker, for a scene that moves as one
+    (a conveyor belt): the frame's shift is voted and the tracks are moved by it in front of every update, `belt` holds BeltTracker
+    keywords (bin, radius, ...), the tracker's frame is the size of each video's first frame, and track_stats() adds "shift", "travel",
+    "votes" and "coasted".  run_on_image ignores it."""
 
-    def __init__(self, cfg, instance_mode=ColorMode.IMAGE, parallel=False, heatmap=None, track=False):
+    def __init__(self, cfg, instance_mode=ColorMode.IMAGE, parallel=False, heatmap=None, track=False, belt=None):
         self.heatmap = heatmap_args(heatmap, "VisualizationDemo: heatmap")
+        if isinstance(track, str) and track != "belt":
+            raise ValueError(f'VisualizationDemo: track is False, True or "belt", got {track!r}')
+        if belt is not None and track != "belt":
+            raise ValueError('VisualizationDemo: belt= goes with track="belt"')
         self.track, self.tracker = bool(track), None
+        self.track_motion, self.belt = ("belt" if track == "belt" else None), dict(belt or {})
         if instance_mode not in (ColorMode.IMAGE, ColorMode.SEGMENTATION):
             raise NotImplementedError(f"VisualizationDemo: {instance_mode} needs instance masks; boxes only")
         self.instance_mode, self.parallel = instance_mode, bool(parallel)
@@ -364,13 +372,26 @@ class VisualizationDemo:
         """The demo's tracker on the model's device, built on first use and empty at the start of every video."""
         import orehip
         if self.tracker is None:
-            self.tracker = orehip.BoxTracker(self.predictor.model.device)
+            if self.track_motion == "belt":
+                self.tracker = orehip.BeltTracker(self.predictor.model.device, **self.belt)
+            else:
+                self.tracker = orehip.BoxTracker(self.predictor.model.device)
         else:
             self.tracker.reset()
         return self.tracker
 
+    def _framed(self, frames, tracker):
+        """The frames as they come; a belt tracker learns the size of the first one before it is used."""
+        first = True
+        for frame in frames:
+            if first:
+                tracker.set_frame(tuple(int(v) for v in frame.shape[:2]))
+            first = False
+            yield frame
+
     def track_stats(self):
-        """BoxTracker.stats() of the last run_on_video: tracks, started (the particle count), frames, dropped.  One host sync."""
+        """BoxTracker.stats() of the last run_on_video: tracks, started (the particle count), frames, dropped (track="belt": and shift,
+        travel, votes, coasted).  One host sync."""
         if self.tracker is None:
             return {"tracks": 0, "started": 0, "frames": 0, "dropped": 0}
         return self.tracker.stats()
@@ -396,6 +417,8 @@ class VisualizationDemo:
         tracker = None
         if self.track:
             tracker = self._tracker()
+            if self.track_motion == "belt":
+                frames = self._framed(frames, tracker)
         if self.parallel:
             draw = {"color_by": "track" if tracker is not None else "class"}
             pending = 0

@@ -1206,6 +1206,52 @@ int ore_track_wide_update_fwd(void* state, int32_t capacity, const float* boxes,
                               const int32_t* n_dev, int32_t n_host, int32_t max_rows, float score_thresh, float iou_thresh, int32_t ttl,
                               int32_t class_aware, int64_t* ids_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The belt's shift: "track v1" matches a row to a track's last observed box, so a track survives only while the scene moves less than
+ * about a quarter of a box per frame.  A conveyor belt moves rigidly and much faster; the one translation the frame shares is voted
+ * here from the boxes alone and every track box is moved by it BEFORE the update, which then associates as it always has.  The launches
+ * are enqueued on `stream` in front of ore_track_update_fwd / ore_track_wide_update_fwd: no host synchronisation, no allocation.
+ * Contract "belt shift v1" -- bit-exact, a function of the inputs alone:
+ *   Parameters: bin in {1, 2, 4, 8, 16} pixels per bin; half_bins K in 1 .. ORE_BELT_MAX_HALF_BINS, the window is (2K + 1)^2 bins, so
+ *     |shift| <= K * bin per axis; size_tol fp32, finite, 0 <= size_tol < 1; min_votes 1 .. 1 << 30; frame_h, frame_w both 0 (no frame
+ *     test) or both > 0; score_thresh and class_aware as in "track v1".
+ *   Inputs: the tracks 0 .. m - 1 of a "track v1" state buffer as they stand at entry; the frame's rows with that contract's conventions
+ *     (boxes, scores, classes or NULL, n = min(*n_dev if n_dev else n_host, max_rows)) and its rule for a live row.
+ *   Per box (track or row), one fp32 operation each: w = x1 - x0, h = y1 - y0, sx = x0 + x1, sy = y0 + y1.
+ *   A pair (track t, row d) votes iff d is live; the classes are equal, unless class_aware == 0; all four extents are > 0;
+ *     fabsf(wt - wd) <= size_tol * fmaxf(wt, wd) and the same for h (the difference, the absolute value, the product and the comparison
+ *     are single fp32 operations); and with inv = 1 / (2 * bin), qx = floorf((sxd - sxt) * inv + 0.5f), qy likewise, fabsf(qx) <= K and
+ *     fabsf(qy) <= K as floats (a NaN or an infinity fails).  The pair adds 1 to H[qy][qx] (int32).
+ *   Smoothing: S[qy][qx] = the sum of H over the 3 x 3 neighbourhood, bins outside the window counting 0.
+ *   Peak: the bin with the largest S; ties by |qx * bin - prev_dx| + |qy * bin - prev_dy| ascending (integers; the previous shift is
+ *     the belt state's dx, dy at entry, 0, 0 after a reset), then qy ascending, then qx ascending.  It is accepted iff S >= min_votes:
+ *     then dx = qx * bin, dy = qy * bin, votes = S.  Otherwise (m = 0 and n = 0 included) dx and dy keep their values -- the belt keeps
+ *     running -- votes = 0 and coasted += 1.  In both cases travel_x += dx, travel_y += dy and frames += 1.
+ *   Apply: every track box gets x0 += dx, x1 += dx, y0 += dy, y1 += dy, one fp32 add each: a track the detector misses travels with the
+ *     belt until its ttl runs out.  With a frame, a track whose moved box has x1 <= 0 || x0 >= frame_w || y1 <= 0 || y0 >= frame_h gets
+ *     ttl = 1: the update that follows drops it unless a row continues it (a NaN compares false: the track stays).  Nothing else of the
+ *     track state changes.
+ * The belt state is a caller-owned device buffer of ore_belt_state_bytes() = 64 bytes, 16-byte aligned: int32 dx, dy, votes, reserved (0);
+ * int64 travel_x, travel_y, frames, coasted; then 16 zero bytes.  ore_belt_reset writes zeros.
+ * Two forms, the same result.  Form 1 (capacity <= ORE_TRACK_MAX_TRACKS and max_rows <= ore_det_record_rows()): one launch of one
+ * workgroup, rows and histogram in LDS, no workspace (NULL is allowed).  Form 2 (capacity <= ORE_TRACK_WIDE_MAX_TRACKS, max_rows <=
+ * ORE_TRACK_WIDE_MAX_ROWS): the histogram's clear, a vote kernel over (track group, row tile) work items on the whole chip -- each block
+ * votes into its own LDS histogram and adds its non-zero bins to the workspace's with integer atomics -- and a one-workgroup finish:
+ * three operations on `stream`.  `workspace`: 256-byte aligned, at least ore_belt_workspace_bytes(capacity, max_rows, half_bins) bytes
+ * (what form 2 needs; 0 for arguments out of range); its contents mean nothing between calls.  ore_belt_shift_form: the form that
+ * form = 0 chooses, 1 or 2, or ORE_EINVAL.  form = 1 or 2 forces one (ORE_EINVAL if form 1 cannot take the shapes); form = 3 is form 2
+ * with every vote added straight to the workspace histogram, a measurement aid with the same result.
+ * Limits (ORE_EINVAL before any launch): the ranges above, boxes 16-byte aligned, the belt state, the track state, the workspace and the
+ * row arrays pairwise disjoint, a workspace that is too small. */
+#define ORE_BELT_MAX_HALF_BINS 64
+size_t ore_belt_state_bytes(void);
+int ore_belt_reset(void* belt, void* stream);
+size_t ore_belt_workspace_bytes(int32_t capacity, int32_t max_rows, int32_t half_bins);
+int ore_belt_shift_form(int32_t capacity, int32_t max_rows, int32_t half_bins);
+int ore_belt_shift_fwd(void* belt, void* track_state, int32_t capacity, const float* boxes, const float* scores, const int64_t* classes,
+                       const int32_t* n_dev, int32_t n_host, int32_t max_rows, float score_thresh, int32_t class_aware, int32_t bin,
+                       int32_t half_bins, float size_tol, int32_t min_votes, int32_t frame_h, int32_t frame_w, int32_t form,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ heat maps ----------------- */
 /* Heat maps of a detection pass drawn over an interleaved [h][w][3] uint8 frame on the device (ref:demo_visualizer.py Have_a_Look /
  * visualize_grid_attention_v2; ref:fewx/modeling/fsod/debug.py debug_test): where the class-agnostic objectness fired, where the

@@ -11,7 +11,11 @@ histogram bin), and the mean shift per frame is printed beside the tracks starte
 this package neither ships nor requires it, and the two flags say so when it is missing.
 --support-json ANN.json --support-root DIR [--shots N] enrols every category of a COCO json from its annotated images (under DIR) before
 the first frame: support crops and prototypes are computed on the device, in place of a support_feature.pkl.  With more than one
-category every one of them is detected (N-way)."""
+category every one of them is detected (N-way).
+--rectify-quad x0 y0 x1 y1 x2 y2 x3 y3 is for a camera that looks at the belt obliquely: the four points of the camera frame where the
+belt plane's corners top-left, top-right, bottom-right, bottom-left lie.  Every frame is warped into that plane on the device before
+anything else looks at it, and the outputs are written rectified, at --rectify-size W H (default: the input frame's size; there is no
+anti-aliasing, so keep it near the belt region's resolution in the camera frame)."""
 import argparse
 import glob
 import os
@@ -39,6 +43,11 @@ def get_parser():
                         "in pixels (default: 128; at most 64 bins of --belt-bin)")
     parser.add_argument("--belt-bin", type=int, default=None, choices=(1, 2, 4, 8, 16), metavar="PX", help="with --track-motion belt: pixels per "
                         "histogram bin, 1, 2, 4, 8 or 16 (default: 2)")
+    parser.add_argument("--rectify-quad", type=float, nargs=8, default=None, metavar="PX", help="x0 y0 x1 y1 x2 y2 x3 y3: where the belt plane's "
+                        "corners (top-left, top-right, bottom-right, bottom-left) lie in the camera frame; every frame is warped into that "
+                        "plane on the device first and the outputs are written rectified")
+    parser.add_argument("--rectify-size", type=int, nargs=2, default=None, metavar=("W", "H"), help="with --rectify-quad: the size of the "
+                        "rectified frame (default: the input frame's size)")
     parser.add_argument("--support-json", metavar="ANN.json", help="enrol every category of this COCO annotation file as a support class before "
                         "the first frame (instead of support_feature.pkl); needs --support-root")
     parser.add_argument("--support-root", metavar="DIR", help="the directory of the images --support-json names")
@@ -70,6 +79,27 @@ def enrol_support(model, args, log):
     if len(shots) > 1:
         model.support_classes = "all"
     log.info("enrolled %s from %s", ", ".join(f"class {c}: {n} shots" for c, n in shots.items()), args.support_json)
+
+
+def make_rectifier(args, cv2=None):
+    """--rectify-quad / --rectify-size as an orehip.Rectifier, or None.  Without a size it is the first input frame's."""
+    if args.rectify_quad is None:
+        return None
+    import orehip
+    if args.rectify_size is not None:
+        w, h = args.rectify_size
+    elif args.input:
+        from PIL import Image
+        with Image.open(input_paths(args.input)[0]) as im:
+            w, h = im.size
+    else:
+        capture = cv2.VideoCapture(0 if args.webcam else args.video_input)
+        w, h = int(capture.get(cv2.CAP_PROP_FRAME_WIDTH)), int(capture.get(cv2.CAP_PROP_FRAME_HEIGHT))
+        capture.release()
+    try:
+        return orehip.Rectifier(quad=[args.rectify_quad[k:k + 2] for k in range(0, 8, 2)], out_hw=(int(h), int(w)))
+    except ValueError as err:
+        sys.exit(f"demo.py: --rectify-quad / --rectify-size: {err}")
 
 
 def input_paths(patterns):
@@ -161,6 +191,8 @@ def main(argv=None):
         bin_, radius = belt.get("bin", 2), belt.get("radius", 128)
         if radius < 1 or -(-radius // bin_) > 64:
             sys.exit(f"demo.py: --belt-radius {radius} at --belt-bin {bin_} is outside 1 .. {64 * bin_} (64 bins a side); use a larger bin")
+    if args.rectify_size is not None and args.rectify_quad is None:
+        sys.exit("demo.py: --rectify-size goes with --rectify-quad")
     if bool(args.support_json) != bool(args.support_root) or (args.shots is not None and not args.support_json):
         sys.exit("demo.py: --support-json and --support-root go together (and --shots with them)")
     if args.shots is not None and args.shots < 1:
@@ -174,10 +206,11 @@ def main(argv=None):
         heatmap = heatmap_args(heatmap, "--heatmap")          # the flags alone, before anything is built
     except ValueError as err:
         sys.exit(f"demo.py: {err}")
+    rectify = make_rectifier(args, cv2)
     if args.track_motion == "belt":
-        demo = VisualizationDemo(setup_cfg(args), heatmap=heatmap, track="belt", belt=belt)
+        demo = VisualizationDemo(setup_cfg(args), heatmap=heatmap, track="belt", belt=belt, rectify=rectify)
     else:
-        demo = VisualizationDemo(setup_cfg(args), heatmap=heatmap, track=args.track)
+        demo = VisualizationDemo(setup_cfg(args), heatmap=heatmap, track=args.track, rectify=rectify)
     if args.support_json:
         enrol_support(demo.predictor.model, args, log)
     if video:

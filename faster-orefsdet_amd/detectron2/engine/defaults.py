@@ -22,9 +22,11 @@ class DefaultPredictor:
     loads `cfg.MODEL.WEIGHTS` (an empty string loads nothing), takes `cfg.DATASETS.TEST[0]`'s metadata, always receives a BGR image
     ([h, w, 3] uint8) and converts it to `cfg.INPUT.FORMAT`, resizes to `cfg.INPUT.MIN_SIZE_TEST` / `MAX_SIZE_TEST`.  The few-shot
     support set comes from the model's `init_model()` on the first call, as for every eval call; `predictor.model.set_support_dict(...)`
-    before that call installs one directly."""
+    before that call installs one directly.  rectify=orehip.Rectifier(...): the camera looks at the scene obliquely; every image is
+    uploaded and warped into the rectifier's plane on the device (contract "rectify v1") before the resize, and the Instances are in
+    rectified coordinates, at rectify.out_hw.  None (the default) enqueues exactly what it always has."""
 
-    def __init__(self, cfg):
+    def __init__(self, cfg, rectify=None):
         from detectron2.checkpoint import DetectionCheckpointer
         from detectron2.data import MetadataCatalog
         from detectron2.modeling import build_model
@@ -36,11 +38,28 @@ class DefaultPredictor:
         DetectionCheckpointer(self.model).load(cfg.MODEL.WEIGHTS)
         self.input_format = cfg.INPUT.FORMAT
         assert self.input_format in ["RGB", "BGR"], self.input_format
+        if rectify is not None and not (callable(rectify) and hasattr(rectify, "out_hw")):
+            raise ValueError("DefaultPredictor: rectify is None or an orehip.Rectifier")
+        self.rectify = rectify
+
+    def _rectified(self, image):
+        """The image on the model's device, warped by self.rectify on the current stream."""
+        import numpy as np
+        import orehip
+        if isinstance(image, np.ndarray):
+            image = torch.from_numpy(np.ascontiguousarray(image))
+        if not torch.is_tensor(image) or image.dim() != 3 or image.shape[2] != 3 or image.dtype != torch.uint8:
+            raise ValueError("DefaultPredictor: a rectified image is [h, w, 3] uint8")
+        dev = torch.device(self.model.device)
+        with torch.cuda.device(dev):
+            return self.rectify(orehip.to_device(image, dev).contiguous())
 
     def __call__(self, original_image):
         """original_image: [h, w, 3] uint8 in BGR order (numpy array, CPU or device tensor).  Returns the model's output for it:
-        {"instances": Instances} with pred_boxes / scores / pred_classes at (h, w)."""
+        {"instances": Instances} with pred_boxes / scores / pred_classes at (h, w); with rectify=, at rectify.out_hw."""
         with torch.no_grad():
+            if self.rectify is not None:
+                original_image = self._rectified(original_image)
             height, width = original_image.shape[:2]
             inputs = {"image_raw": original_image, "swap_rb": self.input_format == "RGB", "height": int(height), "width": int(width)}
             return self.model([inputs])[0]

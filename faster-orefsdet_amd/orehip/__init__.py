@@ -50,6 +50,8 @@ from .overlay import (OVERLAY_MAX_SIDE, OVERLAY_TEXT, OVERLAY_NAME, OVERLAY_PALE
 from .track import (TRACK_MAX_TRACKS, TRACK_WIDE_MAX_TRACKS, TRACK_WIDE_MAX_ROWS, TRACK_WIDE_DEFAULTS, TRACK_DEFAULTS, _TRACK_HEADER,
     _track_params, track_state_empty, track_host, BoxTracker, WideBoxTracker)
 from .belt import (BELT_MAX_HALF_BINS, BELT_BINS, BELT_DEFAULTS, belt_state_empty, belt_shift_host, BeltTracker, WideBeltTracker)
+from .rectify import (RECTIFY_MAX_SIDE, _rectify_m9, _rectify_hw, _rectify_fill, rectify_host, rectify_u8, homography_from_quad,
+    Rectifier)
 from .heatmap import (HEATMAP_MEAN, HEATMAP_MAX_LEVELS, HEATMAP_MAX_MAP_SIDE, HEATMAP_MAX_INPUT_SIDE, HEATMAP_MAX_STRIDE, HEATMAP_LUTS,
     _HEATMAP_TRANSFORMS, _HEATMAP_NORMS, _HEATMAP_ALPHA_MODES, _HEATMAP_LEVEL_BUFFERS, _HEATMAP_WS, _HEATMAP_WS_MAX, heatmap_lut,
     _heatmap_style, _heatmap_geometry, heat_kind, HeatSource, HeatLevels, heatmap_levels, _heatmap_levels_arg, heatmap_draw,

@@ -76,11 +76,13 @@ class TiledPredictor:
     builds the model as DefaultPredictor does (cfg.MODEL.WEIGHTS, the metadata of cfg.DATASETS.TEST[0]) and wraps it in
     fewx.modeling.TiledInference(cfg, model, **tiling).  The frame is BGR [h, w, 3] uint8 (numpy array, CPU or device tensor);
     cfg.INPUT.FORMAT == "RGB" exchanges the channels on the device.  track=True (or an orehip tracker) follows the merged detections
-    across the frames in the order of the calls: outputs["instances"].track_ids, and track_stats() counts the tracks started."""
+    across the frames in the order of the calls: outputs["instances"].track_ids, and track_stats() counts the tracks started.
+    rectify=orehip.Rectifier(...) warps the uploaded frame into the rectifier's plane in front of the tile gather (contract "rectify
+    v1"): the tiles are cut from the rectified frame and the Instances are at rectify.out_hw."""
 
-    def __init__(self, cfg, track=None, **tiling):
+    def __init__(self, cfg, track=None, rectify=None, **tiling):
         from fewx.modeling import TiledInference
-        self.predictor = DefaultPredictor(cfg)
+        self.predictor = DefaultPredictor(cfg, rectify=rectify)
         self.cfg, self.model = self.predictor.cfg, self.predictor.model
         self.metadata = getattr(self.predictor, "metadata", None)
         self.input_format = self.predictor.input_format
@@ -91,6 +93,8 @@ class TiledPredictor:
         return self.tiled.track_stats()
 
     def __call__(self, original_image):
+        if self.predictor.rectify is not None:                # upload and warp in front of the tile gather
+            original_image = self.predictor._rectified(original_image)
         return self.tiled([{"image_raw": original_image, "swap_rb": self.input_format == "RGB"}])[0]
 
 
@@ -119,6 +123,9 @@ class AsyncPredictor:
     update behind the pass, on the same stream, on the pending record and the device-side count: the result's Instances then carries
     track_ids, and a drawn frame is coloured and labelled by them (color_by "track") unless draw says otherwise.  The tracker orders
     its updates across the slots' streams on the device, so the frames are associated in `put` order with the passes still overlapping.
+    put(image, rectify=R) -- an orehip.Rectifier -- warps the frame into R's plane behind the slot's upload, on the slot's stream
+    (contract "rectify v1", one launch): the pass, the heat map, the tracker and the overlay see the rectified frame, the Instances and
+    "vis_image" are at R.out_hw, and there is still one host wait per frame.
 
     1 <= inflight <= 4: a process opens 4 hardware queues by default, and this class does not ask for more.  num_gpus must be 1: one
     process per device is a launcher's job.  The engines are keyed like model.engine(): a `put` that finds the weights or the support
@@ -195,17 +202,20 @@ class AsyncPredictor:
         return kw
 
     @torch.no_grad()
-    def put(self, image, draw=None, heatmap=None, track=None):
+    def put(self, image, draw=None, heatmap=None, track=None, rectify=None):
         import orehip
         if isinstance(image, np.ndarray):
             image = torch.from_numpy(np.ascontiguousarray(image))
         if not torch.is_tensor(image) or image.dim() != 3 or image.shape[2] != 3 or image.dtype != torch.uint8:
             raise ValueError("AsyncPredictor.put takes an [h, w, 3] uint8 BGR image")
         h, w = int(image.shape[0]), int(image.shape[1])
+        if rectify is not None and not isinstance(rectify, orehip.Rectifier):
+            raise ValueError("AsyncPredictor.put: rectify is an orehip.Rectifier")
+        oh, ow = (h, w) if rectify is None else rectify.out_hw     # the size everything behind the upload sees
         if track is not None and not (isinstance(track, orehip.BoxTracker) and track.device == torch.device(self.model.device)):
             raise ValueError("AsyncPredictor.put: track is an orehip.BoxTracker on the model's device")
         try:
-            draw_kw = self._draw_args(draw, h, w, track is not None) if draw else None
+            draw_kw = self._draw_args(draw, oh, ow, track is not None) if draw else None
         except orehip.OreError as err:
             raise ValueError(f"AsyncPredictor.put: {err}") from err
         heat_kw = heatmap_args(heatmap, "AsyncPredictor.put: heatmap")
@@ -217,7 +227,7 @@ class AsyncPredictor:
         slot = self._slots[self._next]                        # completion is first in, first out: the next slot in turn is free
         m, e = self.model, slot.engine
         p = _Pass()
-        p.slot, p.hw, p.vis, p.ids = slot, (h, w), None, None
+        p.slot, p.hw, p.vis, p.ids = slot, (oh, ow), None, None
         if image.is_cuda:                                     # the frame was produced on the caller's stream: the slot's stream follows it
             slot.stream.wait_stream(torch.cuda.current_stream(image.device))
         with torch.cuda.device(m.device), torch.cuda.stream(slot.stream):
@@ -234,9 +244,11 @@ class AsyncPredictor:
                 stage.copy_(image)                            # the slot's previous upload finished with its pass
                 raw, ours = torch.empty(h, w, 3, dtype=torch.uint8, device=m.device), True
                 raw.copy_(stage, non_blocking=True)
-            nh, nw = orehip.resize_shortest_edge_shape(h, w, m._test_size[0], m._test_size[1])
+            if rectify is not None:                           # one more launch behind the upload: the slot's own tensor from here on
+                raw, ours = rectify(raw), True
+            nh, nw = orehip.resize_shortest_edge_shape(oh, ow, m._test_size[0], m._test_size[1])
             img = orehip.resize_bilinear_u8(raw, nh, nw, swap_rb=self.input_format == "RGB")
-            p.rec = e.detect_classes_begin(img, h, w) if getattr(e, "class_ids", None) else e.detect_begin(img, h, w)
+            p.rec = e.detect_classes_begin(img, oh, ow) if getattr(e, "class_ids", None) else e.detect_begin(img, oh, ow)
             p.raw = raw
             try:                                              # in place on the slot's own upload; a caller's device frame is left as it was
                 if heat_kw is not None:
@@ -289,8 +301,8 @@ class AsyncPredictor:
     def __len__(self):
         return len(self._pending) + len(self._done)
 
-    def __call__(self, image, track=None):
-        self.put(image, track=track)
+    def __call__(self, image, track=None, rectify=None):
+        self.put(image, track=track, rectify=rectify)
         return self.get()
 
     def shutdown(self):
@@ -313,10 +325,15 @@ class VisualizationDemo:
     track_stats() then counts the tracks started.  track="belt" is the same with an orehip.BeltTracker, for a scene that moves as one
     (a conveyor belt): the frame's shift is voted and the tracks are moved by it in front of every update, `belt` holds BeltTracker
     keywords (bin, radius, ...), the tracker's frame is the size of each video's first frame, and track_stats() adds "shift", "travel",
-    "votes" and "coasted".  run_on_image ignores it."""
+    "votes" and "coasted".  run_on_image ignores it.  rectify=orehip.Rectifier(...): every frame is warped into the rectifier's plane
+    behind its upload (contract "rectify v1"); predictions and drawn frames are at rectify.out_hw, which is also a belt tracker's frame."""
 
-    def __init__(self, cfg, instance_mode=ColorMode.IMAGE, parallel=False, heatmap=None, track=False, belt=None):
+    def __init__(self, cfg, instance_mode=ColorMode.IMAGE, parallel=False, heatmap=None, track=False, belt=None, rectify=None):
+        import orehip
         self.heatmap = heatmap_args(heatmap, "VisualizationDemo: heatmap")
+        if rectify is not None and not isinstance(rectify, orehip.Rectifier):
+            raise ValueError("VisualizationDemo: rectify is None or an orehip.Rectifier")
+        self.rectify = rectify
         if isinstance(track, str) and track != "belt":
             raise ValueError(f'VisualizationDemo: track is False, True or "belt", got {track!r}')
         if belt is not None and track != "belt":
@@ -337,13 +354,17 @@ class VisualizationDemo:
         import orehip
         if isinstance(image, np.ndarray):
             image = torch.from_numpy(np.ascontiguousarray(image))
-        return orehip.to_device(image, self.predictor.model.device).contiguous()
+        frame = orehip.to_device(image, self.predictor.model.device).contiguous()
+        if self.rectify is not None:
+            with torch.cuda.device(frame.device):
+                frame = self.rectify(frame)
+        return frame
 
     def run_on_image(self, image):
         """image: [h, w, 3] uint8 in BGR order.  Returns the model's predictions and the drawn VisImage."""
         color_by = "class" if self.instance_mode == ColorMode.SEGMENTATION else "instance"
         if self.parallel:
-            self.predictor.put(image, draw={"color_by": color_by}, heatmap=self.heatmap)
+            self.predictor.put(image, draw={"color_by": color_by}, heatmap=self.heatmap, rectify=self.rectify)
             out = self.predictor.get()
             return {"instances": out["instances"]}, VisImage(out["vis_image"], "BGR")
         frame = self._upload(image)
@@ -381,11 +402,11 @@ class VisualizationDemo:
         return self.tracker
 
     def _framed(self, frames, tracker):
-        """The frames as they come; a belt tracker learns the size of the first one before it is used."""
+        """The frames as they come; a belt tracker learns the size of the first one (rectified: out_hw) before it is used."""
         first = True
         for frame in frames:
             if first:
-                tracker.set_frame(tuple(int(v) for v in frame.shape[:2]))
+                tracker.set_frame(self.rectify.out_hw if self.rectify is not None else tuple(int(v) for v in frame.shape[:2]))
             first = False
             yield frame
 
@@ -426,7 +447,7 @@ class VisualizationDemo:
                 if pending == self.predictor.default_buffer_size:
                     yield self.predictor.get()["vis_image"].cpu().numpy()
                     pending -= 1
-                self.predictor.put(frame, draw=draw, heatmap=self.heatmap, track=tracker)
+                self.predictor.put(frame, draw=draw, heatmap=self.heatmap, track=tracker, rectify=self.rectify)
                 pending += 1
             while pending:
                 yield self.predictor.get()["vis_image"].cpu().numpy()

@@ -1367,6 +1367,38 @@ int ore_batch_canvas_fwd(const void* slab, size_t slab_bytes, const int32_t* tab
                          int32_t query_u8, int32_t n_support, int32_t Hs, int32_t Ws, int32_t support_u8,
                          const float* pixel_mean, const float* pixel_std, float* out, size_t out_floats, void* stream);
 
+/* ------------------------------------------------------------------ rectification ------------- */
+/* A fixed camera that looks at the belt obliquely sees it in perspective: the far edge moves fewer pixels per frame than the near one
+ * ("belt shift v1" votes ONE translation), and box sizes are not comparable across the frame.  The remedy is to warp every frame into
+ * the belt plane with the installation's constant homography before anything else looks at it.  One launch on `stream`, no host
+ * synchronisation, no allocation, no table: the nine coefficients travel as kernel arguments, so the launch can be captured.
+ * Contract "rectify v1" -- bit-exact, a function of the inputs alone:
+ *   Inputs: a source frame S [hs][ws][3] uint8 interleaved, any channel order; nine fp32 coefficients m00 .. m22, row-major, which map
+ *     a pixel centre of the OUTPUT to continuous SOURCE coordinates (pixel (i, j) covers [j, j + 1) x [i, i + 1)); the output size (ho,
+ *     wo); a fill colour of 3 bytes.  All four extents lie in 1 .. ORE_RECTIFY_MAX_SIDE.
+ *   Per output pixel (i, j), every operation ONE IEEE binary32 operation in this order, nothing contracted, the divisions correctly
+ *   rounded:
+ *     xo = float(j) + 0.5f;  yo = float(i) + 0.5f
+ *     X = (m00 * xo + m01 * yo) + m02;  Y = (m10 * xo + m11 * yo) + m12;  Z = (m20 * xo + m21 * yo) + m22
+ *     u = X / Z - 0.5f;  v = Y / Z - 0.5f
+ *     inside <=> X, Y, Z finite and Z > 0 and -0.5f <= u <= float(ws) - 0.5f and -0.5f <= v <= float(hs) - 0.5f (a NaN is outside)
+ *     not inside: the three bytes are the fill colour
+ *     U = (int)floorf(u * 256.0f + 0.5f), V likewise (the product is a scaling by a power of two, exact; the sum is one binary32
+ *       addition of a value below 2^23, which the limit on the extents guarantees, so its result still resolves halves and the
+ *       conversion is exact: U is u rounded to the nearest 1/256, ties upwards, up to that one rounding)
+ *     x0 = U >> 8 (arithmetic), fx = U & 255; y0 = V >> 8, fy = V & 255; the taps x0, x0 + 1, y0, y0 + 1 are each clamped to the source
+ *     per channel, integers, with a = S[y0][x0], b = S[y0][x0 + 1], c = S[y0 + 1][x0], d = S[y0 + 1][x0 + 1]:
+ *       top = a * (256 - fx) + b * fx;  bot = c * (256 - fx) + d * fx;  out = (top * (256 - fy) + bot * fy + 32768) >> 16
+ *   The identity matrix returns the source byte for byte; an integer translation returns shifted bytes, with fill where the source ends.
+ *   NOT in the contract: anti-aliasing.  A strongly minifying warp aliases; choose (ho, wo) near the belt region's source resolution.
+ * fill_rgb: channel 0 in bits 0 .. 7, channel 1 in bits 8 .. 15, channel 2 in bits 16 .. 23 (the frame's own channel order).  src, dst
+ * and their rows may start at any byte; nothing outside src[0, hs * ws * 3) is read and nothing outside dst[0, ho * wo * 3) is written.
+ * ORE_EINVAL, with a message, before any launch: a null pointer, an extent outside 1 .. ORE_RECTIFY_MAX_SIDE, a coefficient that is
+ * not finite, a fill outside 0 .. 0xFFFFFF, dst overlapping src. */
+#define ORE_RECTIFY_MAX_SIDE 16384
+int ore_rectify_u8_fwd(const uint8_t* src, int32_t hs, int32_t ws, const float m9_host[9], uint8_t* dst, int32_t ho, int32_t wo,
+                       int32_t fill_rgb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

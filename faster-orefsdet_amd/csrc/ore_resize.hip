@@ -7,6 +7,9 @@
 // 16-byte loads, runs the horizontal pass LDS -> LDS (uint8 intermediate, planar), then the vertical pass LDS -> output planes.  The
 // intermediate never reaches HBM.  Form 2 (two launches): the intermediate [h][nw][3] lives in a caller workspace; taken when a tile's
 // staging exceeds ORE_RESIZE_LDS_BYTES (large reductions: the window grows with the ratio).  Same bytes either way.
+// k_support_fused (ore_support.hip) is form 1 inside a rectangle of a canvas; the two are kept as two bodies over the leaves of
+// ore_resize_internal.h because every shared form measured was slower here (profiles/EXPERIMENTS.md): a change to the staging, the
+// guards or the passes of one is to be made in the other.
 //
 // Exactness: coefficients are >= 0 and sum to 2^22 + at most ksize / 2 (each is rounded once), so an accumulator stays below
 // 2^21 + 255 * (2^22 + 8193) < 2^31: int32 is exact.
@@ -15,10 +18,7 @@
 
 namespace {
 
-constexpr int TW = ORE_RESIZE_TW, TH = ORE_RESIZE_TH, NT = 256;
-// threads of a one-launch block: a tile of a 3x reduction stages ~60 source rows, and with 1080x1920 -> 320x569 only 180 tiles exist for
-// 256 CUs, so the block's own width is what hides its latencies (measured 14.3 / 9.7 / 8.1 us at 256 / 512 / 1024; profiles/EXPERIMENTS.md)
-constexpr int NTF = 1024;
+constexpr int TW = ORE_RESIZE_TW, TH = ORE_RESIZE_TH, NT = 256, NTF = ORE_RESIZE_NTF;
 
 __device__ __forceinline__ uint32_t clip8(int32_t acc) { return ore_resize_clip8(acc); }
 
@@ -100,16 +100,7 @@ __global__ __launch_bounds__(NTF) void k_resize_fused(const FusedArgs a) {
         int32_t a0, a1, a2, a3;
         ore_resize_vtaps_lds(col, TW, cnt, k, a0, a1, a2, a3);
         uint8_t* o = a.dst + ((size_t)c * a.nh + (y0 + y)) * a.nw + x0 + x4;
-        const int n = tw - x4;
-        const uint32_t b0 = clip8(a0), b1 = clip8(a1), b2 = clip8(a2), b3 = clip8(a3);
-        if (n >= 4 && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
-            *reinterpret_cast<uint32_t*>(o) = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
-        } else {
-            o[0] = (uint8_t)b0;
-            if (n > 1) o[1] = (uint8_t)b1;
-            if (n > 2) o[2] = (uint8_t)b2;
-            if (n > 3) o[3] = (uint8_t)b3;
-        }
+        ore_resize_store4(o, tw - x4, clip8(a0), clip8(a1), clip8(a2), clip8(a3));
     }
 }
 
@@ -118,15 +109,7 @@ __global__ __launch_bounds__(NT) void k_resize_h(const uint8_t* __restrict__ src
                                                 const int32_t* __restrict__ xb, const int32_t* __restrict__ kx, int32_t ksx) {
     const int x = blockIdx.x * NT + threadIdx.x, r = blockIdx.y;
     if (x >= nw || r >= h) return;
-    const int xmin = xb[2 * x], cnt = xb[2 * x + 1];
-    const uint8_t* p = src + ((size_t)r * w + xmin) * 3;
-    const int32_t* k = kx + (size_t)x * ksx;
-    int32_t acc0, acc1, acc2;
-    ore_resize_taps_mem(p, 3, cnt, k, acc0, acc1, acc2);
-    uint8_t* o = mid + ((size_t)r * nw + x) * 3;
-    o[0] = (uint8_t)clip8(acc0);
-    o[1] = (uint8_t)clip8(acc1);
-    o[2] = (uint8_t)clip8(acc2);
+    ore_resize_hpass_mem(src + (size_t)r * w * 3, w, xb, kx, ksx, x, mid + ((size_t)r * nw + x) * 3);
 }
 
 __global__ __launch_bounds__(NT) void k_resize_v(const uint8_t* __restrict__ mid, int32_t nw, uint8_t* __restrict__ dst, int32_t nh,
@@ -149,8 +132,7 @@ using FusedLds = ore_resize_fused_lds;
 FusedLds fused_lds(int32_t h, int32_t w, int32_t nh, int32_t nw) { return ore_resize_fused_lds_of(h, w, nh, nw, TH, TW); }
 
 bool sizes_ok(int32_t h, int32_t w, int32_t nh, int32_t nw) {
-    return h >= 1 && w >= 1 && nh >= 1 && nw >= 1 && h <= ORE_RESIZE_MAX_SIDE && w <= ORE_RESIZE_MAX_SIDE && nh <= ORE_RESIZE_MAX_SIDE &&
-           nw <= ORE_RESIZE_MAX_SIDE;
+    return ore_resize_side_ok(h) && ore_resize_side_ok(w) && ore_resize_side_ok(nh) && ore_resize_side_ok(nw);
 }
 
 }  // namespace
@@ -167,19 +149,16 @@ extern "C" size_t ore_resize_workspace_bytes(int32_t h, int32_t w, int32_t nh, i
 
 extern "C" size_t ore_resize_table_ints(int32_t h, int32_t w, int32_t nh, int32_t nw) {
     if (!sizes_ok(h, w, nh, nw)) return 0;
-    return (size_t)nw * 2 + (size_t)nh * 2 + (size_t)nw * ore_resize_ksize(w, nw) + (size_t)nh * ore_resize_ksize(h, nh);
+    return ore_resize_layout_of(h, w, nh, nw).total;
 }
 
 extern "C" int ore_resize_tables_host(int32_t h, int32_t w, int32_t nh, int32_t nw, int32_t* tables_host) {
     ORE_CHECK_ARG(sizes_ok(h, w, nh, nw), "ore_resize_tables_host: %dx%d -> %dx%d outside [1, %d]", h, w, nh, nw, ORE_RESIZE_MAX_SIDE);
     ORE_CHECK_ARG(tables_host, "ore_resize_tables_host: null table");
-    int32_t* xb = tables_host;
-    int32_t* yb = xb + (size_t)nw * 2;
-    int32_t* kx = yb + (size_t)nh * 2;
-    int32_t* ky = kx + (size_t)nw * ore_resize_ksize(w, nw);
-    int rc = ore_resize_plan(w, nw, xb, kx, nullptr);
+    const ore_resize_layout t = ore_resize_layout_of(h, w, nh, nw);
+    int rc = ore_resize_plan(w, nw, tables_host + t.xb, tables_host + t.kx, nullptr);
     if (rc != ORE_OK) return rc;
-    return ore_resize_plan(h, nh, yb, ky, nullptr);
+    return ore_resize_plan(h, nh, tables_host + t.yb, tables_host + t.ky, nullptr);
 }
 
 extern "C" int ore_resize_bilinear_u8_fwd(const uint8_t* src_hwc, int32_t h, int32_t w, uint8_t* dst_chw, int32_t nh, int32_t nw,
@@ -188,11 +167,12 @@ extern "C" int ore_resize_bilinear_u8_fwd(const uint8_t* src_hwc, int32_t h, int
     ORE_CHECK_ARG(sizes_ok(h, w, nh, nw), "ore_resize_bilinear_u8_fwd: %dx%d -> %dx%d outside [1, %d]", h, w, nh, nw, ORE_RESIZE_MAX_SIDE);
     ORE_CHECK_ARG(src_hwc && dst_chw && tables_dev, "ore_resize_bilinear_u8_fwd: null pointer");
     ORE_CHECK_ARG(form == 0 || form == ORE_RESIZE_FORM_LDS || form == ORE_RESIZE_FORM_WORKSPACE, "ore_resize_bilinear_u8_fwd: form %d", form);
-    const int32_t ksx = ore_resize_ksize(w, nw), ksy = ore_resize_ksize(h, nh);
-    const int32_t* xb = tables_dev;
-    const int32_t* yb = xb + (size_t)nw * 2;
-    const int32_t* kx = yb + (size_t)nh * 2;
-    const int32_t* ky = kx + (size_t)nw * ksx;
+    const ore_resize_layout t = ore_resize_layout_of(h, w, nh, nw);
+    const int32_t ksx = t.ksx, ksy = t.ksy;
+    const int32_t* xb = tables_dev + t.xb;
+    const int32_t* yb = tables_dev + t.yb;
+    const int32_t* kx = tables_dev + t.kx;
+    const int32_t* ky = tables_dev + t.ky;
     hipStream_t s = (hipStream_t)stream;
     const FusedLds l = fused_lds(h, w, nh, nw);
     const bool fits = l.bytes <= (size_t)ORE_RESIZE_LDS_BYTES;

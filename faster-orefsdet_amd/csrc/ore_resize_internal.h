@@ -1,7 +1,10 @@
 // Window arithmetic of the 8-bit antialiased BILINEAR resample (Pillow's ImagingResample), shared by the host planner
 // (ore_resize_plan.cpp) and the launcher (ore_resize.hip), which sizes a tile's LDS from the first and last window of the tile.
 // Also what the whole-image kernels (ore_resize.hip) and the support-crop kernels (ore_support.hip, ore_support_plan.cpp) have in
-// common: the tile and its LDS sizing, the 16-byte staging address, the guarded granule, the tap loops and the final clip.
+// common: the side range, the layout of a size pair's tables, the tile, its block width and its LDS sizing, the 16-byte staging
+// address, the guarded granule, the tap loops, the final clip, the word-or-bytes store and the horizontal pass of the workspace form.
+// The two fused tile kernels (k_resize_fused, k_support_fused) string the same leaves together but stay two bodies: every shared
+// form of them that was measured made the resize of 1080x1920 -> 562x1000 slower than its own body (profiles/EXPERIMENTS.md).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -10,7 +13,13 @@
 #define ORE_RESIZE_MAX_SIDE 8192
 #define ORE_RESIZE_TW 64             // output tile of a one-launch block: 16 rows x 64 columns
 #define ORE_RESIZE_TH 16
+// threads of a one-launch block: a tile of a 3x reduction stages ~60 source rows, and with 1080x1920 -> 320x569 only 180 tiles exist for
+// 256 CUs, so the block's own width is what hides its latencies (measured 14.3 / 9.7 / 8.1 us at 256 / 512 / 1024; profiles/EXPERIMENTS.md)
+#define ORE_RESIZE_NTF 1024
 #define ORE_RESIZE_LDS_BYTES (64 * 1024)   // dynamic LDS a launch may ask for without opting in to more
+
+// a side of a frame, a rectangle, an output or a canvas
+static inline bool ore_resize_side_ok(int32_t n) { return n >= 1 && n <= ORE_RESIZE_MAX_SIDE; }
 
 struct ore_resize_axis {
     double scale, filterscale, support;
@@ -72,6 +81,18 @@ static inline ore_resize_fused_lds ore_resize_fused_lds_of(int32_t h, int32_t w,
 // the same for a resample whose output lands at (dy0, dx0) of a canvas that is cut into tiles from its own corner (a support crop)
 static inline ore_resize_fused_lds ore_resize_fused_lds_at(int32_t h, int32_t w, int32_t nh, int32_t nw, int32_t dy0, int32_t dx0) {
     return ore_resize_fused_lds_of(h, w, nh, nw, ORE_RESIZE_TH - dy0 % ORE_RESIZE_TH, ORE_RESIZE_TW - dx0 % ORE_RESIZE_TW);
+}
+
+// The tables of one size pair, one run of int32 words: x bounds [nw][2] | y bounds [nh][2] | x coefficients [nw][ksx] | y coefficients
+// [nh][ksy].  xb .. ky are the word offsets of the four inside the run, total its length.
+struct ore_resize_layout { int32_t ksx, ksy; size_t xb, yb, kx, ky, total; };
+
+static inline ore_resize_layout ore_resize_layout_of(int32_t h, int32_t w, int32_t nh, int32_t nw) {
+    ore_resize_layout t;
+    t.ksx = ore_resize_axis_of(w, nw).ksize, t.ksy = ore_resize_axis_of(h, nh).ksize;
+    t.xb = 0, t.yb = t.xb + (size_t)nw * 2, t.kx = t.yb + (size_t)nh * 2, t.ky = t.kx + (size_t)nw * t.ksx;
+    t.total = t.ky + (size_t)nh * t.ksy;
+    return t;
 }
 
 #ifdef __HIPCC__
@@ -149,5 +170,30 @@ __device__ __forceinline__ void ore_resize_taps_mem(const uint8_t* p, size_t ste
         acc1 += (int32_t)q[1] * kk;
         acc2 += (int32_t)q[2] * kk;
     }
+}
+
+// four neighbouring bytes of an output row, as one word where the address allows; n = how many of them the row still has
+__device__ __forceinline__ void ore_resize_store4(uint8_t* o, int n, uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3) {
+    if (n >= 4 && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
+        *reinterpret_cast<uint32_t*>(o) = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+    } else {
+        o[0] = (uint8_t)b0;
+        if (n > 1) o[1] = (uint8_t)b1;
+        if (n > 2) o[2] = (uint8_t)b2;
+        if (n > 3) o[3] = (uint8_t)b3;
+    }
+}
+
+// Workspace form, horizontal pass: output column x of one source row of a rectangle (`row` = its first pixel, sw = its pixels) -> the
+// three bytes at o.  A window that leaves the row (tables of another size pair) writes nothing.  It takes a row and the tables as plain
+// arguments: a kernel that took a whole descriptor struct as its argument was 0.3 us slower on 1080 rows (profiles/EXPERIMENTS.md).
+__device__ __forceinline__ void ore_resize_hpass_mem(const uint8_t* row, int sw, const int32_t* xb, const int32_t* kx, int ksx, int x, uint8_t* o) {
+    const int xmin = xb[2 * x], cnt = xb[2 * x + 1];
+    if (xmin < 0 || cnt < 0 || cnt > ksx || xmin + cnt > sw) return;
+    int32_t acc0, acc1, acc2;
+    ore_resize_taps_mem(row + (size_t)xmin * 3, 3, cnt, kx + (size_t)x * ksx, acc0, acc1, acc2);
+    o[0] = (uint8_t)ore_resize_clip8(acc0);
+    o[1] = (uint8_t)ore_resize_clip8(acc1);
+    o[2] = (uint8_t)ore_resize_clip8(acc2);
 }
 #endif

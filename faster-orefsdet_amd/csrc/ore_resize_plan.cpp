@@ -6,13 +6,12 @@
 #include "ore_resize_internal.h"
 
 extern "C" int32_t ore_resize_ksize(int32_t in, int32_t out) {
-    if (in < 1 || out < 1 || in > ORE_RESIZE_MAX_SIDE || out > ORE_RESIZE_MAX_SIDE) return 0;
+    if (!ore_resize_side_ok(in) || !ore_resize_side_ok(out)) return 0;
     return ore_resize_axis_of(in, out).ksize;
 }
 
 extern "C" int ore_resize_plan(int32_t in, int32_t out, int32_t* bounds_host, int32_t* coeffs_host, int32_t* ksize_out) {
-    ORE_CHECK_ARG(in >= 1 && out >= 1 && in <= ORE_RESIZE_MAX_SIDE && out <= ORE_RESIZE_MAX_SIDE,
-                  "ore_resize_plan: sizes %d -> %d outside [1, %d]", in, out, ORE_RESIZE_MAX_SIDE);
+    ORE_CHECK_ARG(ore_resize_side_ok(in) && ore_resize_side_ok(out), "ore_resize_plan: sizes %d -> %d outside [1, %d]", in, out, ORE_RESIZE_MAX_SIDE);
     ORE_CHECK_ARG(bounds_host && coeffs_host, "ore_resize_plan: null table");
     const ore_resize_axis a = ore_resize_axis_of(in, out);
     const double ss = 1.0 / a.filterscale;

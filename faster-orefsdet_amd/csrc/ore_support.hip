@@ -17,7 +17,7 @@
 
 namespace {
 
-constexpr int TW = ORE_RESIZE_TW, TH = ORE_RESIZE_TH, NT = 256, NTF = 1024;   // NTF: as k_resize_fused (one tile's latencies hide in the block's own width)
+constexpr int TW = ORE_RESIZE_TW, TH = ORE_RESIZE_TH, NT = 256, NTF = ORE_RESIZE_NTF;
 
 struct Job {
     const uint8_t* src; int32_t h, w;
@@ -42,18 +42,6 @@ __device__ __forceinline__ Job load_job(const int32_t* jobs, int k) {
 }
 
 __device__ __forceinline__ uint32_t fill_of(int32_t fill_rgb, int c) { return ((uint32_t)fill_rgb >> (8 * c)) & 255u; }
-
-// four neighbouring canvas bytes, as one word where the address allows; n = how many of them the row still has
-__device__ __forceinline__ void store4(uint8_t* o, int n, uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3) {
-    if (n >= 4 && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
-        *reinterpret_cast<uint32_t*>(o) = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
-    } else {
-        o[0] = (uint8_t)b0;
-        if (n > 1) o[1] = (uint8_t)b1;
-        if (n > 2) o[2] = (uint8_t)b2;
-        if (n > 3) o[3] = (uint8_t)b3;
-    }
-}
 
 __global__ __launch_bounds__(NTF) void k_support_fused(const int32_t* __restrict__ jobs, uint8_t* __restrict__ dst, int32_t S, int32_t fill_rgb) {
     extern __shared__ uint4 smem_u4[];
@@ -135,7 +123,7 @@ __global__ __launch_bounds__(NTF) void k_support_fused(const int32_t* __restrict
             if (x4 + 3 >= xa && x4 + 3 < xe) b3 = ore_resize_clip8(a3);
         }
         uint8_t* o = dst + (((size_t)blockIdx.z * 3 + c) * S + (Y0 + y)) * S + X0 + x4;
-        store4(o, tw - x4, b0, b1, b2, b3);
+        ore_resize_store4(o, tw - x4, b0, b1, b2, b3);
     }
 }
 
@@ -145,18 +133,12 @@ __global__ __launch_bounds__(NT) void k_support_h(const int32_t* __restrict__ jo
     const int nw = a.dx1 - a.dx0, sh = a.ry1 - a.ry0;
     const int x = blockIdx.x * NT + threadIdx.x, r = blockIdx.y;
     if (a.form != ORE_RESIZE_FORM_WORKSPACE || x >= nw || r >= sh) return;
-    const int xmin = a.xb[2 * x], cnt = a.xb[2 * x + 1];
-    if (xmin < 0 || cnt < 0 || cnt > a.ksx || xmin + cnt > a.rx1 - a.rx0) return;
-    const uint8_t* p = a.src + ((size_t)(a.ry0 + r) * a.w + a.rx0 + xmin) * 3;
-    int32_t acc0, acc1, acc2;
-    ore_resize_taps_mem(p, 3, cnt, a.kx + (size_t)x * a.ksx, acc0, acc1, acc2);
-    uint8_t* o = ws + a.ws_off + ((size_t)r * nw + x) * 3;
-    o[0] = (uint8_t)ore_resize_clip8(acc0);
-    o[1] = (uint8_t)ore_resize_clip8(acc1);
-    o[2] = (uint8_t)ore_resize_clip8(acc2);
+    ore_resize_hpass_mem(a.src + ((size_t)(a.ry0 + r) * a.w + a.rx0) * 3, a.rx1 - a.rx0, a.xb, a.kx, a.ksx, x, ws + a.ws_off + ((size_t)r * nw + x) * 3);
 }
 
-// ---- workspace form, vertical and fill: one canvas row per block, four neighbouring columns of one plane per thread
+// ---- workspace form, vertical and fill: one canvas row per block, four neighbouring columns of one plane per thread.
+// Not merged with k_resize_v on purpose: that one takes one pixel (three planes) per thread across a wide image and has no fill to
+// write; this one covers a narrow canvas with word stores, fill included.  One mapping for both would change the speed of one of them.
 __global__ __launch_bounds__(NT) void k_support_v(const int32_t* __restrict__ jobs, const uint8_t* __restrict__ ws, uint8_t* __restrict__ dst,
                                                   int32_t S, int32_t fill_rgb) {
     const Job a = load_job(jobs, blockIdx.z);
@@ -183,7 +165,7 @@ __global__ __launch_bounds__(NT) void k_support_v(const int32_t* __restrict__ jo
             for (int t = 0; t < cnt; ++t) acc += (int32_t)q[(size_t)t * nw * 3] * k[t];
             b[j] = ore_resize_clip8(acc);
         }
-        store4(dst + (((size_t)blockIdx.z * 3 + c) * S + Y) * S + X, S - X, b[0], b[1], b[2], b[3]);
+        ore_resize_store4(dst + (((size_t)blockIdx.z * 3 + c) * S + Y) * S + X, S - X, b[0], b[1], b[2], b[3]);
     }
 }
 
@@ -194,7 +176,7 @@ inline int64_t word64(const int32_t* r, int lo, int hi) { return (int64_t)(((uin
 extern "C" int ore_support_crop_u8_fwd(const int32_t* jobs_dev, const int32_t* jobs_host, size_t buffer_ints, int32_t K, int32_t S,
                                        int32_t fill_rgb, uint8_t* dst, void* workspace, size_t workspace_bytes, void* stream) {
     ORE_CHECK_ARG(jobs_dev && jobs_host && dst, "ore_support_crop_u8_fwd: null pointer");
-    ORE_CHECK_ARG(K >= 1 && K <= 65535 && S >= 1 && S <= ORE_RESIZE_MAX_SIDE, "ore_support_crop_u8_fwd: K %d (1 .. 65535), size %d", K, S);
+    ORE_CHECK_ARG(K >= 1 && K <= 65535 && ore_resize_side_ok(S), "ore_support_crop_u8_fwd: K %d (1 .. 65535), size %d", K, S);
     ORE_CHECK_ARG(buffer_ints >= (size_t)K * ORE_SUPPORT_JOB_INTS && buffer_ints <= (size_t)INT32_MAX, "ore_support_crop_u8_fwd: a buffer of %zu words for %d jobs", buffer_ints, K);
     // every record against the frame, the canvas, the buffer and the workspace, and its LDS sizing against the sizing the kernel's
     // carve assumes: nothing is launched on a record that could send a kernel outside them
@@ -204,19 +186,20 @@ extern "C" int ore_support_crop_u8_fwd(const int32_t* jobs_dev, const int32_t* j
         const int32_t* r = jobs_host + (size_t)k * ORE_SUPPORT_JOB_INTS;
         const int32_t h = r[ORE_SJ_H], w = r[ORE_SJ_W], rx0 = r[ORE_SJ_RX0], ry0 = r[ORE_SJ_RX0 + 1], rx1 = r[ORE_SJ_RX0 + 2], ry1 = r[ORE_SJ_RX0 + 3];
         const int32_t dx0 = r[ORE_SJ_DX0], dy0 = r[ORE_SJ_DX0 + 1], dx1 = r[ORE_SJ_DX0 + 2], dy1 = r[ORE_SJ_DX0 + 3];
-        ORE_CHECK_ARG(word64(r, ORE_SJ_FRAME_LO, ORE_SJ_FRAME_HI) != 0 && h >= 1 && w >= 1 && h <= ORE_RESIZE_MAX_SIDE && w <= ORE_RESIZE_MAX_SIDE,
+        ORE_CHECK_ARG(word64(r, ORE_SJ_FRAME_LO, ORE_SJ_FRAME_HI) != 0 && ore_resize_side_ok(h) && ore_resize_side_ok(w),
                       "ore_support_crop_u8_fwd: job %d: frame %dx%d", k, h, w);
         ORE_CHECK_ARG(0 <= rx0 && rx0 < rx1 && rx1 <= w && 0 <= ry0 && ry0 < ry1 && ry1 <= h, "ore_support_crop_u8_fwd: job %d: source rectangle (%d, %d, %d, %d) outside the %dx%d frame",
                       k, rx0, ry0, rx1, ry1, h, w);
         ORE_CHECK_ARG(0 <= dx0 && dx0 < dx1 && dx1 <= S && 0 <= dy0 && dy0 < dy1 && dy1 <= S, "ore_support_crop_u8_fwd: job %d: destination rectangle (%d, %d, %d, %d) outside the %d canvas",
                       k, dx0, dy0, dx1, dy1, S);
         const int32_t sw = rx1 - rx0, sh = ry1 - ry0, nw = dx1 - dx0, nh = dy1 - dy0;
-        const int32_t ksx = ore_resize_ksize(sw, nw), ksy = ore_resize_ksize(sh, nh);
-        ORE_CHECK_ARG(r[ORE_SJ_KSX] == ksx && r[ORE_SJ_KSY] == ksy, "ore_support_crop_u8_fwd: job %d: tap counts (%d, %d), planned (%d, %d)", k, r[ORE_SJ_KSX], r[ORE_SJ_KSY], ksx, ksy);
+        const ore_resize_layout t = ore_resize_layout_of(sh, sw, nh, nw);
+        ORE_CHECK_ARG(r[ORE_SJ_KSX] == t.ksx && r[ORE_SJ_KSY] == t.ksy, "ore_support_crop_u8_fwd: job %d: tap counts (%d, %d), planned (%d, %d)", k, r[ORE_SJ_KSX], r[ORE_SJ_KSY], t.ksx, t.ksy);
+        // each table where its own record word puts it, with the layout's length, behind the records and inside the buffer
         const int64_t lo = (int64_t)K * ORE_SUPPORT_JOB_INTS, hi = (int64_t)buffer_ints;
-        ORE_CHECK_ARG(r[ORE_SJ_XB] >= lo && (int64_t)r[ORE_SJ_XB] + nw * 2 <= hi && r[ORE_SJ_YB] >= lo && (int64_t)r[ORE_SJ_YB] + nh * 2 <= hi &&
-                      r[ORE_SJ_KX] >= lo && (int64_t)r[ORE_SJ_KX] + (int64_t)nw * ksx <= hi && r[ORE_SJ_KY] >= lo && (int64_t)r[ORE_SJ_KY] + (int64_t)nh * ksy <= hi,
-                      "ore_support_crop_u8_fwd: job %d: tables outside the buffer", k);
+        auto inside = [&](int32_t at, size_t n) { return at >= lo && (int64_t)at + (int64_t)n <= hi; };
+        ORE_CHECK_ARG(inside(r[ORE_SJ_XB], t.yb - t.xb) && inside(r[ORE_SJ_YB], t.kx - t.yb) && inside(r[ORE_SJ_KX], t.ky - t.kx) &&
+                      inside(r[ORE_SJ_KY], t.total - t.ky), "ore_support_crop_u8_fwd: job %d: tables outside the buffer", k);
         const ore_resize_fused_lds l = ore_resize_fused_lds_at(sh, sw, nh, nw, dy0, dx0);
         if (r[ORE_SJ_FORM] == ORE_RESIZE_FORM_LDS) {
             ORE_CHECK_ARG(l.bytes <= (size_t)ORE_RESIZE_LDS_BYTES && r[ORE_SJ_LDS_R] == l.R && r[ORE_SJ_LDS_S] == l.S,

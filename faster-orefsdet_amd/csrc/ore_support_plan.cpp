@@ -1,7 +1,7 @@
 // Host planner of the support crops ("support crop v1", include/ore_hip.h): the integer geometry of one (frame size, box, S, context),
 // the box inside the crop in fp32 (no contraction: this file is built with -ffp-contract=off), the job's form and LDS sizing, and its
-// resample tables -- which are ore_resize_plan's, one call per axis, so that Pillow's coefficient arithmetic exists once.
-// Host only: callable without a GPU.
+// resample tables -- which are ore_resize_plan's, one call per axis, so that Pillow's coefficient arithmetic exists once, laid out in
+// the job buffer as ore_resize_layout_of lays out any size pair's tables.  Host only: callable without a GPU.
 #include <math.h>
 #include <string.h>
 #include "ore_common.h"
@@ -24,7 +24,7 @@ inline int32_t to_i32(float v) {
 }
 
 bool geometry(int32_t h, int32_t w, const float* b, int32_t S, int32_t c, Geom* g) {
-    if (!b || h < 1 || w < 1 || h > ORE_RESIZE_MAX_SIDE || w > ORE_RESIZE_MAX_SIDE || c < 0 || S > ORE_RESIZE_MAX_SIDE || S - 2 * c < 1) return false;
+    if (!b || !ore_resize_side_ok(h) || !ore_resize_side_ok(w) || c < 0 || !ore_resize_side_ok(S) || S - 2 * c < 1) return false;
     for (int i = 0; i < 4; ++i)
         if (!isfinite(b[i])) return false;
     const int32_t T = S - 2 * c;
@@ -47,9 +47,7 @@ bool geometry(int32_t h, int32_t w, const float* b, int32_t S, int32_t c, Geom* 
     return g->sw >= 1 && g->sh >= 1 && g->nw >= 1 && g->nh >= 1 && g->dx0 >= 0 && g->dy0 >= 0 && g->dx1 <= S && g->dy1 <= S;
 }
 
-inline size_t table_ints(const Geom& g) {
-    return (size_t)g.nw * 2 + (size_t)g.nh * 2 + (size_t)g.nw * ore_resize_axis_of(g.sw, g.nw).ksize + (size_t)g.nh * ore_resize_axis_of(g.sh, g.nh).ksize;
-}
+inline size_t table_ints(const Geom& g) { return ore_resize_layout_of(g.sh, g.sw, g.nh, g.nw).total; }
 
 inline ore_resize_fused_lds lds_of(const Geom& g) { return ore_resize_fused_lds_at(g.sh, g.sw, g.nh, g.nw, g.dy0, g.dx0); }
 
@@ -90,11 +88,10 @@ extern "C" int ore_support_crop_plan(int32_t h, int32_t w, const float* box_xyxy
     ORE_CHECK_ARG(geometry(h, w, box_xyxy, S, context, &g),
                   "ore_support_crop_plan: frame %dx%d, size %d, context %d: the box lies outside the frame or a size is out of range", h, w, S, context);
     ORE_CHECK_ARG(record_host && buffer_host, "ore_support_crop_plan: null buffer");
-    const size_t n = table_ints(g);
-    ORE_CHECK_ARG(table_off >= 0 && workspace_off >= 0 && (uint64_t)table_off + n <= (uint64_t)INT32_MAX,
+    const ore_resize_layout t = ore_resize_layout_of(g.sh, g.sw, g.nh, g.nw);
+    ORE_CHECK_ARG(table_off >= 0 && workspace_off >= 0 && (uint64_t)table_off + t.total <= (uint64_t)INT32_MAX,
                   "ore_support_crop_plan: table offset %lld outside an int32 word index", (long long)table_off);
-    const int32_t ksx = ore_resize_axis_of(g.sw, g.nw).ksize, ksy = ore_resize_axis_of(g.sh, g.nh).ksize;
-    const int32_t xb = (int32_t)table_off, yb = xb + g.nw * 2, kx = yb + g.nh * 2, ky = kx + g.nw * ksx;
+    const int32_t xb = (int32_t)(table_off + t.xb), yb = (int32_t)(table_off + t.yb), kx = (int32_t)(table_off + t.kx), ky = (int32_t)(table_off + t.ky);
     int rc = ore_resize_plan(g.sw, g.nw, buffer_host + xb, buffer_host + kx, nullptr);
     if (rc != ORE_OK) return rc;
     rc = ore_resize_plan(g.sh, g.nh, buffer_host + yb, buffer_host + ky, nullptr);
@@ -108,7 +105,7 @@ extern "C" int ore_support_crop_plan(int32_t h, int32_t w, const float* box_xyxy
     r[ORE_SJ_RX0] = g.rx0, r[ORE_SJ_RX0 + 1] = g.ry0, r[ORE_SJ_RX0 + 2] = g.rx1, r[ORE_SJ_RX0 + 3] = g.ry1;
     r[ORE_SJ_DX0] = g.dx0, r[ORE_SJ_DX0 + 1] = g.dy0, r[ORE_SJ_DX0 + 2] = g.dx1, r[ORE_SJ_DX0 + 3] = g.dy1;
     r[ORE_SJ_XB] = xb, r[ORE_SJ_YB] = yb, r[ORE_SJ_KX] = kx, r[ORE_SJ_KY] = ky;
-    r[ORE_SJ_KSX] = ksx, r[ORE_SJ_KSY] = ksy;
+    r[ORE_SJ_KSX] = t.ksx, r[ORE_SJ_KSY] = t.ksy;
     r[ORE_SJ_FORM] = l.bytes <= (size_t)ORE_RESIZE_LDS_BYTES ? ORE_RESIZE_FORM_LDS : ORE_RESIZE_FORM_WORKSPACE;
     r[ORE_SJ_LDS_R] = l.R, r[ORE_SJ_LDS_S] = l.S;
     r[ORE_SJ_WS_LO] = (int32_t)(uint32_t)wo, r[ORE_SJ_WS_HI] = (int32_t)(uint32_t)(wo >> 32);

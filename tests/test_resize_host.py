@@ -9,10 +9,12 @@ from PIL import Image
 
 from conftest import PKG
 
-# (h, w) -> (nh, nw): both directions, ratios 0.04 .. 25, an identity, one-axis-only cases, window clamping at a tiny input, ksize 51
+# (h, w) -> (nh, nw): both directions, ratios 0.04 .. 25, an identity, one-axis-only cases, window clamping at a tiny input, ksize 51,
+# and (last, behind the pairs other tests take by position) two outputs smaller than one 16 x 64 tile of the device kernel: narrower
+# than 16 columns, and a row shorter than one 4-byte store under 65-tap windows
 PAIRS = [((480, 640), (600, 800)), ((1200, 1600), (600, 800)), ((1080, 1920), (563, 1000)), ((333, 500), (600, 901)),
          ((37, 53), (600, 859)), ((768, 1024), (600, 800)), ((600, 800), (600, 800)), ((2000, 3000), (600, 900)),
-         ((500, 333), (901, 600)), ((3, 5), (320, 533)), ((8000, 6000), (320, 240))]
+         ((500, 333), (901, 600)), ((3, 5), (320, 533)), ((8000, 6000), (320, 240)), ((37, 53), (7, 13)), ((64, 96), (16, 3))]
 
 
 def pil_resize(img, nh, nw):

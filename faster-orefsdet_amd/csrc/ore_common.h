@@ -106,6 +106,11 @@ int roi_predict_post(const float* h, int32_t C, int32_t h_parts, const float* h_
                      int32_t topk, float* det_boxes, float* det_scores, int64_t* det_src, int32_t* det_count,
                      const float* post_dev, float* fin_boxes, float* fin_scores, int32_t* fin_count,
                      int32_t* host_count, void* workspace, size_t workspace_bytes, void* stream);
+// ROIAlign forward for both feature storages (bf16: the maps are bf16 tensors): ore_roi_align_fwd / _bf16_fwd with box_image = null,
+// ore_roi_align_batched_fwd with box_image [n_host] (csrc/ore_roi.hip)
+int roi_align_fwd(const void* const* feat, const int32_t* ld, const int32_t* coff, const int32_t* H, const int32_t* W, const float* scales_host,
+                  int32_t n_levels, int32_t min_level, int32_t C, int32_t pooled, const float* boxes, const int32_t* n_dev, int32_t n_host,
+                  int32_t cap, float* out, void* stream, const int32_t* box_image, bool bf16);
 // N-way pass: merge of the K per-class detection lists (det_boxes / det_scores / det_count of class slot k at k * cap rows / k * 4 words)
 // into one list -- score descending, ties by class slot, then by row -- cut at topk, then detector_postprocess into fin_* and the
 // caller's record (csrc/ore_roi.hip, k_roi_merge_classes).  class_ids [K] int64 device.
@@ -128,11 +133,4 @@ inline PredictWs predict_ws_layout(int32_t cap) {
     w.nms = (o + 255) & ~(size_t)255;
     return w;
 }
-}
-
-namespace oremisc {
-// N-way fan-out correlation and the query copy in front of it (csrc/ore_misc.hip)
-int correlation_classes(const float* q, int32_t q_ld, int32_t q_coff, int32_t n_levels, const int32_t* H, const int32_t* W, int32_t C,
-                        int32_t K, const float* k11s, const float* k13s, const float* k31s, float* out, int32_t out_ld, void* stream);
-int copy_cols(const float* src, int32_t src_ld, int32_t src_coff, int32_t rows, int32_t C, float* dst, int32_t dst_ld, void* stream);
 }

@@ -10,6 +10,9 @@
 // The OSA concat, the eSE product, the FPN upsample+add, torch.cat((attn,q)) and the GroupNorm output
 // are never materialised.  Reference call sites: include/ore_hip.h.
 //
+// Activations are fp32 or (ORE_CONV_BF16S engines) bf16: a Buf knows its element size, and the non-conv layer ops are called through
+// their storage-tagged launchers (ore_layer_ops.h; ROIAlign: oreroi::roi_align_fwd) with e->sb(), once per site.
+//
 // Deep bodies (ore_engine_set_blocks: V-39 / V-57 / V-99-eSE): a stage runs blocks[s] OSA blocks; the blocks j >= 2 add their input
 // to their output (identity blocks) and end in ONE launch each at one image per pass (ore_ese_gate_residual_fwd), DESIGN.md 7o.
 #include <map>
@@ -19,6 +22,7 @@
 #include <string.h>
 #include "ore_common.h"
 #include "ore_conv_internal.h"
+#include "ore_layer_ops.h"
 #include <algorithm>
 
 
@@ -36,7 +40,14 @@ struct Conv {
 // depthwise-separable unit of the *-dw-* bodies (ore_dwpw_fwd): depthwise taps [C][9], pointwise weights [C][C], folded FrozenBN
 struct DwUnit { float* w_dw = nullptr; float* w_pw = nullptr; float* scale = nullptr; float* shift = nullptr; int C = 0, stride = 1; };
 
-struct Buf { float* p = nullptr; int ld = 0; size_t rows = 0; };
+// a row-major matrix [rows][ld].  Activations are fp32 or, in ORE_CONV_BF16S engines, bf16 (esz bytes per element): all offset
+// arithmetic into one lives here, and the launchers take the untyped pointer with the engine's storage (ore_layer_ops.h)
+struct Buf {
+    void* p = nullptr; int ld = 0; size_t rows = 0; int esz = 4;
+    void* row(size_t r) const { return static_cast<char*>(p) + r * ld * esz; }
+    float* f32() const { return static_cast<float*>(p); }    // what is fp32 in every engine: the head rows, the deep / depthwise / N-way bodies
+    uint16_t* bf16() const { return static_cast<uint16_t*>(p); }   // the one C entry that exists for bf16 only (GroupNorm apply)
+};
 
 struct Geo { int B, H, W, Hp, Wp; int h[6], w[6]; };  // h[1]=Hp/2 (stem), h[2]=Hp/4 ... h[5]=Hp/32
 
@@ -90,8 +101,6 @@ struct ore_engine {
     bool head_pred_valu = true;                  // k_head_pred (VALU) instead of the MFMA conv for the head's last step (A/B: ORE_HEAD_MFMA=1)
     Buf tn;                                      // bf16 storage only: GroupNorm + ReLU of the tower, materialised (the DMA-fed kernels cannot touch their A operand)
     bool sb() const { return conv_precision == ORE_CONV_BF16S; }
-    // element offset into an ACTIVATION buffer (fp32, or bf16 in ORE_CONV_BF16S engines)
-    float* at(float* base, size_t elems) const { return sb() ? reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(base) + elems) : base + elems; }
     float* gate[4] = {};
     float* lat_scaled[3] = {};                   // bs = 1: the lateral weights times the stage's eSE gate (written by the gate kernel)
     float* gn_mul = nullptr, *gn_add = nullptr;  // [3*B][C]
@@ -167,6 +176,12 @@ struct ore_engine {
         ORE_HIP(hipMemcpy(*dst, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
         return ORE_OK;
     }
+    int upload_to(float** dst, const float* src, size_t n) {   // *dst is allocated on its first upload and written again by the later ones
+        int rc;
+        if (!*dst && (rc = dalloc(dst, n))) return rc;
+        ORE_HIP(hipMemcpy(*dst, src, n * sizeof(float), hipMemcpyHostToDevice));
+        return ORE_OK;
+    }
     const HostTensor* get(const std::string& n) const {
         auto it = host.find(n);
         return it == host.end() ? nullptr : &it->second;
@@ -210,22 +225,31 @@ int make_wino(ore_engine* e, Conv* c) {
     return ORE_OK;
 }
 
+// FrozenBN `norm` (.weight, .bias, .running_mean, .running_var of C channels) folded to the (scale, shift) of a conv's epilogue
+int fold_bn(ore_engine* e, const std::string& norm, int C, std::vector<float>* sc, std::vector<float>* sh) {
+    const HostTensor *g, *b, *m, *v;
+    int rc;
+    if ((rc = need(e, norm + ".weight", &g, {C}))) return rc;
+    if ((rc = need(e, norm + ".bias", &b, {C}))) return rc;
+    if ((rc = need(e, norm + ".running_mean", &m, {C}))) return rc;
+    if ((rc = need(e, norm + ".running_var", &v, {C}))) return rc;
+    sc->resize(C); sh->resize(C);
+    for (int n = 0; n < C; ++n) {  // d2z:layers/batch_norm.py:48-49
+        (*sc)[n] = g->v[n] * (1.0f / sqrtf(v->v[n] + 1e-5f));
+        (*sh)[n] = b->v[n] - m->v[n] * (*sc)[n];
+    }
+    return ORE_OK;
+}
+
 // conv (no bias) + FrozenBN folded to (scale, shift) applied in the epilogue; weights stay unscaled.
 int make_conv_bn(ore_engine* e, const std::string& name, int Cin, int Cout, int k, int stride, Conv* c) {
-    const HostTensor *w, *g, *b, *m, *v;
+    const HostTensor* w;
     int rc;
     if ((rc = need(e, name + "/conv.weight", &w, {Cout, Cin, k, k}))) return rc;
-    if ((rc = need(e, name + "/norm.weight", &g, {Cout}))) return rc;
-    if ((rc = need(e, name + "/norm.bias", &b, {Cout}))) return rc;
-    if ((rc = need(e, name + "/norm.running_mean", &m, {Cout}))) return rc;
-    if ((rc = need(e, name + "/norm.running_var", &v, {Cout}))) return rc;
+    std::vector<float> sc, sh;
+    if ((rc = fold_bn(e, name + "/norm", Cout, &sc, &sh))) return rc;
     std::vector<float> packed(ore_packed_weight_floats(Cout, Cin, k, k));
     ore_pack_conv_weight_host(w->v.data(), Cout, Cin, k, k, packed.data());
-    std::vector<float> sc(Cout), sh(Cout);
-    for (int n = 0; n < Cout; ++n) {  // d2z:layers/batch_norm.py:48-49
-        sc[n] = g->v[n] * (1.0f / sqrtf(v->v[n] + 1e-5f));
-        sh[n] = b->v[n] - m->v[n] * sc[n];
-    }
     if ((rc = e->upload(&c->w, packed))) return rc;
     if ((rc = e->upload(&c->scale, sc))) return rc;
     if ((rc = e->upload(&c->shift, sh))) return rc;
@@ -236,22 +260,15 @@ int make_conv_bn(ore_engine* e, const std::string& name, int Cin, int Cout, int 
 
 // name/dw_conv3x3 [C,1,3,3] + name/pw_conv1x1 [C,C,1,1] + name/pw_norm (d2z:modeling/backbone/vovnet.py:110-130); fp32 whatever the mode
 int make_dw_unit(ore_engine* e, const std::string& name, int C, int stride, DwUnit* u) {
-    const HostTensor *wd, *wp, *g, *b, *m, *v;
+    const HostTensor *wd, *wp;
     int rc;
     ORE_CHECK_ARG(C % 16 == 0, "ore_engine_finalize: depthwise unit %s of %d channels (a multiple of 16)", name.c_str(), C);
     if ((rc = need(e, name + "/dw_conv3x3.weight", &wd, {C, 1, 3, 3}))) return rc;
     if ((rc = need(e, name + "/pw_conv1x1.weight", &wp, {C, C, 1, 1}))) return rc;
-    if ((rc = need(e, name + "/pw_norm.weight", &g, {C}))) return rc;
-    if ((rc = need(e, name + "/pw_norm.bias", &b, {C}))) return rc;
-    if ((rc = need(e, name + "/pw_norm.running_mean", &m, {C}))) return rc;
-    if ((rc = need(e, name + "/pw_norm.running_var", &v, {C}))) return rc;
+    std::vector<float> sc, sh;
+    if ((rc = fold_bn(e, name + "/pw_norm", C, &sc, &sh))) return rc;
     std::vector<float> packed(ore_packed_weight_floats(C, C, 1, 1));
     ore_pack_conv_weight_host(wp->v.data(), C, C, 1, 1, packed.data());
-    std::vector<float> sc(C), sh(C);
-    for (int n = 0; n < C; ++n) {
-        sc[n] = g->v[n] * (1.0f / sqrtf(v->v[n] + 1e-5f));
-        sh[n] = b->v[n] - m->v[n] * sc[n];
-    }
     if ((rc = e->upload(&u->w_dw, wd->v)) || (rc = e->upload(&u->w_pw, packed))) return rc;
     if ((rc = e->upload(&u->scale, sc)) || (rc = e->upload(&u->shift, sh))) return rc;
     u->C = C; u->stride = stride;
@@ -274,16 +291,17 @@ int make_conv_bias(ore_engine* e, const std::string& name, int Cin, int Cout, in
 }
 
 int alloc_buf(ore_engine* e, Buf* b, size_t rows, int ld, bool activation = true) {
-    b->ld = ld; b->rows = rows;
+    const bool bf16 = activation && e->sb();
+    b->ld = ld; b->rows = rows; b->esz = bf16 ? 2 : 4;
     // bf16 storage: half the bytes, plus slack for the 32-byte over-read of a row's last K chunk when Cin % 32 == 16 (zero weights)
-    const size_t floats = (activation && e->sb()) ? (rows * ld + 1) / 2 + 16 : rows * ld;
-    int rc = e->dalloc(&b->p, floats);
+    const size_t floats = bf16 ? (rows * ld + 1) / 2 + 16 : rows * ld;
+    float* p = nullptr;
+    int rc = e->dalloc(&p, floats);
     if (rc) return rc;
-    if (activation && e->sb()) ORE_HIP(hipMemset(b->p, 0, floats * sizeof(float)));
+    b->p = p;
+    if (bf16) ORE_HIP(hipMemset(b->p, 0, floats * sizeof(float)));
     return ORE_OK;
 }
-
-int pool_out(int n) { int o = (n - 3 + 1) / 2 + 1; if (n < 3) o = 1; if ((o - 1) * 2 >= n) --o; return o < 1 ? 1 : o; }
 
 Geo make_geo(int B, int H, int W) {
     Geo g{};
@@ -291,74 +309,69 @@ Geo make_geo(int B, int H, int W) {
     g.Hp = round_up(H, 32); g.Wp = round_up(W, 32);
     g.h[1] = g.Hp / 2; g.w[1] = g.Wp / 2;
     g.h[2] = (g.h[1] - 1) / 2 + 1; g.w[2] = (g.w[1] - 1) / 2 + 1;  // stem_3: 3x3 s2 p1
-    for (int k = 3; k <= 5; ++k) { g.h[k] = pool_out(g.h[k - 1]); g.w[k] = pool_out(g.w[k - 1]); }
+    for (int k = 3; k <= 5; ++k) { g.h[k] = ore_pool_out(g.h[k - 1]); g.w[k] = ore_pool_out(g.w[k - 1]); }
     return g;
 }
 
 struct Run {
-    ore_engine* e; hipStream_t st; double flops = 0.0; int rc = ORE_OK; bool prof = false;
-    // one launch over all pyramid levels (level-major rows)
-    void conv_levels(const Conv& c, const float* in, int in_ld, int in_coff, int B, const int* H, const int* W, float* out,
-                     int out_ld, int out_coff, int ep_stride = 0, const float* in_mul = nullptr, const float* in_add = nullptr,
-                     int in_relu = 0, bool out_f32 = false, size_t wino_level_stride = 0, size_t w_level_stride = 0) {
+    ore_engine* e; hipStream_t st; double flops = 0.0; int rc = ORE_OK;
+    // One launch of `fl` algorithmic flops: added to the pass and, under eager profiling, bracketed by an event pair.  wino: the launch
+    // is a conv that may land on the Winograd kernel (2.25x fewer multiplies executed; read back after the launch)
+    template <class F> void timed(double fl, bool wino, F&& launch) {
         if (rc) return;
-        ore_conv_desc d{};
-        d.in = in; d.in_ld = in_ld; d.in_coff = in_coff; d.B = B; d.Cin = c.Cin;
-        d.w = c.w; d.Cout = c.Cout; d.kh = d.kw = c.k; d.stride = 1; d.pad = c.pad;
-        d.scale = c.scale; d.shift = c.shift; d.relu_cout = c.relu_cout;
-        d.in_mul = in_mul; d.in_add = in_add; d.in_relu = in_relu;
-        d.out = out; d.out_ld = out_ld; d.out_coff = out_coff;
-        d.splitk = 0; d.workspace = e->ws; d.workspace_floats = e->ws_floats;
-        d.w_wino = c.wino; d.w_wino_level_stride = (int64_t)wino_level_stride; d.w_level_stride = (int64_t)w_level_stride;
-        if (e->sb()) { d.storage = out_f32 ? ORE_ST_BF16_F32OUT : ORE_ST_BF16; d.w = reinterpret_cast<const float*>(c.wh); }
-        double rows = 0;
-        for (int l = 0; l < 3; ++l) rows += (double)B * H[l] * W[l];
-        const double fl = 2.0 * rows * (double)c.Cout * c.Cin * c.k * c.k;
         hipEvent_t ea = nullptr, eb = nullptr;
         size_t ia = 0;
-        if (prof) { ia = e->ev_used; ea = e->next_event(); eb = e->next_event(); if (ea) (void)hipEventRecord(ea, st); }
-        rc = ore_conv2d_levels_fwd(&d, 3, H, W, ep_stride, st);
-        if (prof && ea && eb) { (void)hipEventRecord(eb, st); e->spans.push_back({ia, ia + 1, fl, ore_last_wino() ? fl / 2.25 : fl}); }
+        if (e->profiling) { ia = e->ev_used; ea = e->next_event(); eb = e->next_event(); if (ea) (void)hipEventRecord(ea, st); }
+        rc = launch();
+        if (e->profiling && ea && eb) { (void)hipEventRecord(eb, st); e->spans.push_back({ia, ia + 1, fl, wino && ore_last_wino() ? fl / 2.25 : fl}); }
         flops += fl;
     }
-    void conv(const Conv& c, const float* in, int in_ld, int in_coff, int B, int H, int W, float* out, int out_ld,
-              int out_coff, const float* in_mul = nullptr, const float* in_add = nullptr, int in_relu = 0,
-              const float* add = nullptr, int add_ld = 0, int add_coff = 0, float* colsum = nullptr, int* colsum_rows = nullptr) {
-        if (rc) return;
+    // the descriptor fields conv and conv_levels share
+    ore_conv_desc desc(const Conv& c, const void* in, int in_ld, int in_coff, int B, void* out, int out_ld, int out_coff, const float* in_mul,
+                       const float* in_add, int in_relu) const {
         ore_conv_desc d{};
-        d.in = in; d.in_ld = in_ld; d.in_coff = in_coff; d.B = B; d.H = H; d.W = W; d.Cin = c.Cin;
+        d.in = static_cast<const float*>(in); d.in_ld = in_ld; d.in_coff = in_coff; d.B = B; d.Cin = c.Cin;
         d.w = c.w; d.Cout = c.Cout; d.kh = d.kw = c.k; d.stride = c.stride; d.pad = c.pad;
         d.scale = c.scale; d.shift = c.shift; d.relu_cout = c.relu_cout;
         d.in_mul = in_mul; d.in_add = in_add; d.in_relu = in_relu;
-        d.add = add; d.add_ld = add_ld; d.add_coff = add_coff;
-        d.out = out; d.out_ld = out_ld; d.out_coff = out_coff;
+        d.out = static_cast<float*>(out); d.out_ld = out_ld; d.out_coff = out_coff;
         d.splitk = 0; d.workspace = e->ws; d.workspace_floats = e->ws_floats;
         d.w_wino = c.wino;
         if (e->sb() && c.wh) { d.storage = ORE_ST_BF16; d.w = reinterpret_cast<const float*>(c.wh); }
-        if (colsum) {
+        return d;
+    }
+    // one launch over all pyramid levels (level-major rows); every such layer has stride 1 and, in a bf16-storage engine, bf16 weights
+    void conv_levels(const Conv& c, const void* in, int in_ld, int in_coff, int B, const int* H, const int* W, void* out,
+                     int out_ld, int out_coff, int ep_stride = 0, const float* in_mul = nullptr, const float* in_add = nullptr,
+                     int in_relu = 0, bool out_f32 = false, size_t wino_level_stride = 0, size_t w_level_stride = 0) {
+        if (!rc && e->sb() && !c.wh) { ore_set_error("bf16-storage engine: a level conv without packed bf16 weights"); rc = ORE_EINVAL; }
+        ore_conv_desc d = desc(c, in, in_ld, in_coff, B, out, out_ld, out_coff, in_mul, in_add, in_relu);
+        d.stride = 1;
+        d.w_wino_level_stride = (int64_t)wino_level_stride; d.w_level_stride = (int64_t)w_level_stride;
+        if (e->sb() && out_f32) d.storage = ORE_ST_BF16_F32OUT;
+        double rows = 0;
+        for (int l = 0; l < 3; ++l) rows += (double)B * H[l] * W[l];
+        timed(2.0 * rows * (double)c.Cout * c.Cin * c.k * c.k, true, [&] { return ore_conv2d_levels_fwd(&d, 3, H, W, ep_stride, st); });
+    }
+    void conv(const Conv& c, const void* in, int in_ld, int in_coff, int B, int H, int W, void* out, int out_ld,
+              int out_coff, const float* in_mul = nullptr, const float* in_add = nullptr, int in_relu = 0,
+              const void* add = nullptr, int add_ld = 0, int add_coff = 0, float* colsum = nullptr, int* colsum_rows = nullptr) {
+        ore_conv_desc d = desc(c, in, in_ld, in_coff, B, out, out_ld, out_coff, in_mul, in_add, in_relu);
+        d.H = H; d.W = W;
+        d.add = static_cast<const float*>(add); d.add_ld = add_ld; d.add_coff = add_coff;
+        if (colsum && !rc) {
             const int rows = ore_conv_colsum_rows(&d);
             if ((size_t)rows * round_up(c.Cout, 16) <= e->colsum_floats) { d.colsum = colsum; *colsum_rows = rows; }
         }
         const int Ho = (H + 2 * c.pad - c.k) / c.stride + 1, Wo = (W + 2 * c.pad - c.k) / c.stride + 1;
-        const double fl = 2.0 * B * Ho * Wo * (double)c.Cout * c.Cin * c.k * c.k;
-        hipEvent_t ea = nullptr, eb = nullptr;
-        size_t ia = 0;
-        if (prof) { ia = e->ev_used; ea = e->next_event(); eb = e->next_event(); if (ea) (void)hipEventRecord(ea, st); }
-        rc = ore_conv2d_fwd(&d, st);
-        if (prof && ea && eb) { (void)hipEventRecord(eb, st); e->spans.push_back({ia, ia + 1, fl, ore_last_wino() ? fl / 2.25 : fl}); }
-        flops += fl;
+        timed(2.0 * B * Ho * Wo * (double)c.Cout * c.Cin * c.k * c.k, true, [&] { return ore_conv2d_fwd(&d, st); });
     }
     void dwpw(const DwUnit& u, const float* in, int in_ld, int in_coff, int B, int H, int W, float* out, int out_ld, int out_coff) {
-        if (rc) return;
         const int Ho = (H - 1) / u.stride + 1, Wo = (W - 1) / u.stride + 1;
-        const double fl = ore_dwpw_flops((int64_t)B * Ho * Wo, u.C);
-        hipEvent_t ea = nullptr, eb = nullptr;
-        size_t ia = 0;
-        if (prof) { ia = e->ev_used; ea = e->next_event(); eb = e->next_event(); if (ea) (void)hipEventRecord(ea, st); }
-        rc = ore_dwpw_planned_fwd(in, in_ld, in_coff, B, H, W, u.C, u.stride, u.w_dw, u.w_pw, u.scale, u.shift, out, out_ld, out_coff,
-                                  e->dw_scratch, e->dw_scratch_floats, st);
-        if (prof && ea && eb) { (void)hipEventRecord(eb, st); e->spans.push_back({ia, ia + 1, fl, fl}); }
-        flops += fl;
+        timed(ore_dwpw_flops((int64_t)B * Ho * Wo, u.C), false, [&] {
+            return ore_dwpw_planned_fwd(in, in_ld, in_coff, B, H, W, u.C, u.stride, u.w_dw, u.w_pw, u.scale, u.shift, out, out_ld, out_coff,
+                                        e->dw_scratch, e->dw_scratch_floats, st);
+        });
     }
 };
 
@@ -371,17 +384,14 @@ int lvl_row0(const Geo& g, int l) {   // first row of pyramid level l (0 = p3) i
 int run_backbone(ore_engine* e, const void* img, int is_u8, const Geo& g, hipStream_t st, double* flops) {
     const ore_model_cfg& c = e->cfg;
     Run r{e, st};
-    r.prof = e->profiling;
     const bool sb = e->sb();
-    int rc = sb ? ore_stem1_bf16_fwd(img, is_u8, g.B, g.H, g.W, g.Hp, g.Wp, c.pixel_mean, c.pixel_std, e->stem1_w, e->stem1_scale,
-                                     e->stem1_shift, c.stem_ch[0], reinterpret_cast<uint16_t*>(e->s1.p), e->s1.ld, 0, st)
-                : ore_stem1_fwd(img, is_u8, g.B, g.H, g.W, g.Hp, g.Wp, c.pixel_mean, c.pixel_std, e->stem1_w, e->stem1_scale,
-                                e->stem1_shift, c.stem_ch[0], e->s1.p, e->s1.ld, 0, st);
+    int rc = oremisc::stem1(img, is_u8, g.B, g.H, g.W, g.Hp, g.Wp, c.pixel_mean, c.pixel_std, e->stem1_w, e->stem1_scale, e->stem1_shift,
+                            c.stem_ch[0], e->s1.p, e->s1.ld, 0, st, sb);
     if (rc) return rc;
     r.flops += 2.0 * g.B * g.h[1] * g.w[1] * 27.0 * c.stem_ch[0];
     if (e->depthwise) {
-        r.dwpw(e->dstem2, e->s1.p, e->s1.ld, 0, g.B, g.h[1], g.w[1], e->s2.p, e->s2.ld, 0);
-        r.dwpw(e->dstem3, e->s2.p, e->s2.ld, 0, g.B, g.h[1], g.w[1], e->cat[0].p, e->cat[0].ld, 0);
+        r.dwpw(e->dstem2, e->s1.f32(), e->s1.ld, 0, g.B, g.h[1], g.w[1], e->s2.f32(), e->s2.ld, 0);
+        r.dwpw(e->dstem3, e->s2.f32(), e->s2.ld, 0, g.B, g.h[1], g.w[1], e->cat[0].f32(), e->cat[0].ld, 0);
     } else {
         r.conv(e->stem2, e->s1.p, e->s1.ld, 0, g.B, g.h[1], g.w[1], e->s2.p, e->s2.ld, 0);
         r.conv(e->stem3, e->s2.p, e->s2.ld, 0, g.B, g.h[1], g.w[1], e->cat[0].p, e->cat[0].ld, 0);
@@ -394,23 +404,21 @@ int run_backbone(ore_engine* e, const void* img, int is_u8, const Geo& g, hipStr
         Buf& cat = e->cat[s];
         if (s > 0 && !pooled_next) {
             const float* pool_mul = e->blocks[s - 1] > 1 ? nullptr : e->gate[s - 1];   // a stage that ends in an identity block is whole
-            r.rc = sb ? ore_maxpool3x3s2_bf16_fwd(reinterpret_cast<const uint16_t*>(e->sout[s - 1].p), e->sout[s - 1].ld, 0, g.B, g.h[k - 1],
-                                                  g.w[k - 1], S.in_ch, e->gate[s - 1], reinterpret_cast<uint16_t*>(cat.p), cat.ld, 0, st)
-                      : ore_maxpool3x3s2_fwd(e->sout[s - 1].p, e->sout[s - 1].ld, 0, g.B, g.h[k - 1], g.w[k - 1], S.in_ch,
-                                             pool_mul, cat.p, cat.ld, 0, st);
+            r.rc = oremisc::maxpool3x3s2(e->sout[s - 1].p, e->sout[s - 1].ld, 0, g.B, g.h[k - 1], g.w[k - 1], S.in_ch, pool_mul, cat.p, cat.ld, 0,
+                                         st, sb);
             if (r.rc) break;
         }
         int src = 0, dst = S.in_ch;
         if (e->depthwise) {
-            const float* in = cat.p;
+            const float* in = cat.f32();
             int in_ld = cat.ld;
             if (S.has_reduction) {
                 r.conv(S.reduction, cat.p, cat.ld, 0, g.B, g.h[k], g.w[k], e->red[s].p, e->red[s].ld, 0);
-                in = e->red[s].p; in_ld = e->red[s].ld;
+                in = e->red[s].f32(); in_ld = e->red[s].ld;
             }
             for (int i = 0; i < c.layers_per_block; ++i) {
-                r.dwpw(S.dw[i], in, in_ld, src, g.B, g.h[k], g.w[k], cat.p, cat.ld, dst);
-                in = cat.p; in_ld = cat.ld;
+                r.dwpw(S.dw[i], in, in_ld, src, g.B, g.h[k], g.w[k], cat.f32(), cat.ld, dst);
+                in = cat.f32(); in_ld = cat.ld;
                 src = dst; dst += S.conv_ch;
             }
         }
@@ -434,16 +442,15 @@ int run_backbone(ore_engine* e, const void* img, int is_u8, const Geo& g, hipStr
             for (int j = 1; j <= nblk && !r.rc; ++j) {
                 const float* fw = j == 1 ? S.fc_w : S.more[j - 2].fc_w;
                 const float* fb = j == 1 ? S.fc_b : S.more[j - 2].fc_b;
-                const float* idn = j == 1 ? nullptr : cur->p;
+                const float* idn = j == 1 ? nullptr : cur->f32();
                 const Buf& dstb = j < nblk ? e->icat[s][(j + 1) & 1] : e->sout[s];
+                const Buf& y = e->ycat[s];
                 if (cs_rows > 0)
-                    r.rc = ore_ese_gate_residual_fwd(e->colsum, cs_rows, HW, C, fw, fb, e->gate_blk, e->ycat[s].p, e->ycat[s].ld, 0, idn,
-                                                     cur->ld, 0, dstb.p, dstb.ld, 0, st);
+                    r.rc = ore_ese_gate_residual_fwd(e->colsum, cs_rows, HW, C, fw, fb, e->gate_blk, y.f32(), y.ld, 0, idn, cur->ld, 0, dstb.f32(),
+                                                     dstb.ld, 0, st);
                 else {
-                    r.rc = ore_ese_gate_fwd(e->ycat[s].p, e->ycat[s].ld, 0, g.B, HW, C, fw, fb, e->gate_blk, e->ese_ws, st);
-                    if (!r.rc)
-                        r.rc = ore_scale_residual_fwd(e->ycat[s].p, e->ycat[s].ld, 0, e->gate_blk, idn, cur->ld, 0, g.B, HW, C, dstb.p,
-                                                      dstb.ld, 0, st);
+                    r.rc = ore_ese_gate_fwd(y.f32(), y.ld, 0, g.B, HW, C, fw, fb, e->gate_blk, e->ese_ws, st);
+                    if (!r.rc) r.rc = ore_scale_residual_fwd(y.f32(), y.ld, 0, e->gate_blk, idn, cur->ld, 0, g.B, HW, C, dstb.f32(), dstb.ld, 0, st);
                 }
                 if (r.rc || j == nblk) break;
                 const ore_engine::Block& Bn = S.more[j - 1];  // block j + 1
@@ -464,36 +471,29 @@ int run_backbone(ore_engine* e, const void* img, int is_u8, const Geo& g, hipStr
             const float* lw = s >= 1 ? e->lateral[s - 1].w : nullptr;
             const int lrows = s >= 1 ? round_up(e->lateral[s - 1].Cout, 16) : 0;
             if (s >= 1) lat_scaled_ok[s - 1] = true;
-            r.rc = sb ? ore_ese_gate_pool_bf16_fwd(e->colsum, cs_rows, g.h[k] * g.w[k], S.out_ch, S.fc_w, S.fc_b, e->gate[s], lw, lrows,
-                                                   s >= 1 ? reinterpret_cast<uint16_t*>(e->lat_scaled[s - 1]) : nullptr,
-                                                   reinterpret_cast<const uint16_t*>(e->sout[s].p), e->sout[s].ld, 0, g.h[k], g.w[k],
-                                                   reinterpret_cast<uint16_t*>(nx.p), nx.ld, 0, st)
-                      : ore_ese_gate_pool_fwd(e->colsum, cs_rows, g.h[k] * g.w[k], S.out_ch, S.fc_w, S.fc_b, e->gate[s], lw, lrows,
-                                              s >= 1 ? e->lat_scaled[s - 1] : nullptr, e->sout[s].p, e->sout[s].ld, 0, g.h[k], g.w[k], nx.p,
-                                              nx.ld, 0, st);
+            r.rc = oremisc::ese_gate_pool(e->colsum, cs_rows, g.h[k] * g.w[k], S.out_ch, S.fc_w, S.fc_b, e->gate[s], lw, lrows,
+                                          s >= 1 ? e->lat_scaled[s - 1] : nullptr, e->sout[s].p, e->sout[s].ld, 0, g.h[k], g.w[k], nx.p, nx.ld, 0,
+                                          st, sb);
             pooled_next = true;
         } else if (cs_rows > 0 && s >= 1 && e->lat_scaled[s - 1]) { // bs = 1, last stage: gate + the gate-scaled lateral weight in one launch
             lat_scaled_ok[s - 1] = true;
-            r.rc = sb ? ore_ese_gate_scaled_weight_bf16_fwd(e->colsum, cs_rows, g.h[k] * g.w[k], S.out_ch, S.fc_w, S.fc_b, e->gate[s], e->ese_ws,
-                                                            e->lateral[s - 1].w, round_up(e->lateral[s - 1].Cout, 16),
-                                                            reinterpret_cast<uint16_t*>(e->lat_scaled[s - 1]), st)
-                      : ore_ese_gate_scaled_weight_fwd(e->colsum, cs_rows, g.h[k] * g.w[k], S.out_ch, S.fc_w, S.fc_b, e->gate[s], e->ese_ws,
-                                                       e->lateral[s - 1].w, round_up(e->lateral[s - 1].Cout, 16), e->lat_scaled[s - 1], st);
+            r.rc = oremisc::ese_gate_scaled_weight(e->colsum, cs_rows, g.h[k] * g.w[k], S.out_ch, S.fc_w, S.fc_b, e->gate[s], e->ese_ws,
+                                                   e->lateral[s - 1].w, round_up(e->lateral[s - 1].Cout, 16), e->lat_scaled[s - 1], st, sb);
         } else if (cs_rows > 0)
             r.rc = ore_ese_gate_from_colsum_fwd(e->colsum, cs_rows, 1, g.h[k] * g.w[k], S.out_ch, S.fc_w, S.fc_b, e->gate[s], e->ese_ws, st);
         else if (sb) { ore_set_error("bf16-storage engine: the eSE pool must come fused from the concat conv (one image per pass)"); r.rc = ORE_EINVAL; }
         else
-            r.rc = ore_ese_gate_fwd(e->sout[s].p, e->sout[s].ld, 0, g.B, g.h[k] * g.w[k], S.out_ch, S.fc_w, S.fc_b, e->gate[s],
+            r.rc = ore_ese_gate_fwd(e->sout[s].f32(), e->sout[s].ld, 0, g.B, g.h[k] * g.w[k], S.out_ch, S.fc_w, S.fc_b, e->gate[s],
                                     e->ese_ws, st);
     }
     // FPN top-down: level index 2 = p5, 1 = p4, 0 = p3; outputs land in the q half of pcat
     const int F = c.fpn_ch;
-    float* lat[3];
-    for (int l = 0; l < 3; ++l) lat[l] = e->at(e->lat_all.p, (size_t)lvl_row0(g, l) * F);
+    void* lat[3];
+    for (int l = 0; l < 3; ++l) lat[l] = e->lat_all.row(lvl_row0(g, l));
     const bool grouped = e->out_wino3 != nullptr || e->out_wh3 != nullptr;   // the three output convs run as one launch behind the lateral chain
     for (int l = 2; l >= 0 && !r.rc; --l) {
         const int k = l + 3, s = l + 1;
-        const float* add = l < 2 ? lat[l + 1] : nullptr;
+        const void* add = l < 2 ? lat[l + 1] : nullptr;
         if (lat_scaled_ok[l]) {                             // x * (g W): plain conv on the gate-scaled weights (k_conv_kw)
             Conv lc = e->lateral[l];
             lc.w = e->lat_scaled[l];
@@ -506,7 +506,7 @@ int run_backbone(ore_engine* e, const void* img, int is_u8, const Geo& g, hipStr
                    e->blocks[s] > 1 ? nullptr : e->gate[s], nullptr, 0, add, F, 0);
         }
         if (!grouped)
-            r.conv(e->output[l], lat[l], F, 0, g.B, g.h[k], g.w[k], e->at(e->pcat.p, (size_t)lvl_row0(g, l) * 2 * F), 2 * F, F);
+            r.conv(e->output[l], lat[l], F, 0, g.B, g.h[k], g.w[k], e->pcat.row(lvl_row0(g, l)), 2 * F, F);
     }
     if (grouped && !r.rc) {
         // fpn_output3/4/5 (d2z:modeling/backbone/fpn.py:139-145): three layers of one shape -> ONE Winograd launch, every block keeps the
@@ -526,7 +526,6 @@ int run_heads(ore_engine* e, const Geo& g, hipStream_t st, double* flops, bool c
     const ore_model_cfg& c = e->cfg;
     const int F = c.fpn_ch;
     Run r{e, st};
-    r.prof = e->profiling;
     const int H[3] = {g.h[3], g.h[4], g.h[5]}, W[3] = {g.w[3], g.w[4], g.w[5]};
     const int HW[3] = {H[0] * W[0], H[1] * W[1], H[2] * W[2]};
     const bool sb = e->sb();
@@ -535,9 +534,7 @@ int run_heads(ore_engine* e, const Geo& g, hipStream_t st, double* flops, bool c
         for (int l = 0; l < 3; ++l)
             if (!e->support_set[l]) { ore_set_error("support prototype for level %d not set", l + 3); return ORE_EINVAL; }
         // query<->support depthwise correlation, all levels: attn -> channels [0,F) of pcat (q sits in [F,2F))
-        r.rc = sb ? ore_correlation_levels_bf16_fwd(reinterpret_cast<const uint16_t*>(e->pcat.p), 2 * F, F, g.B, 3, H, W, F, e->k11, e->k13, e->k31,
-                                                    reinterpret_cast<uint16_t*>(e->pcat.p), 2 * F, 0, st)
-                  : ore_correlation_levels_fwd(e->pcat.p, 2 * F, F, g.B, 3, H, W, F, e->k11, e->k13, e->k31, e->pcat.p, 2 * F, 0, st);
+        r.rc = oremisc::correlation_levels(e->pcat.p, 2 * F, F, g.B, 3, H, W, F, e->k11, e->k13, e->k31, e->pcat.p, 2 * F, 0, st, sb);
         if (r.rc) return r.rc;
         r.flops += 2.0 * 8.0 * rows * F;
     }
@@ -550,22 +547,16 @@ int run_heads(ore_engine* e, const Geo& g, hipStream_t st, double* flops, bool c
     if (F == 128 && e->head_pred_valu) {
         // statistics, then ONE kernel for GroupNorm fold + ReLU + the (l,t,r,b | hm) conv + per-level Scale: its blocks combine the chunk
         // statistics of their own (level, image) under their tower loads
-        r.rc = sb ? ore_head_pred_gn_bf16_fwd(reinterpret_cast<const uint16_t*>(e->tow.p), F, g.B, 3, H, W, 32, 1e-5f, e->gn_gamma, e->gn_beta,
-                                              e->pred.w, e->pred.scale, e->pred.shift, 16, e->head.p, 8, e->gn_ws, st)
-                  : ore_head_pred_gn_fwd(e->tow.p, F, g.B, 3, H, W, 32, 1e-5f, e->gn_gamma, e->gn_beta, e->pred.w, e->pred.scale,
-                                         e->pred.shift, 16, e->head.p, 8, e->gn_ws, st);
+        r.rc = oremisc::head_pred_gn(e->tow.p, F, g.B, 3, H, W, 32, 1e-5f, e->gn_gamma, e->gn_beta, e->pred.w, e->pred.scale, e->pred.shift, 16,
+                                     e->head.f32(), 8, e->gn_ws, st, sb);
         r.flops += 2.0 * rows * 5.0 * F * 9.0;
         *flops = r.flops;
         return r.rc;
     }
-    r.rc = sb ? ore_groupnorm_affine_levels_bf16_fwd(reinterpret_cast<const uint16_t*>(e->tow.p), F, 0, g.B, 3, HW, F, 32, 1e-5f, e->gn_gamma,
-                                                     e->gn_beta, e->gn_mul, e->gn_add, e->gn_ws, st)
-              : ore_groupnorm_affine_levels_fwd(e->tow.p, F, 0, g.B, 3, HW, F, 32, 1e-5f, e->gn_gamma, e->gn_beta, e->gn_mul, e->gn_add,
-                                                e->gn_ws, st);
+    r.rc = oremisc::gn_affine_levels(e->tow.p, F, 0, g.B, 3, HW, F, 32, 1e-5f, e->gn_gamma, e->gn_beta, e->gn_mul, e->gn_add, e->gn_ws, st, sb);
     if (r.rc) return r.rc;
     if (sb) {
-        if (!r.rc) r.rc = ore_groupnorm_apply_levels_bf16_fwd(reinterpret_cast<const uint16_t*>(e->tow.p), F, 0, g.B, 3, HW, F, e->gn_mul, e->gn_add, 1,
-                                                              reinterpret_cast<uint16_t*>(e->tn.p), st);
+        r.rc = ore_groupnorm_apply_levels_bf16_fwd(e->tow.bf16(), F, 0, g.B, 3, HW, F, e->gn_mul, e->gn_add, 1, e->tn.bf16(), st);
         if (r.rc) return r.rc;
         r.conv_levels(e->pred, e->tn.p, F, 0, g.B, H, W, e->head.p, 8, 0, 16, nullptr, nullptr, 0, true);
         *flops = r.flops;
@@ -582,7 +573,7 @@ void detect_desc(ore_engine* e, const Geo& g, int b, ore_detect_desc& d) {   // 
     const size_t cap = (size_t)3 * c.pre_topk;
     d.n_levels = 3; d.head_ld = 8;
     for (int l = 0; l < 3; ++l) {
-        d.head[l] = e->head.p + ((size_t)lvl_row0(g, l) + (size_t)b * g.h[l + 3] * g.w[l + 3]) * 8;
+        d.head[l] = e->head.f32() + ((size_t)lvl_row0(g, l) + (size_t)b * g.h[l + 3] * g.w[l + 3]) * 8;
         d.H[l] = g.h[l + 3]; d.W[l] = g.w[l + 3]; d.stride[l] = c.strides[l];
     }
     d.score_thresh = c.score_thresh; d.pre_topk = c.pre_topk; d.nms_thresh = c.nms_thresh; d.post_topk = c.post_topk;
@@ -609,99 +600,90 @@ int run_detect_classes(ore_engine* e, const Geo& g, hipStream_t st, int K) {
     return ore_detect_batch_fwd(d, K, st);
 }
 
-// image b (scratch roi_feat / roi_h / roi_ws is shared: stream order).  class_slot: the N-way pass -- block b = class slot b with that
-// class's composed fc1, detections to det_*#b only (the merge kernel does the postprocess and publishes the count)
-// One stage of the second stage up to the fc1 rows: ROIAlign of `boxes` and the pre-composed GEMM (K-split partial sums or finished rows).
-static int run_roi_rows(ore_engine* e, const Geo& g, hipStream_t st, double* flops, int b, float* roi_W, float* roi_b, const float* out_boxes,
-                        const int32_t* counts);
+// the weights of cascade stage k (0: the single-stage head's): composed fc1 (an N-way pass: of class slot `slot`), predictor, regression
+struct StageW { float *W, *b, *cls_w, *cls_b, *box_w, *box_b; const float* reg_w; };
 
-int run_roi(ore_engine* e, const Geo& g, hipStream_t st, double* flops, int b = 0, bool class_slot = false) {
-    const ore_model_cfg& c = e->cfg;
-    const size_t cap = (size_t)3 * c.pre_topk, rcap = (size_t)e->roi_cap;
-    float* out_boxes = e->out_boxes + b * cap * 4;
-    int32_t* counts = e->counts + b * 4;
-    const int S = e->roi_ksplit, NS = e->roi_stages;
-    const float* h = S > 1 ? e->roi_hp : e->roi_h;
-    *flops = 0.0;
-    // the cascade: stage k pools the boxes stage k - 1 decoded (detached, clipped), with its own composed fc1 and predictor; the
-    // foreground probabilities add up in casc_sum in stage order, the last stage averages them and runs the tail (DESIGN 7q)
-    const float* boxes_k = out_boxes;
-    for (int k = 0; k < NS - 1; ++k) {
-        float* W_k = k == 0 ? (class_slot ? e->roi_W_slot[b] : e->roi_W) : (class_slot ? e->casc_W_slot[b][k] : e->casc_W[k]);
-        float* b_k = k == 0 ? (class_slot ? e->roi_b_slot[b] : e->roi_b) : (class_slot ? e->casc_b_slot[b][k] : e->casc_b[k]);
-        double fl = 0.0;
-        int rc = run_roi_rows(e, g, st, &fl, b, W_k, b_k, boxes_k, counts);
-        if (rc) return rc;
-        *flops += fl;
-        float* next = e->casc_boxes[k & 1];
-        rc = ore_roi_cascade_refine_fwd(h, e->roi_fc, S > 1 ? S : 0, S > 1 ? b_k : nullptr, k == 0 ? e->roi_cls_w : e->casc_cls_w[k],
-                                        k == 0 ? e->roi_cls_b : e->casc_cls_b[k], k == 0 ? e->roi_box_w : e->casc_box_w[k],
-                                        k == 0 ? e->roi_box_b : e->casc_box_b[k], boxes_k, counts + 1, 0, e->roi_cap,
-                                        k == 0 ? e->roi_reg_w : e->casc_reg_w[k], (float)g.H, (float)g.W, next, e->casc_sum, e->casc_dead,
-                                        k > 0 ? 1 : 0, st);
-        if (rc) return rc;
-        boxes_k = next;
-    }
-    const int kl = NS - 1;
-    float* roi_W = kl == 0 ? (class_slot ? e->roi_W_slot[b] : e->roi_W) : (class_slot ? e->casc_W_slot[b][kl] : e->casc_W[kl]);
-    float* roi_b = kl == 0 ? (class_slot ? e->roi_b_slot[b] : e->roi_b) : (class_slot ? e->casc_b_slot[b][kl] : e->casc_b[kl]);
-    double fl = 0.0;
-    int rc = run_roi_rows(e, g, st, &fl, b, roi_W, roi_b, boxes_k, counts);
-    if (rc) return rc;
-    *flops += fl;
-    if (kl == 0)
-        return oreroi::roi_predict_post(h, e->roi_fc, S > 1 ? S : 0, S > 1 ? roi_b : nullptr, e->roi_cls_w, e->roi_cls_b,
-                                        e->roi_box_w, e->roi_box_b, out_boxes, counts + 1, 0,
-                                        e->roi_cap, e->roi_reg_w, (float)g.H, (float)g.W, e->roi_score_thresh, e->roi_nms_thresh, e->roi_topk,
-                                        e->det_boxes + b * rcap * 4, e->det_scores + b * rcap, e->det_src + b * rcap, e->det_count + b * 4,
-                                        class_slot ? nullptr : e->post, e->fin_boxes_of(b), e->fin_scores_of(b), e->fin_count + b * 4,
-                                        b == 0 && !class_slot ? e->pin_count_dev : nullptr, e->roi_ws, e->roi_ws_bytes, st);
-    return ore_roi_predict_cascade_fwd(h, e->roi_fc, e->casc_cls_w[kl], e->casc_cls_b[kl], e->casc_box_w[kl], e->casc_box_b[kl], boxes_k,
-                                       counts + 1, 0, e->roi_cap, e->casc_reg_w[kl], (float)g.H, (float)g.W, e->roi_score_thresh,
-                                       e->roi_nms_thresh, e->roi_topk, e->det_boxes + b * rcap * 4, e->det_scores + b * rcap,
-                                       e->det_src + b * rcap, e->det_count + b * 4, class_slot ? nullptr : e->post, e->fin_boxes_of(b),
-                                       e->fin_scores_of(b), e->fin_count + b * 4, b == 0 && !class_slot ? e->pin_count_dev : nullptr,
-                                       e->roi_ws, e->roi_ws_bytes, st, S > 1 ? S : 0, S > 1 ? roi_b : nullptr, e->casc_sum, e->casc_dead, NS);
+StageW stage_weights(ore_engine* e, int slot, int k, bool class_slot) {
+    if (k == 0)
+        return {class_slot ? e->roi_W_slot[slot] : e->roi_W, class_slot ? e->roi_b_slot[slot] : e->roi_b, e->roi_cls_w, e->roi_cls_b, e->roi_box_w,
+                e->roi_box_b, e->roi_reg_w};
+    return {class_slot ? e->casc_W_slot[slot][k] : e->casc_W[k], class_slot ? e->casc_b_slot[slot][k] : e->casc_b[k], e->casc_cls_w[k],
+            e->casc_cls_b[k], e->casc_box_w[k], e->casc_box_b[k], e->casc_reg_w[k]};
 }
 
-static int run_roi_rows(ore_engine* e, const Geo& g, hipStream_t st, double* flops, int b, float* roi_W, float* roi_b, const float* out_boxes,
-                        const int32_t* counts) {
+// One stage of the second stage up to the fc1 rows: ROIAlign of `boxes` and the pre-composed GEMM (K-split partial sums or finished rows).
+int run_roi_rows(ore_engine* e, const Geo& g, hipStream_t st, double* flops, int b, const StageW& w, const float* boxes, const int32_t* counts) {
     const ore_model_cfg& c = e->cfg;
     const int F = c.fpn_ch;
-    const float* feat[3]; int ld[3], coff[3], H[3], W[3]; float sc[3];
+    const void* feat[3]; int ld[3], coff[3], H[3], W[3]; float sc[3];
     for (int l = 0; l < 3; ++l) {
-        feat[l] = e->at(e->pcat.p, ((size_t)lvl_row0(g, l) + (size_t)b * g.h[l + 3] * g.w[l + 3]) * 2 * F); ld[l] = 2 * F; coff[l] = F;
+        feat[l] = e->pcat.row((size_t)lvl_row0(g, l) + (size_t)b * g.h[l + 3] * g.w[l + 3]); ld[l] = 2 * F; coff[l] = F;
         H[l] = g.h[l + 3]; W[l] = g.w[l + 3]; sc[l] = 1.0f / (float)c.strides[l];
     }
-    int rc = e->sb() ? ore_roi_align_bf16_fwd(reinterpret_cast<const uint16_t* const*>(feat), ld, coff, H, W, sc, 3, 3, F, e->roi_pooled, out_boxes,
-                                              counts + 1, 0, e->roi_cap, e->roi_feat, st)
-                     : ore_roi_align_fwd(feat, ld, coff, H, W, sc, 3, 3, F, e->roi_pooled, out_boxes, counts + 1, 0, e->roi_cap, e->roi_feat, st);
+    int rc = oreroi::roi_align_fwd(feat, ld, coff, H, W, sc, 3, 3, F, e->roi_pooled, boxes, counts + 1, 0, e->roi_cap, e->roi_feat, st, nullptr, e->sb());
     if (rc) return rc;
     const int K = e->roi_pooled * e->roi_pooled * F;
     Run r{e, st};
-    r.prof = e->profiling;
-    Conv fc{};
-    fc.w = roi_W; fc.scale = nullptr; fc.shift = roi_b; fc.Cin = K; fc.Cout = e->roi_fc; fc.k = 1; fc.stride = 1; fc.pad = 0;
-    fc.relu_cout = e->roi_fc;
     // pre-composed DSA mix + flatten + fc1 (+ bias, ReLU).  The second-stage GEMM stays fp32 in every mode (include/ore_hip.h).
     const int S = e->roi_ksplit;
     if (S > 1) {
         // K split over blocks (oreconv::conv_gd_splitk): raw partial sums, added in slice order with bias and ReLU by the predictor kernel
-        const double fl = 2.0 * (double)e->roi_cap * K * e->roi_fc;
-        hipEvent_t ea = nullptr, eb = nullptr;
-        size_t ia = 0;
-        if (r.prof) { ia = e->ev_used; ea = e->next_event(); eb = e->next_event(); if (ea) (void)hipEventRecord(ea, st); }
-        rc = oreconv::conv_gd_splitk(e->roi_feat, K, roi_W, e->roi_cap, K, e->roi_fc, e->roi_hp, S, st);
-        if (r.prof && ea && eb) { (void)hipEventRecord(eb, st); e->spans.push_back({ia, ia + 1, fl, fl}); }
-        if (rc) return rc;
-        *flops = fl;
+        r.timed(2.0 * (double)e->roi_cap * K * e->roi_fc, false,
+                [&] { return oreconv::conv_gd_splitk(e->roi_feat, K, w.W, e->roi_cap, K, e->roi_fc, e->roi_hp, S, st); });
     } else {
+        Conv fc{};
+        fc.w = w.W; fc.scale = nullptr; fc.shift = w.b; fc.Cin = K; fc.Cout = e->roi_fc; fc.k = 1; fc.stride = 1; fc.pad = 0;
+        fc.relu_cout = e->roi_fc;
         PrecisionScope fp32(ORE_CONV_FP32);
         r.conv(fc, e->roi_feat, K, 0, 1, 1, e->roi_cap, e->roi_h, e->roi_fc, 0);
-        if (r.rc) return r.rc;
-        *flops = r.flops;
     }
-    return ORE_OK;
+    *flops = r.flops;
+    return r.rc;
+}
+
+// image b (scratch roi_feat / roi_h / roi_ws is shared: stream order).  class_slot: the N-way pass -- block b = class slot b with that
+// class's composed fc1, detections to det_*#b only (the merge kernel does the postprocess and publishes the count)
+int run_roi(ore_engine* e, const Geo& g, hipStream_t st, double* flops, int b = 0, bool class_slot = false) {
+    const ore_model_cfg& c = e->cfg;
+    const size_t cap = (size_t)3 * c.pre_topk, rcap = (size_t)e->roi_cap;
+    int32_t* counts = e->counts + b * 4;
+    const int NS = e->roi_stages;
+    const int parts = e->roi_ksplit > 1 ? e->roi_ksplit : 0;      // fc1 rows left in K-split partial sums: the predictor adds them up
+    const float* h = parts ? e->roi_hp : e->roi_h;
+    *flops = 0.0;
+    // the cascade: stage k pools the boxes stage k - 1 decoded (detached, clipped), with its own composed fc1 and predictor; the
+    // foreground probabilities add up in casc_sum in stage order, the last stage averages them and runs the tail (DESIGN 7q)
+    const float* boxes_k = e->out_boxes + b * cap * 4;
+    for (int k = 0; k < NS - 1; ++k) {
+        const StageW w = stage_weights(e, b, k, class_slot);
+        double fl = 0.0;
+        int rc = run_roi_rows(e, g, st, &fl, b, w, boxes_k, counts);
+        if (rc) return rc;
+        *flops += fl;
+        float* next = e->casc_boxes[k & 1];
+        rc = ore_roi_cascade_refine_fwd(h, e->roi_fc, parts, parts ? w.b : nullptr, w.cls_w, w.cls_b, w.box_w, w.box_b, boxes_k, counts + 1, 0,
+                                        e->roi_cap, w.reg_w, (float)g.H, (float)g.W, next, e->casc_sum, e->casc_dead, k > 0 ? 1 : 0, st);
+        if (rc) return rc;
+        boxes_k = next;
+    }
+    // the last stage ends in the fused predict + tail kernel: the single-stage head's, or the cascade's (which averages the stages' scores)
+    const StageW w = stage_weights(e, b, NS - 1, class_slot);
+    double fl = 0.0;
+    int rc = run_roi_rows(e, g, st, &fl, b, w, boxes_k, counts);
+    if (rc) return rc;
+    *flops += fl;
+    float* post = class_slot ? nullptr : e->post;
+    int32_t* host_count = b == 0 && !class_slot ? e->pin_count_dev : nullptr;
+    if (NS == 1)
+        return oreroi::roi_predict_post(h, e->roi_fc, parts, parts ? w.b : nullptr, w.cls_w, w.cls_b, w.box_w, w.box_b, boxes_k, counts + 1, 0,
+                                        e->roi_cap, w.reg_w, (float)g.H, (float)g.W, e->roi_score_thresh, e->roi_nms_thresh, e->roi_topk,
+                                        e->det_boxes + b * rcap * 4, e->det_scores + b * rcap, e->det_src + b * rcap, e->det_count + b * 4, post,
+                                        e->fin_boxes_of(b), e->fin_scores_of(b), e->fin_count + b * 4, host_count, e->roi_ws, e->roi_ws_bytes, st);
+    return ore_roi_predict_cascade_fwd(h, e->roi_fc, w.cls_w, w.cls_b, w.box_w, w.box_b, boxes_k, counts + 1, 0, e->roi_cap, w.reg_w, (float)g.H,
+                                       (float)g.W, e->roi_score_thresh, e->roi_nms_thresh, e->roi_topk, e->det_boxes + b * rcap * 4,
+                                       e->det_scores + b * rcap, e->det_src + b * rcap, e->det_count + b * 4, post, e->fin_boxes_of(b),
+                                       e->fin_scores_of(b), e->fin_count + b * 4, host_count, e->roi_ws, e->roi_ws_bytes, st, parts,
+                                       parts ? w.b : nullptr, e->casc_sum, e->casc_dead, NS);
 }
 
 }  // namespace
@@ -721,14 +703,9 @@ extern "C" int ore_engine_set_roi_head(ore_engine* e, const float* W_host, const
     ORE_HIP(hipSetDevice(e->device));
     const size_t K = (size_t)pooled * pooled * e->cfg.fpn_ch;
     int rc;
-    auto up = [&](float** dst, const float* src, size_t n) -> int {
-        if (!*dst && (rc = e->dalloc(dst, n))) return rc;
-        ORE_HIP(hipMemcpy(*dst, src, n * sizeof(float), hipMemcpyHostToDevice));
-        return ORE_OK;
-    };
     if (e->roi_set && (e->roi_fc != fc_dim || e->roi_pooled != pooled)) { ore_set_error("ore_engine_set_roi_head: shape change not supported"); return ORE_EINVAL; }
-    if ((rc = up(&e->roi_W, W_host, (size_t)fc_dim * K)) || (rc = up(&e->roi_b, b_host, fc_dim)) || (rc = up(&e->roi_cls_w, cls_w_host, 2 * (size_t)fc_dim)) ||
-        (rc = up(&e->roi_cls_b, cls_b_host, 2)) || (rc = up(&e->roi_box_w, box_w_host, 4 * (size_t)fc_dim)) || (rc = up(&e->roi_box_b, box_b_host, 4)))
+    if ((rc = e->upload_to(&e->roi_W, W_host, (size_t)fc_dim * K)) || (rc = e->upload_to(&e->roi_b, b_host, fc_dim)) || (rc = e->upload_to(&e->roi_cls_w, cls_w_host, 2 * (size_t)fc_dim)) ||
+        (rc = e->upload_to(&e->roi_cls_b, cls_b_host, 2)) || (rc = e->upload_to(&e->roi_box_w, box_w_host, 4 * (size_t)fc_dim)) || (rc = e->upload_to(&e->roi_box_b, box_b_host, 4)))
         return rc;
     if (!e->roi_set) {
         const size_t cap = (size_t)e->roi_cap;
@@ -784,15 +761,10 @@ extern "C" int ore_engine_set_roi_cascade(ore_engine* e, int32_t n_stages, const
                                      reg_weights4_host, score_thresh, nms_thresh, topk);
     if (rc || n_stages == 1) return rc;
     const size_t K = (size_t)pooled * pooled * e->cfg.fpn_ch, cap = (size_t)e->roi_cap;
-    auto up = [&](float** dst, const float* src, size_t n) -> int {
-        if (!*dst && (rc = e->dalloc(dst, n))) return rc;
-        ORE_HIP(hipMemcpy(*dst, src, n * sizeof(float), hipMemcpyHostToDevice));
-        return ORE_OK;
-    };
     for (int k = 1; k < n_stages; ++k) {
-        if ((rc = up(&e->casc_W[k], W_host[k], (size_t)fc_dim * K)) || (rc = up(&e->casc_b[k], b_host[k], fc_dim)) ||
-            (rc = up(&e->casc_cls_w[k], cls_w_host[k], 2 * (size_t)fc_dim)) || (rc = up(&e->casc_cls_b[k], cls_b_host[k], 2)) ||
-            (rc = up(&e->casc_box_w[k], box_w_host[k], 4 * (size_t)fc_dim)) || (rc = up(&e->casc_box_b[k], box_b_host[k], 4)))
+        if ((rc = e->upload_to(&e->casc_W[k], W_host[k], (size_t)fc_dim * K)) || (rc = e->upload_to(&e->casc_b[k], b_host[k], fc_dim)) ||
+            (rc = e->upload_to(&e->casc_cls_w[k], cls_w_host[k], 2 * (size_t)fc_dim)) || (rc = e->upload_to(&e->casc_cls_b[k], cls_b_host[k], 2)) ||
+            (rc = e->upload_to(&e->casc_box_w[k], box_w_host[k], 4 * (size_t)fc_dim)) || (rc = e->upload_to(&e->casc_box_b[k], box_b_host[k], 4)))
             return rc;
         for (int i = 0; i < 4; ++i) e->casc_reg_w[k][i] = reg_weights4_host[4 * k + i];
     }
@@ -899,15 +871,11 @@ extern "C" int ore_engine_finalize(ore_engine* e) {
     int rc;
     const std::string bu = "backbone.bottom_up.";
     {   // stem_1 stays OIHW-flat [Cout][27]
-        const HostTensor *w, *g, *b, *m, *v;
+        const HostTensor* w;
         const int C0 = c.stem_ch[0];
         if ((rc = need(e, bu + "stem.stem_1/conv.weight", &w, {C0, 3, 3, 3}))) return rc;
-        if ((rc = need(e, bu + "stem.stem_1/norm.weight", &g, {C0}))) return rc;
-        if ((rc = need(e, bu + "stem.stem_1/norm.bias", &b, {C0}))) return rc;
-        if ((rc = need(e, bu + "stem.stem_1/norm.running_mean", &m, {C0}))) return rc;
-        if ((rc = need(e, bu + "stem.stem_1/norm.running_var", &v, {C0}))) return rc;
-        std::vector<float> sc(C0), sh(C0);
-        for (int n = 0; n < C0; ++n) { sc[n] = g->v[n] * (1.0f / sqrtf(v->v[n] + 1e-5f)); sh[n] = b->v[n] - m->v[n] * sc[n]; }
+        std::vector<float> sc, sh;
+        if ((rc = fold_bn(e, bu + "stem.stem_1/norm", C0, &sc, &sh))) return rc;
         if ((rc = e->upload(&e->stem1_w, w->v)) || (rc = e->upload(&e->stem1_scale, sc)) || (rc = e->upload(&e->stem1_shift, sh))) return rc;
     }
     ORE_CHECK_ARG(!e->depthwise || !e->sb(), "ore_engine_finalize: a bf16-storage engine has no depthwise body (the depthwise units are fp32 only)");
@@ -1267,8 +1235,8 @@ static int eval_classes(ore_engine* e, const void* img, int32_t is_u8, int32_t H
         // rows it occupies --, then ONE launch writes [attn_k | query] into every class block k of pcat
         const int rows1 = lvl_row0(g1, 3);
         const int Hl[3] = {g1.h[3], g1.h[4], g1.h[5]}, Wl[3] = {g1.w[3], g1.w[4], g1.w[5]};
-        if (!r) r = oremisc::copy_cols(e->pcat.p, 2 * F, F, rows1, F, e->tow.p, F, s);
-        if (!r) r = oremisc::correlation_classes(e->tow.p, F, 0, 3, Hl, Wl, F, K, e->k11s, e->k13s, e->k31s, e->pcat.p, 2 * F, s);
+        if (!r) r = oremisc::copy_cols(e->pcat.f32(), 2 * F, F, rows1, F, e->tow.f32(), F, s);
+        if (!r) r = oremisc::correlation_classes(e->tow.f32(), F, 0, 3, Hl, Wl, F, K, e->k11s, e->k13s, e->k31s, e->pcat.f32(), 2 * F, s);
         f2 += 2.0 * 8.0 * (double)K * rows1 * F;
         double fh = 0;
         if (!r) r = run_heads(e, gK, s, &fh, false);
@@ -1354,18 +1322,21 @@ extern "C" int ore_engine_set_support_slot(ore_engine* e, int32_t slot, int32_t 
     return ORE_OK;
 }
 
+// the composed fc1 (DSA mix + flatten + fc1) of one class slot and one cascade stage: allocated on the first upload
+static int upload_slot_fc1(ore_engine* e, float** W, float** b, const float* W_host, const float* b_host) {
+    ORE_HIP(hipSetDevice(e->device));
+    const size_t K = (size_t)e->roi_pooled * e->roi_pooled * e->cfg.fpn_ch, fc = (size_t)e->roi_fc;
+    int rc;
+    if ((rc = e->upload_to(W, W_host, fc * K)) || (rc = e->upload_to(b, b_host, fc))) return rc;
+    drop_class_graphs(e);
+    return ORE_OK;
+}
+
 extern "C" int ore_engine_set_roi_support_slot(ore_engine* e, int32_t slot, const float* W_host, const float* b_host) {
     ORE_CHECK_ARG(e && e->roi_set && e->k11s && W_host && b_host,
                   "ore_engine_set_roi_support_slot: needs ore_engine_set_roi_head and ore_engine_set_classes (n >= 1) first, pointers non-null");
     ORE_CHECK_ARG(slot >= 0 && slot < e->n_slots, "ore_engine_set_roi_support_slot: slot %d outside [0, %d)", slot, e->n_slots);
-    ORE_HIP(hipSetDevice(e->device));
-    const size_t K = (size_t)e->roi_pooled * e->roi_pooled * e->cfg.fpn_ch, fc = (size_t)e->roi_fc;
-    int rc;
-    if (!e->roi_W_slot[slot] && ((rc = e->dalloc(&e->roi_W_slot[slot], fc * K)) || (rc = e->dalloc(&e->roi_b_slot[slot], fc)))) return rc;
-    ORE_HIP(hipMemcpy(e->roi_W_slot[slot], W_host, fc * K * sizeof(float), hipMemcpyHostToDevice));
-    ORE_HIP(hipMemcpy(e->roi_b_slot[slot], b_host, fc * sizeof(float), hipMemcpyHostToDevice));
-    drop_class_graphs(e);
-    return ORE_OK;
+    return upload_slot_fc1(e, &e->roi_W_slot[slot], &e->roi_b_slot[slot], W_host, b_host);
 }
 
 extern "C" int ore_engine_set_roi_support_slot_stage(ore_engine* e, int32_t slot, int32_t stage, const float* W_host, const float* b_host) {
@@ -1375,15 +1346,7 @@ extern "C" int ore_engine_set_roi_support_slot_stage(ore_engine* e, int32_t slot
     ORE_CHECK_ARG(slot >= 0 && slot < e->n_slots, "ore_engine_set_roi_support_slot_stage: slot %d outside [0, %d)", slot, e->n_slots);
     ORE_CHECK_ARG(stage > 0 && stage < e->roi_stages, "ore_engine_set_roi_support_slot_stage: stage %d outside the engine's %d cascade stages", stage,
                   e->roi_stages);
-    ORE_HIP(hipSetDevice(e->device));
-    const size_t K = (size_t)e->roi_pooled * e->roi_pooled * e->cfg.fpn_ch, fc = (size_t)e->roi_fc;
-    int rc;
-    if (!e->casc_W_slot[slot][stage] && ((rc = e->dalloc(&e->casc_W_slot[slot][stage], fc * K)) || (rc = e->dalloc(&e->casc_b_slot[slot][stage], fc))))
-        return rc;
-    ORE_HIP(hipMemcpy(e->casc_W_slot[slot][stage], W_host, fc * K * sizeof(float), hipMemcpyHostToDevice));
-    ORE_HIP(hipMemcpy(e->casc_b_slot[slot][stage], b_host, fc * sizeof(float), hipMemcpyHostToDevice));
-    drop_class_graphs(e);
-    return ORE_OK;
+    return upload_slot_fc1(e, &e->casc_W_slot[slot][stage], &e->casc_b_slot[slot][stage], W_host, b_host);
 }
 
 extern "C" double ore_engine_last_flops(ore_engine* e) { return e ? e->last_flops : 0.0; }
@@ -1470,12 +1433,12 @@ extern "C" int ore_engine_buffer(ore_engine* e, const char* name, void** ptr, in
         const std::string k = std::to_string(l + 3);
         const int64_t rows = (int64_t)g.B * g.h[l + 3] * g.w[l + 3];
         const size_t r0 = (size_t)lvl_row0(g, l);
-        if (n == "p" + k) return set(e->at(e->pcat.p, r0 * 2 * F), rows, F, 2 * F, F);
-        if (n == "attn" + k) return set(e->at(e->pcat.p, r0 * 2 * F), rows, F, 2 * F, 0);
-        if (n == "lat" + k) return set(e->at(e->lat_all.p, r0 * F), rows, F, F, 0);
-        if (n == "pos" + k) return set(e->at(e->pos.p, r0 * F), rows, F, F, 0);
-        if (n == "tower" + k) return set(e->at(e->tow.p, r0 * F), rows, F, F, 0);
-        if (n == "head" + k) return set(e->head.p + r0 * 8, rows, 5, 8, 0);
+        if (n == "p" + k) return set(e->pcat.row(r0), rows, F, 2 * F, F);
+        if (n == "attn" + k) return set(e->pcat.row(r0), rows, F, 2 * F, 0);
+        if (n == "lat" + k) return set(e->lat_all.row(r0), rows, F, F, 0);
+        if (n == "pos" + k) return set(e->pos.row(r0), rows, F, F, 0);
+        if (n == "tower" + k) return set(e->tow.row(r0), rows, F, F, 0);
+        if (n == "head" + k) return set(e->head.row(r0), rows, 5, 8, 0);
     }
     // per-image detection outputs: "name" = image 0, "name#b" = image b of the last batch
     size_t ib = 0;

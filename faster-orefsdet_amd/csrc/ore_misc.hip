@@ -1,8 +1,10 @@
 // HBM-bound elementwise / reduction kernels of the path: stem_1 (fused preprocess + conv 3->64),
 // ceil-mode max-pool, eSE gate, depthwise query<->support correlation, support kernel pooling,
-// GroupNorm statistics.  All NHWC fp32, 16-byte vector accesses, 64-wide wavefronts.
+// GroupNorm statistics.  All NHWC fp32 (or bf16: one launcher per op takes the storage, ore_layer_ops.h), 16-byte vector accesses,
+// 64-wide wavefronts.
 #include "ore_common.h"
 #include "ore_ese.h"
+#include "ore_layer_ops.h"
 #include <stdlib.h>
 #include <algorithm>
 
@@ -753,10 +755,17 @@ __global__ __launch_bounds__(256) void k_head_pred(HeadP p) {
 
 }  // namespace
 
+// One launcher per op for both activation storages (ore_layer_ops.h).  `stmt` runs with TS = the element type of the storage.
+#define ORE_WITH_STORAGE(bf16, stmt)                    \
+    do {                                                \
+        if (bf16) { using TS = ore_bf16_t; stmt; }      \
+        else { using TS = float; stmt; }                \
+    } while (0)
+
 struct HeadGn { const float* stats; GnSeg sg; const float* gamma; const float* beta; float eps; int G; };
 static int head_pred_launch(const void* tower, int32_t ld, int32_t B, int32_t n_levels, const int32_t* H, const int32_t* W, const float* mul,
                             const float* add, const float* w_packed16, const float* scale, const float* shift, int32_t ep_stride,
-                            float* out, int32_t out_ld, void* stream, int bf16, const HeadGn* gn = nullptr) {
+                            float* out, int32_t out_ld, void* stream, bool bf16, const HeadGn* gn = nullptr) {
     ORE_CHECK_ARG(tower && H && W && (gn || (mul && add)) && w_packed16 && scale && shift && out, "ore_head_pred_fwd: null pointer");
     ORE_CHECK_ARG(B > 0 && n_levels >= 1 && n_levels <= 4 && ld >= 128 && ld % 4 == 0 && out_ld >= 5, "ore_head_pred_fwd: bad args");
     HeadP p{};
@@ -771,27 +780,25 @@ static int head_pred_launch(const void* tower, int32_t ld, int32_t B, int32_t n_
     p.tile0[n_levels] = tiles;
     p.mul = mul; p.add = add; p.w = w_packed16; p.scale = scale; p.shift = shift; p.ep_stride = ep_stride; p.out = out; p.out_ld = out_ld;
     if (gn) { p.stats = gn->stats; p.sg = gn->sg; p.gamma = gn->gamma; p.beta = gn->beta; p.eps = gn->eps; p.G = gn->G; }
-    if (bf16) hipLaunchKernelGGL(k_head_pred<ore_bf16_t>, dim3(tiles), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(k_head_pred<float>, dim3(tiles), dim3(256), 0, (hipStream_t)stream, p);
+    ORE_WITH_STORAGE(bf16, hipLaunchKernelGGL(k_head_pred<TS>, dim3(tiles), dim3(256), 0, (hipStream_t)stream, p));
     return ore_launch_status("k_head_pred");
 }
 
 extern "C" int ore_head_pred_fwd(const float* tower, int32_t ld, int32_t B, int32_t n_levels, const int32_t* H, const int32_t* W,
                                  const float* gn_mul, const float* gn_add, const float* w_packed16, const float* scale, const float* shift,
                                  int32_t ep_stride, float* out, int32_t out_ld, void* stream) {
-    return head_pred_launch(tower, ld, B, n_levels, H, W, gn_mul, gn_add, w_packed16, scale, shift, ep_stride, out, out_ld, stream, 0);
+    return head_pred_launch(tower, ld, B, n_levels, H, W, gn_mul, gn_add, w_packed16, scale, shift, ep_stride, out, out_ld, stream, false);
 }
 
 extern "C" int ore_head_pred_bf16_fwd(const uint16_t* tower, int32_t ld, int32_t B, int32_t n_levels, const int32_t* H, const int32_t* W,
                                       const float* gn_mul, const float* gn_add, const float* w_packed16, const float* scale,
                                       const float* shift, int32_t ep_stride, float* out, int32_t out_ld, void* stream) {
-    return head_pred_launch(tower, ld, B, n_levels, H, W, gn_mul, gn_add, w_packed16, scale, shift, ep_stride, out, out_ld, stream, 1);
+    return head_pred_launch(tower, ld, B, n_levels, H, W, gn_mul, gn_add, w_packed16, scale, shift, ep_stride, out, out_ld, stream, true);
 }
 
-static int stem1_launch(const void* img, int32_t img_is_u8, int32_t B, int32_t H, int32_t W, int32_t Hp,
-                             int32_t Wp, const float* mean3, const float* std3, const float* w_oihw,
-                             const float* scale, const float* shift, int32_t Cout, void* out, int32_t out_ld,
-                             int32_t out_coff, void* stream, int out_bf16) {
+int oremisc::stem1(const void* img, int32_t img_is_u8, int32_t B, int32_t H, int32_t W, int32_t Hp, int32_t Wp, const float* mean3,
+                   const float* std3, const float* w_oihw, const float* scale, const float* shift, int32_t Cout, void* out, int32_t out_ld,
+                   int32_t out_coff, void* stream, bool bf16) {
     ORE_CHECK_ARG(img && mean3 && std3 && w_oihw && scale && shift && out, "ore_stem1_fwd: null pointer");
     ORE_CHECK_ARG(B > 0 && H > 0 && W > 0 && Hp >= H && Wp >= W && Hp % 2 == 0 && Wp % 2 == 0, "ore_stem1_fwd: geometry");
     ORE_CHECK_ARG(Cout % 16 == 0 && Cout <= 128 && out_coff % 4 == 0 && out_ld % 4 == 0 && out_coff + Cout <= out_ld,
@@ -806,11 +813,10 @@ static int stem1_launch(const void* img, int32_t img_is_u8, int32_t B, int32_t H
     const int ngroups = ceil_div(M, 16);
     const int gpw = ngroups >= 2048 ? 2 : 1;            // groups of 16 pixels per wave (measured at 640x640 with LDS-staged weights: 1 -> 17.6, 2 -> 17.5, 4 -> 20.4, 8 -> 28.0 us)
     const int blocks = ceil_div(ngroups, 4 * gpw);
-#define ORE_STEM1(T, NT)                                                                                              \
-    do { if (out_bf16) hipLaunchKernelGGL((k_stem1<T, NT, ore_bf16_t>), dim3(blocks), dim3(256), 0, st, (const T*)img, B, H, W, Ho, Wo, mean3[0], mean3[1], \
-                       mean3[2], std3[0], std3[1], std3[2], w_oihw, scale, shift, Cout, (ore_bf16_t*)out, out_ld, out_coff, gpw); \
-    else hipLaunchKernelGGL((k_stem1<T, NT, float>), dim3(blocks), dim3(256), 0, st, (const T*)img, B, H, W, Ho, Wo, mean3[0], mean3[1], \
-                       mean3[2], std3[0], std3[1], std3[2], w_oihw, scale, shift, Cout, (float*)out, out_ld, out_coff, gpw); } while (0)
+#define ORE_STEM1(T, NT)                                                                                                                   \
+    ORE_WITH_STORAGE(bf16, hipLaunchKernelGGL((k_stem1<T, NT, TS>), dim3(blocks), dim3(256), 0, st, (const T*)img, B, H, W, Ho, Wo, mean3[0], \
+                                              mean3[1], mean3[2], std3[0], std3[1], std3[2], w_oihw, scale, shift, Cout, (TS*)out, out_ld,     \
+                                              out_coff, gpw))
     switch ((Cout >> 4) * 2 + (img_is_u8 ? 1 : 0)) {
         case 2: ORE_STEM1(float, 1); break;     case 3: ORE_STEM1(uint8_t, 1); break;
         case 4: ORE_STEM1(float, 2); break;     case 5: ORE_STEM1(uint8_t, 2); break;
@@ -826,143 +832,135 @@ extern "C" int ore_stem1_fwd(const void* img, int32_t img_is_u8, int32_t B, int3
                              int32_t Wp, const float* mean3, const float* std3, const float* w_oihw,
                              const float* scale, const float* shift, int32_t Cout, float* out, int32_t out_ld,
                              int32_t out_coff, void* stream) {
-    return stem1_launch(img, img_is_u8, B, H, W, Hp, Wp, mean3, std3, w_oihw, scale, shift, Cout, out, out_ld, out_coff, stream, 0);
+    return oremisc::stem1(img, img_is_u8, B, H, W, Hp, Wp, mean3, std3, w_oihw, scale, shift, Cout, out, out_ld, out_coff, stream, false);
 }
 
 extern "C" int ore_stem1_bf16_fwd(const void* img, int32_t img_is_u8, int32_t B, int32_t H, int32_t W, int32_t Hp,
                                   int32_t Wp, const float* mean3, const float* std3, const float* w_oihw,
                                   const float* scale, const float* shift, int32_t Cout, uint16_t* out, int32_t out_ld,
                                   int32_t out_coff, void* stream) {
-    return stem1_launch(img, img_is_u8, B, H, W, Hp, Wp, mean3, std3, w_oihw, scale, shift, Cout, out, out_ld, out_coff, stream, 1);
+    return oremisc::stem1(img, img_is_u8, B, H, W, Hp, Wp, mean3, std3, w_oihw, scale, shift, Cout, out, out_ld, out_coff, stream, true);
+}
+
+int oremisc::maxpool3x3s2(const void* in, int32_t in_ld, int32_t in_coff, int32_t B, int32_t H, int32_t W, int32_t C, const float* in_mul,
+                          void* out, int32_t out_ld, int32_t out_coff, void* stream, bool bf16) {
+    const char* who = bf16 ? "ore_maxpool3x3s2_bf16_fwd" : "ore_maxpool3x3s2_fwd";
+    ORE_CHECK_ARG(in && out && B > 0 && H >= 1 && W >= 1 && C % 4 == 0, "%s: bad args", who);
+    ORE_CHECK_ARG(in_ld % 4 == 0 && in_coff % 4 == 0 && out_ld % 4 == 0 && out_coff % 4 == 0, "%s: align", who);
+    const int Ho = ore_pool_out(H), Wo = ore_pool_out(W);
+    const int total = B * Ho * Wo * (C / 4);
+    ORE_WITH_STORAGE(bf16, hipLaunchKernelGGL(k_maxpool<TS>, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, (const TS*)in, in_ld,
+                                              in_coff, B, H, W, C / 4, Ho, Wo, in_mul, C, (TS*)out, out_ld, out_coff));
+    return ore_launch_status("k_maxpool");
 }
 
 extern "C" int ore_maxpool3x3s2_fwd(const float* in, int32_t in_ld, int32_t in_coff, int32_t B, int32_t H, int32_t W,
                                     int32_t C, const float* in_mul, float* out, int32_t out_ld, int32_t out_coff,
                                     void* stream) {
-    ORE_CHECK_ARG(in && out && B > 0 && H >= 1 && W >= 1 && C % 4 == 0, "ore_maxpool3x3s2_fwd: bad args");
-    ORE_CHECK_ARG(in_ld % 4 == 0 && in_coff % 4 == 0 && out_ld % 4 == 0 && out_coff % 4 == 0, "ore_maxpool3x3s2_fwd: align");
-    auto osz = [](int n) { int o = (n - 3 + 1) / 2 + 1; if (n < 3) o = 1; if ((o - 1) * 2 >= n) --o; return o < 1 ? 1 : o; };
-    const int Ho = osz(H), Wo = osz(W);
-    const int total = B * Ho * Wo * (C / 4);
-    hipLaunchKernelGGL(k_maxpool<float>, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, in, in_ld, in_coff, B, H,
-                       W, C / 4, Ho, Wo, in_mul, C, out, out_ld, out_coff);
-    return ore_launch_status("k_maxpool");
+    return oremisc::maxpool3x3s2(in, in_ld, in_coff, B, H, W, C, in_mul, out, out_ld, out_coff, stream, false);
 }
 
 extern "C" int ore_maxpool3x3s2_bf16_fwd(const uint16_t* in, int32_t in_ld, int32_t in_coff, int32_t B, int32_t H, int32_t W,
                                          int32_t C, const float* in_mul, uint16_t* out, int32_t out_ld, int32_t out_coff, void* stream) {
-    ORE_CHECK_ARG(in && out && B > 0 && H >= 1 && W >= 1 && C % 4 == 0, "ore_maxpool3x3s2_bf16_fwd: bad args");
-    ORE_CHECK_ARG(in_ld % 4 == 0 && in_coff % 4 == 0 && out_ld % 4 == 0 && out_coff % 4 == 0, "ore_maxpool3x3s2_bf16_fwd: align");
-    auto osz = [](int n) { int o = (n - 3 + 1) / 2 + 1; if (n < 3) o = 1; if ((o - 1) * 2 >= n) --o; return o < 1 ? 1 : o; };
-    const int Ho = osz(H), Wo = osz(W);
-    const int total = B * Ho * Wo * (C / 4);
-    hipLaunchKernelGGL(k_maxpool<ore_bf16_t>, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, (const ore_bf16_t*)in, in_ld,
-                       in_coff, B, H, W, C / 4, Ho, Wo, in_mul, C, (ore_bf16_t*)out, out_ld, out_coff);
-    return ore_launch_status("k_maxpool");
+    return oremisc::maxpool3x3s2(in, in_ld, in_coff, B, H, W, C, in_mul, out, out_ld, out_coff, stream, true);
+}
+
+// pass 2 of the eSE gate (k_ese_gate_fused) over B images; lws: the gate-scaled consumer weight it also writes (one image)
+static int ese_gate_fused_launch(const float* part, int P, int B, int HW, int C, const float* fc_w, const float* fc_b, float* gate, const float* lw,
+                                 void* lws, int lrows, bool lws_bf16, void* stream) {
+    hipLaunchKernelGGL(k_ese_gate_fused, dim3(ceil_div(C, 16), B), dim3(ESE_T), 0, (hipStream_t)stream, part, P, HW, C, fc_w, fc_b, gate, lw,
+                       (float*)lws, lrows, lws_bf16 ? 1 : 0);
+    return ore_launch_status("k_ese_gate_fused");
+}
+
+// the gate from a map: fp32, or bf16 (the frozen stages of a bf16 training step keep their maps in bf16; sums and gate stay fp32)
+static int ese_gate_launch(const void* x, int32_t ld, int32_t coff, int32_t B, int32_t HW, int32_t C, const float* fc_w, const float* fc_b,
+                           float* gate, float* workspace, void* stream, bool bf16) {
+    const char* who = bf16 ? "ore_ese_gate_bf16_fwd" : "ore_ese_gate_fwd";
+    ORE_CHECK_ARG(x && fc_w && fc_b && gate && workspace, "%s: null pointer", who);
+    ORE_CHECK_ARG(B > 0 && HW > 0 && C % 4 == 0 && C <= 4096 && ld % 4 == 0 && coff % 4 == 0, "%s: bad args", who);
+    int P = ceil_div(HW, 32);                      // >= 32 rows per part; enough blocks to pull HBM bandwidth
+    if (P > ORE_ESE_PARTS) P = ORE_ESE_PARTS;
+    ORE_WITH_STORAGE(bf16, hipLaunchKernelGGL(k_colsum_partial<TS>, dim3(P, B), dim3(256), 0, (hipStream_t)stream, (const TS*)x, ld, coff, HW, C,
+                                              workspace));
+    int rc = ore_launch_status("k_colsum_partial");
+    if (rc) return rc;
+    return ese_gate_fused_launch(workspace, P, B, HW, C, fc_w, fc_b, gate, nullptr, nullptr, 0, false, stream);
 }
 
 extern "C" int ore_ese_gate_fwd(const float* x, int32_t ld, int32_t coff, int32_t B, int32_t HW, int32_t C,
                                 const float* fc_w, const float* fc_b, float* gate, float* workspace, void* stream) {
-    ORE_CHECK_ARG(x && fc_w && fc_b && gate && workspace, "ore_ese_gate_fwd: null pointer");
-    ORE_CHECK_ARG(B > 0 && HW > 0 && C % 4 == 0 && C <= 4096 && ld % 4 == 0 && coff % 4 == 0, "ore_ese_gate_fwd: bad args");
-    hipStream_t st = (hipStream_t)stream;
-    int P = ceil_div(HW, 32);                      // >= 32 rows per part; enough blocks to pull HBM bandwidth
-    if (P > ORE_ESE_PARTS) P = ORE_ESE_PARTS;
-    hipLaunchKernelGGL(k_colsum_partial<float>, dim3(P, B), dim3(256), 0, st, x, ld, coff, HW, C, workspace);
-    int rc = ore_launch_status("k_colsum_partial");
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_ese_gate_fused, dim3(ceil_div(C, 16), B), dim3(ESE_T), 0, st, workspace, P, HW, C, fc_w, fc_b, gate,
-                       (const float*)nullptr, (float*)nullptr, 0, 0);
-    return ore_launch_status("k_ese_gate_fused");
+    return ese_gate_launch(x, ld, coff, B, HW, C, fc_w, fc_b, gate, workspace, stream, false);
 }
 
-// the same gate from a bf16 tensor (the frozen stages of a bf16 training step keep their maps in bf16; sums and gate stay fp32)
 extern "C" int ore_ese_gate_bf16_fwd(const uint16_t* x, int32_t ld, int32_t coff, int32_t B, int32_t HW, int32_t C,
                                      const float* fc_w, const float* fc_b, float* gate, float* workspace, void* stream) {
-    ORE_CHECK_ARG(x && fc_w && fc_b && gate && workspace, "ore_ese_gate_bf16_fwd: null pointer");
-    ORE_CHECK_ARG(B > 0 && HW > 0 && C % 4 == 0 && C <= 4096 && ld % 4 == 0 && coff % 4 == 0, "ore_ese_gate_bf16_fwd: bad args");
-    hipStream_t st = (hipStream_t)stream;
-    int P = ceil_div(HW, 32);
-    if (P > ORE_ESE_PARTS) P = ORE_ESE_PARTS;
-    hipLaunchKernelGGL(k_colsum_partial<ore_bf16_t>, dim3(P, B), dim3(256), 0, st, reinterpret_cast<const ore_bf16_t*>(x), ld, coff, HW, C,
-                       workspace);
-    int rc = ore_launch_status("k_colsum_partial");
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_ese_gate_fused, dim3(ceil_div(C, 16), B), dim3(ESE_T), 0, st, workspace, P, HW, C, fc_w, fc_b, gate,
-                       (const float*)nullptr, (float*)nullptr, 0, 0);
-    return ore_launch_status("k_ese_gate_fused");
+    return ese_gate_launch(x, ld, coff, B, HW, C, fc_w, fc_b, gate, workspace, stream, true);
 }
 
 extern "C" int ore_ese_gate_from_colsum_fwd(const float* part, int32_t P, int32_t B, int32_t HW, int32_t C, const float* fc_w,
                                             const float* fc_b, float* gate, float* mean_ws, void* stream) {
     ORE_CHECK_ARG(part && fc_w && fc_b && gate && mean_ws && P > 0 && B > 0 && HW > 0 && C > 0 && C % 4 == 0 && C <= 4096,
                   "ore_ese_gate_from_colsum_fwd: bad args");
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_ese_gate_fused, dim3(ceil_div(C, 16), B), dim3(ESE_T), 0, st, part, P, HW, C, fc_w, fc_b, gate,
-                       (const float*)nullptr, (float*)nullptr, 0, 0);
-    return ore_launch_status("k_ese_gate_fused");
+    return ese_gate_fused_launch(part, P, B, HW, C, fc_w, fc_b, gate, nullptr, nullptr, 0, false, stream);
+}
+
+// gate + the gate-scaled consumer weight (bf16 storage: a bf16 tensor, whose rows need C % 32 == 0) in one launch
+int oremisc::ese_gate_scaled_weight(const float* part, int32_t P, int32_t HW, int32_t C, const float* fc_w, const float* fc_b, float* gate,
+                                    float* mean_ws, const float* w_packed, int32_t w_rows, void* w_scaled, void* stream, bool bf16) {
+    const bool ok = part && fc_w && fc_b && gate && mean_ws && w_packed && w_scaled && P > 0 && HW > 0 && C > 0 && C % 4 == 0 && C <= 4096 &&
+                    w_rows > 0;
+    ORE_CHECK_ARG(bf16 || ok, "ore_ese_gate_scaled_weight_fwd: bad args");
+    ORE_CHECK_ARG(!bf16 || (ok && C % 32 == 0), "ore_ese_gate_scaled_weight_bf16_fwd: bad args (C must be a multiple of 32)");
+    return ese_gate_fused_launch(part, P, 1, HW, C, fc_w, fc_b, gate, w_packed, w_scaled, w_rows, bf16, stream);
 }
 
 extern "C" int ore_ese_gate_scaled_weight_fwd(const float* part, int32_t P, int32_t HW, int32_t C, const float* fc_w, const float* fc_b,
                                               float* gate, float* mean_ws, const float* w_packed, int32_t w_rows, float* w_scaled,
                                               void* stream) {
-    ORE_CHECK_ARG(part && fc_w && fc_b && gate && mean_ws && w_packed && w_scaled && P > 0 && HW > 0 && C > 0 && C % 4 == 0 && C <= 4096 &&
-                      w_rows > 0, "ore_ese_gate_scaled_weight_fwd: bad args");
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_ese_gate_fused, dim3(ceil_div(C, 16), 1), dim3(ESE_T), 0, st, part, P, HW, C, fc_w, fc_b, gate, w_packed, w_scaled,
-                       (int)w_rows, 0);
-    return ore_launch_status("k_ese_gate_fused");
+    return oremisc::ese_gate_scaled_weight(part, P, HW, C, fc_w, fc_b, gate, mean_ws, w_packed, w_rows, w_scaled, stream, false);
 }
 
 extern "C" int ore_ese_gate_scaled_weight_bf16_fwd(const float* part, int32_t P, int32_t HW, int32_t C, const float* fc_w, const float* fc_b,
                                                    float* gate, float* mean_ws, const float* w_packed_f32, int32_t w_rows,
                                                    uint16_t* w_scaled_bf16, void* stream) {
-    ORE_CHECK_ARG(part && fc_w && fc_b && gate && mean_ws && w_packed_f32 && w_scaled_bf16 && P > 0 && HW > 0 && C > 0 && C % 32 == 0 &&
-                      C <= 4096 && w_rows > 0, "ore_ese_gate_scaled_weight_bf16_fwd: bad args (C must be a multiple of 32)");
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_ese_gate_fused, dim3(ceil_div(C, 16), 1), dim3(ESE_T), 0, st, part, P, HW, C, fc_w, fc_b, gate, w_packed_f32,
-                       reinterpret_cast<float*>(w_scaled_bf16), (int)w_rows, 1);
-    return ore_launch_status("k_ese_gate_fused");
+    return oremisc::ese_gate_scaled_weight(part, P, HW, C, fc_w, fc_b, gate, mean_ws, w_packed_f32, w_rows, w_scaled_bf16, stream, true);
 }
 
 // gate + gate-scaled consumer weight (optional) + max-pool of x * gate, one launch (bs = 1; see k_ese_gate_pool)
-static int ese_gate_pool_launch(const float* part, int P, int HW, int C, const float* fc_w, const float* fc_b, float* gate, const float* lw,
-                                int lrows, void* lws, int lws_bf16, const void* x, int x_ld, int x_coff, int H, int W, void* out,
-                                int out_ld, int out_coff, int bf16, hipStream_t st) {
+int oremisc::ese_gate_pool(const float* part, int32_t P, int32_t HW, int32_t C, const float* fc_w, const float* fc_b, float* gate, const float* lw,
+                           int32_t lrows, void* lws, const void* x, int32_t x_ld, int32_t x_coff, int32_t H, int32_t W, void* out,
+                           int32_t out_ld, int32_t out_coff, void* stream, bool bf16) {
+    ORE_CHECK_ARG(!(bf16 && lws) || C % 32 == 0, "ore_ese_gate_pool_bf16_fwd: C must be a multiple of 32 for the bf16 scaled weight");
     ORE_CHECK_ARG(part && fc_w && fc_b && gate && x && out && P > 0 && HW == H * W && C > 0 && C % 4 == 0 && C <= 4096,
                   "ore_ese_gate_pool_fwd: bad args");
     ORE_CHECK_ARG((lws == nullptr) == (lw == nullptr) && (!lws || lrows > 0), "ore_ese_gate_pool_fwd: scaled weight needs source, rows and destination");
     ORE_CHECK_ARG(x_ld % 4 == 0 && x_coff % 4 == 0 && out_ld % 4 == 0 && out_coff % 4 == 0, "ore_ese_gate_pool_fwd: align");
-    auto osz = [](int n) { int o = (n - 3 + 1) / 2 + 1; if (n < 3) o = 1; if ((o - 1) * 2 >= n) --o; return o < 1 ? 1 : o; };
-    const int Ho = osz(H), Wo = osz(W);
+    const int Ho = ore_pool_out(H), Wo = ore_pool_out(W);
     const int gx = ceil_div(C, 16);
     static int tb = 0;                                                // blocks aimed at (env ORE_GATE_POOL_BLOCKS for A/B)
     if (!tb) { const char* e = getenv("ORE_GATE_POOL_BLOCKS"); tb = e ? atoi(e) : 224; if (tb < 8) tb = 224; }
     int gy = ceil_div(tb, gx);                                        // ~ one block per CU, at least 64 output pixels per block
     gy = std::max(1, std::min(gy, ceil_div(Ho * Wo, 64)));
-    if (bf16)
-        hipLaunchKernelGGL(k_ese_gate_pool<ore_bf16_t>, dim3(gx, gy), dim3(ESE_T), 0, st, part, P, HW, C, fc_w, fc_b, gate, lw, (float*)lws, lrows,
-                           lws_bf16, (const ore_bf16_t*)x, x_ld, x_coff, H, W, Ho, Wo, (ore_bf16_t*)out, out_ld, out_coff);
-    else
-        hipLaunchKernelGGL(k_ese_gate_pool<float>, dim3(gx, gy), dim3(ESE_T), 0, st, part, P, HW, C, fc_w, fc_b, gate, lw, (float*)lws, lrows,
-                           lws_bf16, (const float*)x, x_ld, x_coff, H, W, Ho, Wo, (float*)out, out_ld, out_coff);
+    ORE_WITH_STORAGE(bf16, hipLaunchKernelGGL(k_ese_gate_pool<TS>, dim3(gx, gy), dim3(ESE_T), 0, (hipStream_t)stream, part, P, HW, C, fc_w, fc_b, gate,
+                                              lw, (float*)lws, lrows, bf16 ? 1 : 0, (const TS*)x, x_ld, x_coff, H, W, Ho, Wo, (TS*)out, out_ld,
+                                              out_coff));
     return ore_launch_status("k_ese_gate_pool");
 }
 
 extern "C" int ore_ese_gate_pool_fwd(const float* part, int32_t P, int32_t HW, int32_t C, const float* fc_w, const float* fc_b, float* gate,
                                      const float* w_packed, int32_t w_rows, float* w_scaled, const float* x, int32_t x_ld, int32_t x_coff,
                                      int32_t H, int32_t W, float* out, int32_t out_ld, int32_t out_coff, void* stream) {
-    return ese_gate_pool_launch(part, P, HW, C, fc_w, fc_b, gate, w_packed, w_rows, w_scaled, 0, x, x_ld, x_coff, H, W, out, out_ld, out_coff, 0,
-                                (hipStream_t)stream);
+    return oremisc::ese_gate_pool(part, P, HW, C, fc_w, fc_b, gate, w_packed, w_rows, w_scaled, x, x_ld, x_coff, H, W, out, out_ld, out_coff, stream,
+                                  false);
 }
 
 extern "C" int ore_ese_gate_pool_bf16_fwd(const float* part, int32_t P, int32_t HW, int32_t C, const float* fc_w, const float* fc_b,
                                           float* gate, const float* w_packed_f32, int32_t w_rows, uint16_t* w_scaled_bf16, const uint16_t* x,
                                           int32_t x_ld, int32_t x_coff, int32_t H, int32_t W, uint16_t* out, int32_t out_ld, int32_t out_coff,
                                           void* stream) {
-    ORE_CHECK_ARG(!w_scaled_bf16 || C % 32 == 0, "ore_ese_gate_pool_bf16_fwd: C must be a multiple of 32 for the bf16 scaled weight");
-    return ese_gate_pool_launch(part, P, HW, C, fc_w, fc_b, gate, w_packed_f32, w_rows, w_scaled_bf16, 1, x, x_ld, x_coff, H, W, out, out_ld,
-                                out_coff, 1, (hipStream_t)stream);
+    return oremisc::ese_gate_pool(part, P, HW, C, fc_w, fc_b, gate, w_packed_f32, w_rows, w_scaled_bf16, x, x_ld, x_coff, H, W, out, out_ld,
+                                  out_coff, stream, true);
 }
 
 extern "C" int ore_scale_channels_fwd(const float* x, int32_t ld, int32_t coff, int32_t B, int32_t HW, int32_t C,
@@ -975,49 +973,46 @@ extern "C" int ore_scale_channels_fwd(const float* x, int32_t ld, int32_t coff, 
     return ore_launch_status("k_scale_channels");
 }
 
+// n_levels maps, level-major rows; kstride: channels between the levels' kernels (a single map: n_levels = 1, kstride = 0)
+static int correlation_launch(const char* who, const void* q, int32_t q_ld, int32_t q_coff, int32_t B, int32_t n_levels, const int32_t* H,
+                              const int32_t* W, int32_t C, const float* k11, const float* k13, const float* k31, int32_t kstride, void* out,
+                              int32_t out_ld, int32_t out_coff, void* stream, bool bf16) {
+    ORE_CHECK_ARG(C % 4 == 0 && q_ld % 4 == 0 && q_coff % 4 == 0 && out_ld % 4 == 0 && out_coff % 4 == 0, "%s: alignment", who);
+    CorrP p{};
+    p.q = q; p.q_ld = q_ld; p.q_coff = q_coff; p.B = B; p.C4 = C / 4; p.nlev = n_levels;
+    int rows = 0;
+    for (int l = 0; l < n_levels; ++l) { p.lv[l] = {rows, H[l], W[l]}; rows += B * H[l] * W[l]; }
+    p.rows = rows;
+    p.k11 = k11; p.k13 = k13; p.k31 = k31; p.kstride = kstride; p.out = out; p.out_ld = out_ld; p.out_coff = out_coff;
+    ORE_WITH_STORAGE(bf16, hipLaunchKernelGGL(k_correlation<TS>, dim3(ceil_div(p.rows * p.C4, 256)), dim3(256), 0, (hipStream_t)stream, p));
+    return ore_launch_status("k_correlation");
+}
+
 extern "C" int ore_correlation_fwd(const float* q, int32_t q_ld, int32_t q_coff, int32_t B, int32_t H, int32_t W,
                                    int32_t C, const float* k11, const float* k13, const float* k31, float* out,
                                    int32_t out_ld, int32_t out_coff, void* stream) {
     ORE_CHECK_ARG(q && k11 && k13 && k31 && out, "ore_correlation_fwd: null pointer");
-    ORE_CHECK_ARG(C % 4 == 0 && q_ld % 4 == 0 && q_coff % 4 == 0 && out_ld % 4 == 0 && out_coff % 4 == 0,
-                  "ore_correlation_fwd: alignment");
-    CorrP p{};
-    p.q = q; p.q_ld = q_ld; p.q_coff = q_coff; p.B = B; p.C4 = C / 4; p.nlev = 1; p.lv[0] = {0, H, W}; p.rows = B * H * W;
-    p.k11 = k11; p.k13 = k13; p.k31 = k31; p.kstride = 0; p.out = out; p.out_ld = out_ld; p.out_coff = out_coff;
-    hipLaunchKernelGGL(k_correlation<float>, dim3(ceil_div(p.rows * p.C4, 256)), dim3(256), 0, (hipStream_t)stream, p);
-    return ore_launch_status("k_correlation");
+    return correlation_launch("ore_correlation_fwd", q, q_ld, q_coff, B, 1, &H, &W, C, k11, k13, k31, 0, out, out_ld, out_coff, stream, false);
+}
+
+int oremisc::correlation_levels(const void* q, int32_t q_ld, int32_t q_coff, int32_t B, int32_t n_levels, const int32_t* H, const int32_t* W,
+                                int32_t C, const float* k11, const float* k13, const float* k31, void* out, int32_t out_ld, int32_t out_coff,
+                                void* stream, bool bf16) {
+    const char* who = bf16 ? "ore_correlation_levels_bf16_fwd" : "ore_correlation_levels_fwd";
+    ORE_CHECK_ARG(q && k11 && k13 && k31 && out && H && W && n_levels >= 1 && n_levels <= 4, "%s: bad args", who);
+    return correlation_launch(who, q, q_ld, q_coff, B, n_levels, H, W, C, k11, k13, k31, C, out, out_ld, out_coff, stream, bf16);
 }
 
 extern "C" int ore_correlation_levels_fwd(const float* q, int32_t q_ld, int32_t q_coff, int32_t B, int32_t n_levels,
                                           const int32_t* H, const int32_t* W, int32_t C, const float* k11, const float* k13,
                                           const float* k31, float* out, int32_t out_ld, int32_t out_coff, void* stream) {
-    ORE_CHECK_ARG(q && k11 && k13 && k31 && out && H && W && n_levels >= 1 && n_levels <= 4, "ore_correlation_levels_fwd: bad args");
-    ORE_CHECK_ARG(C % 4 == 0 && q_ld % 4 == 0 && q_coff % 4 == 0 && out_ld % 4 == 0 && out_coff % 4 == 0,
-                  "ore_correlation_levels_fwd: alignment");
-    CorrP p{};
-    p.q = q; p.q_ld = q_ld; p.q_coff = q_coff; p.B = B; p.C4 = C / 4; p.nlev = n_levels;
-    int rows = 0;
-    for (int l = 0; l < n_levels; ++l) { p.lv[l] = {rows, H[l], W[l]}; rows += B * H[l] * W[l]; }
-    p.rows = rows;
-    p.k11 = k11; p.k13 = k13; p.k31 = k31; p.kstride = C; p.out = out; p.out_ld = out_ld; p.out_coff = out_coff;
-    hipLaunchKernelGGL(k_correlation<float>, dim3(ceil_div(p.rows * p.C4, 256)), dim3(256), 0, (hipStream_t)stream, p);
-    return ore_launch_status("k_correlation");
+    return oremisc::correlation_levels(q, q_ld, q_coff, B, n_levels, H, W, C, k11, k13, k31, out, out_ld, out_coff, stream, false);
 }
 
 extern "C" int ore_correlation_levels_bf16_fwd(const uint16_t* q, int32_t q_ld, int32_t q_coff, int32_t B, int32_t n_levels,
                                                const int32_t* H, const int32_t* W, int32_t C, const float* k11, const float* k13,
                                                const float* k31, uint16_t* out, int32_t out_ld, int32_t out_coff, void* stream) {
-    ORE_CHECK_ARG(q && k11 && k13 && k31 && out && H && W && n_levels >= 1 && n_levels <= 4, "ore_correlation_levels_bf16_fwd: bad args");
-    ORE_CHECK_ARG(C % 4 == 0 && q_ld % 4 == 0 && q_coff % 4 == 0 && out_ld % 4 == 0 && out_coff % 4 == 0,
-                  "ore_correlation_levels_bf16_fwd: alignment");
-    CorrP p{};
-    p.q = q; p.q_ld = q_ld; p.q_coff = q_coff; p.B = B; p.C4 = C / 4; p.nlev = n_levels;
-    int rows = 0;
-    for (int l = 0; l < n_levels; ++l) { p.lv[l] = {rows, H[l], W[l]}; rows += B * H[l] * W[l]; }
-    p.rows = rows;
-    p.k11 = k11; p.k13 = k13; p.k31 = k31; p.kstride = C; p.out = out; p.out_ld = out_ld; p.out_coff = out_coff;
-    hipLaunchKernelGGL(k_correlation<ore_bf16_t>, dim3(ceil_div(p.rows * p.C4, 256)), dim3(256), 0, (hipStream_t)stream, p);
-    return ore_launch_status("k_correlation");
+    return oremisc::correlation_levels(q, q_ld, q_coff, B, n_levels, H, W, C, k11, k13, k31, out, out_ld, out_coff, stream, true);
 }
 
 extern "C" int ore_support_kernels_fwd(const float* proto_chw, int32_t C, int32_t s, float* k11, float* k13,
@@ -1029,7 +1024,7 @@ extern "C" int ore_support_kernels_fwd(const float* proto_chw, int32_t C, int32_
 
 // GroupNorm chunk statistics of all levels in one launch -> workspace, *sg = the segment table the consumers need
 static int gn_stats_levels(const void* xv, int32_t ld, int32_t coff, int32_t B, int32_t n_levels, const int32_t* HW, int32_t C, int32_t groups,
-                           float* workspace, hipStream_t st, int x_bf16, GnSeg* out_sg) {
+                           float* workspace, hipStream_t st, bool x_bf16, GnSeg* out_sg) {
     const float* x = (const float*)xv;
     ORE_CHECK_ARG(x && HW && workspace && n_levels >= 1 && n_levels <= 4 && groups > 0 && groups <= 64 && C % groups == 0 && C <= 256 &&
                       256 % C == 0, "ore_groupnorm_affine_levels_fwd: bad args (need C | 256, groups <= 64)");
@@ -1058,9 +1053,9 @@ static int gn_stats_levels(const void* xv, int32_t ld, int32_t coff, int32_t B, 
     return ore_launch_status("k_gn_chunk_stats");
 }
 
-static int gn_affine_levels(const void* xv, int32_t ld, int32_t coff, int32_t B, int32_t n_levels,
-                                               const int32_t* HW, int32_t C, int32_t groups, float eps, const float* gamma,
-                                               const float* beta, float* mul, float* add, float* workspace, void* stream, int x_bf16) {
+int oremisc::gn_affine_levels(const void* xv, int32_t ld, int32_t coff, int32_t B, int32_t n_levels, const int32_t* HW, int32_t C, int32_t groups,
+                              float eps, const float* gamma, const float* beta, float* mul, float* add, float* workspace, void* stream,
+                              bool x_bf16) {
     ORE_CHECK_ARG(gamma && beta && mul && add, "ore_groupnorm_affine_levels_fwd: null pointer");
     hipStream_t st = (hipStream_t)stream;
     GnSeg sg{};
@@ -1073,20 +1068,20 @@ static int gn_affine_levels(const void* xv, int32_t ld, int32_t coff, int32_t B,
 extern "C" int ore_groupnorm_affine_levels_fwd(const float* x, int32_t ld, int32_t coff, int32_t B, int32_t n_levels,
                                                const int32_t* HW, int32_t C, int32_t groups, float eps, const float* gamma,
                                                const float* beta, float* mul, float* add, float* workspace, void* stream) {
-    return gn_affine_levels(x, ld, coff, B, n_levels, HW, C, groups, eps, gamma, beta, mul, add, workspace, stream, 0);
+    return oremisc::gn_affine_levels(x, ld, coff, B, n_levels, HW, C, groups, eps, gamma, beta, mul, add, workspace, stream, false);
 }
 
 extern "C" int ore_groupnorm_affine_levels_bf16_fwd(const uint16_t* x, int32_t ld, int32_t coff, int32_t B, int32_t n_levels,
                                                     const int32_t* HW, int32_t C, int32_t groups, float eps, const float* gamma,
                                                     const float* beta, float* mul, float* add, float* workspace, void* stream) {
-    return gn_affine_levels(x, ld, coff, B, n_levels, HW, C, groups, eps, gamma, beta, mul, add, workspace, stream, 1);
+    return oremisc::gn_affine_levels(x, ld, coff, B, n_levels, HW, C, groups, eps, gamma, beta, mul, add, workspace, stream, true);
 }
 
 // GroupNorm statistics + the head's last step in two launches: the k_head_pred blocks fold the chunk statistics of their own (level,
 // image) -- k_gn_combine's work, ~1 us under their tower loads -- instead of waiting for a third launch (5.5 us on 3 blocks).
-static int head_pred_gn(const void* tower, int32_t ld, int32_t B, int32_t n_levels, const int32_t* H, const int32_t* W, int32_t groups, float eps,
-                        const float* gamma, const float* beta, const float* w_packed16, const float* scale, const float* shift,
-                        int32_t ep_stride, float* out, int32_t out_ld, float* workspace, void* stream, int bf16) {
+int oremisc::head_pred_gn(const void* tower, int32_t ld, int32_t B, int32_t n_levels, const int32_t* H, const int32_t* W, int32_t groups, float eps,
+                          const float* gamma, const float* beta, const float* w_packed16, const float* scale, const float* shift,
+                          int32_t ep_stride, float* out, int32_t out_ld, float* workspace, void* stream, bool bf16) {
     ORE_CHECK_ARG(H && W && gamma && beta && n_levels >= 1 && n_levels <= 4, "ore_head_pred_gn_fwd: bad args");
     int32_t HW[4];
     for (int l = 0; l < n_levels; ++l) HW[l] = H[l] * W[l];
@@ -1101,14 +1096,14 @@ extern "C" int ore_head_pred_gn_fwd(const float* tower, int32_t ld, int32_t B, i
                                     int32_t groups, float eps, const float* gamma, const float* beta, const float* w_packed16,
                                     const float* scale, const float* shift, int32_t ep_stride, float* out, int32_t out_ld, float* workspace,
                                     void* stream) {
-    return head_pred_gn(tower, ld, B, n_levels, H, W, groups, eps, gamma, beta, w_packed16, scale, shift, ep_stride, out, out_ld, workspace, stream, 0);
+    return oremisc::head_pred_gn(tower, ld, B, n_levels, H, W, groups, eps, gamma, beta, w_packed16, scale, shift, ep_stride, out, out_ld, workspace, stream, false);
 }
 
 extern "C" int ore_head_pred_gn_bf16_fwd(const uint16_t* tower, int32_t ld, int32_t B, int32_t n_levels, const int32_t* H, const int32_t* W,
                                          int32_t groups, float eps, const float* gamma, const float* beta, const float* w_packed16,
                                          const float* scale, const float* shift, int32_t ep_stride, float* out, int32_t out_ld,
                                          float* workspace, void* stream) {
-    return head_pred_gn(tower, ld, B, n_levels, H, W, groups, eps, gamma, beta, w_packed16, scale, shift, ep_stride, out, out_ld, workspace, stream, 1);
+    return oremisc::head_pred_gn(tower, ld, B, n_levels, H, W, groups, eps, gamma, beta, w_packed16, scale, shift, ep_stride, out, out_ld, workspace, stream, true);
 }
 
 extern "C" int ore_groupnorm_affine_fwd(const float* x, int32_t ld, int32_t coff, int32_t B, int32_t HW, int32_t C,

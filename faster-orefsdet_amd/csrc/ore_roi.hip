@@ -1045,28 +1045,9 @@ __global__ __launch_bounds__(T) void k_roi_merge_classes(MergeP p) {
 extern "C" int ore_nms_device_n_fwd(const float* boxes, const float* scores, const int32_t* n_dev, int32_t cap, float thr,
                                     int64_t* keep_idx, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
-static int roi_align_fwd_impl(const void* const* feat, const int32_t* ld, const int32_t* coff, const int32_t* H, const int32_t* W,
-                              const float* scales_host, int32_t n_levels, int32_t min_level, int32_t C, int32_t pooled,
-                              const float* boxes, const int32_t* n_dev, int32_t n_host, int32_t cap, float* out, void* stream,
-                              const int32_t* box_image, int feat_bf16);
-
-extern "C" int ore_roi_align_fwd(const float* const* feat, const int32_t* ld, const int32_t* coff, const int32_t* H, const int32_t* W,
-                                 const float* scales_host, int32_t n_levels, int32_t min_level, int32_t C, int32_t pooled,
-                                 const float* boxes, const int32_t* n_dev, int32_t n_host, int32_t cap, float* out, void* stream) {
-    return roi_align_fwd_impl((const void* const*)feat, ld, coff, H, W, scales_host, n_levels, min_level, C, pooled, boxes, n_dev, n_host, cap, out, stream, nullptr, 0);
-}
-
-extern "C" int ore_roi_align_batched_fwd(const float* const* feat, const int32_t* ld, const int32_t* coff, const int32_t* H, const int32_t* W,
-                                         const float* scales_host, int32_t n_levels, int32_t min_level, int32_t C, int32_t pooled,
-                                         const float* boxes, const int32_t* box_image, int32_t n, float* out, void* stream) {
-    ORE_CHECK_ARG(box_image, "ore_roi_align_batched_fwd: null box_image");
-    return roi_align_fwd_impl((const void* const*)feat, ld, coff, H, W, scales_host, n_levels, min_level, C, pooled, boxes, nullptr, n, n, out, stream, box_image, 0);
-}
-
-static int roi_align_fwd_impl(const void* const* feat, const int32_t* ld, const int32_t* coff, const int32_t* H, const int32_t* W,
-                              const float* scales_host, int32_t n_levels, int32_t min_level, int32_t C, int32_t pooled,
-                              const float* boxes, const int32_t* n_dev, int32_t n_host, int32_t cap, float* out, void* stream,
-                              const int32_t* box_image, int feat_bf16) {
+int oreroi::roi_align_fwd(const void* const* feat, const int32_t* ld, const int32_t* coff, const int32_t* H, const int32_t* W,
+                          const float* scales_host, int32_t n_levels, int32_t min_level, int32_t C, int32_t pooled, const float* boxes,
+                          const int32_t* n_dev, int32_t n_host, int32_t cap, float* out, void* stream, const int32_t* box_image, bool bf16) {
     ORE_CHECK_ARG(feat && ld && coff && H && W && scales_host && boxes && out, "ore_roi_align_fwd: null pointer");
     ORE_CHECK_ARG(n_levels >= 1 && n_levels <= 4 && C % 4 == 0 && pooled >= 1 && pooled <= 16 && cap >= 1, "ore_roi_align_fwd: bad args");
     RoiP p{};
@@ -1077,17 +1058,30 @@ static int roi_align_fwd_impl(const void* const* feat, const int32_t* ld, const 
     p.n_levels = n_levels; p.min_level = min_level; p.C = C; p.pooled = pooled;
     p.canonical_size = 224.0f; p.canonical_level = 4;      // ROIPooler defaults (poolers.py:96-97)
     p.boxes = boxes; p.n_ptr = n_dev; p.n_host = n_host; p.cap = cap; p.out = out; p.bidx = box_image;
-    if (feat_bf16) hipLaunchKernelGGL(k_roi_align<ore_bf16_t>, dim3(cap * ROI_FWD_SPLIT), dim3(256), 0, (hipStream_t)stream, p);
+    if (bf16) hipLaunchKernelGGL(k_roi_align<ore_bf16_t>, dim3(cap * ROI_FWD_SPLIT), dim3(256), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(k_roi_align<float>, dim3(cap * ROI_FWD_SPLIT), dim3(256), 0, (hipStream_t)stream, p);
     return ore_launch_status("k_roi_align");
+}
+
+extern "C" int ore_roi_align_fwd(const float* const* feat, const int32_t* ld, const int32_t* coff, const int32_t* H, const int32_t* W,
+                                 const float* scales_host, int32_t n_levels, int32_t min_level, int32_t C, int32_t pooled,
+                                 const float* boxes, const int32_t* n_dev, int32_t n_host, int32_t cap, float* out, void* stream) {
+    return oreroi::roi_align_fwd((const void* const*)feat, ld, coff, H, W, scales_host, n_levels, min_level, C, pooled, boxes, n_dev, n_host, cap, out, stream, nullptr, false);
+}
+
+extern "C" int ore_roi_align_batched_fwd(const float* const* feat, const int32_t* ld, const int32_t* coff, const int32_t* H, const int32_t* W,
+                                         const float* scales_host, int32_t n_levels, int32_t min_level, int32_t C, int32_t pooled,
+                                         const float* boxes, const int32_t* box_image, int32_t n, float* out, void* stream) {
+    ORE_CHECK_ARG(box_image, "ore_roi_align_batched_fwd: null box_image");
+    return oreroi::roi_align_fwd((const void* const*)feat, ld, coff, H, W, scales_host, n_levels, min_level, C, pooled, boxes, nullptr, n, n, out, stream, box_image, false);
 }
 
 // bf16 feature maps (ORE_ST_BF16 pyramid), fp32 boxes and fp32 pooled output
 extern "C" int ore_roi_align_bf16_fwd(const uint16_t* const* feat, const int32_t* ld, const int32_t* coff, const int32_t* H, const int32_t* W,
                                       const float* scales_host, int32_t n_levels, int32_t min_level, int32_t C, int32_t pooled,
                                       const float* boxes, const int32_t* n_dev, int32_t n_host, int32_t cap, float* out, void* stream) {
-    return roi_align_fwd_impl((const void* const*)feat, ld, coff, H, W, scales_host, n_levels, min_level, C, pooled, boxes, n_dev, n_host, cap, out,
-                              stream, nullptr, 1);
+    return oreroi::roi_align_fwd((const void* const*)feat, ld, coff, H, W, scales_host, n_levels, min_level, C, pooled, boxes, n_dev, n_host, cap, out,
+                                 stream, nullptr, true);
 }
 
 extern "C" size_t ore_roi_predict_workspace_bytes(int32_t cap) {
